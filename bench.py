@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- Groth16 proofs/s on the nzcp_live-shaped R1CS (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU, backend nccl = RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`).
+`--dump-outputs DIR` writes what the last timed step returned (the proof points and the public signals) as
+DIR/*.npy.  `--full` adds every other measurement and check listed below.
 
 A "step" is ONE Groth16 proof of the workload circuit through the C ABI (g16_prove_staged: QAP
 evaluation -> 6 NTTs -> join -> 5 Pippenger MSMs -> blinding -> affine proof bytes), the witness
@@ -17,7 +21,8 @@ shape-matched synthetic circuit of SURVEY 8d config 2: nVars = nConstraints = 1.
 structural estimate, domain 2^21), 513 public signals, NZCP witness value mix; trapdoor setup by
 the product's own g16_synth_setup.  `data` says so.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only; the --no-* options and --batch-streams select among them):
+  phases_ms    -- HIP-event phase times of the timed steps, read after each step
   roofline     -- the dominant kernel (msm_accumulate_kernel<G1>): algorithmic bytes
                   (points x 96 B) / HIP-event kernel time, vs 8 TB/s HBM.  The kernel is
                   integer-VALU bound by construction; the fraction is reported as the metric asks.
@@ -75,6 +80,21 @@ def fixed_rs(seed):
         return (u[0] | (u[1] << 64) | (u[2] << 128) | (u[3] << 192)) % R
     r, s_ = fr(), fr()
     return r.to_bytes(32, "little"), s_.to_bytes(32, "little")
+
+
+def dump_outputs(dirname, pr, pub, n_public):
+    """What a caller of the timed path receives from g16_prove_staged: the proof points (affine, canonical) and the
+    public signals.  Every 256-bit field element is stored as its 32 little-endian bytes in float32, which is exact, so
+    two builds compare output for output: proof_a, proof_c (x|y, 32); proof_b (x|y, c0|c1, 32); public_signals (n, 32)."""
+    import numpy as np
+
+    def elements(raw, n):
+        return np.frombuffer(raw, dtype=np.uint8).reshape(n, 32).astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"proof_a": elements(bytes(pr.a), 2), "proof_b": elements(bytes(pr.b), 4).reshape(2, 2, 32),
+              "proof_c": elements(bytes(pr.c), 2), "public_signals": elements(pub.raw[:n_public * 32], n_public)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def cpu_leg(amd, args, full_proof, full_pub, full_vkey, full_zkey, full_wtns, full_gpu_bytes, log):
@@ -380,6 +400,99 @@ def upper_bracket_leg(amd, args, dev, threads, log):
                       "ms_per_proof": round(1e3 * dt / total, 3), "all_verified_on_device": True}}
 
 
+def full_figures(args, info, acc, K, world, upload_ms):
+    """--full: phase times of the timed steps and the roofline figures built on them."""
+    # roofline of the dominant kernel: the G1 bucket-accumulate launches -- one over the fused witness group
+    # (the resident points of A, B1 and C) and one over H
+    launches = [(pts_, acc["accum"][i] / K) for pts_, i in ((info.n_a + info.n_b1 + info.n_c, 0), (info.n_h, 4))
+                if pts_ > 0]
+    bytes_per_launch = sum(96.0 * n for n, _ in launches) / max(1, len(launches))
+    ms_per_launch = sum(ms for _, ms in launches) / max(1, len(launches))
+    achieved = bytes_per_launch / (ms_per_launch * 1e-3) / 1e9 if ms_per_launch > 0 else 0.0
+    # HBM traffic of that kernel from the PMC passes committed under profiles/ (bench.py cannot collect counters
+    # itself).  The summary records the hash of the kernel sources and the workload it was taken on: anything
+    # else -- a kernel edited since, another circuit -- reports null with the reason instead of a stale figure.
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_costs
+    src_hash = kernel_costs.kernel_source_hash()
+    workload_id = (f"sha256x{args.sha256_blocks}" if args.sha256_blocks > 0 else
+                   f"{args.circuit}:{args.n_vars}:{args.n_constraints}")
+    traffic, traffic_note = None, "no PMC summary (profiles/r03_pmc_traffic.json) for this build and workload"
+    try:
+        pm = json.load(open(os.path.join(ROOT, "profiles", "r03_pmc_traffic.json")))
+        if world != 1:
+            traffic_note = "PMC summary is a 1-GPU profile"
+        elif pm.get("kernel_src_sha256") != src_hash:
+            traffic_note = "stale: profiles/r03_pmc_traffic.json was taken on other kernel sources (re-run tools/profile_round.sh)"
+        elif pm.get("workload_id") != workload_id:
+            traffic_note = f"profiles/r03_pmc_traffic.json was taken on workload {pm.get('workload_id')}, not {workload_id}"
+        else:
+            traffic = pm["avg_traffic_bytes_per_launch"]
+            traffic_note = ("rocprofv3 FETCH_SIZE + WRITE_SIZE per launch, profiles/r03_pmc_traffic.json "
+                            "(separate --pmc passes, raw counters: see its 'method')")
+    except Exception:
+        pass
+    # static instruction counts of the accumulate kernel, generated at build time from the compiler's assembly
+    costs = None
+    try:
+        costs = json.load(open(os.path.join(ROOT, "nzcp-circom_amd", "lib", "kernel_costs.json")))
+        if costs.get("kernel_src_sha256") != src_hash:
+            costs = None
+    except Exception:
+        pass
+    # the integer-issue peak comes from the committed summary of tools/microbench.hip (measured on an MI355X),
+    # valid only for the microbenchmark source it was taken with
+    peak_tmad, peak_note = None, "no profiles/r03_microbench_int_rates.json for tools/microbench.hip as it is now"
+    try:
+        import hashlib
+        mb = json.load(open(os.path.join(ROOT, "profiles", "r03_microbench_int_rates.json")))
+        if mb.get("src_sha256") == hashlib.sha256(open(os.path.join(ROOT, "tools", "microbench.hip"), "rb").read()).hexdigest():
+            peak_tmad = mb["peak_Tmad_per_s"]
+            peak_note = (f"{mb['cus']} CU x 4 SIMD x 64 lanes x {mb['clock_ghz']} GHz / {mb['cycles_per_v_mad_u64_u32']} cycles per "
+                         "wave-instruction at 4 waves/SIMD (tools/microbench.hip -> profiles/r03_microbench_int_rates.json)")
+    except Exception:
+        pass
+    nn, N, k = info.n_vars, info.domain_size, info.n_coefs
+    b_proof = 44 * k + 384 * nn + 512 * N - 64 * (info.n_public + 1)
+    return {
+        "phases_ms": {"qap": round(acc["qap_ms"] / K, 3), "ntt_x6_join": round(acc["ntt_ms"] / K, 3),
+                      "msm_A_B1_B2_C_H": [round(x / K, 3) for x in acc["msm_ms"]],
+                      "device_total": round(acc["total_ms"] / K, 3),
+                      "witness_upload_pcie": round(upload_ms, 3)},
+        "algorithmic_bytes_per_proof": b_proof,
+        # the HBM-side phases against the same roofline (SURVEY 8d byte formulas; phase times of the product schedule,
+        # i.e. with the witness MSMs running beside them)
+        "phase_rooflines": {
+            "qap_eval": {"algorithmic_bytes": 44 * k + 32 * nn + 96 * N,
+                         "GBps": round((44 * k + 32 * nn + 96 * N) / (acc["qap_ms"] / K * 1e-3) / 1e9, 1) if acc["qap_ms"] else None,
+                         "frac": round((44 * k + 32 * nn + 96 * N) / (acc["qap_ms"] / K * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if acc["qap_ms"] else None},
+            "ntt_x6_join": {"algorithmic_bytes": 320 * N,
+                            "GBps": round(320 * N / (acc["ntt_ms"] / K * 1e-3) / 1e9, 1) if acc["ntt_ms"] else None,
+                            "frac": round(320 * N / (acc["ntt_ms"] / K * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if acc["ntt_ms"] else None,
+                            "note": "VALU-bound like the MSM: 317 VALU instructions per butterfly (floor 289), 5.2-6.2 cycles each "
+                                    "(profiles/r03_pmc_accumulate.txt)"}},
+        "proof_hbm_GBps": round(b_proof / (acc["total_ms"] / K * 1e-3) / 1e9, 2) if acc["total_ms"] else None,
+        "roofline": {"bound": "hbm", "kernel": "msm_accumulate_kernel<G1> (avg over its two launches per proof: fused witness group A+B1+C, and H)",
+                     "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_note": traffic_note,
+                     "algorithmic_bytes_per_launch": round(bytes_per_launch),
+                     "avg_launch_ms": round(ms_per_launch, 4),
+                     "int_roofline": ({
+                         "kernel": "H-MSM accumulate launch (uniform 254-bit scalars)",
+                         "additions_per_point": -(-255 // info.window_bits[4]),
+                         "mads_per_addition": costs["static_v_mad_u64_u32"],
+                         "valu_per_addition": costs["static_valu"],
+                         "achieved_Tmad_per_s": round(info.n_h * (-(-255 // info.window_bits[4])) * costs["static_v_mad_u64_u32"]
+                                                      / max(1e-9, acc["accum"][4] / K * 1e-3) / 1e12, 3),
+                         "peak_Tmad_per_s": peak_tmad, "peak_note": peak_note,
+                         "note": "v_mad_u64_u32 count = points x window digits (full window precomputation: ceil(255/c) "
+                                 "additions per point, c = window bits) x the kernel's static mad count per loop iteration "
+                                 "(lib/kernel_costs.json, generated at build time from the compiler's gfx950 assembly)"}
+                                      if costs else {"note": "lib/kernel_costs.json missing or generated from other sources: run make"}),
+                     "note": "integer-VALU bound: ~2.2k VALU instructions (1.47k v_mad_u64_u32) per mixed addition at ~5 cycles each, 13 (H, c = 20, precomputed windows) to 20 (witness, c = 13) additions per 96-byte point; see DESIGN.md 3.3"},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -410,7 +523,15 @@ def main():
     ap.add_argument("--no-plonk", action="store_true", help="skip the PLONK prover leg (extra figure at N=1)")
     ap.add_argument("--no-brackets", action="store_true",
                     help="skip the upper_bracket leg (1.7 M-constraint synthetic circuit) and the shard_rehearsal leg (N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, measure and check everything else: phase times and rooflines, "
+                         "g16_prove with upload, the batch, verifier, shard-rehearsal, upper-bracket, PLONK and CPU-baseline "
+                         "legs, and at N > 1 the replicas reading (the --no-* options still select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the proof and public signals of the last timed step to DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     args.nz = None
     rank = int(os.environ.get("RANK", "0"))
@@ -439,7 +560,11 @@ def main():
 
     amd = entry.load_package()
     amd.load()
-    ncpu = os.cpu_count() or 1
+    # the CPUs this process may use: its affinity mask, capped by the job's OMP_NUM_THREADS where one is set (a pool
+    # sized by the whole machine only slows the setup down)
+    ncpu = len(os.sched_getaffinity(0))
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+        ncpu = min(ncpu, int(os.environ["OMP_NUM_THREADS"]))
     threads = max(1, ncpu // world)
     # the trapdoor setup's fixed-base multiplications run on this rank's GPU (csrc/setup_gpu.hip; same key bytes as the
     # host-thread path, tests/test_gpu_setup.py) -- untimed preparation either way
@@ -487,15 +612,15 @@ def main():
     prover = amd.Prover(zkey, device=dev, shard_rank=rank if sharded else 0,
                         shard_count=world if sharded else 1, window_bits=args.window_bits,
                         task_len=args.task_len)
-    zkey_r = zkey if sharded else None      # kept for the replicas measurement below
-    if world > 1 or (args.no_cpu and args.no_brackets):
+    zkey_r = zkey if sharded and args.full else None      # kept for the replicas measurement below
+    if world > 1 or not args.full or (args.no_cpu and args.no_brackets):
         zkey = None
     info = prover.info
     log(f"g16_create: {time.time() - t0:.1f}s; domain 2^{info.domain_size.bit_length() - 1}, nCoefs {info.n_coefs}, "
         f"resident bases A/B1/B2/C/H = {info.n_a}/{info.n_b1}/{info.n_b2}/{info.n_c}/{info.n_h}, "
         f"window bits {list(info.window_bits)}")
     prover.stage(0, wtns)
-    upload_ms = prover.timings()["upload_ms"]
+    upload_ms = prover.timings()["upload_ms"] if args.full else None
     r, s = fixed_rs(SEED)
     pr = amd.Proof()
     pub = ctypes.create_string_buffer(max(1, args.n_public * 32))
@@ -553,6 +678,8 @@ def main():
         ts = time.perf_counter()
         step()
         step_ms.append(1e3 * (time.perf_counter() - ts))
+        if not args.full:
+            continue
         tm = prover.timings()
         for k in ("qap_ms", "ntt_ms", "total_ms"):
             acc[k] += tm[k]
@@ -568,6 +695,8 @@ def main():
     K = args.steps
     proofs = K * (world if (world > 1 and not sharded) else 1)
     value = proofs / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, pr, pub, args.n_public)
 
     # N > 1, sharded run: also record the throughput reading (BASELINE config 3 across GPUs): every
     # rank proves `steps` independent proofs on an UNSHARDED handle, no collective -- weak scaling.
@@ -597,7 +726,7 @@ def main():
         rp.close()
     # the ABI entry a snarkjs user hits: g16_prove = witness upload over PCIe + the same pipeline
     incl_upload = None
-    if world == 1:
+    if world == 1 and args.full:
         for _ in range(2):
             assert lib.g16_prove(prover._h, wtns, len(wtns), r, s, ctypes.byref(pr), pub) == 0, lib.g16_last_error()
         t_u = []
@@ -609,11 +738,11 @@ def main():
         incl_upload = {"ms_per_proof_p50": round(t_u[len(t_u) // 2], 3), "proofs_per_sec": round(1e3 / t_u[len(t_u) // 2], 3),
                        "entry": "g16_prove(wtns in pageable host memory): upload + canonicity check + proof, no staging"}
     batch = verify = None
-    if world == 1 and args.batch_streams > 0:
+    if world == 1 and args.full and args.batch_streams > 0:
         batch, batch_proofs, batch_pubs = batch_leg(amd, args, None, wtns, prover, r, s, log)
         verify = verify_leg(amd, args, vkey, batch_proofs, batch_pubs, dev, log)
     rehearsal = None
-    if world == 1 and not args.no_brackets and args.circuit != "synthetic" and zkey is not None:
+    if world == 1 and args.full and not args.no_brackets and args.circuit != "synthetic" and zkey is not None:
         want = amd.proof_to_obj(pr)
         try:
             rehearsal = shard_rehearsal_leg(amd, args, zkey, wtns, prover, r, s, want, dev, log)
@@ -622,60 +751,7 @@ def main():
         except Exception as e:  # noqa: BLE001  (an extra leg must not cost the headline line)
             rehearsal = {"error": repr(e)[:300]}
     if rank == 0:
-        proof_obj = amd.proof_to_obj(pr)
-        pub_list = [str(int.from_bytes(pub.raw[i * 32:(i + 1) * 32], "little")) for i in range(args.n_public)]
-        # roofline of the dominant kernel: the G1 bucket-accumulate launches -- one over the fused witness group
-        # (the resident points of A, B1 and C) and one over H
-        launches = [(pts_, acc["accum"][i] / K) for pts_, i in ((info.n_a + info.n_b1 + info.n_c, 0), (info.n_h, 4))
-                    if pts_ > 0]
-        bytes_per_launch = sum(96.0 * n for n, _ in launches) / max(1, len(launches))
-        ms_per_launch = sum(ms for _, ms in launches) / max(1, len(launches))
-        achieved = bytes_per_launch / (ms_per_launch * 1e-3) / 1e9 if ms_per_launch > 0 else 0.0
-        # HBM traffic of that kernel from the PMC passes committed under profiles/ (bench.py cannot collect counters
-        # itself).  The summary records the hash of the kernel sources and the workload it was taken on: anything
-        # else -- a kernel edited since, another circuit -- reports null with the reason instead of a stale figure.
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        import kernel_costs
-        src_hash = kernel_costs.kernel_source_hash()
-        workload_id = (f"sha256x{args.sha256_blocks}" if args.sha256_blocks > 0 else
-                       f"{args.circuit}:{args.n_vars}:{args.n_constraints}")
-        traffic, traffic_note = None, "no PMC summary (profiles/r03_pmc_traffic.json) for this build and workload"
-        try:
-            pm = json.load(open(os.path.join(ROOT, "profiles", "r03_pmc_traffic.json")))
-            if world != 1:
-                traffic_note = "PMC summary is a 1-GPU profile"
-            elif pm.get("kernel_src_sha256") != src_hash:
-                traffic_note = "stale: profiles/r03_pmc_traffic.json was taken on other kernel sources (re-run tools/profile_round.sh)"
-            elif pm.get("workload_id") != workload_id:
-                traffic_note = f"profiles/r03_pmc_traffic.json was taken on workload {pm.get('workload_id')}, not {workload_id}"
-            else:
-                traffic = pm["avg_traffic_bytes_per_launch"]
-                traffic_note = ("rocprofv3 FETCH_SIZE + WRITE_SIZE per launch, profiles/r03_pmc_traffic.json "
-                                "(separate --pmc passes, raw counters: see its 'method')")
-        except Exception:
-            pass
-        # static instruction counts of the accumulate kernel, generated at build time from the compiler's assembly
-        costs = None
-        try:
-            costs = json.load(open(os.path.join(ROOT, "nzcp-circom_amd", "lib", "kernel_costs.json")))
-            if costs.get("kernel_src_sha256") != src_hash:
-                costs = None
-        except Exception:
-            pass
-        # the integer-issue peak comes from the committed summary of tools/microbench.hip (measured on this pool's MI355X),
-        # valid only for the microbenchmark source it was taken with
-        peak_tmad, peak_note = None, "no profiles/r03_microbench_int_rates.json for tools/microbench.hip as it is now"
-        try:
-            import hashlib
-            mb = json.load(open(os.path.join(ROOT, "profiles", "r03_microbench_int_rates.json")))
-            if mb.get("src_sha256") == hashlib.sha256(open(os.path.join(ROOT, "tools", "microbench.hip"), "rb").read()).hexdigest():
-                peak_tmad = mb["peak_Tmad_per_s"]
-                peak_note = (f"{mb['cus']} CU x 4 SIMD x 64 lanes x {mb['clock_ghz']} GHz / {mb['cycles_per_v_mad_u64_u32']} cycles per "
-                             "wave-instruction at 4 waves/SIMD (tools/microbench.hip -> profiles/r03_microbench_int_rates.json)")
-        except Exception:
-            pass
         nn, N, k = info.n_vars, info.domain_size, info.n_coefs
-        b_proof = 44 * k + 384 * nn + 512 * N - 64 * (info.n_public + 1)
         out = {
             "metric": "groth16_proofs_per_sec_nzcp_live", "value": round(value, 4), "unit": "proofs/s",
             "n_gpus": world, "steps": K, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / K, 3),
@@ -703,42 +779,9 @@ def main():
                                        (f"msm-point-range-shard{world}+abc-vector-split+scatter+allgather" if sharded
                                         else f"replicas{world}")),
                        "window_bits": list(info.window_bits)},
-            "phases_ms": {"qap": round(acc["qap_ms"] / K, 3), "ntt_x6_join": round(acc["ntt_ms"] / K, 3),
-                          "msm_A_B1_B2_C_H": [round(x / K, 3) for x in acc["msm_ms"]],
-                          "device_total": round(acc["total_ms"] / K, 3),
-                          "witness_upload_pcie": round(upload_ms, 3)},
-            "algorithmic_bytes_per_proof": b_proof,
-            # the HBM-side phases against the same roofline (SURVEY 8d byte formulas; phase times of the product schedule,
-            # i.e. with the witness MSMs running beside them)
-            "phase_rooflines": {
-                "qap_eval": {"algorithmic_bytes": 44 * k + 32 * nn + 96 * N,
-                             "GBps": round((44 * k + 32 * nn + 96 * N) / (acc["qap_ms"] / K * 1e-3) / 1e9, 1) if acc["qap_ms"] else None,
-                             "frac": round((44 * k + 32 * nn + 96 * N) / (acc["qap_ms"] / K * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if acc["qap_ms"] else None},
-                "ntt_x6_join": {"algorithmic_bytes": 320 * N,
-                                "GBps": round(320 * N / (acc["ntt_ms"] / K * 1e-3) / 1e9, 1) if acc["ntt_ms"] else None,
-                                "frac": round(320 * N / (acc["ntt_ms"] / K * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if acc["ntt_ms"] else None,
-                                "note": "VALU-bound like the MSM: 317 VALU instructions per butterfly (floor 289), 5.2-6.2 cycles each "
-                                        "(profiles/r03_pmc_accumulate.txt)"}},
-            "proof_hbm_GBps": round(b_proof / (acc["total_ms"] / K * 1e-3) / 1e9, 2) if acc["total_ms"] else None,
-            "roofline": {"bound": "hbm", "kernel": "msm_accumulate_kernel<G1> (avg over its two launches per proof: fused witness group A+B1+C, and H)",
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_note": traffic_note,
-                         "algorithmic_bytes_per_launch": round(bytes_per_launch),
-                         "avg_launch_ms": round(ms_per_launch, 4),
-                         "int_roofline": ({
-                             "kernel": "H-MSM accumulate launch (uniform 254-bit scalars)",
-                             "additions_per_point": -(-255 // info.window_bits[4]),
-                             "mads_per_addition": costs["static_v_mad_u64_u32"],
-                             "valu_per_addition": costs["static_valu"],
-                             "achieved_Tmad_per_s": round(info.n_h * (-(-255 // info.window_bits[4])) * costs["static_v_mad_u64_u32"]
-                                                          / max(1e-9, acc["accum"][4] / K * 1e-3) / 1e12, 3),
-                             "peak_Tmad_per_s": peak_tmad, "peak_note": peak_note,
-                             "note": "v_mad_u64_u32 count = points x window digits (full window precomputation: ceil(255/c) "
-                                     "additions per point, c = window bits) x the kernel's static mad count per loop iteration "
-                                     "(lib/kernel_costs.json, generated at build time from the compiler's gfx950 assembly)"}
-                                          if costs else {"note": "lib/kernel_costs.json missing or generated from other sources: run make"}),
-                         "note": "integer-VALU bound: ~2.2k VALU instructions (1.47k v_mad_u64_u32) per mixed addition at ~5 cycles each, 13 (H, c = 20, precomputed windows) to 20 (witness, c = 13) additions per 96-byte point; see DESIGN.md 3.3"},
         }
+        if args.full:
+            out.update(full_figures(args, info, acc, K, world, upload_ms))
         if incl_upload is not None:
             out["value_incl_upload"] = incl_upload
         if batch is not None:
@@ -748,7 +791,7 @@ def main():
             out["replicas_throughput"] = replicas
         if rehearsal is not None:
             out["shard_rehearsal"] = rehearsal
-        if world == 1 and not args.no_brackets and args.circuit == "nzcp_live" and args.sha256_blocks == 0:
+        if world == 1 and args.full and not args.no_brackets and args.circuit == "nzcp_live" and args.sha256_blocks == 0:
             prover.close()
             try:
                 out["upper_bracket"] = upper_bracket_leg(amd, args, dev, threads, log)
@@ -756,13 +799,15 @@ def main():
                 raise
             except Exception as e:  # noqa: BLE001
                 out["upper_bracket"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_plonk and not args.no_cpu:
+        if world == 1 and args.full and not args.no_plonk and not args.no_cpu:
             prover.close()
             try:
                 out["plonk_prover"] = plonk_leg(amd, dev, log)
             except Exception as e:  # noqa: BLE001  (an extra leg must not cost the headline line)
                 out["plonk_prover"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
+            proof_obj = amd.proof_to_obj(pr)
+            pub_list = [str(int.from_bytes(pub.raw[i * 32:(i + 1) * 32], "little")) for i in range(args.n_public)]
             gpu_bytes = bytes(pr.a) + bytes(pr.b) + bytes(pr.c)
             prover.close()
             out["cpu_baseline"] = cpu_leg(amd, args, proof_obj, pub_list, vkey, zkey, wtns, gpu_bytes, log)

@@ -75,7 +75,7 @@ traffic = {
 json.dump(traffic, open(os.path.join(prof, f"{tag}_pmc_traffic.json"), "w"), indent=1)
 
 with open(os.path.join(prof, f"{tag}_pmc_accumulate.txt"), "w") as o:
-    o.write("# rocprofv3 --pmc, serial-MSM mode (G16_SERIAL_MSM=1), python3 bench.py --steps 2 --warmup 1 --no-cpu "
+    o.write("# rocprofv3 --pmc, serial-MSM mode (G16_SERIAL_MSM=1), python3 bench.py --full --steps 2 --warmup 1 --no-cpu "
             "--batch-streams 0; rows = dispatches of the last proof (tools/profile_round.sh)\n")
     o.write("# pass 3: SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU "
             "SQ_INSTS_VALU SQ_WAVES\n")

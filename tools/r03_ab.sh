@@ -12,7 +12,7 @@ while [ $# -gt 0 ]; do
   envs=""
   while [ "$1" != "--" ] && [ $# -gt 0 ]; do envs="$envs $1"; shift; done
   shift
-  env $envs timeout -k 10 200 python bench.py --steps 30 --warmup 5 --no-cpu --no-plonk --no-brackets --batch-streams 0 $EXTRA > $OUT/$name.json 2> $OUT/$name.err || { echo "$name FAILED"; tail -3 $OUT/$name.err; continue; }
+  env $envs timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --no-cpu --no-plonk --no-brackets --batch-streams 0 $EXTRA > $OUT/$name.json 2> $OUT/$name.err || { echo "$name FAILED"; tail -3 $OUT/$name.err; continue; }
   python - <<PY
 import json
 d=json.load(open("$OUT/$name.json"))

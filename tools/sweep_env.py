@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def main():
     settings = sys.argv[1:] or [""]
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    extra = os.environ.get("SWEEP_BENCH_ARGS", "--steps 40 --warmup 5 --no-cpu --batch-streams 0").split()
+    extra = os.environ.get("SWEEP_BENCH_ARGS", "--full --steps 40 --warmup 5 --no-cpu --batch-streams 0").split()
     with open(os.path.join(ROOT, "gpurun_out", "sweep.txt"), "a") as log:
         for st in settings:
             env = dict(os.environ)
