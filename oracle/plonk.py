@@ -488,6 +488,49 @@ def write_zkey(zk, with_lagrange=True):
     return write_binfile("zkey", 1, secs)
 
 
+def read_zkey(buf):
+    """The inverse of write_zkey: a PLONK .zkey (for example one g16_plonk_setup wrote) -> the dict `prove` reads, so
+    that a key too large for the Python setup can still be proved by this oracle.  Section 13 must hold the Lagrange
+    polynomials of the public inputs."""
+    import struct
+    from bn254 import RR
+    from formats import read_binfile, section, g1_from_lem, g2_from_lem, from_le
+    secs = read_binfile(buf, "zkey", 2, "zkey")
+    rinv = pow(RR, -1, R)
+
+    def frs(b):
+        return [from_le(b[i:i + 32]) * rinv % R for i in range(0, len(b), 32)]
+    h = section(buf, secs, 2)
+    n_vars, n_public, n, n_add, n_cons = struct.unpack_from("<IIIII", h, 72)
+    k1, k2 = frs(h[92:156])
+    zk = {"protocol": "plonk", "nVars": n_vars, "nPublic": n_public, "domainSize": n, "power": n.bit_length() - 1,
+          "nAdditions": n_add, "nConstraints": n_cons, "k1": k1, "k2": k2}
+    pos = 156
+    for name in ("Qm", "Ql", "Qr", "Qo", "Qc", "S1", "S2", "S3"):
+        zk[name] = g1_from_lem(h[pos:pos + 64])
+        pos += 64
+    zk["X_2"] = g2_from_lem(h[pos:pos + 128])
+    s3 = section(buf, secs, 3)
+    zk["additions"] = []
+    for k in range(n_add):
+        s1, s2 = struct.unpack_from("<II", s3, 72 * k)
+        f1, f2 = frs(s3[72 * k + 8:72 * k + 72])
+        zk["additions"].append((s1, s2, f1, f2))
+    zk["maps"] = [list(struct.unpack_from("<%dI" % n_cons, section(buf, secs, 4 + c))) + [0] * (n - n_cons) for c in range(3)]
+
+    def polys(b):
+        v = frs(b)
+        return [(v[k:k + n], v[k + n:k + 5 * n]) for k in range(0, len(v), 5 * n)]
+    for sid, name in zip(range(7, 12), ("Qm", "Ql", "Qr", "Qo", "Qc")):
+        zk["pol_" + name], zk["ext_" + name] = polys(section(buf, secs, sid))[0]
+    for k, (c, e4) in enumerate(polys(section(buf, secs, 12))):
+        zk["pol_S%d" % (k + 1)], zk["ext_S%d" % (k + 1)] = c, e4
+    zk["lagrange"] = polys(section(buf, secs, 13))
+    s14 = section(buf, secs, 14)
+    zk["srs"] = [g1_from_lem(s14[i:i + 64]) for i in range(0, len(s14), 64)]
+    return zk
+
+
 def proof_obj(proof):
     """The object `snarkjs plonk prove` stringifies (key order of plonk_prove.js)."""
     def g1(P):

@@ -67,3 +67,18 @@ def test_oracle_reproduces_the_plonk_golden_fixture():
     proof, pub = pk.prove(zk, w, bl)
     assert pk.proof_obj(proof) == meta["proof"] and [str(x) for x in pub] == meta["public"]
     assert pk.verify(pk.vkey(zk), pub, pk.proof_from_obj(meta["proof"]))
+
+
+def test_read_zkey_inverts_write_zkey():
+    """read_zkey (the oracle's view of a key the device setup wrote) gives back every field `prove` reads: the padded
+    signal maps, the additions, the polynomials, the Lagrange polynomials of the public inputs and the powers of tau."""
+    n, p, m, seed = 60, 5, 40, 3
+    rows, w = synth.make(n, p, m, seed)
+    zk = pk.setup(n, p, rows, tau=0x1234567 + seed)
+    back = pk.read_zkey(pk.write_zkey(zk))
+    assert len(zk["additions"]) > 0 and zk["nConstraints"] < zk["domainSize"]
+    for k in zk:
+        assert back[k] == zk[k], k
+    rng = synth.Xoshiro(seed + 40)
+    bl = {i: rng.rand_fr() for i in range(1, 10)}
+    assert pk.prove(back, w, bl) == pk.prove(zk, w, bl)

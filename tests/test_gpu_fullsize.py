@@ -37,6 +37,13 @@ def _oracle_c():
     return lib
 
 
+def cpu_threads():
+    """Host threads for the oracle's C prover and the setup builders: OMP_NUM_THREADS when set, else at most 16 (a GPU
+    job gets 16 CPUs; os.cpu_count() reports the whole machine's)."""
+    env = os.environ.get("OMP_NUM_THREADS", "")
+    return int(env) if env.isdigit() and int(env) > 0 else min(16, os.cpu_count() or 1)
+
+
 def _rs(seed):
     rng = synth.Xoshiro(seed + 2)
     return rng.rand_fr(), rng.rand_fr()
@@ -76,7 +83,7 @@ def test_config2_nzcp_live_shape(amd, n):
     olib = _oracle_c()
     out = ctypes.create_string_buffer(256)
     opub = ctypes.create_string_buffer(P_NZCP * 32)
-    assert olib.g16o_prove(zkey, len(zkey), wtns, len(wtns), f.le(r), f.le(s), out, opub, os.cpu_count() or 1) == 0
+    assert olib.g16o_prove(zkey, len(zkey), wtns, len(wtns), f.le(r), f.le(s), out, opub, cpu_threads()) == 0
     pr = amd.Proof()
     gpub = ctypes.create_string_buffer(P_NZCP * 32)
     prover.stage(0, wtns)
@@ -199,7 +206,7 @@ def test_real_nzcp_circuit_with_in_circuit_cbor_search(amd, which):
     obuf = ctypes.create_string_buffer(256)
     opub = ctypes.create_string_buffer(P_NZCP * 32)
     assert olib.g16o_prove(out["zkey"], len(out["zkey"]), out["wtns"], len(out["wtns"]), f.le(r), f.le(s), obuf, opub,
-                           os.cpu_count() or 1) == 0
+                           cpu_threads()) == 0
     pr = amd.Proof()
     gpub = ctypes.create_string_buffer(P_NZCP * 32)
     prover.stage(0, out["wtns"])
@@ -235,7 +242,7 @@ def test_config5_sha256_chain_real_circuit(amd, blocks):
         olib = _oracle_c()
         obuf = ctypes.create_string_buffer(256)
         opub = ctypes.create_string_buffer(256 * 32)
-        assert olib.g16o_prove(zkey, len(zkey), wtns, len(wtns), f.le(r), f.le(s), obuf, opub, os.cpu_count() or 1) == 0
+        assert olib.g16o_prove(zkey, len(zkey), wtns, len(wtns), f.le(r), f.le(s), obuf, opub, cpu_threads()) == 0
         pr = amd.Proof()
         gpub = ctypes.create_string_buffer(256 * 32)
         prover.stage(0, wtns)

@@ -67,7 +67,8 @@ def test_ec_add(amd, curve):
             assert got == f.le(exp[0][0]) + f.le(exp[0][1]) + f.le(exp[1][0]) + f.le(exp[1][1]), i
 
 
-@pytest.mark.parametrize("logn", [0, 1, 3, 6, 10, 11, 13])
+# pass plans (ntt_tables_create, tile 2^9, min_tb 2): one pass up to 2^9, two up to 2^16, then a third of L - 16 stages
+@pytest.mark.parametrize("logn", [0, 1, 3, 6, 10, 11, 13, 14, 15, 16, 17, 19])
 def test_fft_matches_oracle(amd, logn):
     n = 1 << logn
     rng = random.Random(logn)

@@ -13,6 +13,7 @@ import formats as f
 import groth16 as g
 import synth
 from conftest import golden_path
+from test_gpu_fullsize import _oracle_c, cpu_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -201,16 +202,9 @@ def test_prove_errors_match_snarkjs(amd):
     prover.close()
 
 
-def test_trapdoor_kat_medium(amd):
-    """2^15-domain circuit: too slow for the big-int prover, so pin against the trapdoor known
-    answer: proof == ([a]G1, [b]G2, [c]G1) with a, b, c from Fr arithmetic only."""
-    n, p, m, seed = 30000, 513, 30000, 77
-    zkey, wtns, _ = amd.synth_setup(n, p, m, seed)
-    rows, w = synth.make(n, p, m, seed)
-    assert f.write_wtns(w) == wtns
-    # scalar side of the setup only (no point multiplications): u, v, t
+def kat_secrets(rows, n, p, m, seed, N):
+    """The scalar side of synth_setup's key (no point multiplications): u, v, t of every signal and the trapdoor."""
     td = g.trapdoor(seed + 1)
-    N = 1 << 15
     L = g.lagrange_at(N, td["tau"])
     u = [0] * n; v = [0] * n; t = [0] * n
     for c, (A, B, C) in enumerate(rows):
@@ -219,16 +213,45 @@ def test_trapdoor_kat_medium(amd):
         for sg, cf in C: t[sg] = (t[sg] + cf * L[c]) % b.R
     for i in range(p + 1):
         u[i] = (u[i] + L[m + i]) % b.R
-    sec = {"u": u, "v": v, "t": t, **td}
+    return {"u": u, "v": v, "t": t, **td}
+
+
+def domain_of(m, p):
+    N = 1
+    while N < m + p + 1:
+        N <<= 1
+    return N
+
+
+def trapdoor_kat(amd, n, p, m, seed, wseeds=(None,), key=None, **prover_kw):
+    """Circuits too large for the big-int prover are pinned against the trapdoor known answer:
+    proof == ([a]G1, [b]G2, [c]G1) with a, b, c from Fr arithmetic only.  One key (synth_setup's, or `key` = the
+    (zkey, wtns) it returned before), one proof per witness seed (None = the setup's own witness), all on one resident
+    handle.  Returns the handle's g16_info."""
+    zkey, wtns0 = key or amd.synth_setup(n, p, m, seed, threads=cpu_threads())[:2]
+    cls, rows, slack = synth.gen_circuit(n, p, m, seed)
+    N = domain_of(m, p)
+    sec = kat_secrets(rows, n, p, m, seed, N)
     rng = synth.Xoshiro(seed + 2)
     r, s = rng.rand_fr(), rng.rand_fr()
-    exp = g.expected_proof(sec, p, w, r, s)
-    prover = amd.Prover(zkey)
-    assert prover.info.domain_size == N
-    proof, pub = prover.prove(wtns, f.le(r), f.le(s))
-    assert proof == f.proof_obj(*exp)
-    assert pub == [str(x) for x in w[1:p + 1]]
+    prover = amd.Prover(zkey, **prover_kw)
+    info = prover.info
+    assert info.domain_size == N
+    for ws in wseeds:
+        w = synth.gen_witness(n, p, cls, rows, slack, seed if ws is None else ws)
+        wtns = wtns0 if ws is None else amd.synth_witness(n, p, m, seed, ws)
+        assert wtns == f.write_wtns(w)
+        proof, pub = prover.prove(wtns, f.le(r), f.le(s))
+        assert proof == f.proof_obj(*g.expected_proof(sec, p, w, r, s)), ws
+        assert pub == [str(x) for x in w[1:p + 1]]
     prover.close()
+    return info
+
+
+def test_trapdoor_kat_medium(amd):
+    """2^15-domain circuit, pinned by the trapdoor known answer."""
+    info = trapdoor_kat(amd, 30000, 513, 30000, 77)
+    assert info.domain_size == 1 << 15
 
 
 def test_public_json_matches_reference_golden_tobesigned_hash(amd):
@@ -238,7 +261,6 @@ def test_public_json_matches_reference_golden_tobesigned_hash(amd):
     (/root/reference/test/nzcp.js:41-47, value from SURVEY App. D.2) -- and the proof must verify and equal
     the C oracle's bytes."""
     import ctypes
-    import os
     from test_cpu_sha256_circuit import EXAMPLE_TBS_SHA256, example_to_be_signed
     tbs = example_to_be_signed()
     out = amd.sha256_message_setup(tbs, 4242)
@@ -263,16 +285,15 @@ def test_public_json_matches_reference_golden_tobesigned_hash(amd):
     pts2 = (f.g1_from_obj(proof2["pi_a"]), f.g2_from_obj(proof2["pi_b"]), f.g1_from_obj(proof2["pi_c"]))
     assert not g.verify(vk, [int(x) for x in want], pts2)
     assert g.verify(vk, [int(x) for x in pub2], pts2)
-    lib_path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_build", "libg16oracle.so")
-    if os.path.exists(lib_path):
-        olib = ctypes.CDLL(lib_path)
-        olib.g16o_prove.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
-                                    ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int]
-        obuf, opub = ctypes.create_string_buffer(256), ctypes.create_string_buffer(256 * 32)
-        assert olib.g16o_prove(zkey, len(zkey), wtns, len(wtns), f.le(r), f.le(s), obuf, opub, os.cpu_count() or 1) == 0
-        assert f.proof_obj(f.g1_from_obj(proof["pi_a"]), f.g2_from_obj(proof["pi_b"]), f.g1_from_obj(proof["pi_c"])) == proof
-        A = (f.from_le(obuf.raw[0:32]), f.from_le(obuf.raw[32:64]))
-        assert proof["pi_a"][:2] == [str(A[0]), str(A[1])]
+    # the same bytes from the oracle's C prover: pi_a, pi_b, pi_c and the public signals
+    olib = _oracle_c()
+    obuf, opub = ctypes.create_string_buffer(256), ctypes.create_string_buffer(256 * 32)
+    assert olib.g16o_prove(zkey, len(zkey), wtns, len(wtns), f.le(r), f.le(s), obuf, opub, cpu_threads()) == 0
+    pr, gpub = amd.Proof(), ctypes.create_string_buffer(256 * 32)
+    prover.stage(0, wtns)
+    assert prover.prove_staged_raw(0, f.le(r), f.le(s), pr, gpub) == 0
+    assert bytes(pr.a) + bytes(pr.b) + bytes(pr.c) == obuf.raw and gpub.raw == opub.raw
+    assert amd.proof_to_obj(pr) == proof
     prover.close()
 
 
