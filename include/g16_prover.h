@@ -117,7 +117,11 @@ int g16_prove_finish(g16_prover* p, uint32_t slot, const uint8_t* partials, uint
  *   (exchange)       shard r needs elements [lo, hi) = g16_shard_range(domain_size, r, count) of all three vectors:
  *                    an RCCL scatter / all-to-all between processes, peer copies inside one process.
  *   g16_shard_end    takes the three slices ((hi - lo) elements each), joins P = A.B - C on the slice, runs the
- *                    H-MSM over its bases and returns the partial sums exactly like g16_prove_partial. */
+ *                    H-MSM over its bases and returns the partial sums exactly like g16_prove_partial.
+ * Between the two, the handle's proof context runs the begun witness MSMs: g16_get_info, g16_get_timings and
+ * g16_prove_finish (host only) are allowed; every other call on the handle -- g16_prove, g16_prove_batch,
+ * g16_stage_witness, g16_prove_staged, g16_prove_partial, g16_qap_eval, a second g16_shard_begin -- fails with
+ * G16_E_STATE ("g16_shard_begin in progress: call g16_shard_end first") and changes nothing. */
 #define G16_LAZY_FR_BYTES 40
 int g16_shard_begin(g16_prover* p, uint32_t slot, uint32_t vec_mask, void* const out_vecs[3]);
 int g16_shard_end(g16_prover* p, uint32_t slot, const void* const slices[3], uint8_t partial[G16_PARTIAL_BYTES]);
@@ -141,9 +145,13 @@ int g16_finish_host(const uint8_t* zkey, size_t zkey_len, const uint8_t* partial
 void g16_shard_range(uint32_t total, int32_t rank, int32_t count, uint32_t* lo, uint32_t* hi);
 
 int g16_get_info(const g16_prover* p, g16_info* out);
-/* Device-side phase times of the last proof this handle completed (of the last one collected, after g16_prove_batch).
- * Read from the proof's HIP events when called -- a proof itself no longer pays for them -- so call it before the next
- * proof is started on the handle; serialised with the handle's other entry points. */
+/* Device-side phase times of the last proof this handle completed: a g16_prove, g16_prove_staged, g16_prove_partial
+ * or g16_shard_end that succeeded (after g16_prove_batch: the last proof of the batch it collected).  A proof that
+ * failed, a refused call and a g16_shard_begin still in progress leave them unchanged, and two reads with nothing
+ * completed in between return the same struct.  Read from that proof's HIP events when called (a proof itself does
+ * not pay for them; the events are kept apart from those of the next launch, so a read never waits for work still
+ * in flight); upload_ms is the last staging's (g16_stage_witness, or the upload of a successful g16_prove).
+ * Serialised with the handle's other entry points. */
 int g16_get_timings(const g16_prover* p, g16_timings* out);
 void g16_destroy(g16_prover* p);
 const char* g16_last_error(void);

@@ -192,12 +192,16 @@ int g16_multi_prove(g16_multi* m, const uint8_t* wtns, size_t wtns_len, const ui
   if (!m || !wtns || !out) { set_error("NULL argument"); return G16_E_ARG; }
   std::lock_guard<std::mutex> lk(m->mu);
   const size_t G = m->h.size();
-  // 1. the witness goes to shard 0 (format checks and the canonicity check of its words happen there)
+  // 1. the witness goes to shard 0 (format checks and the canonicity check of its words happen there); on a failure
+  // the upload from the caller's buffer is waited for
   int rc = shard_upload_witness(m->h[0], 0, wtns, wtns_len);
-  if (rc) return rc;
-  if (hipSetDevice(m->dev[0]) != hipSuccess || hipEventRecord(m->ev_w, m->view[0].st) != hipSuccess) {
+  if (!rc && (hipSetDevice(m->dev[0]) != hipSuccess || hipEventRecord(m->ev_w, m->view[0].st) != hipSuccess)) {
     set_error("hipEventRecord failed");
-    return G16_E_HIP;
+    rc = G16_E_HIP;
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(m->view[0].st);
+    return rc;
   }
   // 2. fan the witness out, start the witness MSMs and the vector evaluations
   rc = m->pool->run([&](size_t k) {
@@ -217,7 +221,8 @@ int g16_multi_prove(g16_multi* m, const uint8_t* wtns, size_t wtns_len, const ui
         if (hipEventRecord(m->ev_vec[v], m->view[k].st) != hipSuccess) { set_error("hipEventRecord failed"); return (int)G16_E_HIP; }
     return (int)G16_OK;
   });
-  // 3. slices to their shards, join + H-MSM + fold (after a failure above: drain what was begun)
+  // 3. slices to their shards, join + H-MSM + fold (after a failure above: drain every shard's streams -- shard_drain
+  // is unconditional, and shard_begin_async marks a shard begun before its first launch)
   std::vector<uint8_t> parts(G * G16_PARTIAL_BYTES);
   if (rc) {
     const std::string first_err = g16_last_error();
@@ -236,6 +241,7 @@ int g16_multi_prove(g16_multi* m, const uint8_t* wtns, size_t wtns_len, const ui
       e = shard_copy(m, k, me.vec[v] + me.lo, owner, m->view[owner].vec[v] + me.lo, (size_t)(me.hi - me.lo) * sizeof(F29));
     }
     if (e) { shard_drain(m->h[k]); return e; }
+    // (collects the H lanes even when the witness group failed, and drains after a failed launch)
     return shard_end_collect(m->h[k], parts.data() + k * G16_PARTIAL_BYTES);
   });
   if (rc) return rc;

@@ -133,15 +133,20 @@ struct g16_prover {
     hipStream_t st = nullptr;                        // QAP -> NTT -> H-MSM (critical chain)
     hipStream_t wst = nullptr, wst2 = nullptr;       // witness group: front end + G1 lane; G2 lane
     MsmWorkspace* ws[3] = {nullptr, nullptr, nullptr};   // one per group: they run concurrently
-    hipEvent_t ev[8] = {};
-    hipEvent_t mev[3][2] = {};
+    // Proof events in two sets: a launch records into one (next_event_set) while the other may still hold the last
+    // completed proof's, which g16_get_timings reads lazily.  ev[0], ev[1] (staging upload) are used from set 0 only.
+    hipEvent_t evs[2][8] = {};
+    hipEvent_t mevs[2][3][2] = {};
+    g16_timings tms[2] = {};
+    int set = 0;
+    hipEvent_t* ev = evs[0];            // = evs[set]
+    hipEvent_t (*mev)[2] = mevs[0];     // = mevs[set]
     F29 *d_a = nullptr, *d_b = nullptr, *d_c = nullptr;   // QAP/NTT vectors, lazy 9x29 format
     F29* d_wm = nullptr;                                  // Montgomery image of the witness (qap_eval's +-1 records)
     Fr* d_p = nullptr;                                    // H-MSM scalars, standard form
     Fr* d_w = nullptr;                                    // batch mode: this context's witness copy
     uint32_t* d_flag = nullptr;                           // canonicity check of the witness this context proves
     uint32_t* h_flag = nullptr;                           // ... its pinned host copy
-    g16_timings tm{};
   };
   static constexpr int kCtx = 3;   // at most; `nctx` are created (a fourth context has to share hardware queues: r03, 272 proofs/s against 299)
   ProofCtx ctx[kCtx];
@@ -149,7 +154,8 @@ struct g16_prover {
   std::vector<Fr*> slot_dev;
   std::vector<std::vector<uint8_t>> slot_pub;
   g16_timings tm{};    // of the last completed proof (refresh_timings)
-  int tm_ctx = -1;     // context whose events hold newer timings than `tm`, or -1
+  int tm_ctx = -1;     // context whose event set `tm_set` holds the last completed proof, newer than `tm`; or -1
+  int tm_set = 0;
   std::mutex mu;
 
   ~g16_prover() {
@@ -162,8 +168,10 @@ struct g16_prover {
       for (auto& w : c.ws) msm_workspace_destroy(w);
       if (c.wst && c.wst != c.st) (void)hipStreamDestroy(c.wst);
       if (c.wst2 && c.wst2 != c.st) (void)hipStreamDestroy(c.wst2);
-      for (auto& e : c.mev) { if (e[0]) (void)hipEventDestroy(e[0]); if (e[1]) (void)hipEventDestroy(e[1]); }
-      for (auto& e : c.ev) if (e) (void)hipEventDestroy(e);
+      for (auto& set : c.mevs)
+        for (auto& e : set) { if (e[0]) (void)hipEventDestroy(e[0]); if (e[1]) (void)hipEventDestroy(e[1]); }
+      for (auto& set : c.evs)
+        for (auto& e : set) if (e) (void)hipEventDestroy(e);
       if (c.st) (void)hipStreamDestroy(c.st);
     }
     for (int m = 0; m < 2; m++) {
@@ -361,7 +369,8 @@ static int create_impl(const uint8_t* zkey, size_t len, const g16_opts* opts, g1
       G16_HIP(hipStreamCreateWithPriority(&c.wst2, hipStreamNonBlocking, prio_hi));
       G16_HIP(hipStreamCreateWithPriority(&c.wst, hipStreamNonBlocking, prio_lo));
     }
-    for (auto& e : c.ev) G16_HIP(hipEventCreate(&e));
+    for (auto& set : c.evs)
+      for (auto& e : set) G16_HIP(hipEventCreate(&e));
     break;   // context 1 (batch pipelining) after context 0's workspaces, below
   }
   P->st = P->ctx[0].st;
@@ -436,13 +445,16 @@ static int create_impl(const uint8_t* zkey, size_t len, const g16_opts* opts, g1
         G16_HIP(hipStreamCreateWithPriority(&c.wst2, hipStreamNonBlocking, p_g2));
         G16_HIP(hipStreamCreateWithPriority(&c.wst, hipStreamNonBlocking, prio_lo));
       }
-      for (auto& e : c.ev) G16_HIP(hipEventCreate(&e));
+      for (auto& set : c.evs)
+        for (auto& e : set) G16_HIP(hipEventCreate(&e));
       msm_set_aux_stream_priority(p_dup);
     }
     for (int i = 0; i < 3; i++) {
       if ((rc = msm_workspace_create(&c.ws[i], P->grp[i]))) return rc;   // (creates the G2 lane's dup-row stream)
-      G16_HIP(hipEventCreate(&c.mev[i][0]));
-      G16_HIP(hipEventCreate(&c.mev[i][1]));
+      for (auto& set : c.mevs) {
+        G16_HIP(hipEventCreate(&set[i][0]));
+        G16_HIP(hipEventCreate(&set[i][1]));
+      }
     }
     const size_t vb = (size_t)P->N * sizeof(F29);
     G16_HIP(hipMalloc(&c.d_a, vb));
@@ -501,15 +513,14 @@ static int stage_impl(g16_prover* P, uint32_t slot, const uint8_t* wtns, size_t 
   if (P->slot_dev.size() <= slot) { P->slot_dev.resize(slot + 1, nullptr); P->slot_pub.resize(slot + 1); }
   if (!P->slot_dev[slot]) G16_HIP(hipMalloc(&P->slot_dev[slot], (size_t)P->nVars * sizeof(Fr)));
   auto& c0 = P->ctx[0];
-  G16_HIP(hipEventRecord(c0.ev[0], P->st));
+  G16_HIP(hipEventRecord(c0.evs[0][0], P->st));
   G16_HIP(hipMemcpyAsync(P->slot_dev[slot], body, (size_t)P->nVars * 32, hipMemcpyHostToDevice, P->st));
-  G16_HIP(hipEventRecord(c0.ev[1], P->st));
+  G16_HIP(hipEventRecord(c0.evs[0][1], P->st));
   if ((rc = qap_check_witness(P->slot_dev[slot], P->nVars, c0.d_flag, c0.h_flag, P->st))) return rc;
   P->slot_pub[slot].assign(body + 32, body + 32 + (size_t)P->nPublic * 32);
   if (!sync) return G16_OK;   // g16_prove: the proof pipeline follows on the same stream; witness_ok() after it
   G16_HIP(hipStreamSynchronize(P->st));
-  (void)hipEventElapsedTime(&c0.tm.upload_ms, c0.ev[0], c0.ev[1]);
-  P->tm.upload_ms = c0.tm.upload_ms;
+  (void)hipEventElapsedTime(&P->tm.upload_ms, c0.evs[0][0], c0.evs[0][1]);
   return witness_ok(c0);
 }
 
@@ -733,6 +744,7 @@ static int launch_h_lanes(g16_prover* P, ProofCtx& c, bool w_launched) {
 // `pipelined`: one of several proofs in flight (g16_prove_batch) -- the device is then the bottleneck, not the host's
 // share of one proof nor the depth of its chains: the repeated-value stage and the H-MSM's bucket reduce run in their
 // cheaper-on-the-device forms (msm_set_throughput: MsmGroup::dup_chunk_wide, MsmLaneWs::seg_len_thr)
+static void next_event_set(g16_prover* P, ProofCtx& c);
 static int launch_ctx(g16_prover* P, ProofCtx& c, const Fr* d_w, bool pipelined = false) {
   G16_HIP(hipSetDevice(P->device));
   int rc;
@@ -741,7 +753,7 @@ static int launch_ctx(g16_prover* P, ProofCtx& c, const Fr* d_w, bool pipelined 
   if (P->b2_solo) msm_set_throughput(c.ws[2], P->grp[2], pipelined);
   const auto th0 = std::chrono::steady_clock::now();
   g_trace_origin = th0;
-  if (P->tm_ctx == (int)(&c - P->ctx)) P->tm_ctx = -1;   // (its events are about to be recorded again)
+  next_event_set(P, c);
   G16_HIP(hipEventRecord(c.ev[2], c.st));
   // critical chain first (host launch order matters: the witness group's ~35 launches cost host time)
   static const bool fuse = !(getenv("G16_NO_FUSED_JOIN") && atoi(getenv("G16_NO_FUSED_JOIN")));
@@ -761,38 +773,47 @@ static int launch_ctx(g16_prover* P, ProofCtx& c, const Fr* d_w, bool pipelined 
   return G16_OK;
 }
 
-// Stream timings of the last collected proof, from the events its launch recorded (c.ev[5] closes the main stream in
-// launch_h_lanes); valid until that context launches its next proof
+// Stream timings of the last completed proof, from the event set its launch recorded (ev[5] closes the main stream in
+// launch_h_lanes).  The proof was collected, so its events are done: no wait on a stream, which may already run the
+// next proof of the context.  A failed query keeps the previous snapshot.
 static int refresh_timings(g16_prover* P) {
   if (P->tm_ctx < 0) return G16_OK;
   ProofCtx& c = P->ctx[P->tm_ctx];
+  const int set = P->tm_set;
   P->tm_ctx = -1;
   G16_HIP(hipSetDevice(P->device));
-  G16_HIP(hipEventSynchronize(c.ev[5]));
-  if (c.wst != c.st) G16_HIP(hipStreamSynchronize(c.wst));
-  if (c.wst2 != c.st) G16_HIP(hipStreamSynchronize(c.wst2));
-  (void)hipEventElapsedTime(&c.tm.qap_ms, c.ev[2], c.ev[3]);
-  (void)hipEventElapsedTime(&c.tm.ntt_ms, c.ev[3], c.ev[4]);
-  (void)hipEventElapsedTime(&c.tm.total_ms, c.ev[2], c.ev[5]);
+  hipEvent_t* ev = c.evs[set];
+  hipEvent_t (*mev)[2] = c.mevs[set];
+  G16_HIP(hipEventSynchronize(ev[5]));
+  G16_HIP(hipEventSynchronize(mev[0][1]));
+  if (P->b2_solo) G16_HIP(hipEventSynchronize(mev[2][1]));
+  g16_timings t = c.tms[set];
   // msm_ms: [0] = witness group on its main stream (front end + G1 lane over A, B1, C), [2] = until the G2 lane
   // (B2) is done, [4] = H group; [1], [3] unused since the witness MSMs share one front end
-  float wg = 0.f, hg = 0.f, g2 = 0.f;
-  (void)hipEventElapsedTime(&wg, c.mev[0][0], c.mev[0][1]);
-  (void)hipEventElapsedTime(&hg, c.mev[1][0], c.mev[1][1]);
-  g2 = msm_event_offset_ms(c.ws[P->b2_solo ? 2 : 0], c.mev[P->b2_solo ? 2 : 0][0], 1, 9);
-  c.tm.msm_ms[0] = wg; c.tm.msm_ms[1] = 0.f; c.tm.msm_ms[2] = g2; c.tm.msm_ms[3] = 0.f; c.tm.msm_ms[4] = hg;
+  float wg = 0.f, hg = 0.f;
+  const hipEvent_t span[5][2] = {{ev[2], ev[3]}, {ev[3], ev[4]}, {ev[2], ev[5]}, {mev[0][0], mev[0][1]}, {mev[1][0], mev[1][1]}};
+  float* dst[5] = {&t.qap_ms, &t.ntt_ms, &t.total_ms, &wg, &hg};
+  for (int k = 0; k < 5; k++) {
+    const hipError_t e = hipEventElapsedTime(dst[k], span[k][0], span[k][1]);
+    if (e != hipSuccess) {
+      set_error(std::string("g16_get_timings: hipEventElapsedTime: ") + hipGetErrorString(e));
+      return G16_E_HIP;
+    }
+  }
+  const float g2 = msm_event_offset_ms(c.ws[P->b2_solo ? 2 : 0], mev[P->b2_solo ? 2 : 0][0], 1, 9);
+  t.msm_ms[0] = wg; t.msm_ms[1] = 0.f; t.msm_ms[2] = g2; t.msm_ms[3] = 0.f; t.msm_ms[4] = hg;
   static const bool trace_dev = getenv("G16_TRACE_HOST") != nullptr;
   if (trace_dev) {
     float t_ntt0 = 0, t_ntt1 = 0;
-    (void)hipEventElapsedTime(&t_ntt0, c.ev[2], c.ev[3]);
-    (void)hipEventElapsedTime(&t_ntt1, c.ev[2], c.ev[4]);
-    fprintf(stderr, "[g16 dev] qap 0..%.3f  ntt+join ..%.3f  total %.3f\n", t_ntt0, t_ntt1, c.tm.total_ms);
+    (void)hipEventElapsedTime(&t_ntt0, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&t_ntt1, ev[2], ev[4]);
+    fprintf(stderr, "[g16 dev] qap 0..%.3f  ntt+join ..%.3f  total %.3f\n", t_ntt0, t_ntt1, t.total_ms);
     static const char* nm[2] = {"W", "H"};
     for (int gi = 0; gi < 2; gi++) {
       float s0 = 0, s1 = 0;
-      (void)hipEventElapsedTime(&s0, c.ev[2], c.mev[gi][0]);
-      (void)hipEventElapsedTime(&s1, c.ev[2], c.mev[gi][1]);
-      auto off = [&](int lane, int k) { return msm_event_offset_ms(c.ws[gi], c.ev[2], lane, k); };
+      (void)hipEventElapsedTime(&s0, ev[2], mev[gi][0]);
+      (void)hipEventElapsedTime(&s1, ev[2], mev[gi][1]);
+      auto off = [&](int lane, int k) { return msm_event_offset_ms(c.ws[gi], ev[2], lane, k); };
       fprintf(stderr, "[g16 dev] %s  start %.3f pass0 %.3f binscan %.3f pass1 %.3f binsort+scans %.3f | G1 queue %.3f accumulate "
               "%.3f..%.3f combine %.3f reduce %.3f end %.3f (stream end %.3f)\n", nm[gi], s0, off(0, 0), off(0, 1), off(0, 2),
               off(0, 3), off(0, 6), off(0, 4), off(0, 5), off(0, 7), off(0, 8), off(0, 9), s1);
@@ -801,10 +822,27 @@ static int refresh_timings(g16_prover* P) {
                 off(1, 6), off(1, 4), off(1, 5), off(1, 7), off(1, 8), off(1, 9));
     }
   }
-  const float up = P->tm.upload_ms;
-  P->tm = c.tm;
-  P->tm.upload_ms = up;
+  t.upload_ms = P->tm.upload_ms;   // (of the last staging)
+  P->tm = t;
   return G16_OK;
+}
+
+// Before a launch records the proof events of context `c`: switch it to its other event set.  That set still holds
+// the last completed proof only when the context's previous proof failed; read its timings out first.
+static void next_event_set(g16_prover* P, ProofCtx& c) {
+  const int ci = (int)(&c - P->ctx), ns = c.set ^ 1;
+  if (P->tm_ctx == ci && P->tm_set == ns) (void)refresh_timings(P);   // (on failure the previous snapshot stays)
+  c.set = ns;
+  c.ev = c.evs[ns];
+  c.mev = c.mevs[ns];
+  c.tms[ns] = g16_timings{};
+}
+// A proof of context `c` completed (collected, and its witness verdict good): its events hold the timings to report
+static void mark_completed(g16_prover* P, ProofCtx& c) {
+  P->tm_ctx = (int)(&c - P->ctx);
+  P->tm_set = c.set;
+  static const bool trace_dev = getenv("G16_TRACE_HOST") != nullptr;
+  if (trace_dev) (void)refresh_timings(P);
 }
 
 // Wait for context `c` and fold each MSM's row sums, in two halves: the witness group (A, B1, B2, C finish
@@ -818,13 +856,14 @@ static int collect_witness_msms(g16_prover* P, ProofCtx& c, Partial& out,
   out.B1 = r.g1[1];
   out.C = r.g1[2];
   out.B2 = r.g2;
-  c.tm.msm_accum_kernel_ms[0] = msm_last_accum_ms(c.ws[0], 0);
-  c.tm.msm_accum_kernel_ms[1] = c.tm.msm_accum_kernel_ms[3] = 0.f;
-  c.tm.msm_accum_kernel_ms[2] = msm_last_accum_ms(c.ws[0], 1);
+  g16_timings& tm = c.tms[c.set];
+  tm.msm_accum_kernel_ms[0] = msm_last_accum_ms(c.ws[0], 0);
+  tm.msm_accum_kernel_ms[1] = tm.msm_accum_kernel_ms[3] = 0.f;
+  tm.msm_accum_kernel_ms[2] = msm_last_accum_ms(c.ws[0], 1);
   if (P->b2_solo) {
     if ((rc = msm_collect(P->grp[2], c.ws[2], &r))) return rc;
     out.B2 = r.g2;
-    c.tm.msm_accum_kernel_ms[2] = msm_last_accum_ms(c.ws[2], 1);
+    tm.msm_accum_kernel_ms[2] = msm_last_accum_ms(c.ws[2], 1);
   }
   return G16_OK;
 }
@@ -834,19 +873,30 @@ static int collect_h_msm(g16_prover* P, ProofCtx& c, Partial& out) {
   if (rc) return rc;
   out.H = r.g1[0];
   trace_tail("H sum folded");
-  c.tm.msm_accum_kernel_ms[4] = msm_last_accum_ms(c.ws[1], 0);
-  // the stream timings of this proof are read from its events when somebody asks (g16_get_timings): the record +
-  // synchronise + eight elapsed-time queries cost 0.05 ms of every proof when they sat here (r03 host trace).  The
-  // streams need no draining either: each lane's ev_done, just waited for, is the last work on its stream.
-  P->tm_ctx = (int)(&c - P->ctx);
-  static const bool trace_dev = getenv("G16_TRACE_HOST") != nullptr;
-  if (trace_dev) return refresh_timings(P);
+  c.tms[c.set].msm_accum_kernel_ms[4] = msm_last_accum_ms(c.ws[1], 0);
+  // the stream timings of this proof are read from its events when somebody asks (g16_get_timings, after
+  // mark_completed): the record + synchronise + eight elapsed-time queries cost 0.05 ms of every proof when they sat
+  // here (r03 host trace).  The streams need no draining either: each lane's ev_done, just waited for, is the last
+  // work on its stream.
   return G16_OK;
 }
+// (the H lanes are collected even when the witness group fails: nothing of the proof stays in flight)
 static int collect_ctx(g16_prover* P, ProofCtx& c, Partial& out) {
-  int rc = collect_witness_msms(P, c, out);
-  if (rc) return rc;
-  return collect_h_msm(P, c, out);
+  const int rc = collect_witness_msms(P, c, out);
+  const int rch = collect_h_msm(P, c, out);
+  return rc ? rc : rch;
+}
+// Error paths: whatever context `c` has in flight, collected (so that its workspaces are consistent for the next
+// launch) and its streams synchronised (a launch that failed half-way has no complete set of events to wait for)
+static void drain_ctx(g16_prover* P, ProofCtx& c) {
+  const std::string err = get_error();
+  (void)hipSetDevice(P->device);
+  Partial part;
+  (void)collect_ctx(P, c, part);
+  (void)hipStreamSynchronize(c.st);
+  if (c.wst != c.st) (void)hipStreamSynchronize(c.wst);
+  if (c.wst2 != c.st) (void)hipStreamSynchronize(c.wst2);
+  set_error(err);
 }
 // launch-independent second half of a proof on context `c`: collect, and assemble around the H wait
 static int collect_and_assemble(g16_prover* P, ProofCtx& c, const Blinding& bl, g16_proof* out) {
@@ -878,8 +928,18 @@ static int collect_and_assemble(g16_prover* P, ProofCtx& c, const Blinding& bl, 
 static int device_impl(g16_prover* P, uint32_t slot, Partial& out) {
   if (slot >= P->slot_dev.size() || !P->slot_dev[slot]) { set_error("witness slot not staged"); return G16_E_STATE; }
   int rc = launch_ctx(P, P->ctx[0], P->slot_dev[slot]);
-  if (rc) return rc;
-  return collect_ctx(P, P->ctx[0], out);
+  if (rc) { drain_ctx(P, P->ctx[0]); return rc; }
+  if ((rc = collect_ctx(P, P->ctx[0], out))) return rc;
+  mark_completed(P, P->ctx[0]);
+  return G16_OK;
+}
+
+// Between g16_shard_begin and g16_shard_end context 0 runs the begun shard's witness MSMs and holds its vectors:
+// every entry point that enqueues device work or writes a slot is refused (a flag check on the success path).
+static int shard_guard(const g16_prover* P) {
+  if (!P->shard_begun) return G16_OK;
+  set_error("g16_shard_begin in progress: call g16_shard_end first");
+  return G16_E_STATE;
 }
 
 // ====================================================================== in-process sharding (multi.cpp)
@@ -912,6 +972,8 @@ int shard_begin_async(g16_prover* P, uint32_t slot, uint32_t mask) {
   G16_HIP(hipSetDevice(P->device));
   ProofCtx& c = P->ctx[0];
   int rc;
+  P->shard_begun = true;   // (before the first launch: shard_drain then drains whatever a failure left behind)
+  next_event_set(P, c);
   G16_HIP(hipEventRecord(c.ev[2], c.st));
   if (mask) {
     if ((rc = launch_qap_ntt(P, c, P->slot_dev[slot], mask))) return rc;
@@ -919,9 +981,7 @@ int shard_begin_async(g16_prover* P, uint32_t slot, uint32_t mask) {
     G16_HIP(hipEventRecord(c.ev[3], c.st));
   }
   if ((rc = launch_witness_front(P, c, P->slot_dev[slot]))) return rc;
-  if ((rc = launch_witness_lanes(P, c, false))) return rc;
-  P->shard_begun = true;
-  return G16_OK;
+  return launch_witness_lanes(P, c, false);
 }
 
 int shard_end_collect(g16_prover* P, uint8_t partial[G16_PARTIAL_BYTES]) {
@@ -935,21 +995,19 @@ int shard_end_collect(g16_prover* P, uint8_t partial[G16_PARTIAL_BYTES]) {
   if (!rc) rc = launch_h_lanes(P, c, false);
   Partial part;
   if (rc) {
-    (void)collect_witness_msms(P, c, part);
+    drain_ctx(P, c);
     return rc;
   }
   if ((rc = collect_ctx(P, c, part))) return rc;
+  mark_completed(P, c);
   memcpy(partial, &part, sizeof(part));
   return G16_OK;
 }
 
+// unconditional: also after a g16_multi_prove step that failed before, or half-way through, shard_begin_async
 void shard_drain(g16_prover* P) {
-  if (!P->shard_begun) return;
   P->shard_begun = false;
-  (void)hipSetDevice(P->device);
-  Partial part;
-  (void)collect_witness_msms(P, P->ctx[0], part);
-  (void)hipStreamSynchronize(P->ctx[0].st);
+  drain_ctx(P, P->ctx[0]);
 }
 
 }  // namespace g16
@@ -974,12 +1032,14 @@ void g16_destroy(g16_prover* p) { delete p; }
 int g16_stage_witness(g16_prover* p, uint32_t slot, const uint8_t* wtns, size_t wtns_len) {
   if (!p) { set_error("prover is NULL"); return G16_E_ARG; }
   std::lock_guard<std::mutex> lk(p->mu);
+  if (int rc = shard_guard(p)) return rc;
   return stage_impl(p, slot, wtns, wtns_len);
 }
 
 int g16_prove_partial(g16_prover* p, uint32_t slot, uint8_t partial[G16_PARTIAL_BYTES]) {
   if (!p || !partial) { set_error("NULL argument"); return G16_E_ARG; }
   std::lock_guard<std::mutex> lk(p->mu);
+  if (int rc = shard_guard(p)) return rc;
   Partial part;
   int rc = device_impl(p, slot, part);
   if (rc) return rc;
@@ -991,25 +1051,31 @@ int g16_prove_partial(g16_prover* p, uint32_t slot, uint8_t partial[G16_PARTIAL_
 int g16_shard_begin(g16_prover* p, uint32_t slot, uint32_t vec_mask, void* const out_vecs[3]) {
   if (!p || (vec_mask & ~7u)) { set_error("g16_shard_begin: bad argument"); return G16_E_ARG; }
   std::lock_guard<std::mutex> lk(p->mu);
+  if (int rc = shard_guard(p)) return rc;
   if (slot >= p->slot_dev.size() || !p->slot_dev[slot]) { set_error("witness slot not staged"); return G16_E_STATE; }
   for (int v = 0; v < 3; v++)
     if ((vec_mask & (1u << v)) && (!out_vecs || !out_vecs[v])) { set_error("g16_shard_begin: missing output vector"); return G16_E_ARG; }
   G16_HIP(hipSetDevice(p->device));
   ProofCtx& c = p->ctx[0];
-  int rc;
-  G16_HIP(hipEventRecord(c.ev[2], c.st));
-  if (vec_mask) {
-    if ((rc = launch_qap_ntt(p, c, p->slot_dev[slot], vec_mask))) return rc;
-  } else {
-    G16_HIP(hipEventRecord(c.ev[3], c.st));
-  }
-  if ((rc = launch_witness_front(p, c, p->slot_dev[slot]))) return rc;   // keeps running behind the exchange
-  if ((rc = launch_witness_lanes(p, c, false))) return rc;
-  const F29* src[3] = {c.d_a, c.d_b, c.d_c};
-  for (int v = 0; v < 3; v++)
-    if (vec_mask & (1u << v))
-      G16_HIP(hipMemcpyAsync(out_vecs[v], src[v], (size_t)p->N * sizeof(F29), hipMemcpyDefault, c.st));
-  G16_HIP(hipStreamSynchronize(c.st));
+  const int rc = [&]() -> int {
+    int e;
+    next_event_set(p, c);
+    G16_HIP(hipEventRecord(c.ev[2], c.st));
+    if (vec_mask) {
+      if ((e = launch_qap_ntt(p, c, p->slot_dev[slot], vec_mask))) return e;
+    } else {
+      G16_HIP(hipEventRecord(c.ev[3], c.st));
+    }
+    if ((e = launch_witness_front(p, c, p->slot_dev[slot]))) return e;   // keeps running behind the exchange
+    if ((e = launch_witness_lanes(p, c, false))) return e;
+    const F29* src[3] = {c.d_a, c.d_b, c.d_c};
+    for (int v = 0; v < 3; v++)
+      if (vec_mask & (1u << v))
+        G16_HIP(hipMemcpyAsync(out_vecs[v], src[v], (size_t)p->N * sizeof(F29), hipMemcpyDefault, c.st));
+    G16_HIP(hipStreamSynchronize(c.st));
+    return G16_OK;
+  }();
+  if (rc) { drain_ctx(p, c); return rc; }
   p->shard_begun = true;
   return G16_OK;
 }
@@ -1036,10 +1102,11 @@ int g16_shard_end(g16_prover* p, uint32_t slot, const void* const slices[3], uin
   if (!rc) rc = launch_h_lanes(p, c, false);
   Partial part;
   if (rc) {   // drain the witness group that g16_shard_begin started, then report
-    (void)collect_witness_msms(p, c, part);
+    drain_ctx(p, c);
     return rc;
   }
   if ((rc = collect_ctx(p, c, part))) return rc;
+  mark_completed(p, c);
   memcpy(partial, &part, sizeof(part));
   return G16_OK;
 }
@@ -1060,50 +1127,56 @@ int g16_prove_finish(g16_prover* p, uint32_t slot, const uint8_t* partials, uint
   return rc;
 }
 
+// `mark`: the proof counts as completed for g16_get_timings (g16_prove: only after the witness verdict)
 static int prove_staged_locked(g16_prover* p, uint32_t slot, const uint8_t r[32], const uint8_t s[32], g16_proof* out,
-                               uint8_t* pub) {
+                               uint8_t* pub, bool mark = true) {
   if (p->shard_count != 1) { set_error("sharded handle: use g16_prove_partial/g16_prove_finish"); return G16_E_STATE; }
   if (slot >= p->slot_dev.size() || !p->slot_dev[slot]) { set_error("witness slot not staged"); return G16_E_STATE; }
   Blinding bl;
   int rc = launch_ctx(p, p->ctx[0], p->slot_dev[slot]);
   const int rcb = prepare_blinding(&p->kp, r, s, bl);    // host work while the GPU runs
   if (rc || rcb) {                                       // drain whatever was launched, then report
-    Partial part;
-    if (!rc) (void)collect_ctx(p, p->ctx[0], part);
+    drain_ctx(p, p->ctx[0]);
     return rc ? rc : rcb;
   }
   rc = collect_and_assemble(p, p->ctx[0], bl, out);
-  if (!rc && pub && p->nPublic) memcpy(pub, p->slot_pub[slot].data(), (size_t)p->nPublic * 32);
-  return rc;
+  if (rc) return rc;
+  if (mark) mark_completed(p, p->ctx[0]);
+  if (pub && p->nPublic) memcpy(pub, p->slot_pub[slot].data(), (size_t)p->nPublic * 32);
+  return G16_OK;
 }
 
 int g16_prove_staged(g16_prover* p, uint32_t slot, const uint8_t r[32], const uint8_t s[32], g16_proof* out,
                      uint8_t* pub) {
   if (!p || !out) { set_error("NULL argument"); return G16_E_ARG; }
   std::lock_guard<std::mutex> lk(p->mu);
+  if (int rc = shard_guard(p)) return rc;
   return prove_staged_locked(p, slot, r, s, out, pub);
 }
 
 int g16_prove(g16_prover* p, const uint8_t* wtns, size_t wtns_len, const uint8_t r[32], const uint8_t s[32],
               g16_proof* out, uint8_t* pub) {
   if (!p || !out) { set_error("NULL argument"); return G16_E_ARG; }
-  if (p->shard_count != 1) { set_error("sharded handle: use g16_prove_partial/g16_prove_finish"); return G16_E_STATE; }
   std::lock_guard<std::mutex> lk(p->mu);
+  if (int rc = shard_guard(p)) return rc;
+  if (p->shard_count != 1) { set_error("sharded handle: use g16_prove_partial/g16_prove_finish"); return G16_E_STATE; }
   // upload and proof pipeline back to back on the main stream: no host synchronisation in between (the caller's
   // buffer stays valid until this call returns), the canonicity verdict of the words is read after the proof
   int rc = stage_impl(p, 0, wtns, wtns_len, /*sync=*/false);
-  if (rc) return rc;
-  rc = prove_staged_locked(p, 0, r, s, out, pub);
-  (void)hipEventElapsedTime(&p->ctx[0].tm.upload_ms, p->ctx[0].ev[0], p->ctx[0].ev[1]);
-  p->tm.upload_ms = p->ctx[0].tm.upload_ms;
+  if (rc) { (void)hipStreamSynchronize(p->st); return rc; }   // (an upload may be in flight from the caller's buffer)
+  rc = prove_staged_locked(p, 0, r, s, out, pub, /*mark=*/false);
   const int wrc = witness_ok(p->ctx[0]);
-  return wrc ? wrc : rc;
+  if (rc || wrc) return wrc ? wrc : rc;
+  (void)hipEventElapsedTime(&p->tm.upload_ms, p->ctx[0].evs[0][0], p->ctx[0].evs[0][1]);
+  mark_completed(p, p->ctx[0]);
+  return G16_OK;
 }
 
 int g16_prove_batch(g16_prover* p, const uint8_t* const* wtns, const size_t* wtns_lens, size_t count,
                     const uint8_t* rs, g16_proof* out, uint8_t* pub) {
   if (!p || !wtns || !wtns_lens || !out) { set_error("NULL argument"); return G16_E_ARG; }
   std::lock_guard<std::mutex> lk(p->mu);
+  if (int rc = shard_guard(p)) return rc;
   if (p->shard_count != 1) { set_error("sharded handle: use g16_prove_partial/g16_prove_finish"); return G16_E_STATE; }
   // Software pipeline over the contexts: while the host waits for, folds and finishes proof i-1,
   // proof i is already running on the GPU.
@@ -1111,8 +1184,10 @@ int g16_prove_batch(g16_prover* p, const uint8_t* const* wtns, const size_t* wtn
   const size_t nctx = (size_t)p->nctx;
   Blinding bl[g16_prover::kCtx];
   int bl_rc[g16_prover::kCtx] = {};
+  bool busy[g16_prover::kCtx] = {};   // the context holds an uncollected launch (or an upload from the caller's buffer)
   auto finish_one = [&](size_t i) -> int {
     ProofCtx& c = p->ctx[i % nctx];
+    busy[i % nctx] = false;
     if (bl_rc[i % nctx]) {
       Partial part;
       (void)collect_ctx(p, c, part);
@@ -1120,7 +1195,15 @@ int g16_prove_batch(g16_prover* p, const uint8_t* const* wtns, const size_t* wtn
     }
     const int frc = collect_and_assemble(p, c, bl[i % nctx], &out[i]);
     const int wrc = witness_ok(c);
+    if (!frc && !wrc) mark_completed(p, c);
     return wrc ? wrc : frc;
+  };
+  // every error exit: the contexts still busy are drained before the first error is returned, so that no work of
+  // this call is left on the device and the caller's buffers are not read after the return
+  auto fail = [&](int rc) -> int {
+    for (size_t k = 0; k < nctx; k++)
+      if (busy[k]) { drain_ctx(p, p->ctx[k]); busy[k] = false; }
+    return rc;
   };
   static const bool trace = getenv("G16_TRACE_HOST") != nullptr;
   const auto tb0 = std::chrono::steady_clock::now();
@@ -1130,19 +1213,24 @@ int g16_prove_batch(g16_prover* p, const uint8_t* const* wtns, const size_t* wtn
     const double t_a = now_ms();
     if (i >= nctx) {   // the context is still busy with proof i - kCtx
       int rc = finish_one(i - nctx);
-      if (rc) return rc;
+      if (rc) return fail(rc);
     }
     const double t_b = now_ms();
-    const uint8_t* body = nullptr;
-    int rc = parse_wtns(p, wtns[i], wtns_lens[i], &body);
-    if (rc) return rc;
-    G16_HIP(hipSetDevice(p->device));
-    if (!c.d_w) G16_HIP(hipMalloc(&c.d_w, wbytes));
-    G16_HIP(hipMemcpyAsync(c.d_w, body, wbytes, hipMemcpyHostToDevice, c.st));
-    const double t_c = now_ms();
-    if ((rc = qap_check_witness(c.d_w, p->nVars, c.d_flag, c.h_flag, c.st))) return rc;
-    if (pub && p->nPublic) memcpy(pub + i * (size_t)p->nPublic * 32, body + 32, (size_t)p->nPublic * 32);
-    if ((rc = launch_ctx(p, c, c.d_w, count > 1))) return rc;
+    double t_c = t_b;
+    const int rc = [&]() -> int {
+      const uint8_t* body = nullptr;
+      int e = parse_wtns(p, wtns[i], wtns_lens[i], &body);
+      if (e) return e;
+      G16_HIP(hipSetDevice(p->device));
+      if (!c.d_w) G16_HIP(hipMalloc(&c.d_w, wbytes));
+      busy[i % nctx] = true;
+      G16_HIP(hipMemcpyAsync(c.d_w, body, wbytes, hipMemcpyHostToDevice, c.st));
+      t_c = now_ms();
+      if ((e = qap_check_witness(c.d_w, p->nVars, c.d_flag, c.h_flag, c.st))) return e;
+      if (pub && p->nPublic) memcpy(pub + i * (size_t)p->nPublic * 32, body + 32, (size_t)p->nPublic * 32);
+      return launch_ctx(p, c, c.d_w, count > 1);
+    }();
+    if (rc) return fail(rc);
     const double t_d = now_ms();
     bl_rc[i % nctx] = prepare_blinding(&p->kp, rs ? rs + i * 64 : nullptr, rs ? rs + i * 64 + 32 : nullptr,
                                                     bl[i % nctx]);
@@ -1152,7 +1240,7 @@ int g16_prove_batch(g16_prover* p, const uint8_t* const* wtns, const size_t* wtn
   }
   for (size_t i = count > nctx ? count - nctx : 0; i < count; i++) {
     int rc = finish_one(i);
-    if (rc) return rc;
+    if (rc) return fail(rc);
   }
   return G16_OK;
 }
@@ -1214,6 +1302,7 @@ int g16_get_timings(const g16_prover* p, g16_timings* o) {
 int g16_qap_eval(g16_prover* p, uint32_t slot, uint8_t* a, uint8_t* b, uint8_t* c) {
   if (!p || !a || !b || !c) { set_error("NULL argument"); return G16_E_ARG; }
   std::lock_guard<std::mutex> lk(p->mu);
+  if (int rc = shard_guard(p)) return rc;
   if (slot >= p->slot_dev.size() || !p->slot_dev[slot]) { set_error("witness slot not staged"); return G16_E_STATE; }
   G16_HIP(hipSetDevice(p->device));
   ProofCtx& cx = p->ctx[0];
