@@ -337,6 +337,33 @@ int g16_plonk_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* pt
  * file is 4.6 GB, the key it yields 5.8 GB without the Lagrange section */
 int g16_plonk_setup_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device, int with_lagrange);
 
+/* `snarkjs groth16 setup c.r1cs pot.ptau c_0000.zkey` (alias `zkey new`): a Groth16 .zkey from an iden3 .r1cs v1 and a
+ * PREPARED .ptau v1 image (`powersoftau prepare phase2`; the Hermez _final_ files are prepared).  Sections 4-6 give
+ * alpha1, beta1, beta2; the Lagrange sections 12-15 (blocks k of 2^k points from point 2^k - 1; the block count is
+ * taken from each section's length) give every point section, as sums of the R1CS coefficients times the ceremony's
+ * points on `device` (there is no CPU path: G16_E_NOGPU).  Only blocks L (13-15) and L + 1 (12) are uploaded, 2^L the
+ * smallest domain with 2^L >= m + p + 1.  The key is a fresh _0000 key: gamma = delta = 1 and section 10 (the
+ * contribution hash, csHash) is 64 zero bytes and no contributions.  Correct, but NOT safe to deploy until a phase-2
+ * contribution changes delta (`zkey contribute`, not implemented here).
+ * Every input is checked before the device is touched: the r1cs as g16_r1cs_setup reads it; "Powers of tau is not
+ * prepared." (no section 12); "ptau: Invalid File format" (a section that is not whole blocks or has more than the
+ * power allows); "circuit too big for this power of tau ceremony. M > 2**P" when block L or L + 1 is missing. */
+int g16_groth16_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len, int device,
+                           uint8_t** zkey, size_t* zkey_len);
+/* the same from / to files: the inputs are mapped read-only and the key is written in chunks (ceremony files are GBs) */
+int g16_groth16_setup_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device);
+/* TEST-ONLY.  g16_r1cs_setup with the caller's trapdoor td = tau | alpha | beta | gamma | delta (standard-form 32-byte
+ * LE scalars below r; gamma, delta non-zero) instead of the seed stream; where its multiplications run follows
+ * g16_setup_device.  A key anyone holding td can forge proofs for. */
+int g16_r1cs_setup_trapdoor(const uint8_t* r1cs, size_t r1cs_len, const uint8_t td[5 * 32], int threads, uint8_t** zkey,
+                            size_t* zkey_len, uint8_t** vkey, size_t* vkey_len);
+/* TEST-ONLY.  A .ptau v1 image (g16_free) for a KNOWN tau | alpha | beta (standard-form LE scalars): sections 1-7 as
+ * snarkjs lays them out (2 = [tau^i]G1, i < 2^(power+1) - 1; 3 = [tau^i]G2, 4 = [alpha tau^i]G1, 5 = [beta tau^i]G1,
+ * i < 2^power; 6 = [beta]G2; 7 = no contributions) and, when `prepared`, sections 12-15 in the block layout above
+ * (12 through block power + 1, 13-15 through block power).  power <= 24; device -1 = host threads. */
+int g16_ptau_synth(uint32_t power, const uint8_t tau_alpha_beta[3 * 32], int prepared, int device, uint8_t** ptau,
+                   size_t* ptau_len);
+
 /* PLONK batch verifier on the device: [EXT] snarkjs 0.4.12 plonk_verify.js `plonk.verify(vk, publicSignals, proof)` for
  * many proofs against one key, one verdict per proof (transcript and scalar arithmetic on host threads, the twenty
  * scalar multiplications, two Miller loops and the final exponentiation of every proof on the device).

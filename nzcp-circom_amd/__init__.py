@@ -67,7 +67,8 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_nzcp_gadget", "g16_nzcp_circuit_setup", "g16_setup_device",
            "g16_verifier_create", "g16_verify_batch", "g16_verifier_timings", "g16_verifier_destroy", "g16_pairing_op",
            "g16_plonk_create", "g16_plonk_prove", "g16_plonk_get_info", "g16_plonk_destroy", "g16_plonk_setup", "g16_plonk_timings", "g16_plonk_setup_ptau", "g16_plonk_setup_files",
-           "g16_plonk_verifier_create", "g16_plonk_verify_batch", "g16_plonk_verifier_destroy"]
+           "g16_plonk_verifier_create", "g16_plonk_verify_batch", "g16_plonk_verifier_destroy",
+           "g16_groth16_setup_ptau", "g16_groth16_setup_files", "g16_r1cs_setup_trapdoor", "g16_ptau_synth"]
 
 
 def load():
@@ -139,6 +140,11 @@ def load():
     lib.g16_plonk_verifier_destroy.restype = None
     lib.g16_plonk_setup_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int]
     lib.g16_plonk_setup_ptau.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(sz)]
+    lib.g16_groth16_setup_ptau.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_int, C.POINTER(vp), C.POINTER(sz)]
+    lib.g16_groth16_setup_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
+    lib.g16_r1cs_setup_trapdoor.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp),
+                                            C.POINTER(sz)]
+    lib.g16_ptau_synth.argtypes = [C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(sz)]
     lib.g16_r1cs_setup.argtypes = [C.c_char_p, sz, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
     lib.g16_sha256_chain_setup.argtypes = [C.c_uint32, C.c_char_p, C.c_uint64, C.c_int] + [C.c_void_p] * 8
     lib.g16_sha256_message_setup.argtypes = [C.c_char_p, C.c_uint32, C.c_uint64, C.c_int] + [C.c_void_p] * 8
@@ -703,6 +709,33 @@ def plonk_setup_ptau(r1cs, ptau, device=0, with_lagrange=True):
     """`snarkjs plonk setup c.r1cs pot.ptau c.zkey`: .r1cs and .ptau bytes -> PLONK .zkey bytes."""
     z, zl = C.c_void_p(), C.c_size_t()
     _check(load().g16_plonk_setup_ptau(r1cs, len(r1cs), ptau, len(ptau), device, 1 if with_lagrange else 0, C.byref(z), C.byref(zl)))
+    return _take(z, zl)
+
+
+def groth16_setup_ptau(r1cs, ptau, device=0):
+    """`snarkjs groth16 setup c.r1cs pot.ptau c_0000.zkey`: .r1cs and prepared .ptau bytes -> Groth16 .zkey bytes
+    (gamma = delta = 1, no contribution yet)."""
+    z, zl = C.c_void_p(), C.c_size_t()
+    _check(load().g16_groth16_setup_ptau(r1cs, len(r1cs), ptau, len(ptau), device, C.byref(z), C.byref(zl)))
+    return _take(z, zl)
+
+
+def r1cs_setup_trapdoor(r1cs, td, threads=0):
+    """TEST-ONLY trapdoor setup of a .r1cs with td = dict(tau, alpha, beta, gamma, delta) of ints -> (zkey, vkey) bytes;
+    runs where setup_device() says."""
+    lib = load()
+    blob = b"".join(int(td[k]).to_bytes(32, "little") for k in ("tau", "alpha", "beta", "gamma", "delta"))
+    z, v = C.c_void_p(), C.c_void_p()
+    zl, vl = C.c_size_t(), C.c_size_t()
+    _check(lib.g16_r1cs_setup_trapdoor(r1cs, len(r1cs), blob, threads, C.byref(z), C.byref(zl), C.byref(v), C.byref(vl)))
+    return _take(z, zl), _take(v, vl)
+
+
+def ptau_synth(power, tau, alpha, beta, prepared=True, device=0):
+    """TEST-ONLY .ptau image for a known (tau, alpha, beta); device -1 = host threads."""
+    blob = b"".join(int(x).to_bytes(32, "little") for x in (tau, alpha, beta))
+    z, zl = C.c_void_p(), C.c_size_t()
+    _check(load().g16_ptau_synth(power, blob, 1 if prepared else 0, device, C.byref(z), C.byref(zl)))
     return _take(z, zl)
 
 

@@ -57,6 +57,24 @@ void shard_drain(g16_prover* p);
 int setup_fixed_mul_g1(int device, const G1Affine* tbl, int wb, int nwin, const Fr* ks_mont, size_t n, uint8_t* out);
 int setup_fixed_mul_g2(int device, const G2Affine* tbl, int wb, int nwin, const Fr* ks_mont, size_t n, uint8_t* out);
 
+// ---------------------------------------------------------------- setup from a prepared .ptau (setup_ptau.hip)
+// Sparse point combination: out[o] = sum of coef_t * bases[base_t] over the terms t of output o, terms in CSC order
+// (output o owns [start[o], start[o + 1])).  bases = the concatenation of the nseg host segments (affine Montgomery
+// images, seg_n[s] points each), uploaded once; out = nout affine points.  No CPU path (G16_E_NOGPU).
+struct SparseTerms {
+  std::vector<uint64_t> start;   // nout + 1
+  std::vector<uint32_t> base;    // per term: index into the concatenated bases
+  std::vector<Fr> coef;          // per term: standard form, < r
+};
+struct SparseStats {
+  uint64_t pm1 = 0, shorts = 0, full = 0, zero = 0;   // term classes (zero coefficients are dropped)
+  float kern_ms = 0.f;                                  // device time of the kernels
+};
+int setup_sparse_g1(int device, const uint8_t* const* seg, const size_t* seg_n, int nseg, const SparseTerms& t,
+                    uint8_t* out, SparseStats* st);
+int setup_sparse_g2(int device, const uint8_t* const* seg, const size_t* seg_n, int nseg, const SparseTerms& t,
+                    uint8_t* out, SparseStats* st);
+
 // ---------------------------------------------------------------- NTT (ntt.hip)
 struct NttPass { int lo_bits, S, tb; };
 struct NttTables {

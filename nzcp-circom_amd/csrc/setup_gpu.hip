@@ -1,29 +1,26 @@
 // Fixed-base scalar multiplication on the device: out[i] = [k_i] G for the millions of trapdoor scalars of a
-// Groth16 setup (".r1cs reader + native Groth16 trapdoor setup at scale on GPU (fixed-base MSM
-// kernel)").  What it stands in for: `snarkjs groth16 setup` ([EXT] snarkjs 0.4.12, pin /root/reference/yarn.lock:987-1001;
-// the reference records only its PLONK twin and the 2^22-power ptau it used, /root/reference/Makefile:30-31) --
-// there the section points come from a powers-of-tau file, here (test-only, known trapdoor) from the scalars
-// u_i(tau), v_i(tau), (beta u_i + alpha v_i + w_i)/gamma|delta, L_{2i+1}(tau)/delta that synth.cpp::setup_core
-// evaluates on the host.
+// TEST-ONLY Groth16 setup, the trapdoor route of synth.cpp::setup_core: the scalars
+// u_i(tau), v_i(tau), (beta u_i + alpha v_i + w_i)/gamma|delta, L_{2i+1}(tau)/delta are evaluated on the host from a
+// KNOWN trapdoor, so anyone holding it can forge proofs.  The real `snarkjs groth16 setup` ([EXT] snarkjs 0.4.12) takes
+// its points from a prepared powers-of-tau file instead: that route is synth.cpp::g16_groth16_setup_ptau with the
+// sparse point sums of setup_ptau.hip.  Also the generator of the test ceremonies (g16_ptau_synth).
 //
 // Two kernels per chunk of points, both on the canonical 8x32-bit Montgomery field (fp.cuh / ec.cuh: exact,
 // complete additions -- this is create-time work, the bytes must equal the host path's bytes):
 //   setup_fixed_mul_kernel : one lane per scalar; the scalar leaves Montgomery form, its `nwin` wb-bit digits index
 //                            the table [nwin][2^wb - 1] of d * 2^(wb j) * G (a few hundred KB: L2 resident) and are
 //                            mixed-added into an XYZZ accumulator.
-//   setup_to_affine_kernel : one lane per kBatch consecutive points: Montgomery's trick on their ZZZ (3 products per
-//                            point + one Fermat inversion per batch), then x = X (ZZ/ZZZ)^2, y = Y / ZZZ.
+//   setup_to_affine_kernel : (setup_affine.cuh) one lane per kBatch consecutive points, one inversion per batch.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #include "ec.cuh"
 #include "internal.h"
+#include "setup_affine.cuh"
 
 namespace g16 {
 namespace {
-
-constexpr int kBatch = 8;
 
 template <class FC>
 __global__ __launch_bounds__(256) void setup_fixed_mul_kernel(const Affine<FC>* __restrict__ tbl, int wb, int nwin,
@@ -46,38 +43,6 @@ __global__ __launch_bounds__(256) void setup_fixed_mul_kernel(const Affine<FC>* 
     }
   }
   out[i] = acc;
-}
-
-template <class FC>
-__global__ __launch_bounds__(256) void setup_to_affine_kernel(const XYZZ<FC>* __restrict__ in, Affine<FC>* __restrict__ out,
-                                                               uint32_t n) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t lo = t * kBatch;
-  if (lo >= n) return;
-  const uint32_t cnt = n - lo < (uint32_t)kBatch ? n - lo : (uint32_t)kBatch;
-  typename FC::T pref[kBatch];
-  typename FC::T acc = FC::one();
-  for (uint32_t e = 0; e < cnt; e++) {
-    pref[e] = acc;
-    const typename FC::T zzz = in[lo + e].zzz;
-    if (!FC::is_zero(zzz)) acc = FC::mul(acc, zzz);
-  }
-  typename FC::T inv = FC::inv(acc);
-  for (uint32_t e = cnt; e-- > 0;) {
-    const XYZZ<FC> p = in[lo + e];
-    Affine<FC> a;
-    if (xyzz_is_inf(p)) {
-      a.x = FC::zero();
-      a.y = FC::zero();
-    } else {
-      const typename FC::T zi = FC::mul(inv, pref[e]);
-      inv = FC::mul(inv, p.zzz);
-      const typename FC::T zzi = FC::sqr(FC::mul(zi, p.zz));
-      a.x = FC::mul(p.x, zzi);
-      a.y = FC::mul(p.y, zi);
-    }
-    out[lo + e] = a;
-  }
 }
 
 template <class FC>

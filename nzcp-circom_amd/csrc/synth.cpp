@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <chrono>
 #include <new>
 #include <thread>
 
@@ -372,36 +373,50 @@ extern "C" int g16_synth_witness(uint32_t n, uint32_t p, uint32_t m, uint64_t se
   return G16_OK;
 }
 
-// Trapdoor Groth16 setup of an arbitrary R1CS held in `c` (rows of (signal, Montgomery coefficient)
-// terms): snarkjs zkey layout out, plus the verification-key points.  Trapdoor from stream seed+1.
-static int setup_core(const Circuit& c, uint64_t seed, int threads, uint8_t** zkey, size_t* zkey_len,
-                      uint8_t** vkey, size_t* vkey_len) {
+// The .zkey image of a Groth16 key for circuit `c` over the domain 2^L, shared by the trapdoor setups and the .ptau
+// route (g16_groth16_setup_ptau) so both write the same bytes: every section laid out, section 1, the scalars of
+// section 2, section 4 (the coefficient records: A terms then B terms in constraint order, then the p + 1 public-input
+// binding rows (A, row m + i, wire i, 1)) and section 10 (64 zero bytes, u32 0) written.  The caller fills the six
+// section-2 points (G16ZkeyImage::hdr_points) and sections 3 (IC), 5 (A), 6 (B1), 7 (B2), 8 (C) and 9 (H).
+struct G16ZkeyImage {
+  Buf z;
+  uint8_t* sec[11] = {};
+  size_t size[11] = {};
+  uint8_t* hdr_points = nullptr;   // alpha1 | beta1 | beta2 | gamma2 | delta1 | delta2 (64 / 64 / 128 / 128 / 64 / 128)
+};
+static int g16_zkey_layout(const Circuit& c, int L, G16ZkeyImage& im) {
   const uint32_t n = c.n, p = c.p, m = c.m;
-  if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
-  if (threads <= 0) threads = 1;
-  int L = 0;
-  while (((uint64_t)1 << L) < (uint64_t)m + p + 1) L++;
-  if (L > 27) { set_error("setup: circuit too large"); return G16_E_ARG; }
   const size_t N = (size_t)1 << L;
-
-  // trapdoor (stream seed+1): tau, alpha, beta, gamma, delta, all non-zero
-  Xo trng(seed + 1);
-  FrM td[5];
-  for (int k = 0; k < 5;) {
-    const FrM v = trng.rand_fr();
-    if (!fp_is_zero(v)) td[k++] = v;
-  }
-  const FrM tau = td[0], alpha = td[1], beta = td[2], gamma = td[3], delta = td[4];
-  std::vector<FrM> Lg;
-  lagrange_at(L, tau, 0, 1, N, Lg);
-  std::vector<FrM> u(n, fp_zero<FrParams>()), v(n, fp_zero<FrParams>()), t(n, fp_zero<FrParams>());
   const size_t ncoef = c.tA.size() + c.tB.size() + (size_t)p + 1;
-  // section 4 image: records in constraint order, A terms then B terms, then the binding rows
-  std::vector<uint8_t> s4(4 + ncoef * 44);
+  const size_t nC = (size_t)n - p - 1;
+  const size_t hdr2 = 4 + 32 + 4 + 32 + 12 + 64 + 64 + 128 + 128 + 64 + 128;
+  const size_t sizes[11] = {0, 4, hdr2, (size_t)(p + 1) * 64, 4 + ncoef * 44, (size_t)n * 64, (size_t)n * 64,
+                            (size_t)n * 128, nC * 64, N * 64, 64 + 4};
+  size_t total = 12;
+  for (int i = 1; i <= 10; i++) total += 12 + sizes[i];
+  Buf& z = im.z;
+  if (!z.reserve(total)) { set_error("synth: out of memory"); return G16_E_STATE; }
+  z.put("zkey", 4); z.u32(1); z.u32(10);
+  for (uint32_t id = 1; id <= 10; id++) {
+    z.u32(id); z.u64(sizes[id]);
+    im.size[id] = sizes[id];
+    im.sec[id] = z.skip(sizes[id]);
+  }
+  { uint32_t one = 1; memcpy(im.sec[1], &one, 4); }
+  {
+    static const uint32_t Qp[8] = G16_FQ_P, Rp[8] = G16_FR_P;
+    uint32_t v32 = 32;
+    uint8_t* q = im.sec[2];
+    memcpy(q, &v32, 4); q += 4; memcpy(q, Qp, 32); q += 32;
+    memcpy(q, &v32, 4); q += 4; memcpy(q, Rp, 32); q += 32;
+    uint32_t dom = (uint32_t)N;
+    memcpy(q, &n, 4); memcpy(q + 4, &p, 4); memcpy(q + 8, &dom, 4); q += 12;
+    im.hdr_points = q;
+  }
   {
     uint32_t nc32 = (uint32_t)ncoef;
-    memcpy(s4.data(), &nc32, 4);
-    uint8_t* q = s4.data() + 4;
+    memcpy(im.sec[4], &nc32, 4);
+    uint8_t* q = im.sec[4] + 4;
     auto rec = [&](uint32_t mm, uint32_t cc, uint32_t ss, const FrM& cf) {
       memcpy(q, &mm, 4); memcpy(q + 4, &cc, 4); memcpy(q + 8, &ss, 4);
       const Fr raw = fp_to_mont(cf);  // Montgomery(coef) * R = coef * R^2, stored as a plain integer
@@ -409,22 +424,45 @@ static int setup_core(const Circuit& c, uint64_t seed, int threads, uint8_t** zk
       q += 44;
     };
     for (uint32_t r = 0; r < m; r++) {
-      for (uint32_t k = c.rowA[r]; k < c.rowA[r + 1]; k++) {
-        rec(0, r, c.tA[k].s, c.tA[k].cf);
-        u[c.tA[k].s] = fp_add(u[c.tA[k].s], fp_mul(c.tA[k].cf, Lg[r]));
-      }
-      for (uint32_t k = c.rowB[r]; k < c.rowB[r + 1]; k++) {
-        rec(1, r, c.tB[k].s, c.tB[k].cf);
-        v[c.tB[k].s] = fp_add(v[c.tB[k].s], fp_mul(c.tB[k].cf, Lg[r]));
-      }
-      for (uint32_t k = c.rowC[r]; k < c.rowC[r + 1]; k++)
-        t[c.tC[k].s] = fp_add(t[c.tC[k].s], fp_mul(c.tC[k].cf, Lg[r]));
+      for (uint32_t k = c.rowA[r]; k < c.rowA[r + 1]; k++) rec(0, r, c.tA[k].s, c.tA[k].cf);
+      for (uint32_t k = c.rowB[r]; k < c.rowB[r + 1]; k++) rec(1, r, c.tB[k].s, c.tB[k].cf);
     }
-    for (uint32_t i = 0; i <= p; i++) {
-      rec(0, m + i, i, fr_one());
-      u[i] = fp_add(u[i], Lg[m + i]);
-    }
+    for (uint32_t i = 0; i <= p; i++) rec(0, m + i, i, fr_one());
   }
+  memset(im.sec[10], 0, sizes[10]);
+  return G16_OK;
+}
+
+static int g16_domain_log(const Circuit& c) {   // smallest L with 2^L >= m + p + 1
+  int L = 0;
+  while (((uint64_t)1 << L) < (uint64_t)c.m + c.p + 1) L++;
+  return L;
+}
+
+// Trapdoor Groth16 setup of an arbitrary R1CS held in `c` (rows of (signal, Montgomery coefficient)
+// terms): snarkjs zkey layout out, plus the verification-key points.  td = (tau, alpha, beta, gamma, delta), Montgomery.
+static int setup_core_td(const Circuit& c, const FrM td[5], int threads, uint8_t** zkey, size_t* zkey_len,
+                         uint8_t** vkey, size_t* vkey_len) {
+  const uint32_t n = c.n, p = c.p, m = c.m;
+  if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
+  if (threads <= 0) threads = 1;
+  const int L = g16_domain_log(c);
+  if (L > 27) { set_error("setup: circuit too large"); return G16_E_ARG; }
+  const size_t N = (size_t)1 << L;
+
+  const FrM tau = td[0], alpha = td[1], beta = td[2], gamma = td[3], delta = td[4];
+  std::vector<FrM> Lg;
+  lagrange_at(L, tau, 0, 1, N, Lg);
+  std::vector<FrM> u(n, fp_zero<FrParams>()), v(n, fp_zero<FrParams>()), t(n, fp_zero<FrParams>());
+  for (uint32_t r = 0; r < m; r++) {
+    for (uint32_t k = c.rowA[r]; k < c.rowA[r + 1]; k++)
+      u[c.tA[k].s] = fp_add(u[c.tA[k].s], fp_mul(c.tA[k].cf, Lg[r]));
+    for (uint32_t k = c.rowB[r]; k < c.rowB[r + 1]; k++)
+      v[c.tB[k].s] = fp_add(v[c.tB[k].s], fp_mul(c.tB[k].cf, Lg[r]));
+    for (uint32_t k = c.rowC[r]; k < c.rowC[r + 1]; k++)
+      t[c.tC[k].s] = fp_add(t[c.tC[k].s], fp_mul(c.tC[k].cf, Lg[r]));
+  }
+  for (uint32_t i = 0; i <= p; i++) u[i] = fp_add(u[i], Lg[m + i]);   // public-input binding rows
   const FrM ginv = fp_inv(gamma), dinv = fp_inv(delta);
   std::vector<FrM> kic(p + 1), kc(n - p - 1), hs;
   for (uint32_t i = 0; i < n; i++) {
@@ -460,27 +498,11 @@ static int setup_core(const Circuit& c, uint64_t seed, int threads, uint8_t** zk
     if (r && !mul_rc) mul_rc = r;
   };
 
-  const size_t nC = (size_t)n - p - 1;
-  const size_t hdr2 = 4 + 32 + 4 + 32 + 12 + 64 + 64 + 128 + 128 + 64 + 128;
-  const size_t sizes[11] = {0, 4, hdr2, (size_t)(p + 1) * 64, s4.size(), (size_t)n * 64, (size_t)n * 64,
-                            (size_t)n * 128, nC * 64, N * 64, 64 + 4};
-  size_t total = 12;
-  for (int i = 1; i <= 10; i++) total += 12 + sizes[i];
-  Buf z;
-  if (!z.reserve(total)) { set_error("synth: out of memory"); return G16_E_STATE; }
-  z.put("zkey", 4); z.u32(1); z.u32(10);
-  auto sec = [&](uint32_t id) { z.u32(id); z.u64(sizes[id]); return z.skip(sizes[id]); };
-  uint8_t* p1 = sec(1);
-  { uint32_t one = 1; memcpy(p1, &one, 4); }
-  uint8_t* p2 = sec(2);
+  G16ZkeyImage im;
+  int rc = g16_zkey_layout(c, L, im);
+  if (rc) return rc;
   {
-    static const uint32_t Qp[8] = G16_FQ_P, Rp[8] = G16_FR_P;
-    uint32_t v32 = 32;
-    uint8_t* q = p2;
-    memcpy(q, &v32, 4); q += 4; memcpy(q, Qp, 32); q += 32;
-    memcpy(q, &v32, 4); q += 4; memcpy(q, Rp, 32); q += 32;
-    uint32_t dom = (uint32_t)N;
-    memcpy(q, &n, 4); memcpy(q + 4, &p, 4); memcpy(q + 8, &dom, 4); q += 12;
+    uint8_t* q = im.hdr_points;
     const FrM hk[3] = {alpha, beta, delta};
     uint8_t g1pts[3 * 64], g2pts[3 * 128];
     fixed_mul_many(fb1, hk, 3, g1pts, 1);
@@ -493,39 +515,41 @@ static int setup_core(const Circuit& c, uint64_t seed, int threads, uint8_t** zk
     memcpy(q, g1pts + 128, 64); q += 64;      // delta1
     memcpy(q, g2pts + 256, 128);              // delta2
   }
-  uint8_t* p3 = sec(3);
-  mul1(kic.data(), kic.size(), p3);
-  uint8_t* p4 = sec(4);
-  memcpy(p4, s4.data(), s4.size());
-  uint8_t* p5 = sec(5);
-  mul1(u.data(), n, p5);
-  uint8_t* p6 = sec(6);
-  mul1(v.data(), n, p6);
-  uint8_t* p7 = sec(7);
-  mul2(v.data(), n, p7);
-  uint8_t* p8 = sec(8);
-  mul1(kc.data(), kc.size(), p8);
-  uint8_t* p9 = sec(9);
-  mul1(hs.data(), hs.size(), p9);
-  uint8_t* p10 = sec(10);
-  memset(p10, 0, sizes[10]);
-  if (mul_rc) { free(z.p); return mul_rc; }
-  *zkey = z.p;
-  *zkey_len = z.len;
+  mul1(kic.data(), kic.size(), im.sec[3]);
+  mul1(u.data(), n, im.sec[5]);
+  mul1(v.data(), n, im.sec[6]);
+  mul2(v.data(), n, im.sec[7]);
+  mul1(kc.data(), kc.size(), im.sec[8]);
+  mul1(hs.data(), hs.size(), im.sec[9]);
+  if (mul_rc) { free(im.z.p); return mul_rc; }
+  *zkey = im.z.p;
+  *zkey_len = im.z.len;
   if (vkey && vkey_len) {
     // alpha1 | beta2 | gamma2 | delta2 | IC[0..p]   (affine Montgomery LE)
     Buf b;
     b.reserve(64 + 3 * 128 + (size_t)(p + 1) * 64);
-    const uint8_t* h = p2 + 84;
+    const uint8_t* h = im.hdr_points;
     b.put(h, 64);              // alpha1
     b.put(h + 128, 128);       // beta2
     b.put(h + 256, 128);       // gamma2
     b.put(h + 448, 128);       // delta2
-    b.put(p3, (size_t)(p + 1) * 64);
+    b.put(im.sec[3], (size_t)(p + 1) * 64);
     *vkey = b.p;
     *vkey_len = b.len;
   }
   return G16_OK;
+}
+
+// the same with the trapdoor drawn from stream seed+1: tau, alpha, beta, gamma, delta, all non-zero
+static int setup_core(const Circuit& c, uint64_t seed, int threads, uint8_t** zkey, size_t* zkey_len,
+                      uint8_t** vkey, size_t* vkey_len) {
+  Xo trng(seed + 1);
+  FrM td[5];
+  for (int k = 0; k < 5;) {
+    const FrM v = trng.rand_fr();
+    if (!fp_is_zero(v)) td[k++] = v;
+  }
+  return setup_core_td(c, td, threads, zkey, zkey_len, vkey, vkey_len);
 }
 
 extern "C" int g16_synth_setup(uint32_t n, uint32_t p, uint32_t m, uint64_t seed, int threads, uint8_t** zkey,
@@ -1515,25 +1539,43 @@ extern "C" int g16_plonk_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, const 
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
+namespace {
+struct MappedFile {
+  void* p = MAP_FAILED;
+  size_t len = 0;
+  int open_ro(const char* path) {
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) { set_error(std::string(path) + ": cannot open"); return G16_E_ARG; }
+    struct stat sb;
+    if (fstat(fd, &sb) != 0 || sb.st_size <= 0) { close(fd); set_error(std::string(path) + ": Invalid File format"); return G16_E_FORMAT; }
+    len = (size_t)sb.st_size;
+    p = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (p == MAP_FAILED) { set_error(std::string(path) + ": cannot map"); return G16_E_STATE; }
+    return G16_OK;
+  }
+  ~MappedFile() { if (p != MAP_FAILED) munmap(p, len); }
+};
+// writes z[0, zl) to path in chunks of 256 MB and frees z
+int write_key_file(const char* path, uint8_t* z, size_t zl) {
+  FILE* f = fopen(path, "wb");
+  if (!f) { free(z); set_error(std::string(path) + ": cannot create"); return G16_E_ARG; }
+  size_t off = 0;
+  while (off < zl) {
+    const size_t chunk = zl - off < ((size_t)1 << 28) ? zl - off : ((size_t)1 << 28);
+    if (fwrite(z + off, 1, chunk, f) != chunk) { fclose(f); free(z); set_error(std::string(path) + ": write failed"); return G16_E_STATE; }
+    off += chunk;
+  }
+  free(z);
+  if (fclose(f) != 0) { set_error(std::string(path) + ": write failed"); return G16_E_STATE; }
+  return G16_OK;
+}
+}  // namespace
+
 extern "C" int g16_plonk_setup_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device,
                                      int with_lagrange) {
   if (!r1cs_path || !ptau_path || !zkey_path) { set_error("NULL argument"); return G16_E_ARG; }
-  struct Map {
-    void* p = MAP_FAILED;
-    size_t len = 0;
-    int open_ro(const char* path) {
-      const int fd = open(path, O_RDONLY);
-      if (fd < 0) { set_error(std::string(path) + ": cannot open"); return G16_E_ARG; }
-      struct stat sb;
-      if (fstat(fd, &sb) != 0 || sb.st_size <= 0) { close(fd); set_error(std::string(path) + ": Invalid File format"); return G16_E_FORMAT; }
-      len = (size_t)sb.st_size;
-      p = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
-      close(fd);
-      if (p == MAP_FAILED) { set_error(std::string(path) + ": cannot map"); return G16_E_STATE; }
-      return G16_OK;
-    }
-    ~Map() { if (p != MAP_FAILED) munmap(p, len); }
-  } r1cs, ptau;
+  MappedFile r1cs, ptau;
   int rc = r1cs.open_ro(r1cs_path);
   if (!rc) rc = ptau.open_ro(ptau_path);
   if (rc) return rc;
@@ -1541,21 +1583,343 @@ extern "C" int g16_plonk_setup_files(const char* r1cs_path, const char* ptau_pat
   size_t zl = 0;
   rc = g16_plonk_setup_ptau((const uint8_t*)r1cs.p, r1cs.len, (const uint8_t*)ptau.p, ptau.len, device, with_lagrange, &z, &zl);
   if (rc) return rc;
-  FILE* f = fopen(zkey_path, "wb");
-  if (!f) { free(z); set_error(std::string(zkey_path) + ": cannot create"); return G16_E_ARG; }
-  size_t off = 0;
-  while (off < zl) {
-    const size_t chunk = zl - off < ((size_t)1 << 28) ? zl - off : ((size_t)1 << 28);
-    if (fwrite(z + off, 1, chunk, f) != chunk) { fclose(f); free(z); set_error(std::string(zkey_path) + ": write failed"); return G16_E_STATE; }
-    off += chunk;
-  }
-  free(z);
-  if (fclose(f) != 0) { set_error(std::string(zkey_path) + ": write failed"); return G16_E_STATE; }
-  return G16_OK;
+  return write_key_file(zkey_path, z, zl);
 }
 
 extern "C" int g16_setup_device(int device) {
   if (device < -1) { set_error("setup: bad device ordinal"); return G16_E_ARG; }
   g_setup_device.store(device);
   return G16_OK;
+}
+
+// ------------------------------------------------------------------ Groth16 setup from a prepared .ptau
+// `snarkjs groth16 setup c.r1cs pot.ptau c_0000.zkey` ([EXT] snarkjs 0.4.12 zkey_new.js).  The prepared ceremony file
+// (`powersoftau prepare phase2`) carries the Lagrange-basis sections 12 = [L_i(tau)]G1, 13 = [L_i(tau)]G2,
+// 14 = [alpha L_i(tau)]G1, 15 = [beta L_i(tau)]G1, each stored as blocks k = 0, 1, ... of 2^k points (block k starts at
+// point 2^k - 1).  The block count is derived from each section's length.  With N = 2^L the domain of setup_core:
+//   A_j = sum a_cj [L_c] (+ [L_{m+j}] for j <= p),  B1_j = sum b_cj [L_c]G1,  B2_j = sum b_cj [L_c]G2,
+//   K_j = sum (a_cj [beta L_c] + b_cj [alpha L_c] + c_cj [L_c]) (+ [beta L_{m+j}] for j <= p): IC for j <= p, C above,
+//   H_i = point 2i + 1 of block L + 1 of section 12 ([L^(2N)_{2i+1}(tau)]G1),
+// gamma = delta = 1 (a fresh _0000 key), section 10 as setup_core writes it.  The sums run on the device
+// (setup_ptau.hip); the key for a ptau of a known (tau, alpha, beta) is byte for byte setup_core's with
+// (tau, alpha, beta, 1, 1).
+namespace {
+
+struct PtauView {
+  uint32_t power = 0;
+  const uint8_t* sec[16] = {};
+  uint64_t len[16] = {};
+  int blocks[16] = {};   // sections 12-15: whole blocks present
+};
+
+int ptau_bad(const char* why) { set_error(std::string("ptau: ") + why); return G16_E_FORMAT; }
+
+// binfile header, section table, bn128 section 1 (the PLONK reader's checks) and the prepared-section block layout
+int ptau_open_prepared(const uint8_t* ptau, size_t ptau_len, PtauView& v) {
+  if (!ptau || ptau_len < 12 || memcmp(ptau, "ptau", 4) != 0) return ptau_bad("Invalid File format");
+  uint32_t version, nsec;
+  memcpy(&version, ptau + 4, 4);
+  memcpy(&nsec, ptau + 8, 4);
+  if (version > 1) { set_error("Version not supported"); return G16_E_FORMAT; }
+  size_t pos = 12;
+  for (uint32_t i = 0; i < nsec; i++) {
+    if (pos + 12 > ptau_len) return ptau_bad("Invalid File format");
+    uint32_t id;
+    uint64_t sz;
+    memcpy(&id, ptau + pos, 4);
+    memcpy(&sz, ptau + pos + 4, 8);
+    pos += 12;
+    if (sz > ptau_len - pos) return ptau_bad("Invalid File format");
+    if (id < 16 && !v.sec[id]) { v.sec[id] = ptau + pos; v.len[id] = sz; }
+    pos += sz;
+  }
+  static const uint32_t Qp[8] = G16_FQ_P;
+  uint32_t n8 = 0;
+  if (v.sec[1] && v.len[1] >= 4) memcpy(&n8, v.sec[1], 4);
+  if (!v.sec[1] || v.len[1] < 4 + 32 + 8 || n8 != 32 || memcmp(v.sec[1] + 4, Qp, 32) != 0)
+    return ptau_bad("Invalid File format (bn128 powers of tau expected)");
+  memcpy(&v.power, v.sec[1] + 36, 4);
+  if (v.power > 28) return ptau_bad("Invalid File format");
+  if (!v.sec[12]) { set_error("Powers of tau is not prepared."); return G16_E_FORMAT; }
+  if (!v.sec[4] || v.len[4] < 64 || !v.sec[5] || v.len[5] < 64 || !v.sec[6] || v.len[6] < 128)
+    return ptau_bad("Invalid File format");
+  for (int id = 12; id <= 15; id++) {
+    if (!v.sec[id]) return ptau_bad("Invalid File format");
+    const uint64_t psz = id == 13 ? 128 : 64;
+    if (v.len[id] % psz) return ptau_bad("Invalid File format");
+    const uint64_t pts = v.len[id] / psz;   // blocks 0 .. K-1 hold 2^K - 1 points
+    int K = 0;
+    while (K < 40 && (((uint64_t)1 << K) - 1) < pts) K++;
+    const int max_blocks = (int)v.power + (id == 12 ? 2 : 1);
+    if ((((uint64_t)1 << K) - 1) != pts || K > max_blocks) return ptau_bad("Invalid File format");
+    v.blocks[id] = K;
+  }
+  return G16_OK;
+}
+
+G1Affine g1_generator() {
+  G1Affine g;
+  g.x = fp_one<FqParams>();
+  g.y = fp_add(g.x, g.x);
+  return g;
+}
+G2Affine g2_generator() {
+  G2Affine g;
+  g.x.a = Fq{G16_G2X0}; g.x.b = Fq{G16_G2X1}; g.y.a = Fq{G16_G2Y0}; g.y.b = Fq{G16_G2Y1};
+  return g;
+}
+
+}  // namespace
+
+extern "C" int g16_groth16_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len,
+                                      int device, uint8_t** zkey, size_t* zkey_len) {
+  if (!r1cs || !ptau || !zkey || !zkey_len) { set_error("NULL argument"); return G16_E_ARG; }
+  try {
+    // every input is checked before the device is touched
+    Circuit c;
+    int rc = read_r1cs(r1cs, r1cs_len, c);
+    if (rc) return rc;
+    PtauView pv;
+    if ((rc = ptau_open_prepared(ptau, ptau_len, pv))) return rc;
+    const uint32_t n = c.n, p = c.p, m = c.m;
+    const int L = g16_domain_log(c);
+    if (L > 27) { set_error("r1cs: circuit too large"); return G16_E_ARG; }
+    if ((uint32_t)L > pv.power || pv.blocks[12] < L + 2 || pv.blocks[13] < L + 1 || pv.blocks[14] < L + 1 ||
+        pv.blocks[15] < L + 1) {
+      set_error("circuit too big for this power of tau ceremony. " + std::to_string((uint64_t)m + p + 1) + " > 2**" +
+                std::to_string(pv.power));
+      return G16_E_FORMAT;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+      set_error("groth16 setup: no HIP device (there is no CPU path)");
+      return G16_E_NOGPU;
+    }
+    if (device < 0 || device >= ndev) { set_error("groth16 setup: bad device ordinal"); return G16_E_ARG; }
+    const size_t N = (size_t)1 << L;
+    const size_t blkL = N - 1, blkL1 = 2 * N - 1;   // first point of block L / L + 1
+    const uint8_t* lag1 = pv.sec[12] + blkL * 64;
+    const uint8_t* lag2 = pv.sec[13] + blkL * 128;
+    const uint8_t* alag = pv.sec[14] + blkL * 64;
+    const uint8_t* blag = pv.sec[15] + blkL * 64;
+    const uint8_t* hblk = pv.sec[12] + blkL1 * 64;
+
+    // the term lists, CSC by output (counting sort): G1 outputs A_j = j, B1_j = n + j, K_j = 2n + j over the bases
+    // [L_c] | [alpha L_c] | [beta L_c] (3N points); G2 outputs B2_j over [L_c]G2
+    SparseTerms t1, t2;
+    const uint64_t no1 = 3 * (uint64_t)n;
+    t1.start.assign(no1 + 1, 0);
+    t2.start.assign((uint64_t)n + 1, 0);
+    for (const Term& x : c.tA) { t1.start[x.s + 1]++; t1.start[2 * (uint64_t)n + x.s + 1]++; }
+    for (const Term& x : c.tB) { t1.start[(uint64_t)n + x.s + 1]++; t1.start[2 * (uint64_t)n + x.s + 1]++; t2.start[x.s + 1]++; }
+    for (const Term& x : c.tC) t1.start[2 * (uint64_t)n + x.s + 1]++;
+    for (uint32_t i = 0; i <= p; i++) { t1.start[i + 1]++; t1.start[2 * (uint64_t)n + i + 1]++; }
+    for (uint64_t o = 0; o < no1; o++) t1.start[o + 1] += t1.start[o];
+    for (uint64_t o = 0; o < n; o++) t2.start[o + 1] += t2.start[o];
+    t1.base.resize(t1.start[no1]);
+    t1.coef.resize(t1.start[no1]);
+    t2.base.resize(t2.start[n]);
+    t2.coef.resize(t2.start[n]);
+    std::vector<uint64_t> f1(t1.start.begin(), t1.start.end() - 1), f2(t2.start.begin(), t2.start.end() - 1);
+    auto put1 = [&](uint64_t o, uint32_t b, const Fr& cf) { const uint64_t k = f1[o]++; t1.base[k] = b; t1.coef[k] = cf; };
+    auto put2 = [&](uint64_t o, uint32_t b, const Fr& cf) { const uint64_t k = f2[o]++; t2.base[k] = b; t2.coef[k] = cf; };
+    const uint32_t NN = (uint32_t)N;
+    for (uint32_t r = 0; r < m; r++) {
+      for (uint32_t k = c.rowA[r]; k < c.rowA[r + 1]; k++) {
+        const Fr cf = fp_from_mont(c.tA[k].cf);
+        put1(c.tA[k].s, r, cf);
+        put1(2 * (uint64_t)n + c.tA[k].s, 2 * NN + r, cf);
+      }
+      for (uint32_t k = c.rowB[r]; k < c.rowB[r + 1]; k++) {
+        const Fr cf = fp_from_mont(c.tB[k].cf);
+        put1((uint64_t)n + c.tB[k].s, r, cf);
+        put1(2 * (uint64_t)n + c.tB[k].s, NN + r, cf);
+        put2(c.tB[k].s, r, cf);
+      }
+      for (uint32_t k = c.rowC[r]; k < c.rowC[r + 1]; k++)
+        put1(2 * (uint64_t)n + c.tC[k].s, r, fp_from_mont(c.tC[k].cf));
+    }
+    Fr one = fp_zero<FrParams>();
+    one.v[0] = 1;
+    for (uint32_t i = 0; i <= p; i++) {   // public-input binding rows
+      put1(i, m + i, one);
+      put1(2 * (uint64_t)n + i, 2 * NN + m + i, one);
+    }
+
+    G16ZkeyImage im;
+    if ((rc = g16_zkey_layout(c, L, im))) return rc;
+    {
+      uint8_t* q = im.hdr_points;
+      const G1Affine g1 = g1_generator();
+      const G2Affine g2 = g2_generator();
+      memcpy(q, pv.sec[4], 64);          // alpha1 = [alpha tau^0]G1
+      memcpy(q + 64, pv.sec[5], 64);     // beta1
+      memcpy(q + 128, pv.sec[6], 128);   // beta2
+      memcpy(q + 256, &g2, 128);         // gamma2 = [1]G2
+      memcpy(q + 384, &g1, 64);          // delta1 = [1]G1
+      memcpy(q + 448, &g2, 128);         // delta2 = [1]G2
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    SparseStats s1, s2;
+    std::vector<uint8_t> o1((size_t)no1 * 64);
+    {
+      const uint8_t* seg[3] = {lag1, alag, blag};
+      const size_t segn[3] = {N, N, N};
+      rc = setup_sparse_g1(device, seg, segn, 3, t1, o1.data(), &s1);
+    }
+    if (!rc) {
+      const uint8_t* seg[1] = {lag2};
+      const size_t segn[1] = {N};
+      rc = setup_sparse_g2(device, seg, segn, 1, t2, im.sec[7], &s2);
+    }
+    if (rc) { free(im.z.p); return rc; }
+    const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    memcpy(im.sec[5], o1.data(), (size_t)n * 64);
+    memcpy(im.sec[6], o1.data() + (size_t)n * 64, (size_t)n * 64);
+    memcpy(im.sec[3], o1.data() + (size_t)2 * n * 64, (size_t)(p + 1) * 64);
+    memcpy(im.sec[8], o1.data() + ((size_t)2 * n + p + 1) * 64, ((size_t)n - p - 1) * 64);
+    for (size_t i = 0; i < N; i++) memcpy(im.sec[9] + i * 64, hblk + (2 * i + 1) * 64, 64);
+    if (getenv("G16_TRACE_HOST"))
+      fprintf(stderr,
+              "[g16 groth16 setup ptau] domain 2^%d, nnz A %zu B %zu C %zu; G1 terms: +-1 %llu short %llu full %llu zero %llu; "
+              "G2 terms: +-1 %llu short %llu full %llu zero %llu; kernels G1 %.3f ms G2 %.3f ms; device wall %.3f ms\n",
+              L, c.tA.size(), c.tB.size(), c.tC.size(), (unsigned long long)s1.pm1, (unsigned long long)s1.shorts,
+              (unsigned long long)s1.full, (unsigned long long)s1.zero, (unsigned long long)s2.pm1,
+              (unsigned long long)s2.shorts, (unsigned long long)s2.full, (unsigned long long)s2.zero, s1.kern_ms,
+              s2.kern_ms, wall_ms);
+    *zkey = im.z.p;
+    *zkey_len = im.z.len;
+    return G16_OK;
+  } catch (const std::bad_alloc&) {   // no C++ exception crosses the C ABI
+    set_error("groth16 setup: out of memory");
+    return G16_E_STATE;
+  }
+}
+
+extern "C" int g16_groth16_setup_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device) {
+  if (!r1cs_path || !ptau_path || !zkey_path) { set_error("NULL argument"); return G16_E_ARG; }
+  MappedFile r1cs, ptau;
+  int rc = r1cs.open_ro(r1cs_path);
+  if (!rc) rc = ptau.open_ro(ptau_path);
+  if (rc) return rc;
+  uint8_t* z = nullptr;
+  size_t zl = 0;
+  rc = g16_groth16_setup_ptau((const uint8_t*)r1cs.p, r1cs.len, (const uint8_t*)ptau.p, ptau.len, device, &z, &zl);
+  if (rc) return rc;
+  return write_key_file(zkey_path, z, zl);
+}
+
+// test-only: setup_core with the caller's trapdoor (standard-form LE scalars, each < r; gamma, delta non-zero)
+extern "C" int g16_r1cs_setup_trapdoor(const uint8_t* r1cs, size_t r1cs_len, const uint8_t td[5 * 32], int threads,
+                                       uint8_t** zkey, size_t* zkey_len, uint8_t** vkey, size_t* vkey_len) {
+  if (!r1cs || !td || !zkey || !zkey_len) { set_error("NULL argument"); return G16_E_ARG; }
+  static const uint32_t Rp[8] = G16_FR_P;
+  FrM tdm[5];
+  for (int k = 0; k < 5; k++) {
+    Fr x;
+    memcpy(x.v, td + 32 * k, 32);
+    bool lt = false;
+    for (int i = 7; i >= 0; i--)
+      if (x.v[i] != Rp[i]) { lt = x.v[i] < Rp[i]; break; }
+    if (!lt) { set_error("setup: trapdoor scalar not below r"); return G16_E_ARG; }
+    tdm[k] = fp_to_mont(x);
+  }
+  if (fp_is_zero(tdm[3]) || fp_is_zero(tdm[4])) { set_error("setup: gamma and delta must be non-zero"); return G16_E_ARG; }
+  try {
+    Circuit c;
+    int rc = read_r1cs(r1cs, r1cs_len, c);
+    if (rc) return rc;
+    if ((uint64_t)c.m + c.p + 1 > ((uint64_t)1 << 27)) { set_error("r1cs: circuit too large"); return G16_E_ARG; }
+    return setup_core_td(c, tdm, threads, zkey, zkey_len, vkey, vkey_len);
+  } catch (const std::bad_alloc&) {
+    set_error("setup: out of memory");
+    return G16_E_STATE;
+  }
+}
+
+// test-only: a .ptau v1 image for a known (tau, alpha, beta): sections 1-7 as snarkjs lays them out (2 = [tau^i]G1,
+// i < 2^(power+1) - 1; 3 = [tau^i]G2, 4 = [alpha tau^i]G1, 5 = [beta tau^i]G1, i < 2^power; 6 = [beta]G2; 7 = no
+// contributions) and, when prepared, 12-15 in the block layout (12 through block power + 1, 13-15 through block power)
+extern "C" int g16_ptau_synth(uint32_t power, const uint8_t tab[3 * 32], int prepared, int device, uint8_t** ptau,
+                              size_t* ptau_len) {
+  if (!tab || !ptau || !ptau_len) { set_error("NULL argument"); return G16_E_ARG; }
+  if (power > 24) { set_error("ptau synth: power above 24"); return G16_E_ARG; }
+  if (device < -1) { set_error("ptau synth: bad device ordinal"); return G16_E_ARG; }
+  FrM s[3];
+  for (int k = 0; k < 3; k++) {
+    Fr x;
+    memcpy(x.v, tab + 32 * k, 32);
+    s[k] = fp_to_mont(x);   // (reduces a value >= r)
+  }
+  const FrM tau = s[0], alpha = s[1], beta = s[2];
+  try {
+    const uint64_t n = (uint64_t)1 << power;
+    const int threads = (int)std::thread::hardware_concurrency() > 0 ? (int)std::thread::hardware_concurrency() : 1;
+    const uint64_t sizes[16] = {0, 44, (2 * n - 1) * 64, n * 128, n * 64, n * 64, 128, 4, 0, 0, 0, 0,
+                                (4 * n - 1) * 64, (2 * n - 1) * 128, (2 * n - 1) * 64, (2 * n - 1) * 64};
+    std::vector<int> ids = {1, 2, 3, 4, 5, 6, 7};
+    if (prepared) for (int id = 12; id <= 15; id++) ids.push_back(id);
+    size_t total = 12;
+    for (int id : ids) total += 12 + sizes[id];
+    Buf z;
+    if (!z.reserve(total)) { set_error("ptau synth: out of memory"); return G16_E_STATE; }
+    z.put("ptau", 4); z.u32(1); z.u32((uint32_t)ids.size());
+    uint8_t* sp[16] = {};
+    for (int id : ids) { z.u32((uint32_t)id); z.u64(sizes[id]); sp[id] = z.skip(sizes[id]); }
+    {
+      static const uint32_t Qp[8] = G16_FQ_P;
+      uint32_t v32 = 32;
+      memcpy(sp[1], &v32, 4); memcpy(sp[1] + 4, Qp, 32); memcpy(sp[1] + 36, &power, 4); memcpy(sp[1] + 40, &power, 4);
+      memset(sp[7], 0, 4);
+    }
+    FixedBase<FqOps> fb1;
+    FixedBase<Fq2Ops> fb2;
+    build_table(fb1, g1_generator(), 8, threads);
+    build_table(fb2, g2_generator(), 8, threads);
+    int rc = G16_OK;
+    auto mul1 = [&](const std::vector<FrM>& ks, uint8_t* out) {
+      if (rc) return;
+      if (device >= 0) rc = setup_fixed_mul_g1(device, fb1.tbl.data(), fb1.wb, fb1.nwin, ks.data(), ks.size(), out);
+      else fixed_mul_many(fb1, ks.data(), ks.size(), out, threads);
+    };
+    auto mul2 = [&](const std::vector<FrM>& ks, uint8_t* out) {
+      if (rc) return;
+      if (device >= 0) rc = setup_fixed_mul_g2(device, fb2.tbl.data(), fb2.wb, fb2.nwin, ks.data(), ks.size(), out);
+      else fixed_mul_many(fb2, ks.data(), ks.size(), out, threads);
+    };
+    auto scaled = [](const std::vector<FrM>& v, const FrM& k, size_t cnt) {
+      std::vector<FrM> o(cnt);
+      for (size_t i = 0; i < cnt; i++) o[i] = fp_mul(v[i], k);
+      return o;
+    };
+    {
+      std::vector<FrM> pw(2 * n - 1);
+      FrM x = fr_one();
+      for (auto& y : pw) { y = x; x = fp_mul(x, tau); }
+      mul1(pw, sp[2]);
+      mul2(std::vector<FrM>(pw.begin(), pw.begin() + n), sp[3]);
+      mul1(scaled(pw, alpha, n), sp[4]);
+      mul1(scaled(pw, beta, n), sp[5]);
+      mul2(std::vector<FrM>{beta}, sp[6]);
+    }
+    if (prepared) {
+      // block k of the Lagrange basis of the size-2^k domain: all blocks in one scalar vector per section
+      std::vector<FrM> lag(4 * n - 1), blk;
+      for (uint32_t k = 0; k <= power + 1; k++) {
+        lagrange_at((int)k, tau, 0, 1, (size_t)1 << k, blk);
+        std::copy(blk.begin(), blk.end(), lag.begin() + (((size_t)1 << k) - 1));
+      }
+      mul1(lag, sp[12]);
+      mul2(std::vector<FrM>(lag.begin(), lag.begin() + (2 * n - 1)), sp[13]);
+      mul1(scaled(lag, alpha, 2 * n - 1), sp[14]);
+      mul1(scaled(lag, beta, 2 * n - 1), sp[15]);
+    }
+    if (rc) { free(z.p); return rc; }
+    *ptau = z.p;
+    *ptau_len = z.len;
+    return G16_OK;
+  } catch (const std::bad_alloc&) {
+    set_error("ptau synth: out of memory");
+    return G16_E_STATE;
+  }
 }

@@ -2,6 +2,7 @@
 // CLI twin of `snarkjs groth16 prove <circuit.zkey> <witness.wtns> <proof.json> <public.json>`
 // (snarkjs cli.js groth16Prove [EXT]; the reference's Makefile scripts the sibling PLONK lines,
 // /root/reference/Makefile:30-33).  Writes JSON.stringify(x, null, 1) like snarkjs.
+// And of `snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>` (alias `zkey new`; prepared ptau only).
 // And of `snarkjs groth16 verify <verification_key.json> <public.json> <proof.json>` (groth16Verify [EXT]): prints
 // "[INFO]  snarkJS: OK!" and exits 0, or "[ERROR] snarkJS: Invalid proof" and exits 1.
 "use strict";
@@ -14,6 +15,14 @@ async function main(argv) {
     const { exportVerificationKey } = require("./index.js");
     const [zk, out = "verification_key.json"] = a.slice(3);
     fs.writeFileSync(out, JSON.stringify(exportVerificationKey(zk), null, 1), "utf-8");
+    return;
+  }
+  if ((a[0] === "groth16" && a[1] === "setup") || (a[0] === "zkey" && a[1] === "new")) {
+    // snarkjs groth16 setup <circuit.r1cs> <powersoftau.ptau> <circuit_0000.zkey>   (alias: zkey new)
+    const pos = a.slice(2).filter((x) => !x.startsWith("--"));
+    if (pos.length < 3) { console.error("usage: cli.js groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>"); process.exit(2); }
+    const { newZKey } = require("./index.js");
+    await newZKey(pos[0], pos[1], pos[2]);
     return;
   }
   if (a[0] === "plonk" && a[1] === "setup") {   // snarkjs plonk setup <circuit.r1cs> <powersoftau.ptau> <circuit.zkey>

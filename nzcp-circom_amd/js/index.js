@@ -270,6 +270,15 @@ const plonk = {
   },
 };
 
+// ------------------------------------------------------------------ groth16 setup (zkey new)
+// snarkjs: zKey.newZKey(r1csName, ptauName, zkeyName[, logger]) / CLI `groth16 setup` = `zkey new` -- file names (a
+// ceremony file exceeds a Buffer).  The ptau must be prepared (`powersoftau prepare phase2`).  The key is a fresh
+// _0000 key (gamma = delta = 1, no contribution): not safe to deploy before a phase-2 contribution.
+async function newZKey(r1csName, ptauName, zkeyName, opts = {}) {
+  if (opts && typeof opts.debug === "function") opts = {};
+  await native().groth16SetupFiles(String(r1csName), String(ptauName), String(zkeyName), opts.device | 0);
+}
+
 // ------------------------------------------------------------------ zkey export verificationkey (host-only: header reads)
 // snarkjs `zKey.exportVerificationKey(zkey)` / CLI `zkey export verificationkey <zkey> <vk.json>` -- the second line of
 // the reference's PLONK flow (/root/reference/Makefile:32).  Groth16 and PLONK keys; points leave Montgomery form here
@@ -351,4 +360,4 @@ const groth16 = {
   createProver,
 };
 
-module.exports = { groth16, plonk, zKey: { exportVerificationKey }, exportVerificationKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
+module.exports = { groth16, plonk, zKey: { exportVerificationKey, newZKey }, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
