@@ -352,6 +352,24 @@ int g16_groth16_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* 
                            uint8_t** zkey, size_t* zkey_len);
 /* the same from / to files: the inputs are mapped read-only and the key is written in chunks (ceremony files are GBs) */
 int g16_groth16_setup_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device);
+/* `snarkjs powersoftau prepare phase2 in.ptau out.ptau` (alias `pt2`): the .ptau v1 image (g16_free) that holds
+ * sections 1-7 of the input, byte for byte and in that order, then the sections 12-15 the setups above read, computed
+ * on `device` (there is no CPU path: G16_E_NOGPU).  Section 12 comes from section 2, 13 / 14 / 15 from 3 / 4 / 5: block
+ * k (2^k points from point 2^k - 1) is the inverse Fourier transform of size 2^k over group elements of the source's
+ * first 2^k points, point j = (1 / 2^k) sum_i w_k^(-ij) P_i -- for a ceremony of trapdoor tau the Lagrange basis
+ * [L_j(tau)] of the size-2^k domain.  Sections 13-15 run through block `power`; section 12 through block power + 1,
+ * whose missing last input (section 2 holds 2^(power+1) - 1 points) is the point at infinity, as in snarkjs: that one
+ * block is [L_j(tau) - w^j tau^(M-1) / M]G1, M = 2^(power+1), which Groth16's H basis (its odd points) cannot tell from
+ * the Lagrange basis.  Sections 12-15 of an already prepared input are ignored and recomputed; other section ids are
+ * not carried over; a missing section 7 is written as "no contributions".  Points keep the file's format (affine,
+ * little-endian Montgomery, infinity = zero bytes); infinity inputs and outputs are handled.
+ * Checked before the device is touched: "ptau: Invalid File format..." as above for the header, the section table and
+ * the curve; sections 2-6 present with exactly the sizes the header's power implies, else "ptau: Invalid File format";
+ * a power above 24: G16_E_ARG, the text names the limit. */
+int g16_ptau_prepare(const uint8_t* ptau, size_t ptau_len, int device, uint8_t** out, size_t* out_len);
+/* the same from / to files: the input is mapped read-only and the output written in chunks (a power-22 output is
+ * several GB) */
+int g16_ptau_prepare_files(const char* in_path, const char* out_path, int device);
 /* TEST-ONLY.  g16_r1cs_setup with the caller's trapdoor td = tau | alpha | beta | gamma | delta (standard-form 32-byte
  * LE scalars below r; gamma, delta non-zero) instead of the seed stream; where its multiplications run follows
  * g16_setup_device.  A key anyone holding td can forge proofs for. */

@@ -68,7 +68,8 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_verifier_create", "g16_verify_batch", "g16_verifier_timings", "g16_verifier_destroy", "g16_pairing_op",
            "g16_plonk_create", "g16_plonk_prove", "g16_plonk_get_info", "g16_plonk_destroy", "g16_plonk_setup", "g16_plonk_timings", "g16_plonk_setup_ptau", "g16_plonk_setup_files",
            "g16_plonk_verifier_create", "g16_plonk_verify_batch", "g16_plonk_verifier_destroy",
-           "g16_groth16_setup_ptau", "g16_groth16_setup_files", "g16_r1cs_setup_trapdoor", "g16_ptau_synth"]
+           "g16_groth16_setup_ptau", "g16_groth16_setup_files", "g16_r1cs_setup_trapdoor", "g16_ptau_synth",
+           "g16_ptau_prepare", "g16_ptau_prepare_files"]
 
 
 def load():
@@ -145,6 +146,8 @@ def load():
     lib.g16_r1cs_setup_trapdoor.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp),
                                             C.POINTER(sz)]
     lib.g16_ptau_synth.argtypes = [C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(sz)]
+    lib.g16_ptau_prepare.argtypes = [C.c_char_p, sz, C.c_int, C.POINTER(vp), C.POINTER(sz)]
+    lib.g16_ptau_prepare_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
     lib.g16_r1cs_setup.argtypes = [C.c_char_p, sz, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
     lib.g16_sha256_chain_setup.argtypes = [C.c_uint32, C.c_char_p, C.c_uint64, C.c_int] + [C.c_void_p] * 8
     lib.g16_sha256_message_setup.argtypes = [C.c_char_p, C.c_uint32, C.c_uint64, C.c_int] + [C.c_void_p] * 8
@@ -717,6 +720,14 @@ def groth16_setup_ptau(r1cs, ptau, device=0):
     (gamma = delta = 1, no contribution yet)."""
     z, zl = C.c_void_p(), C.c_size_t()
     _check(load().g16_groth16_setup_ptau(r1cs, len(r1cs), ptau, len(ptau), device, C.byref(z), C.byref(zl)))
+    return _take(z, zl)
+
+
+def ptau_prepare(ptau, device=0):
+    """`snarkjs powersoftau prepare phase2 in.ptau out.ptau`: .ptau bytes (sections 1-7) -> the prepared .ptau bytes
+    (sections 1-7, then 12-15 computed on the device)."""
+    z, zl = C.c_void_p(), C.c_size_t()
+    _check(load().g16_ptau_prepare(ptau, len(ptau), device, C.byref(z), C.byref(zl)))
     return _take(z, zl)
 
 

@@ -75,6 +75,18 @@ int setup_sparse_g1(int device, const uint8_t* const* seg, const size_t* seg_n, 
 int setup_sparse_g2(int device, const uint8_t* const* seg, const size_t* seg_n, int nseg, const SparseTerms& t,
                     uint8_t* out, SparseStats* st);
 
+// ---------------------------------------------------------------- powersoftau prepare phase2 (ptau_prepare.hip)
+// One section: out = blocks k = 0 .. kmax in the file's layout (block k = 2^k affine points from point 2^k - 1), block k
+// the inverse Fourier transform of size 2^k of the first 2^k source points, scaled by 1 / 2^k.  src = nsrc <= 2^kmax
+// affine Montgomery points (host); a source index from nsrc on reads as infinity.  out = 2^(kmax+1) - 1 points (host).
+// No CPU path (G16_E_NOGPU).
+struct PtauPrepareStats {
+  float kern_ms = 0.f;          // device time of the kernels
+  uint64_t muls = 0, adds = 0;  // scalar multiplications of a point; point additions (two per butterfly)
+};
+int ptau_prepare_g1(int device, const uint8_t* src, uint64_t nsrc, int kmax, uint8_t* out, PtauPrepareStats* st);
+int ptau_prepare_g2(int device, const uint8_t* src, uint64_t nsrc, int kmax, uint8_t* out, PtauPrepareStats* st);
+
 // ---------------------------------------------------------------- NTT (ntt.hip)
 struct NttPass { int lo_bits, S, tb; };
 struct NttTables {

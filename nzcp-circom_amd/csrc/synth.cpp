@@ -1614,8 +1614,9 @@ struct PtauView {
 
 int ptau_bad(const char* why) { set_error(std::string("ptau: ") + why); return G16_E_FORMAT; }
 
-// binfile header, section table, bn128 section 1 (the PLONK reader's checks) and the prepared-section block layout
-int ptau_open_prepared(const uint8_t* ptau, size_t ptau_len, PtauView& v) {
+// binfile header, section table and bn128 section 1 (the PLONK reader's checks): shared by the prepared reader below
+// and by g16_ptau_prepare
+int ptau_open(const uint8_t* ptau, size_t ptau_len, PtauView& v) {
   if (!ptau || ptau_len < 12 || memcmp(ptau, "ptau", 4) != 0) return ptau_bad("Invalid File format");
   uint32_t version, nsec;
   memcpy(&version, ptau + 4, 4);
@@ -1640,6 +1641,12 @@ int ptau_open_prepared(const uint8_t* ptau, size_t ptau_len, PtauView& v) {
     return ptau_bad("Invalid File format (bn128 powers of tau expected)");
   memcpy(&v.power, v.sec[1] + 36, 4);
   if (v.power > 28) return ptau_bad("Invalid File format");
+  return G16_OK;
+}
+
+// ptau_open and the prepared-section block layout
+int ptau_open_prepared(const uint8_t* ptau, size_t ptau_len, PtauView& v) {
+  if (const int rc = ptau_open(ptau, ptau_len, v)) return rc;
   if (!v.sec[12]) { set_error("Powers of tau is not prepared."); return G16_E_FORMAT; }
   if (!v.sec[4] || v.len[4] < 64 || !v.sec[5] || v.len[5] < 64 || !v.sec[6] || v.len[6] < 128)
     return ptau_bad("Invalid File format");
@@ -1807,6 +1814,103 @@ extern "C" int g16_groth16_setup_files(const char* r1cs_path, const char* ptau_p
   rc = g16_groth16_setup_ptau((const uint8_t*)r1cs.p, r1cs.len, (const uint8_t*)ptau.p, ptau.len, device, &z, &zl);
   if (rc) return rc;
   return write_key_file(zkey_path, z, zl);
+}
+
+// ------------------------------------------------------------------ powersoftau prepare phase2
+// `snarkjs powersoftau prepare phase2 in.ptau out.ptau` ([EXT] snarkjs 0.4.12 powersoftau_preparephase2.js): the image
+// with sections 1-7 of the input, byte for byte and in that order, then 12, 13, 14, 15 computed from sections 2, 3,
+// 4, 5: block k of a section is the inverse Fourier transform of size 2^k of its source's first 2^k points (the layout
+// above; ptau_prepare.hip).  Section 12 runs through block power + 1, whose last input -- section 2 holds
+// 2^(power+1) - 1 points -- is the point at infinity, as in snarkjs: that block is [L_j(tau) - w^j tau^(M-1) / M]G1
+// (M = 2^(power+1)), not the Lagrange basis itself; Groth16 reads its odd points as the H basis, against a polynomial
+// of degree <= M - 2, where the extra term cancels.  Sections 12-15 of an input that is already prepared are ignored
+// and recomputed, other section ids are dropped, and a missing section 7 is written as "no contributions" (four zero
+// bytes).  Sections 2-6 must have exactly the sizes the header's power implies.  Powers up to kPreparePowerMax.
+namespace {
+constexpr uint32_t kPreparePowerMax = 24;   // (what g16_ptau_synth can produce; the device arrays index with 32 bits)
+
+int ptau_prepare_core(const uint8_t* ptau, size_t ptau_len, int device, uint8_t** out, size_t* out_len) {
+  const auto t0 = std::chrono::steady_clock::now();
+  PtauView pv;
+  if (const int rc = ptau_open(ptau, ptau_len, pv)) return rc;
+  if (pv.power > kPreparePowerMax) {
+    set_error("ptau prepare: power " + std::to_string(pv.power) + " is above the supported limit of " +
+              std::to_string(kPreparePowerMax));
+    return G16_E_ARG;
+  }
+  const uint64_t n = (uint64_t)1 << pv.power;
+  const uint64_t want[7] = {0, 0, (2 * n - 1) * 64, n * 128, n * 64, n * 64, 128};
+  for (int id = 2; id <= 6; id++)
+    if (!pv.sec[id] || pv.len[id] != want[id]) return ptau_bad("Invalid File format");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    set_error("ptau prepare: no HIP device (there is no CPU path)");
+    return G16_E_NOGPU;
+  }
+  if (device < 0 || device >= ndev) { set_error("ptau prepare: bad device ordinal"); return G16_E_ARG; }
+
+  static const uint8_t no_contributions[4] = {0, 0, 0, 0};
+  const uint8_t* in[8] = {};
+  uint64_t sizes[16] = {};
+  for (int id = 1; id <= 7; id++) { in[id] = pv.sec[id]; sizes[id] = pv.len[id]; }
+  if (!in[7]) { in[7] = no_contributions; sizes[7] = 4; }
+  sizes[12] = (4 * n - 1) * 64;
+  sizes[13] = (2 * n - 1) * 128;
+  sizes[14] = sizes[15] = (2 * n - 1) * 64;
+  static const int ids[11] = {1, 2, 3, 4, 5, 6, 7, 12, 13, 14, 15};
+  size_t total = 12;
+  for (int id : ids) total += 12 + sizes[id];
+  Buf z;
+  if (!z.reserve(total)) { set_error("ptau prepare: out of memory"); return G16_E_STATE; }
+  z.put("ptau", 4); z.u32(1); z.u32(11);
+  uint8_t* sp[16] = {};
+  for (int id : ids) {
+    z.u32((uint32_t)id); z.u64(sizes[id]);
+    sp[id] = z.skip(sizes[id]);
+    if (id <= 7) memcpy(sp[id], in[id], sizes[id]);
+  }
+  const int P = (int)pv.power;
+  PtauPrepareStats st[4];
+  int rc = ptau_prepare_g1(device, pv.sec[2], 2 * n - 1, P + 1, sp[12], &st[0]);
+  if (!rc) rc = ptau_prepare_g2(device, pv.sec[3], n, P, sp[13], &st[1]);
+  if (!rc) rc = ptau_prepare_g1(device, pv.sec[4], n, P, sp[14], &st[2]);
+  if (!rc) rc = ptau_prepare_g1(device, pv.sec[5], n, P, sp[15], &st[3]);
+  if (rc) { free(z.p); return rc; }
+  if (getenv("G16_TRACE_HOST")) {
+    const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    fprintf(stderr,
+            "[g16] ptau prepare: power %d; kernels section 12 %.3f ms, 13 %.3f ms, 14 %.3f ms, 15 %.3f ms; point "
+            "multiplications G1 %llu G2 %llu, additions G1 %llu G2 %llu; call %.3f ms\n",
+            P, st[0].kern_ms, st[1].kern_ms, st[2].kern_ms, st[3].kern_ms,
+            (unsigned long long)(st[0].muls + st[2].muls + st[3].muls), (unsigned long long)st[1].muls,
+            (unsigned long long)(st[0].adds + st[2].adds + st[3].adds), (unsigned long long)st[1].adds, wall_ms);
+  }
+  *out = z.p;
+  *out_len = z.len;
+  return G16_OK;
+}
+}  // namespace
+
+extern "C" int g16_ptau_prepare(const uint8_t* ptau, size_t ptau_len, int device, uint8_t** out, size_t* out_len) {
+  if (!ptau || !out || !out_len) { set_error("NULL argument"); return G16_E_ARG; }
+  try {
+    return ptau_prepare_core(ptau, ptau_len, device, out, out_len);
+  } catch (const std::bad_alloc&) {   // no C++ exception crosses the C ABI
+    set_error("ptau prepare: out of memory");
+    return G16_E_STATE;
+  }
+}
+
+extern "C" int g16_ptau_prepare_files(const char* in_path, const char* out_path, int device) {
+  if (!in_path || !out_path) { set_error("NULL argument"); return G16_E_ARG; }
+  MappedFile in;
+  int rc = in.open_ro(in_path);
+  if (rc) return rc;
+  uint8_t* z = nullptr;
+  size_t zl = 0;
+  rc = g16_ptau_prepare((const uint8_t*)in.p, in.len, device, &z, &zl);
+  if (rc) return rc;
+  return write_key_file(out_path, z, zl);
 }
 
 // test-only: setup_core with the caller's trapdoor (standard-form LE scalars, each < r; gamma, delta non-zero)

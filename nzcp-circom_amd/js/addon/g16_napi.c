@@ -21,6 +21,7 @@
  *           plonkDestroy(phandle)
  *           plonkSetupFiles(r1csPath, ptauPath, zkeyPath, device, withLagrange) -> Promise<undefined>   (g16_plonk_setup_files)
  *           groth16SetupFiles(r1csPath, ptauPath, zkeyPath, device) -> Promise<undefined>   (g16_groth16_setup_files)
+ *           ptauPrepareFiles(inPath, outPath, device) -> Promise<undefined>   (g16_ptau_prepare_files)
  */
 #include <node_api.h>
 #include <stdlib.h>
@@ -681,12 +682,14 @@ typedef struct {
   char r1cs[1024], ptau[1024], zkey[1024];
   int device, lagrange, rc;
   int groth16;   /* 1: g16_groth16_setup_files (groth16SetupFiles) */
+  int prepare;   /* 1: g16_ptau_prepare_files (ptauPrepareFiles): ptau = input, zkey = output */
   char err[512];
 } sjob_t;
 static void sjob_execute(napi_env env, void* data) {
   sjob_t* j = (sjob_t*)data;
-  j->rc = j->groth16 ? g16_groth16_setup_files(j->r1cs, j->ptau, j->zkey, j->device)
-                     : g16_plonk_setup_files(j->r1cs, j->ptau, j->zkey, j->device, j->lagrange);
+  j->rc = j->prepare   ? g16_ptau_prepare_files(j->ptau, j->zkey, j->device)
+          : j->groth16 ? g16_groth16_setup_files(j->r1cs, j->ptau, j->zkey, j->device)
+                       : g16_plonk_setup_files(j->r1cs, j->ptau, j->zkey, j->device, j->lagrange);
   if (j->rc) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
 }
 static void sjob_complete(napi_env env, napi_status status, void* data) {
@@ -754,6 +757,30 @@ static napi_value js_groth16_setup_files(napi_env env, napi_callback_info info) 
   return promise;
 }
 
+/* powersoftau prepare phase2 from / to files: the same async job */
+static napi_value js_ptau_prepare_files(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3], promise, resname;
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) { napi_throw_type_error(env, NULL, "ptauPrepareFiles(inPath, outPath, device)"); return NULL; }
+  sjob_t* j = (sjob_t*)calloc(1, sizeof(sjob_t));
+  size_t n = 0;
+  if (napi_get_value_string_utf8(env, argv[0], j->ptau, sizeof(j->ptau), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], j->zkey, sizeof(j->zkey), &n) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, "ptauPrepareFiles: two path strings expected");
+    return NULL;
+  }
+  j->prepare = 1;
+  int32_t v = 0;
+  if (argc > 2 && napi_get_value_int32(env, argv[2], &v) == napi_ok) j->device = v;
+  NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
+  NAPI_OK(napi_create_string_utf8(env, "g16_ptau_prepare_files", NAPI_AUTO_LENGTH, &resname));
+  NAPI_OK(napi_create_async_work(env, NULL, resname, sjob_execute, sjob_complete, j, &j->work));
+  NAPI_OK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"create", NULL, js_create, NULL, NULL, NULL, napi_default, NULL},
@@ -770,6 +797,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"plonkDestroy", NULL, js_plonk_destroy, NULL, NULL, NULL, napi_default, NULL},
       {"plonkSetupFiles", NULL, js_plonk_setup_files, NULL, NULL, NULL, napi_default, NULL},
       {"groth16SetupFiles", NULL, js_groth16_setup_files, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauPrepareFiles", NULL, js_ptau_prepare_files, NULL, NULL, NULL, napi_default, NULL},
   };
   NAPI_OK(napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props));
   return exports;

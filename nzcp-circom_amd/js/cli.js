@@ -3,6 +3,7 @@
 // (snarkjs cli.js groth16Prove [EXT]; the reference's Makefile scripts the sibling PLONK lines,
 // /root/reference/Makefile:30-33).  Writes JSON.stringify(x, null, 1) like snarkjs.
 // And of `snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>` (alias `zkey new`; prepared ptau only).
+// And of `snarkjs powersoftau prepare phase2 <powersoftau.ptau> <new_powersoftau.ptau>` (alias `pt2`).
 // And of `snarkjs groth16 verify <verification_key.json> <public.json> <proof.json>` (groth16Verify [EXT]): prints
 // "[INFO]  snarkJS: OK!" and exits 0, or "[ERROR] snarkJS: Invalid proof" and exits 1.
 "use strict";
@@ -23,6 +24,14 @@ async function main(argv) {
     if (pos.length < 3) { console.error("usage: cli.js groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>"); process.exit(2); }
     const { newZKey } = require("./index.js");
     await newZKey(pos[0], pos[1], pos[2]);
+    return;
+  }
+  if ((a[0] === "powersoftau" && a[1] === "prepare" && a[2] === "phase2") || a[0] === "pt2") {
+    // snarkjs powersoftau prepare phase2 <powersoftau.ptau> <new_powersoftau.ptau>   (alias: pt2)
+    const pos = a.slice(a[0] === "pt2" ? 1 : 3).filter((x) => !x.startsWith("--"));
+    if (pos.length < 2) { console.error("usage: cli.js powersoftau prepare phase2 <powersoftau.ptau> <new_powersoftau.ptau>"); process.exit(2); }
+    const { powersOfTau } = require("./index.js");
+    await powersOfTau.preparePhase2(pos[0], pos[1]);
     return;
   }
   if (a[0] === "plonk" && a[1] === "setup") {   // snarkjs plonk setup <circuit.r1cs> <powersoftau.ptau> <circuit.zkey>

@@ -279,6 +279,16 @@ async function newZKey(r1csName, ptauName, zkeyName, opts = {}) {
   await native().groth16SetupFiles(String(r1csName), String(ptauName), String(zkeyName), opts.device | 0);
 }
 
+// ------------------------------------------------------------------ powersoftau prepare phase2
+// snarkjs: powersOfTau.preparePhase2(oldPtauFilename, newPTauFilename[, logger]) / CLI `powersoftau prepare phase2`
+// (alias `pt2`) -- file names.  Sections 1-7 are copied; the Lagrange sections 12-15 are computed on the device.
+const powersOfTau = {
+  async preparePhase2(oldPtauName, newPtauName, opts = {}) {
+    if (opts && typeof opts.debug === "function") opts = {};
+    await native().ptauPrepareFiles(String(oldPtauName), String(newPtauName), opts.device | 0);
+  },
+};
+
 // ------------------------------------------------------------------ zkey export verificationkey (host-only: header reads)
 // snarkjs `zKey.exportVerificationKey(zkey)` / CLI `zkey export verificationkey <zkey> <vk.json>` -- the second line of
 // the reference's PLONK flow (/root/reference/Makefile:32).  Groth16 and PLONK keys; points leave Montgomery form here
@@ -360,4 +370,4 @@ const groth16 = {
   createProver,
 };
 
-module.exports = { groth16, plonk, zKey: { exportVerificationKey, newZKey }, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
+module.exports = { groth16, plonk, powersOfTau, zKey: { exportVerificationKey, newZKey }, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
