@@ -31,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include "binfile.h"
 #include "fr29.cuh"
 #include "internal.h"
 #include "transcript.h"
@@ -540,28 +541,6 @@ struct g16_plonk {
 
 namespace {
 
-struct Sec { const uint8_t* p = nullptr; uint64_t size = 0; };
-int find_sections(const uint8_t* buf, size_t len, const char* magic, Sec out[16], const char* name) {
-  if (len < 12 || memcmp(buf, magic, 4) != 0) { set_error(std::string(name) + ": Invalid File format"); return G16_E_FORMAT; }
-  uint32_t version, nsec;
-  memcpy(&version, buf + 4, 4);
-  memcpy(&nsec, buf + 8, 4);
-  if (version > 2) { set_error("Version not supported"); return G16_E_FORMAT; }
-  size_t pos = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    if (pos + 12 > len) { set_error(std::string(name) + ": Invalid File format"); return G16_E_FORMAT; }
-    uint32_t id;
-    uint64_t size;
-    memcpy(&id, buf + pos, 4);
-    memcpy(&size, buf + pos + 4, 8);
-    pos += 12;
-    if (size > len - pos) { set_error(std::string(name) + ": Invalid File format"); return G16_E_FORMAT; }
-    if (id < 16 && !out[id].p) { out[id].p = buf + pos; out[id].size = size; }
-    pos += size;
-  }
-  return G16_OK;
-}
-
 // transforms of Montgomery vectors through the lazy working vector (natural order in and out)
 int do_ifft(const NttTables& t, const FrM* in, FrM* out, F29* lazy, hipStream_t st) {
   int rc = ntt_import(t, in, lazy, false, st);
@@ -588,24 +567,19 @@ int coset_fft(g16_plonk* P, const FrM* d_coefs, uint32_t len, F29* out, hipStrea
 }
 
 int plonk_create_impl(const uint8_t* zkey, size_t len, int device, g16_plonk* P) {
-  Sec s[16];
-  int rc = find_sections(zkey, len, "zkey", s, "zkey");
+  BinView f;
+  int rc = bin_open(zkey, len, "zkey", 2, f);
   if (rc) return rc;
+  const BinSection* s = f.sec;   // (an absent section is reported as Invalid File format on this route)
   if (!s[1].p || s[1].size < 4) { set_error("zkey: Invalid File format"); return G16_E_FORMAT; }
   uint32_t proto;
   memcpy(&proto, s[1].p, 4);
   if (proto != 2) { set_error("zkey file is not plonk"); return G16_E_FORMAT; }
   const size_t hdr = 4 + 32 + 4 + 32 + 20 + 64 + 8 * 64 + 128;
   if (!s[2].p || s[2].size < hdr) { set_error("zkey: Invalid File format"); return G16_E_FORMAT; }
-  {
-    static const uint32_t Qp[8] = G16_FQ_P, Rp[8] = G16_FR_P;
-    uint32_t n8q, n8r;
-    memcpy(&n8q, s[2].p, 4);
-    memcpy(&n8r, s[2].p + 36, 4);
-    if (n8q != 32 || n8r != 32 || memcmp(s[2].p + 4, Qp, 32) != 0 || memcmp(s[2].p + 40, Rp, 32) != 0) {
-      set_error("zkey: curve not supported (bn128 only)");
-      return G16_E_FORMAT;
-    }
+  if (!bin_is_field(s[2].p, 36, kFqP) || !bin_is_field(s[2].p + 36, 36, kFrP)) {
+    set_error("zkey: curve not supported (bn128 only)");
+    return G16_E_FORMAT;
   }
   const uint8_t* h = s[2].p + 72;
   memcpy(&P->nVars, h, 4);
@@ -878,15 +852,13 @@ int random_fr(FrM* out) {
 }
 
 int plonk_prove_impl(g16_plonk* P, const uint8_t* wtns, size_t wlen, const uint8_t* blind, PlonkProofM* pr, uint8_t* pub) {
-  Sec s[16];
-  int rc = find_sections(wtns, wlen, "wtns", s, "wtns");
+  BinView f;
+  int rc = bin_open(wtns, wlen, "wtns", 2, f);
   if (rc) return rc;
+  const BinSection* s = f.sec;
   if (!s[1].p || s[1].size < 40 || !s[2].p) { set_error("wtns: Invalid File format"); return G16_E_FORMAT; }
   {
-    static const uint32_t Rp[8] = G16_FR_P;
-    uint32_t n8;
-    memcpy(&n8, s[1].p, 4);
-    if (n8 != 32 || memcmp(s[1].p + 4, Rp, 32) != 0) {
+    if (!bin_is_field(s[1].p, s[1].size, kFrP)) {
       set_error("Curve of the witness does not match the curve of the proving key");
       return G16_E_FORMAT;
     }

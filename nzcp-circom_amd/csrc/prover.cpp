@@ -10,11 +10,11 @@
 #include <string.h>
 #include <unistd.h>
 
-#include <map>
 #include <memory>
 #include <mutex>
 
 #include "../../include/g16_prover.h"
+#include "binfile.h"
 #include "internal.h"
 
 namespace g16 {
@@ -24,48 +24,13 @@ static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 const char* get_error() { return g_err.c_str(); }
 
-// ------------------------------------------------------------------ binfile (App. A.1)
-struct Section { const uint8_t* p = nullptr; uint64_t size = 0; bool present = false; };
-struct BinFile { std::map<uint32_t, Section> secs; uint32_t version = 0; };
-
-static uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
-static uint64_t rd64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
-
-// @iden3/binfileutils readBinFile(fileName, type, maxVersion) [EXT]
-static int read_binfile(const uint8_t* buf, size_t len, const char* magic, uint32_t max_version,
-                        const char* name, BinFile& out) {
-  if (!buf || len < 12 || memcmp(buf, magic, 4) != 0) {
-    set_error(std::string(name) + ": Invalid File format");
-    return G16_E_FORMAT;
-  }
-  out.version = rd32(buf + 4);
-  if (out.version > max_version) { set_error("Version not supported"); return G16_E_FORMAT; }
-  const uint32_t nsec = rd32(buf + 8);
-  size_t pos = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    if (pos + 12 > len) { set_error(std::string(name) + ": Invalid File format"); return G16_E_FORMAT; }
-    const uint32_t id = rd32(buf + pos);
-    const uint64_t sz = rd64(buf + pos + 4);
-    pos += 12;
-    if (sz > len - pos) { set_error(std::string(name) + ": Invalid File format"); return G16_E_FORMAT; }
-    Section& s = out.secs[id];
-    if (!s.present) { s.p = buf + pos; s.size = sz; s.present = true; }
-    pos += sz;
-  }
-  return G16_OK;
+// ------------------------------------------------------------------ binfile (App. A.1): binfile.h
+static int need_section(const BinView& f, uint32_t id, const char* name, BinSection& out) {
+  out = f.sec[id];
+  if (out.p) return G16_OK;
+  set_error(std::string(name) + ": Missing section " + std::to_string(id));
+  return G16_E_FORMAT;
 }
-static int need_section(const BinFile& f, uint32_t id, const char* name, Section& out) {
-  auto it = f.secs.find(id);
-  if (it == f.secs.end()) {
-    set_error(std::string(name) + ": Missing section " + std::to_string(id));
-    return G16_E_FORMAT;
-  }
-  out = it->second;
-  return G16_OK;
-}
-
-static const uint32_t kQ[8] = G16_FQ_P;
-static const uint32_t kR[8] = G16_FR_P;
 
 // ------------------------------------------------------------------ host point helpers
 static void g1_out(uint8_t out[64], const G1Affine& p) {  // Montgomery affine -> standard LE bytes
@@ -77,20 +42,13 @@ static void g2_out(uint8_t out[128], const G2Affine& p) {
   Fq v[4] = {fp_from_mont(p.x.a), fp_from_mont(p.x.b), fp_from_mont(p.y.a), fp_from_mont(p.y.b)};
   for (int i = 0; i < 4; i++) memcpy(out + 32 * i, v[i].v, 32);
 }
-static bool scalar_lt_r(const uint32_t s[8]) {
-  for (int i = 7; i >= 0; i--) {
-    if (s[i] < kR[i]) return true;
-    if (s[i] > kR[i]) return false;
-  }
-  return false;
-}
 static int random_scalar(uint32_t out[8]) {  // snarkjs Fr.random() counterpart: uniform in [0, r)
   int fd = open("/dev/urandom", O_RDONLY);
   if (fd < 0) { set_error("cannot open /dev/urandom"); return G16_E_STATE; }
   for (;;) {
     if (read(fd, out, 32) != 32) { close(fd); set_error("short read from /dev/urandom"); return G16_E_STATE; }
     out[7] &= 0x3fffffffu;  // r < 2^254
-    if (scalar_lt_r(out)) break;
+    if (fr_below_modulus(out)) break;
   }
   close(fd);
   return G16_OK;
@@ -203,7 +161,7 @@ static void shard_range(uint32_t total, int rank, int count, uint32_t& lo, uint3
   hi = (uint32_t)((uint64_t)total * (rank + 1) / count);
 }
 
-static int build_csr(g16_prover* P, const Section& s4) {
+static int build_csr(g16_prover* P, const BinSection& s4) {
   if (s4.size < 4) { set_error("zkey: Invalid File format"); return G16_E_FORMAT; }
   const uint32_t nc = rd32(s4.p);
   if ((uint64_t)nc * 44 + 4 > s4.size) { set_error("zkey: Invalid File format"); return G16_E_FORMAT; }
@@ -301,10 +259,10 @@ static int build_csr(g16_prover* P, const Section& s4) {
 }
 
 static int create_impl(const uint8_t* zkey, size_t len, const g16_opts* opts, g16_prover* P) {
-  BinFile f;
-  int rc = read_binfile(zkey, len, "zkey", 2, "zkey", f);
+  BinView f;
+  int rc = bin_open(zkey, len, "zkey", 2, f);
   if (rc) return rc;
-  Section s1, s2, s4, sb[5];
+  BinSection s1, s2, s4, sb[5];
   if ((rc = need_section(f, 1, "zkey", s1))) return rc;
   if (s1.size < 4 || rd32(s1.p) != 1) { set_error("zkey file is not groth16"); return G16_E_FORMAT; }
   if ((rc = need_section(f, 2, "zkey", s2))) return rc;
@@ -314,7 +272,7 @@ static int create_impl(const uint8_t* zkey, size_t len, const g16_opts* opts, g1
     set_error("zkey: Invalid File format");
     return G16_E_FORMAT;
   }
-  if (memcmp(s2.p + 4, kQ, 32) != 0 || memcmp(s2.p + 40, kR, 32) != 0) {
+  if (!bin_is_field(s2.p, 36, kFqP) || !bin_is_field(s2.p + 36, 36, kFrP)) {
     set_error("Curve not supported: zkey is not over bn128");
     return G16_E_FORMAT;
   }
@@ -473,15 +431,15 @@ static int create_impl(const uint8_t* zkey, size_t len, const g16_opts* opts, g1
 
 // wtns_utils.readHeader + the checks of groth16.prove [EXT]
 static int parse_wtns(const g16_prover* P, const uint8_t* wtns, size_t len, const uint8_t** body) {
-  BinFile f;
-  int rc = read_binfile(wtns, len, "wtns", 2, "wtns", f);
+  BinView f;
+  int rc = bin_open(wtns, len, "wtns", 2, f);
   if (rc) return rc;
-  Section s1, s2;
+  BinSection s1, s2;
   if ((rc = need_section(f, 1, "wtns", s1))) return rc;
   if (s1.size < 8) { set_error("wtns: Invalid File format"); return G16_E_FORMAT; }
   const uint32_t n8 = rd32(s1.p);
   if (s1.size < 8 + (uint64_t)n8) { set_error("wtns: Invalid File format"); return G16_E_FORMAT; }
-  if (n8 != 32 || memcmp(s1.p + 4, kR, 32) != 0) {
+  if (!bin_is_field(s1.p, s1.size, kFrP)) {
     set_error("Curve of the witness does not match the curve of the proving key");
     return G16_E_FORMAT;
   }
@@ -538,7 +496,7 @@ static int prepare_blinding(const KeyPoints* P, const uint8_t* r_in, const uint8
   int rc;
   if (r_in) memcpy(b.r, r_in, 32); else if ((rc = random_scalar(b.r))) return rc;
   if (s_in) memcpy(b.s, s_in, 32); else if ((rc = random_scalar(b.s))) return rc;
-  if (!scalar_lt_r(b.r) || !scalar_lt_r(b.s)) { set_error("blinding scalar not reduced mod r"); return G16_E_ARG; }
+  if (!fr_below_modulus(b.r) || !fr_below_modulus(b.s)) { set_error("blinding scalar not reduced mod r"); return G16_E_ARG; }
   xyzz_mul_scalar(b.r_delta1, P->delta1, b.r);
   xyzz_mul_scalar(b.s_delta1, P->delta1, b.s);
   xyzz_mul_scalar(b.s_delta2, P->delta2, b.s);
@@ -1250,10 +1208,10 @@ int g16_prove_batch(g16_prover* p, const uint8_t* const* wtns, const size_t* wtn
 int g16_finish_host(const uint8_t* zkey, size_t zkey_len, const uint8_t* partials, uint32_t count,
                     const uint8_t r[32], const uint8_t s[32], g16_proof* out) {
   if (!zkey || !partials || !count || !out) { set_error("NULL argument"); return G16_E_ARG; }
-  BinFile f;
-  int rc = read_binfile(zkey, zkey_len, "zkey", 2, "zkey", f);
+  BinView f;
+  int rc = bin_open(zkey, zkey_len, "zkey", 2, f);
   if (rc) return rc;
-  Section s1, s2;
+  BinSection s1, s2;
   if ((rc = need_section(f, 1, "zkey", s1))) return rc;
   if (s1.size < 4 || rd32(s1.p) != 1) { set_error("zkey file is not groth16"); return G16_E_FORMAT; }
   if ((rc = need_section(f, 2, "zkey", s2))) return rc;

@@ -19,6 +19,7 @@
 #include <new>
 #include <thread>
 
+#include "binfile.h"
 #include "internal.h"
 
 namespace g16 {
@@ -193,27 +194,12 @@ void gen_witness(const Circuit& c, uint64_t wseed, std::vector<FrM>& w) {
 }
 
 // ------------------------------------------------------------------ binfile writer
-struct Buf {
-  uint8_t* p = nullptr;
-  size_t len = 0, cap = 0;
-  bool reserve(size_t c) {
-    p = (uint8_t*)malloc(c ? c : 1);
-    cap = c;
-    return p != nullptr;
-  }
-  void put(const void* src, size_t n) { memcpy(p + len, src, n); len += n; }
-  void u32(uint32_t v) { put(&v, 4); }
-  void u64(uint64_t v) { put(&v, 8); }
-  uint8_t* skip(size_t n) { uint8_t* q = p + len; len += n; return q; }
-};
-
 void write_wtns(const std::vector<FrM>& w, Buf& b) {
   const size_t n = w.size();
   b.reserve(12 + 12 + 40 + 12 + n * 32);
   b.put("wtns", 4); b.u32(2); b.u32(2);
   b.u32(1); b.u64(40);
-  static const uint32_t R[8] = G16_FR_P;
-  b.u32(32); b.put(R, 32); b.u32((uint32_t)n);
+  b.u32(32); b.put(kFrP, 32); b.u32((uint32_t)n);
   b.u32(2); b.u64((uint64_t)n * 32);
   for (size_t i = 0; i < n; i++) {
     const Fr s = fp_from_mont(w[i]);
@@ -380,8 +366,7 @@ extern "C" int g16_synth_witness(uint32_t n, uint32_t p, uint32_t m, uint64_t se
 // section-2 points (G16ZkeyImage::hdr_points) and sections 3 (IC), 5 (A), 6 (B1), 7 (B2), 8 (C) and 9 (H).
 struct G16ZkeyImage {
   Buf z;
-  uint8_t* sec[11] = {};
-  size_t size[11] = {};
+  uint8_t* sec[16] = {};
   uint8_t* hdr_points = nullptr;   // alpha1 | beta1 | beta2 | gamma2 | delta1 | delta2 (64 / 64 / 128 / 128 / 64 / 128)
 };
 static int g16_zkey_layout(const Circuit& c, int L, G16ZkeyImage& im) {
@@ -390,25 +375,13 @@ static int g16_zkey_layout(const Circuit& c, int L, G16ZkeyImage& im) {
   const size_t ncoef = c.tA.size() + c.tB.size() + (size_t)p + 1;
   const size_t nC = (size_t)n - p - 1;
   const size_t hdr2 = 4 + 32 + 4 + 32 + 12 + 64 + 64 + 128 + 128 + 64 + 128;
-  const size_t sizes[11] = {0, 4, hdr2, (size_t)(p + 1) * 64, 4 + ncoef * 44, (size_t)n * 64, (size_t)n * 64,
-                            (size_t)n * 128, nC * 64, N * 64, 64 + 4};
-  size_t total = 12;
-  for (int i = 1; i <= 10; i++) total += 12 + sizes[i];
-  Buf& z = im.z;
-  if (!z.reserve(total)) { set_error("synth: out of memory"); return G16_E_STATE; }
-  z.put("zkey", 4); z.u32(1); z.u32(10);
-  for (uint32_t id = 1; id <= 10; id++) {
-    z.u32(id); z.u64(sizes[id]);
-    im.size[id] = sizes[id];
-    im.sec[id] = z.skip(sizes[id]);
-  }
+  const uint64_t sizes[16] = {0, 4, hdr2, (uint64_t)(p + 1) * 64, 4 + ncoef * 44, (uint64_t)n * 64, (uint64_t)n * 64,
+                              (uint64_t)n * 128, nC * 64, N * 64, 64 + 4};
+  static const int ids[10] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10};
+  if (!bin_layout(im.z, "zkey", 1, ids, 10, sizes, im.sec)) { set_error("synth: out of memory"); return G16_E_STATE; }
   { uint32_t one = 1; memcpy(im.sec[1], &one, 4); }
   {
-    static const uint32_t Qp[8] = G16_FQ_P, Rp[8] = G16_FR_P;
-    uint32_t v32 = 32;
-    uint8_t* q = im.sec[2];
-    memcpy(q, &v32, 4); q += 4; memcpy(q, Qp, 32); q += 32;
-    memcpy(q, &v32, 4); q += 4; memcpy(q, Rp, 32); q += 32;
+    uint8_t* q = bin_put_field(bin_put_field(im.sec[2], kFqP), kFrP);
     uint32_t dom = (uint32_t)N;
     memcpy(q, &n, 4); memcpy(q + 4, &p, 4); memcpy(q + 8, &dom, 4); q += 12;
     im.hdr_points = q;
@@ -869,9 +842,8 @@ void write_r1cs(const Circuit& c, uint32_t n_pub_out, uint32_t n_pub_in, Buf& b)
   const size_t s1 = 4 + 32 + 16 + 8 + 4, s2 = (size_t)c.m * 12 + nnz * 36, s3 = (size_t)c.n * 8;
   b.reserve(12 + 3 * 12 + s1 + s2 + s3);
   b.put("r1cs", 4); b.u32(1); b.u32(3);
-  static const uint32_t R[8] = G16_FR_P;
   b.u32(1); b.u64(s1);
-  b.u32(32); b.put(R, 32); b.u32(c.n); b.u32(n_pub_out); b.u32(n_pub_in); b.u32(c.n - 1 - n_pub_out - n_pub_in);
+  b.u32(32); b.put(kFrP, 32); b.u32(c.n); b.u32(n_pub_out); b.u32(n_pub_in); b.u32(c.n - 1 - n_pub_out - n_pub_in);
   b.u64(c.n); b.u32(c.m);
   b.u32(2); b.u64(s2);
   const std::vector<Term>* ts[3] = {&c.tA, &c.tB, &c.tC};
@@ -1118,27 +1090,17 @@ extern "C" int g16_nzcp_circuit_setup(const uint32_t params[7], const uint8_t* t
 // nPublic of the zkey = nPubOut + nPubIn ([EXT] r1csfile 0.0.35, pin /root/reference/yarn.lock:909-917).
 static int read_r1cs(const uint8_t* buf, size_t len, Circuit& c) {
   auto bad = [](const char* why) { set_error(std::string("r1cs: ") + why); return G16_E_FORMAT; };
-  if (!buf || len < 12 || memcmp(buf, "r1cs", 4) != 0) { set_error("r1cs: Invalid File format"); return G16_E_FORMAT; }
-  uint32_t version, nsec;
-  memcpy(&version, buf + 4, 4);
-  memcpy(&nsec, buf + 8, 4);
-  if (version > 1) { set_error("Version not supported"); return G16_E_FORMAT; }
-  const uint8_t *s1 = nullptr, *s2 = nullptr;
-  uint64_t l1 = 0, l2 = 0;
-  size_t pos = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    if (pos + 12 > len) return bad("truncated section table");
-    uint32_t id; uint64_t sz;
-    memcpy(&id, buf + pos, 4); memcpy(&sz, buf + pos + 4, 8); pos += 12;
-    if (sz > len - pos) return bad("truncated section");
-    if (id == 1 && !s1) { s1 = buf + pos; l1 = sz; }
-    if (id == 2 && !s2) { s2 = buf + pos; l2 = sz; }
-    pos += sz;
+  BinView f;
+  BinFault why;
+  if (const int rc = bin_open(buf, len, "r1cs", 1, f, &why)) {
+    if (why == BinFault::table) return bad("truncated section table");
+    if (why == BinFault::section) return bad("truncated section");
+    return rc;
   }
+  const uint8_t *s1 = f.sec[1].p, *s2 = f.sec[2].p, *s3 = f.sec[3].p;
+  const uint64_t l1 = f.sec[1].size, l2 = f.sec[2].size, l3 = f.sec[3].size;
   if (!s1 || !s2 || l1 < 4 + 32 + 16 + 8 + 4) return bad("missing header or constraint section");
-  uint32_t n8; memcpy(&n8, s1, 4);
-  static const uint32_t Rp[8] = G16_FR_P;
-  if (n8 != 32 || memcmp(s1 + 4, Rp, 32) != 0) return bad("field is not the bn128 scalar field");
+  if (!bin_is_field(s1, l1, kFrP)) return bad("field is not the bn128 scalar field");
   uint32_t nWires, nPubOut, nPubIn, nPrvIn, nCons;
   memcpy(&nWires, s1 + 36, 4); memcpy(&nPubOut, s1 + 40, 4); memcpy(&nPubIn, s1 + 44, 4);
   memcpy(&nPrvIn, s1 + 48, 4); memcpy(&nCons, s1 + 60, 4);
@@ -1149,19 +1111,8 @@ static int read_r1cs(const uint8_t* buf, size_t len, Circuit& c) {
   // that appears nowhere still has its 8-byte entry in the wire map (section 3) when the file carries one
   if ((uint64_t)nCons * 12 > l2) return bad("constraint count exceeds the constraint section");
   if (nWires > (1u << 28)) return bad("too many wires");
-  {
-    const uint8_t* s3 = nullptr;
-    uint64_t l3 = 0;
-    size_t q3 = 12;
-    for (uint32_t i = 0; i < nsec; i++) {
-      uint32_t id; uint64_t sz;
-      memcpy(&id, buf + q3, 4); memcpy(&sz, buf + q3 + 4, 8); q3 += 12;
-      if (id == 3 && !s3) { s3 = buf + q3; l3 = sz; }
-      q3 += sz;
-    }
-    if (s3 && l3 != (uint64_t)nWires * 8) return bad("wire map does not match the wire count");
-    if (!s3 && (uint64_t)nWires > l2) return bad("wire count exceeds the file");
-  }
+  if (s3 && l3 != (uint64_t)nWires * 8) return bad("wire map does not match the wire count");
+  if (!s3 && (uint64_t)nWires > l2) return bad("wire count exceeds the file");
   c.rowA.assign(1, 0); c.rowB.assign(1, 0); c.rowC.assign(1, 0);
   const uint8_t* q = s2;
   const uint8_t* end = s2 + l2;
@@ -1362,15 +1313,12 @@ static int plonk_setup_core(const uint8_t* r1cs, size_t r1cs_len, const PlonkTau
   const size_t nlag = with_lagrange ? (c.p > 0 ? c.p : 1) : 0;
   const size_t polb = N * 32 * 5;
   const size_t hdr = 4 + 32 + 4 + 32 + 20 + 64 + 8 * 64 + 128;
-  const size_t sizes[15] = {0, 4, hdr, pb.adds.size() * 72, ng * 4, ng * 4, ng * 4, polb, polb, polb, polb, polb, 3 * polb,
-                            nlag * polb, (N + 6) * 64};
-  size_t total = 12;
-  for (int i = 1; i <= 14; i++) total += 12 + sizes[i];
+  const uint64_t sizes[16] = {0, 4, hdr, pb.adds.size() * 72, ng * 4, ng * 4, ng * 4, polb, polb, polb, polb, polb, 3 * polb,
+                              nlag * polb, (N + 6) * 64};
+  static const int ids[14] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14};
   Buf z;
-  if (!z.reserve(total)) { set_error("plonk setup: out of memory"); return G16_E_STATE; }
-  z.put("zkey", 4); z.u32(1); z.u32(14);
-  uint8_t* sp[15] = {};
-  for (uint32_t id = 1; id <= 14; id++) { z.u32(id); z.u64(sizes[id]); sp[id] = z.skip(sizes[id]); }
+  uint8_t* sp[16] = {};
+  if (!bin_layout(z, "zkey", 1, ids, 14, sizes, sp)) { set_error("plonk setup: out of memory"); return G16_E_STATE; }
   { uint32_t two = 2; memcpy(sp[1], &two, 4); }
   for (size_t k = 0; k < pb.adds.size(); k++) {
     uint8_t* q = sp[3] + k * 72;
@@ -1402,11 +1350,7 @@ static int plonk_setup_core(const uint8_t* r1cs, size_t r1cs_len, const PlonkTau
     }
   }
   auto write_header = [&](const uint8_t* commitments /* 8 x 64 */, const uint8_t* x2 /* 128 */) {
-    uint8_t* q = sp[2];
-    static const uint32_t Qp[8] = G16_FQ_P, Rp[8] = G16_FR_P;
-    uint32_t v32 = 32;
-    memcpy(q, &v32, 4); memcpy(q + 4, Qp, 32); memcpy(q + 36, &v32, 4); memcpy(q + 40, Rp, 32);
-    q += 72;
+    uint8_t* q = bin_put_field(bin_put_field(sp[2], kFqP), kFrP);
     const uint32_t hv[5] = {pb.nv, c.p, (uint32_t)N, (uint32_t)pb.adds.size(), (uint32_t)ng};
     memcpy(q, hv, 20); q += 20;
     memcpy(q, k1.v, 32); memcpy(q + 32, k2.v, 32); q += 64;
@@ -1482,6 +1426,33 @@ extern "C" int g16_plonk_setup(const uint8_t* r1cs, size_t r1cs_len, uint64_t se
   }
 }
 
+// ------------------------------------------------------------------ .ptau reader (the three routes that take one)
+namespace {
+
+struct PtauView : BinView {
+  uint32_t power = 0;
+  int blocks[16] = {};   // sections 12-15: whole blocks present
+};
+
+int ptau_bad(const char* why) { set_error(std::string("ptau: ") + why); return G16_E_FORMAT; }
+
+// Container, bn128 section 1 and the power: shared by the PLONK route, the prepared reader and g16_ptau_prepare.
+// tau_sections: sections 2 and 3 must be there too, their absence reported with the curve text ahead of the power
+// check.  That is the PLONK route's order, and it cannot check them itself after this call: a file without section 2
+// AND with a power above 28 would then get the bare text of the power check instead of the curve text.  The other two
+// routes check the sections they read after the power, with the bare text, and pass false.
+int ptau_open(const uint8_t* ptau, size_t ptau_len, PtauView& v, bool tau_sections) {
+  if (const int rc = bin_open(ptau, ptau_len, "ptau", 1, v)) return rc;
+  const BinSection& s1 = v.sec[1];
+  if (!s1.p || (tau_sections && (!v.sec[2].p || !v.sec[3].p)) || s1.size < 4 + 32 + 8 || !bin_is_field(s1.p, s1.size, kFqP))
+    return ptau_bad("Invalid File format (bn128 powers of tau expected)");
+  v.power = rd32(s1.p + 36);
+  if (v.power > 28) return ptau_bad("Invalid File format");
+  return G16_OK;
+}
+
+}  // namespace
+
 // `snarkjs plonk setup c.r1cs pot.ptau c.zkey` (/root/reference/Makefile:31) with a REAL powers-of-tau file: .ptau v1
 // ([EXT] snarkjs powersoftau_utils.js: section 1 = n8, q, power, ceremonyPower; section 2 = 2^(power+1) - 1 points
 // [tau^i]G1; section 3 = 2^power points [tau^i]G2; affine Montgomery LE).  The N + 6 powers are copied into the key and
@@ -1489,42 +1460,16 @@ extern "C" int g16_plonk_setup(const uint8_t* r1cs, size_t r1cs_len, uint64_t se
 extern "C" int g16_plonk_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len, int device,
                                     int with_lagrange, uint8_t** zkey, size_t* zkey_len) {
   if (!r1cs || !ptau || !zkey || !zkey_len) { set_error("NULL argument"); return G16_E_ARG; }
-  if (ptau_len < 12 || memcmp(ptau, "ptau", 4) != 0) { set_error("ptau: Invalid File format"); return G16_E_FORMAT; }
-  uint32_t version, nsec;
-  memcpy(&version, ptau + 4, 4);
-  memcpy(&nsec, ptau + 8, 4);
-  if (version > 1) { set_error("Version not supported"); return G16_E_FORMAT; }
-  const uint8_t* sp[4] = {nullptr, nullptr, nullptr, nullptr};
-  uint64_t sl[4] = {0, 0, 0, 0};
-  size_t pos = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    if (pos + 12 > ptau_len) { set_error("ptau: Invalid File format"); return G16_E_FORMAT; }
-    uint32_t id;
-    uint64_t sz;
-    memcpy(&id, ptau + pos, 4);
-    memcpy(&sz, ptau + pos + 4, 8);
-    pos += 12;
-    if (sz > ptau_len - pos) { set_error("ptau: Invalid File format"); return G16_E_FORMAT; }
-    if (id >= 1 && id <= 3 && !sp[id]) { sp[id] = ptau + pos; sl[id] = sz; }
-    pos += sz;
-  }
-  static const uint32_t Qp[8] = G16_FQ_P;
-  uint32_t n8 = 0;
-  if (sp[1] && sl[1] >= 4) memcpy(&n8, sp[1], 4);
-  if (!sp[1] || !sp[2] || !sp[3] || sl[1] < 4 + 32 + 8 || n8 != 32 || memcmp(sp[1] + 4, Qp, 32) != 0) {
-    set_error("ptau: Invalid File format (bn128 powers of tau expected)");
-    return G16_E_FORMAT;
-  }
+  PtauView pv;
+  if (const int rc = ptau_open(ptau, ptau_len, pv, /*tau_sections=*/true)) return rc;
+  const BinSection &s2 = pv.sec[2], &s3 = pv.sec[3];
+  if (s2.size < (((uint64_t)2 << pv.power) - 1) * 64 || s3.size < 2 * 128) return ptau_bad("Invalid File format");
   PlonkTauSrc src;
   src.known = false;
-  memcpy(&src.power, sp[1] + 36, 4);
-  if (src.power > 28 || sl[2] < (((uint64_t)2 << src.power) - 1) * 64 || sl[3] < 2 * 128) {
-    set_error("ptau: Invalid File format");
-    return G16_E_FORMAT;
-  }
-  src.tau_g1 = sp[2];
-  src.n_g1 = sl[2] / 64;
-  src.tau_g2_1 = sp[3] + 128;
+  src.power = pv.power;
+  src.tau_g1 = s2.p;
+  src.n_g1 = s2.size / 64;
+  src.tau_g2_1 = s3.p + 128;
   try {
     return plonk_setup_core(r1cs, r1cs_len, src, device, with_lagrange, zkey, zkey_len);
   } catch (const std::bad_alloc&) {
@@ -1605,56 +1550,17 @@ extern "C" int g16_setup_device(int device) {
 // (tau, alpha, beta, 1, 1).
 namespace {
 
-struct PtauView {
-  uint32_t power = 0;
-  const uint8_t* sec[16] = {};
-  uint64_t len[16] = {};
-  int blocks[16] = {};   // sections 12-15: whole blocks present
-};
-
-int ptau_bad(const char* why) { set_error(std::string("ptau: ") + why); return G16_E_FORMAT; }
-
-// binfile header, section table and bn128 section 1 (the PLONK reader's checks): shared by the prepared reader below
-// and by g16_ptau_prepare
-int ptau_open(const uint8_t* ptau, size_t ptau_len, PtauView& v) {
-  if (!ptau || ptau_len < 12 || memcmp(ptau, "ptau", 4) != 0) return ptau_bad("Invalid File format");
-  uint32_t version, nsec;
-  memcpy(&version, ptau + 4, 4);
-  memcpy(&nsec, ptau + 8, 4);
-  if (version > 1) { set_error("Version not supported"); return G16_E_FORMAT; }
-  size_t pos = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    if (pos + 12 > ptau_len) return ptau_bad("Invalid File format");
-    uint32_t id;
-    uint64_t sz;
-    memcpy(&id, ptau + pos, 4);
-    memcpy(&sz, ptau + pos + 4, 8);
-    pos += 12;
-    if (sz > ptau_len - pos) return ptau_bad("Invalid File format");
-    if (id < 16 && !v.sec[id]) { v.sec[id] = ptau + pos; v.len[id] = sz; }
-    pos += sz;
-  }
-  static const uint32_t Qp[8] = G16_FQ_P;
-  uint32_t n8 = 0;
-  if (v.sec[1] && v.len[1] >= 4) memcpy(&n8, v.sec[1], 4);
-  if (!v.sec[1] || v.len[1] < 4 + 32 + 8 || n8 != 32 || memcmp(v.sec[1] + 4, Qp, 32) != 0)
-    return ptau_bad("Invalid File format (bn128 powers of tau expected)");
-  memcpy(&v.power, v.sec[1] + 36, 4);
-  if (v.power > 28) return ptau_bad("Invalid File format");
-  return G16_OK;
-}
-
 // ptau_open and the prepared-section block layout
 int ptau_open_prepared(const uint8_t* ptau, size_t ptau_len, PtauView& v) {
-  if (const int rc = ptau_open(ptau, ptau_len, v)) return rc;
-  if (!v.sec[12]) { set_error("Powers of tau is not prepared."); return G16_E_FORMAT; }
-  if (!v.sec[4] || v.len[4] < 64 || !v.sec[5] || v.len[5] < 64 || !v.sec[6] || v.len[6] < 128)
+  if (const int rc = ptau_open(ptau, ptau_len, v, /*tau_sections=*/false)) return rc;
+  if (!v.sec[12].p) { set_error("Powers of tau is not prepared."); return G16_E_FORMAT; }
+  if (!v.sec[4].p || v.sec[4].size < 64 || !v.sec[5].p || v.sec[5].size < 64 || !v.sec[6].p || v.sec[6].size < 128)
     return ptau_bad("Invalid File format");
   for (int id = 12; id <= 15; id++) {
-    if (!v.sec[id]) return ptau_bad("Invalid File format");
+    if (!v.sec[id].p) return ptau_bad("Invalid File format");
     const uint64_t psz = id == 13 ? 128 : 64;
-    if (v.len[id] % psz) return ptau_bad("Invalid File format");
-    const uint64_t pts = v.len[id] / psz;   // blocks 0 .. K-1 hold 2^K - 1 points
+    if (v.sec[id].size % psz) return ptau_bad("Invalid File format");
+    const uint64_t pts = v.sec[id].size / psz;   // blocks 0 .. K-1 hold 2^K - 1 points
     int K = 0;
     while (K < 40 && (((uint64_t)1 << K) - 1) < pts) K++;
     const int max_blocks = (int)v.power + (id == 12 ? 2 : 1);
@@ -1705,11 +1611,11 @@ extern "C" int g16_groth16_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, cons
     if (device < 0 || device >= ndev) { set_error("groth16 setup: bad device ordinal"); return G16_E_ARG; }
     const size_t N = (size_t)1 << L;
     const size_t blkL = N - 1, blkL1 = 2 * N - 1;   // first point of block L / L + 1
-    const uint8_t* lag1 = pv.sec[12] + blkL * 64;
-    const uint8_t* lag2 = pv.sec[13] + blkL * 128;
-    const uint8_t* alag = pv.sec[14] + blkL * 64;
-    const uint8_t* blag = pv.sec[15] + blkL * 64;
-    const uint8_t* hblk = pv.sec[12] + blkL1 * 64;
+    const uint8_t* lag1 = pv.sec[12].p + blkL * 64;
+    const uint8_t* lag2 = pv.sec[13].p + blkL * 128;
+    const uint8_t* alag = pv.sec[14].p + blkL * 64;
+    const uint8_t* blag = pv.sec[15].p + blkL * 64;
+    const uint8_t* hblk = pv.sec[12].p + blkL1 * 64;
 
     // the term lists, CSC by output (counting sort): G1 outputs A_j = j, B1_j = n + j, K_j = 2n + j over the bases
     // [L_c] | [alpha L_c] | [beta L_c] (3N points); G2 outputs B2_j over [L_c]G2
@@ -1759,9 +1665,9 @@ extern "C" int g16_groth16_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, cons
       uint8_t* q = im.hdr_points;
       const G1Affine g1 = g1_generator();
       const G2Affine g2 = g2_generator();
-      memcpy(q, pv.sec[4], 64);          // alpha1 = [alpha tau^0]G1
-      memcpy(q + 64, pv.sec[5], 64);     // beta1
-      memcpy(q + 128, pv.sec[6], 128);   // beta2
+      memcpy(q, pv.sec[4].p, 64);          // alpha1 = [alpha tau^0]G1
+      memcpy(q + 64, pv.sec[5].p, 64);     // beta1
+      memcpy(q + 128, pv.sec[6].p, 128);   // beta2
       memcpy(q + 256, &g2, 128);         // gamma2 = [1]G2
       memcpy(q + 384, &g1, 64);          // delta1 = [1]G1
       memcpy(q + 448, &g2, 128);         // delta2 = [1]G2
@@ -1832,7 +1738,7 @@ constexpr uint32_t kPreparePowerMax = 24;   // (what g16_ptau_synth can produce;
 int ptau_prepare_core(const uint8_t* ptau, size_t ptau_len, int device, uint8_t** out, size_t* out_len) {
   const auto t0 = std::chrono::steady_clock::now();
   PtauView pv;
-  if (const int rc = ptau_open(ptau, ptau_len, pv)) return rc;
+  if (const int rc = ptau_open(ptau, ptau_len, pv, /*tau_sections=*/false)) return rc;
   if (pv.power > kPreparePowerMax) {
     set_error("ptau prepare: power " + std::to_string(pv.power) + " is above the supported limit of " +
               std::to_string(kPreparePowerMax));
@@ -1841,7 +1747,7 @@ int ptau_prepare_core(const uint8_t* ptau, size_t ptau_len, int device, uint8_t*
   const uint64_t n = (uint64_t)1 << pv.power;
   const uint64_t want[7] = {0, 0, (2 * n - 1) * 64, n * 128, n * 64, n * 64, 128};
   for (int id = 2; id <= 6; id++)
-    if (!pv.sec[id] || pv.len[id] != want[id]) return ptau_bad("Invalid File format");
+    if (!pv.sec[id].p || pv.sec[id].size != want[id]) return ptau_bad("Invalid File format");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     set_error("ptau prepare: no HIP device (there is no CPU path)");
@@ -1852,29 +1758,22 @@ int ptau_prepare_core(const uint8_t* ptau, size_t ptau_len, int device, uint8_t*
   static const uint8_t no_contributions[4] = {0, 0, 0, 0};
   const uint8_t* in[8] = {};
   uint64_t sizes[16] = {};
-  for (int id = 1; id <= 7; id++) { in[id] = pv.sec[id]; sizes[id] = pv.len[id]; }
+  for (int id = 1; id <= 7; id++) { in[id] = pv.sec[id].p; sizes[id] = pv.sec[id].size; }
   if (!in[7]) { in[7] = no_contributions; sizes[7] = 4; }
   sizes[12] = (4 * n - 1) * 64;
   sizes[13] = (2 * n - 1) * 128;
   sizes[14] = sizes[15] = (2 * n - 1) * 64;
   static const int ids[11] = {1, 2, 3, 4, 5, 6, 7, 12, 13, 14, 15};
-  size_t total = 12;
-  for (int id : ids) total += 12 + sizes[id];
   Buf z;
-  if (!z.reserve(total)) { set_error("ptau prepare: out of memory"); return G16_E_STATE; }
-  z.put("ptau", 4); z.u32(1); z.u32(11);
   uint8_t* sp[16] = {};
-  for (int id : ids) {
-    z.u32((uint32_t)id); z.u64(sizes[id]);
-    sp[id] = z.skip(sizes[id]);
-    if (id <= 7) memcpy(sp[id], in[id], sizes[id]);
-  }
+  if (!bin_layout(z, "ptau", 1, ids, 11, sizes, sp)) { set_error("ptau prepare: out of memory"); return G16_E_STATE; }
+  for (int id = 1; id <= 7; id++) memcpy(sp[id], in[id], sizes[id]);
   const int P = (int)pv.power;
   PtauPrepareStats st[4];
-  int rc = ptau_prepare_g1(device, pv.sec[2], 2 * n - 1, P + 1, sp[12], &st[0]);
-  if (!rc) rc = ptau_prepare_g2(device, pv.sec[3], n, P, sp[13], &st[1]);
-  if (!rc) rc = ptau_prepare_g1(device, pv.sec[4], n, P, sp[14], &st[2]);
-  if (!rc) rc = ptau_prepare_g1(device, pv.sec[5], n, P, sp[15], &st[3]);
+  int rc = ptau_prepare_g1(device, pv.sec[2].p, 2 * n - 1, P + 1, sp[12], &st[0]);
+  if (!rc) rc = ptau_prepare_g2(device, pv.sec[3].p, n, P, sp[13], &st[1]);
+  if (!rc) rc = ptau_prepare_g1(device, pv.sec[4].p, n, P, sp[14], &st[2]);
+  if (!rc) rc = ptau_prepare_g1(device, pv.sec[5].p, n, P, sp[15], &st[3]);
   if (rc) { free(z.p); return rc; }
   if (getenv("G16_TRACE_HOST")) {
     const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1917,15 +1816,11 @@ extern "C" int g16_ptau_prepare_files(const char* in_path, const char* out_path,
 extern "C" int g16_r1cs_setup_trapdoor(const uint8_t* r1cs, size_t r1cs_len, const uint8_t td[5 * 32], int threads,
                                        uint8_t** zkey, size_t* zkey_len, uint8_t** vkey, size_t* vkey_len) {
   if (!r1cs || !td || !zkey || !zkey_len) { set_error("NULL argument"); return G16_E_ARG; }
-  static const uint32_t Rp[8] = G16_FR_P;
   FrM tdm[5];
   for (int k = 0; k < 5; k++) {
     Fr x;
     memcpy(x.v, td + 32 * k, 32);
-    bool lt = false;
-    for (int i = 7; i >= 0; i--)
-      if (x.v[i] != Rp[i]) { lt = x.v[i] < Rp[i]; break; }
-    if (!lt) { set_error("setup: trapdoor scalar not below r"); return G16_E_ARG; }
+    if (!fr_below_modulus(x.v)) { set_error("setup: trapdoor scalar not below r"); return G16_E_ARG; }
     tdm[k] = fp_to_mont(x);
   }
   if (fp_is_zero(tdm[3]) || fp_is_zero(tdm[4])) { set_error("setup: gamma and delta must be non-zero"); return G16_E_ARG; }
@@ -1961,19 +1856,13 @@ extern "C" int g16_ptau_synth(uint32_t power, const uint8_t tab[3 * 32], int pre
     const int threads = (int)std::thread::hardware_concurrency() > 0 ? (int)std::thread::hardware_concurrency() : 1;
     const uint64_t sizes[16] = {0, 44, (2 * n - 1) * 64, n * 128, n * 64, n * 64, 128, 4, 0, 0, 0, 0,
                                 (4 * n - 1) * 64, (2 * n - 1) * 128, (2 * n - 1) * 64, (2 * n - 1) * 64};
-    std::vector<int> ids = {1, 2, 3, 4, 5, 6, 7};
-    if (prepared) for (int id = 12; id <= 15; id++) ids.push_back(id);
-    size_t total = 12;
-    for (int id : ids) total += 12 + sizes[id];
+    static const int ids[11] = {1, 2, 3, 4, 5, 6, 7, 12, 13, 14, 15};
     Buf z;
-    if (!z.reserve(total)) { set_error("ptau synth: out of memory"); return G16_E_STATE; }
-    z.put("ptau", 4); z.u32(1); z.u32((uint32_t)ids.size());
     uint8_t* sp[16] = {};
-    for (int id : ids) { z.u32((uint32_t)id); z.u64(sizes[id]); sp[id] = z.skip(sizes[id]); }
+    if (!bin_layout(z, "ptau", 1, ids, prepared ? 11 : 7, sizes, sp)) { set_error("ptau synth: out of memory"); return G16_E_STATE; }
     {
-      static const uint32_t Qp[8] = G16_FQ_P;
-      uint32_t v32 = 32;
-      memcpy(sp[1], &v32, 4); memcpy(sp[1] + 4, Qp, 32); memcpy(sp[1] + 36, &power, 4); memcpy(sp[1] + 40, &power, 4);
+      uint8_t* q = bin_put_field(sp[1], kFqP);
+      memcpy(q, &power, 4); memcpy(q + 4, &power, 4);
       memset(sp[7], 0, 4);
     }
     FixedBase<FqOps> fb1;

@@ -54,6 +54,18 @@ def test_plonk_errors(amd):
     with pytest.raises(amd.G16Error) as e:
         prover.prove(f.write_wtns(bad))
     assert "not divisible" in str(e.value) or "Copy constraints" in str(e.value) or "does not divide" in str(e.value)
+    # the container of the witness (checked ahead of the witness length; the witness body itself stays as it is)
+    import struct
+    wt = open(__import__("conftest").golden_path("plonk_small.wtns"), "rb").read()
+    secs = f.read_binfile(wt, "wtns", 2)
+    pos2, len2 = secs[2][0]
+    for case, text in ((wt[:20], "wtns: Invalid File format"),                                                   # cut inside the first record
+                       (wt[:pos2 - 8] + struct.pack("<Q", len2 + 1) + wt[pos2:], "wtns: Invalid File format"),   # section 2 one past the end
+                       (wt[:4] + struct.pack("<I", 3) + wt[8:], "Version not supported"),
+                       (f.write_binfile("wtns", 2, [(1, f.section(wt, secs, 1))]), "wtns: Invalid File format")):
+        with pytest.raises(amd.G16Error) as e:
+            prover.prove(case)
+        assert (e.value.code, str(e.value)) == (-2, text)
     prover.close()
 
 

@@ -199,6 +199,15 @@ def test_prove_errors_match_snarkjs(amd):
     bad[pos2 + 32 * 5:pos2 + 32 * 6] = f.le(b.R + 3)
     with pytest.raises(amd.G16Error, match="signal 5 is not reduced"):
         prover.prove(bytes(bad))
+    # the container of the witness (the witness body itself stays as it is)
+    size2 = struct.pack("<Q", secs[2][0][1] + 1)
+    for case, text in ((wt[:20], "wtns: Invalid File format"),                                     # cut inside the first record
+                       (wt[:pos2 - 8] + size2 + wt[pos2:], "wtns: Invalid File format"),           # section 2 one past the end
+                       (wt[:4] + struct.pack("<I", 3) + wt[8:], "Version not supported"),
+                       (f.write_binfile("wtns", 2, [(1, f.section(wt, secs, 1))]), "wtns: Missing section 2")):
+        with pytest.raises(amd.G16Error) as e:
+            prover.prove(case)
+        assert (e.value.code, str(e.value)) == (-2, text)
     prover.close()
 
 
