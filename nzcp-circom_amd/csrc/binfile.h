@@ -78,6 +78,7 @@ struct Buf {   // a malloc'd image handed to the caller of the C ABI (g16_free)
   void u32(uint32_t v) { put(&v, 4); }
   void u64(uint64_t v) { put(&v, 8); }
   uint8_t* skip(size_t n) { uint8_t* q = p + len; len += n; return q; }
+  void give(uint8_t** out, size_t* out_len) const { *out = p; *out_len = len; }
 };
 
 // The whole image reserved and framed: header, then for each of ids[0, nids) (each below 16, in file order) its record

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <functional>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -28,6 +29,24 @@ const char* get_error();
     }                                                                                      \
   } while (0)
 
+// the device check of the routes without a CPU path; called after every input check
+inline int require_hip_device(const char* route, int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    set_error(std::string(route) + ": no HIP device (there is no CPU path)");
+    return G16_E_NOGPU;
+  }
+  if (device < 0 || device >= ndev) { set_error(std::string(route) + ": bad device ordinal"); return G16_E_ARG; }
+  return G16_OK;
+}
+template <class Fn> int no_bad_alloc(const char* route, Fn fn) {   // no C++ exception crosses the C ABI
+  try {
+    return fn();
+  } catch (const std::bad_alloc&) {
+    set_error(std::string(route) + ": out of memory");
+    return G16_E_STATE;
+  }
+}
 
 // ---------------------------------------------------------------- sharded pipeline inside ONE process (prover.cpp -> multi.cpp)
 // Enqueue-only pieces of the two-phase sharded proof (g16_shard_begin / g16_shard_end are the same pieces with host
@@ -56,6 +75,10 @@ void shard_drain(g16_prover* p);
 // out[i] = [k_i] G as affine Montgomery bytes; tbl = host table [nwin][2^wb - 1] of d * 2^(wb j) * G, k in Montgomery form
 int setup_fixed_mul_g1(int device, const G1Affine* tbl, int wb, int nwin, const Fr* ks_mont, size_t n, uint8_t* out);
 int setup_fixed_mul_g2(int device, const G2Affine* tbl, int wb, int nwin, const Fr* ks_mont, size_t n, uint8_t* out);
+
+// ---------------------------------------------------------------- PLONK setup on the device (plonk.hip)
+int plonk_setup_polys(int device, int L, const Fr* const evals[8], uint8_t* const out[8]);
+int plonk_setup_commit(int device, const uint8_t* tau_g1, uint32_t N, const uint8_t* const coefs[8], uint8_t* out);
 
 // ---------------------------------------------------------------- setup from a prepared .ptau (setup_ptau.hip)
 // Sparse point combination: out[o] = sum of coef_t * bases[base_t] over the terms t of output o, terms in CSC order

@@ -14,10 +14,13 @@
 // template by template, and is pinned by the reference's own test vectors (tests/test_cpu_nzcp_circuit.py:
 // /root/reference/test/cbor.js, quinSelector.js, nzcp.js) and its golden public signals.
 //
-// Implementation header of synth.cpp: included inside namespace g16 { namespace { ... } } after ShaBuilder.
+// CBuilder extends sha_builder.h's ShaBuilder; the entry points are in circuit_builders.cpp.
 #pragma once
-
 #include <unordered_map>
+
+#include "sha_builder.h"
+
+namespace g16 {
 
 struct CBuilder : ShaBuilder {
   // ShaBuilder::w holds small non-negative wire values; the few wires that carry a general field element (the
@@ -527,3 +530,5 @@ struct CBuilder : ShaBuilder {
     c.m = (uint32_t)c.rowA.size() - 1;
   }
 };
+
+}  // namespace g16

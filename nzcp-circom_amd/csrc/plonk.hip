@@ -1106,7 +1106,7 @@ int plonk_prove_impl(g16_plonk* P, const uint8_t* wtns, size_t wlen, const uint8
 
 }  // namespace
 
-// setup helper (synth.cpp::g16_plonk_setup): for each of 8 evaluation vectors (N Montgomery words on the host), the N
+// setup helper (setup_plonk.cpp::g16_plonk_setup): for each of 8 evaluation vectors (N Montgomery words on the host), the N
 // coefficients and the 4N evaluations, written back to back at out[k] (5N words)
 namespace g16 {
 int plonk_setup_polys(int device, int L, const Fr* const evals[8], uint8_t* const out[8]) {
@@ -1153,7 +1153,7 @@ int plonk_setup_polys(int device, int L, const Fr* const evals[8], uint8_t* cons
 }
 }  // namespace g16
 
-// setup with a real .ptau (synth.cpp::g16_plonk_setup_ptau): the eight commitments sum coef_i [tau^i]G1 by MSM over the
+// setup with a real .ptau (setup_plonk.cpp::g16_plonk_setup_ptau): the eight commitments sum coef_i [tau^i]G1 by MSM over the
 // first N powers; coefs[k] = N Montgomery words on the host, out = 8 affine Montgomery points
 namespace g16 {
 int plonk_setup_commit(int device, const uint8_t* tau_g1, uint32_t N, const uint8_t* const coefs[8], uint8_t* out) {

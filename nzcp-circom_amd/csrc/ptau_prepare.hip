@@ -1,5 +1,5 @@
 // Inverse Fourier transform over group elements on the device: `snarkjs powersoftau prepare phase2`
-// (synth.cpp::g16_ptau_prepare).  One call transforms one section of a .ptau file:
+// (ptau.cpp::g16_ptau_prepare).  One call transforms one section of a .ptau file:
 //   block k (k = 0 .. kmax, 2^k points, first point 2^k - 1) holds  out_j = (1/2^k) sum_{i<2^k} w_k^(-ij) P_i
 // with P_i the i-th point of the source section (infinity from index nsrc on: the top block of section 12 has one
 // input less than points) and w_k = the 2^k-th root of unity of oracle/groth16.py::fr_root (w_k = w_{k+1}^2).

@@ -1,8 +1,8 @@
 // Fixed-base scalar multiplication on the device: out[i] = [k_i] G for the millions of trapdoor scalars of a
-// TEST-ONLY Groth16 setup, the trapdoor route of synth.cpp::setup_core: the scalars
+// TEST-ONLY Groth16 setup, the trapdoor route of setup_groth16.cpp::setup_core: the scalars
 // u_i(tau), v_i(tau), (beta u_i + alpha v_i + w_i)/gamma|delta, L_{2i+1}(tau)/delta are evaluated on the host from a
 // KNOWN trapdoor, so anyone holding it can forge proofs.  The real `snarkjs groth16 setup` ([EXT] snarkjs 0.4.12) takes
-// its points from a prepared powers-of-tau file instead: that route is synth.cpp::g16_groth16_setup_ptau with the
+// its points from a prepared powers-of-tau file instead: that route is setup_groth16.cpp::g16_groth16_setup_ptau with the
 // sparse point sums of setup_ptau.hip.  Also the generator of the test ceremonies (g16_ptau_synth).
 //
 // Two kernels per chunk of points, both on the canonical 8x32-bit Montgomery field (fp.cuh / ec.cuh: exact,

@@ -1,5 +1,5 @@
 // Sparse point combination on the device: the Groth16 setup from a prepared powers-of-tau file
-// (synth.cpp::g16_groth16_setup_ptau, `snarkjs groth16 setup c.r1cs pot.ptau c_0000.zkey`).
+// (setup_groth16.cpp::g16_groth16_setup_ptau, `snarkjs groth16 setup c.r1cs pot.ptau c_0000.zkey`).
 //
 // Every point section of that key is a sparse matrix times a vector of ceremony points, one sum per wire:
 //   out[o] = sum over the terms t of output o of  coef_t * bases[base_t]
