@@ -344,7 +344,7 @@ int g16_plonk_setup_files(const char* r1cs_path, const char* ptau_path, const ch
  * points on `device` (there is no CPU path: G16_E_NOGPU).  Only blocks L (13-15) and L + 1 (12) are uploaded, 2^L the
  * smallest domain with 2^L >= m + p + 1.  The key is a fresh _0000 key: gamma = delta = 1 and section 10 (the
  * contribution hash, csHash) is 64 zero bytes and no contributions.  Correct, but NOT safe to deploy until a phase-2
- * contribution changes delta (`zkey contribute`, not implemented here).
+ * contribution changes delta (`zkey contribute`: g16_zkey_contribute below).
  * Every input is checked before the device is touched: the r1cs as g16_r1cs_setup reads it; "Powers of tau is not
  * prepared." (no section 12); "ptau: Invalid File format" (a section that is not whole blocks or has more than the
  * power allows); "circuit too big for this power of tau ceremony. M > 2**P" when block L or L + 1 is missing. */
@@ -381,6 +381,51 @@ int g16_r1cs_setup_trapdoor(const uint8_t* r1cs, size_t r1cs_len, const uint8_t 
  * (12 through block power + 1, 13-15 through block power).  power <= 24; device -1 = host threads. */
 int g16_ptau_synth(uint32_t power, const uint8_t tau_alpha_beta[3 * 32], int prepared, int device, uint8_t** ptau,
                    size_t* ptau_len);
+
+/* `snarkjs zkey contribute old.zkey new.zkey --name=.. -e=..`: one phase-2 contribution to a Groth16 .zkey (g16_free).
+ * secret = d | s, two standard-form 32-byte LE scalars in [1, r) (anything else: G16_E_ARG), or NULL for the OS CSPRNG;
+ * like g16_prove's explicit r, s the same inputs give the same bytes.  g1_s = [s]G1, g1_sx = [d]g1_s; transcript =
+ * Blake2b-512(csHash | hashPubKey of every earlier record | g1_s | g1_sx); g2_sp = the transcript's point on G2
+ * (g16_zkey_hash_to_g2), g2_spx = [d]g2_sp; delta1, delta2 of the header <- [d]delta; sections 8 and 9 <- [1/d] section,
+ * on `device` (there is no CPU path: G16_E_NOGPU); sections 1, 3-7 byte for byte; section 10 = the old csHash, the old
+ * records and the new one (deltaAfter | g1_s | g1_sx | g2_spx | transcript | u32 type = 0 | u32 paramsLen | params;
+ * params = byte 1, byte len, the name's UTF-8 bytes cut to 64 characters and 255 bytes, or nothing without a name).
+ * Section order and ids as in the input.  contribution_hash (optional) = Blake2b-512(hashPubKey(new record)), what
+ * snarkjs prints as "Contribution Hash".  hashPubKey feeds deltaAfter, g1_s, g1_sx, g2_spx in uncompressed big-endian
+ * standard form (G1: x | y; G2: x.c1 | x.c0 | y.c1 | y.c0; infinity: zeros with bit 0x40 of byte 0), then the transcript.
+ * Every input is checked before the device is touched: "zkey file is not groth16", "zkey: Invalid File format" (the
+ * container, the header, section sizes, a section 10 shorter than its records say or with trailing bytes, a point
+ * coordinate >= q or a point off its curve).  A beacon record (type 1) in the input is carried and hashed like any other.
+ * NOT implemented: `zkey beacon`; the csHash of `zkey new` (this library's _0000 keys hold 64 zero bytes there, the
+ * chain is hashed from whatever section 10 holds), so `snarkjs zkey verify` rejects these keys: the file layout and the
+ * proofs are snarkjs's, its ceremony verifier is not claimed.  The G2 derivation is NOT cross-checked against snarkjs. */
+int g16_zkey_contribute(const uint8_t* zkey, size_t zkey_len, const char* name /* or NULL */,
+                        const uint8_t secret[64] /* d | s, or NULL = OS CSPRNG */, int device,
+                        uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]);
+/* the same from / to files: the input is mapped read-only and the key is written in chunks */
+int g16_zkey_contribute_files(const char* in_path, const char* out_path, const char* name,
+                              const uint8_t secret[64], int device, uint8_t contribution_hash[64]);
+/* `snarkjs zkey verify frominit init.zkey pot.ptau circuit.zkey` without the ptau leg (section 9 is not recomputed from
+ * a ceremony file): is `zkey` the key `init` plus a chain of honest contributions?  G16_OK with *ok = 1 / 0; for 0
+ * g16_last_error() holds the reason, one fixed text per check, each led by "zkey verify: ":
+ *   "the header differs from the initial key's (sizes, alpha, beta or gamma)", "sections 3 to 7 differ from the initial
+ *   key's", "the circuit hash differs from the initial key's", "the contributions do not begin with the initial key's",
+ *   "section 8 or 9 has not the initial key's length", "a contribution's transcript hash does not match", "a
+ *   contribution holds the point at infinity", "a contribution's public key is not consistent" (e(g1_s, g2_spx) !=
+ *   e(g1_sx, g2_sp)), "a contribution's delta does not continue the chain" (e(cur, g2_spx) != e(deltaAfter, g2_sp)),
+ *   "delta1 of the header is not the last contribution's", "delta2 does not match delta1", "sections 8 and 9 are not the
+ *   initial key's scaled by 1 / delta" (with fresh random rho_i over both sections together: S = sum rho_i new_i, T =
+ *   sum rho_i init_i, e(S, delta2) != e(T, delta2 of init), or the infinity points differ), "the combination of
+ *   sections 8 and 9 is the point at infinity".
+ * A key with no records beyond init's (init against itself) is accepted.  A malformed file is G16_E_FORMAT, not a
+ * verdict.  The two sums are MSMs and the pairings Miller loops + final exponentiations on `device` (G16_E_NOGPU). */
+int g16_zkey_verify_from_init(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_t zkey_len,
+                              int device, int* ok);
+int g16_zkey_verify_from_init_files(const char* init_path, const char* zkey_path, int device, int* ok);
+/* Layer operators of the two routes above, host only.  Blake2b-512 (RFC 7693, unkeyed); the transcript's point on G2
+ * (ChaCha20 keyed with the first 32 bytes, x drawn as the Montgomery image, cofactor 2q - r; affine LE Montgomery). */
+int g16_blake2b512(const uint8_t* data, size_t len, uint8_t out[64]);
+int g16_zkey_hash_to_g2(const uint8_t transcript[64], uint8_t out[128] /* affine LE Montgomery */);
 
 /* PLONK batch verifier on the device: [EXT] snarkjs 0.4.12 plonk_verify.js `plonk.verify(vk, publicSignals, proof)` for
  * many proofs against one key, one verdict per proof (transcript and scalar arithmetic on host threads, the twenty

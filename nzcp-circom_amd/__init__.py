@@ -69,7 +69,9 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_plonk_create", "g16_plonk_prove", "g16_plonk_get_info", "g16_plonk_destroy", "g16_plonk_setup", "g16_plonk_timings", "g16_plonk_setup_ptau", "g16_plonk_setup_files",
            "g16_plonk_verifier_create", "g16_plonk_verify_batch", "g16_plonk_verifier_destroy",
            "g16_groth16_setup_ptau", "g16_groth16_setup_files", "g16_r1cs_setup_trapdoor", "g16_ptau_synth",
-           "g16_ptau_prepare", "g16_ptau_prepare_files"]
+           "g16_ptau_prepare", "g16_ptau_prepare_files",
+           "g16_zkey_contribute", "g16_zkey_contribute_files", "g16_zkey_verify_from_init",
+           "g16_zkey_verify_from_init_files", "g16_blake2b512", "g16_zkey_hash_to_g2"]
 
 
 def load():
@@ -148,6 +150,12 @@ def load():
     lib.g16_ptau_synth.argtypes = [C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(sz)]
     lib.g16_ptau_prepare.argtypes = [C.c_char_p, sz, C.c_int, C.POINTER(vp), C.POINTER(sz)]
     lib.g16_ptau_prepare_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
+    lib.g16_zkey_contribute.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
+    lib.g16_zkey_contribute_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
+    lib.g16_zkey_verify_from_init.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_zkey_verify_from_init_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_blake2b512.argtypes = [C.c_char_p, sz, C.c_char_p]
+    lib.g16_zkey_hash_to_g2.argtypes = [C.c_char_p, C.c_char_p]
     lib.g16_r1cs_setup.argtypes = [C.c_char_p, sz, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
     lib.g16_sha256_chain_setup.argtypes = [C.c_uint32, C.c_char_p, C.c_uint64, C.c_int] + [C.c_void_p] * 8
     lib.g16_sha256_message_setup.argtypes = [C.c_char_p, C.c_uint32, C.c_uint64, C.c_int] + [C.c_void_p] * 8
@@ -729,6 +737,43 @@ def ptau_prepare(ptau, device=0):
     z, zl = C.c_void_p(), C.c_size_t()
     _check(load().g16_ptau_prepare(ptau, len(ptau), device, C.byref(z), C.byref(zl)))
     return _take(z, zl)
+
+
+def zkey_contribute(zkey, name=None, d=None, s=None, device=0):
+    """`snarkjs zkey contribute`: Groth16 .zkey bytes -> (contributed .zkey bytes, 64-byte contribution hash).  d, s:
+    the contribution's secret scalars in [1, r) (both or neither; neither = OS CSPRNG): delta <- d delta."""
+    if (d is None) != (s is None):
+        raise ValueError("zkey_contribute: give both d and s, or neither")
+    secret = None if d is None else int(d).to_bytes(32, "little") + int(s).to_bytes(32, "little")
+    z, zl = C.c_void_p(), C.c_size_t()
+    h = C.create_string_buffer(64)
+    nm = None if name is None else name.encode("utf-8")
+    _check(load().g16_zkey_contribute(zkey, len(zkey), nm, secret, device, C.byref(z), C.byref(zl), h))
+    return _take(z, zl), h.raw
+
+
+def zkey_verify_from_init(init, zkey, device=0):
+    """`snarkjs zkey verify frominit` without the ptau leg -> (ok, reason): is `zkey` the key `init` plus a chain of
+    honest contributions?  reason is empty when ok.  A malformed file raises G16Error(-2)."""
+    ok = C.c_int(0)
+    lib = load()
+    _check(lib.g16_zkey_verify_from_init(init, len(init), zkey, len(zkey), device, C.byref(ok)))
+    return bool(ok.value), ("" if ok.value else lib.g16_last_error().decode("utf-8", "replace"))
+
+
+def blake2b512(data):
+    out = C.create_string_buffer(64)
+    _check(load().g16_blake2b512(data, len(data), out))
+    return out.raw
+
+
+def zkey_hash_to_g2(transcript):
+    """The point on G2 a contribution's 64-byte transcript hash selects (affine little-endian Montgomery, 128 bytes)."""
+    if len(transcript) != 64:
+        raise ValueError("zkey_hash_to_g2: 64 bytes expected")
+    out = C.create_string_buffer(128)
+    _check(load().g16_zkey_hash_to_g2(transcript, out))
+    return out.raw
 
 
 def r1cs_setup_trapdoor(r1cs, td, threads=0):

@@ -110,6 +110,16 @@ struct PtauPrepareStats {
 int ptau_prepare_g1(int device, const uint8_t* src, uint64_t nsrc, int kmax, uint8_t* out, PtauPrepareStats* st);
 int ptau_prepare_g2(int device, const uint8_t* src, uint64_t nsrc, int kmax, uint8_t* out, PtauPrepareStats* st);
 
+// ---------------------------------------------------------------- zkey contribute (zkey_scale.hip)
+// out[i] = [k] in[i]: n affine Montgomery G1 points (host, file layout; infinity = zero bytes in and out) times ONE
+// scalar k (standard form, in [1, r)), in chunks over two streams.  No CPU path (G16_E_NOGPU).
+struct ZkeyScaleStats {
+  float kern_ms = 0.f;   // device time of the kernels (scaling + conversion to affine), all chunks
+  float xfer_ms = 0.f;   // device time of the copies in and out
+  uint64_t points = 0;
+};
+int zkey_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& k_std, uint8_t* out, ZkeyScaleStats* st);
+
 // ---------------------------------------------------------------- NTT (ntt.hip)
 struct NttPass { int lo_bits, S, tb; };
 struct NttTables {

@@ -1,0 +1,638 @@
+// `snarkjs zkey contribute` and the chain check of `snarkjs zkey verify` for Groth16 keys ([EXT] snarkjs 0.4.12
+// zkey_contribute.js, zkey_verify_frominit.js, zkey_utils.js, mpc_applykey.js; ffjavascript chacha.js / random point).
+//   contribute: delta <- d delta in the header, sections 8 and 9 <- [1/d] section (zkey_scale.hip), one record more in
+//               section 10; everything else byte for byte.
+//   verify:     the key is the initial key plus a chain of honest contributions -- the hash chain and the same-ratio
+//               pairing checks of every record, and one random linear combination over sections 8 and 9 (two MSMs on
+//               the G1 Pippenger, pairings on the verifier's device code).
+// NOT here, on purpose: `zkey beacon`; the real csHash of `zkey new` (section 10 of this library's _0000 keys holds 64
+// zero bytes, and the chain is hashed from whatever section 10 holds); the ptau-based recomputation of section 9.
+// Because csHash is not snarkjs's, `snarkjs zkey verify` rejects these keys: the file LAYOUT and the proofs are
+// compatible, snarkjs's ceremony verifier is not claimed.
+#include "zkey_mpc.h"
+
+#include <fcntl.h>
+#include <unistd.h>
+
+#include <chrono>
+
+#include "internal.h"
+#include "mapped_file.h"
+
+namespace g16 {
+
+// ------------------------------------------------------------------ Blake2b-512 (RFC 7693)
+namespace {
+const uint64_t kB2Iv[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                           0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+const uint8_t kB2Sigma[12][16] = {
+    {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
+    {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
+    {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
+    {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
+    {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0},
+    {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3}};
+inline uint64_t rotr64(uint64_t x, int n) { return (x >> n) | (x << (64 - n)); }
+
+void b2_compress(uint64_t h[8], const uint8_t block[128], uint64_t t, bool last) {
+  uint64_t m[16], v[16];
+  for (int i = 0; i < 16; i++) m[i] = rd64(block + 8 * i);
+  for (int i = 0; i < 8; i++) { v[i] = h[i]; v[i + 8] = kB2Iv[i]; }
+  v[12] ^= t;   // (t < 2^64: the high counter word stays zero)
+  if (last) v[14] = ~v[14];
+  auto G = [&](int a, int b, int c, int d, uint64_t x, uint64_t y) {
+    v[a] = v[a] + v[b] + x; v[d] = rotr64(v[d] ^ v[a], 32);
+    v[c] = v[c] + v[d];     v[b] = rotr64(v[b] ^ v[c], 24);
+    v[a] = v[a] + v[b] + y; v[d] = rotr64(v[d] ^ v[a], 16);
+    v[c] = v[c] + v[d];     v[b] = rotr64(v[b] ^ v[c], 63);
+  };
+  for (int r = 0; r < 12; r++) {
+    const uint8_t* s = kB2Sigma[r];
+    G(0, 4, 8, 12, m[s[0]], m[s[1]]);
+    G(1, 5, 9, 13, m[s[2]], m[s[3]]);
+    G(2, 6, 10, 14, m[s[4]], m[s[5]]);
+    G(3, 7, 11, 15, m[s[6]], m[s[7]]);
+    G(0, 5, 10, 15, m[s[8]], m[s[9]]);
+    G(1, 6, 11, 12, m[s[10]], m[s[11]]);
+    G(2, 7, 8, 13, m[s[12]], m[s[13]]);
+    G(3, 4, 9, 14, m[s[14]], m[s[15]]);
+  }
+  for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
+}
+}  // namespace
+
+void blake2b512(const uint8_t* data, size_t len, uint8_t out[64]) {
+  uint64_t h[8];
+  for (int i = 0; i < 8; i++) h[i] = kB2Iv[i];
+  h[0] ^= 0x01010000ull ^ 64;   // digest length 64, no key, fanout = depth = 1
+  size_t off = 0;
+  while (len - off > 128) {
+    b2_compress(h, data + off, (uint64_t)off + 128, false);
+    off += 128;
+  }
+  uint8_t block[128] = {0};
+  if (len - off) memcpy(block, data + off, len - off);
+  b2_compress(h, block, (uint64_t)len, true);
+  memcpy(out, h, 64);   // little-endian words
+}
+
+// ------------------------------------------------------------------ field and curve helpers
+namespace {
+
+bool limbs_below(const uint32_t a[8], const uint32_t m[8]) {
+  for (int i = 7; i >= 0; i--)
+    if (a[i] != m[i]) return a[i] < m[i];
+  return false;
+}
+Fq fq_load(const uint8_t* p) { Fq x; memcpy(x.v, p, 32); return x; }
+Fq fq_b3() { Fq t = fp_zero<FqParams>(); t.v[0] = 3; return fp_to_mont(t); }
+Fq2 twist_b() { return Fq2{Fq{G16_G2B_C0}, Fq{G16_G2B_C1}}; }
+
+// file images (affine LE Montgomery): coordinates below q and the point on its curve; the all-zero image is infinity
+bool g1_image_ok(const uint8_t* p) {
+  const Fq x = fq_load(p), y = fq_load(p + 32);
+  if (!limbs_below(x.v, kFqP) || !limbs_below(y.v, kFqP)) return false;
+  if (fp_is_zero(x) && fp_is_zero(y)) return true;
+  return fp_eq(fp_sqr(y), fp_add(fp_mul(fp_sqr(x), x), fq_b3()));
+}
+bool g2_image_ok(const uint8_t* p) {
+  Fq c[4];
+  for (int i = 0; i < 4; i++) {
+    c[i] = fq_load(p + 32 * i);
+    if (!limbs_below(c[i].v, kFqP)) return false;
+  }
+  const Fq2 x{c[0], c[1]}, y{c[2], c[3]};
+  if (Fq2Ops::is_zero(x) && Fq2Ops::is_zero(y)) return true;
+  return Fq2Ops::eq(Fq2Ops::sqr(y), Fq2Ops::add(Fq2Ops::mul(Fq2Ops::sqr(x), x), twist_b()));
+}
+bool all_zero(const uint8_t* p, size_t n) {
+  for (size_t i = 0; i < n; i++) if (p[i]) return false;
+  return true;
+}
+
+void be32(const Fq& std_form, uint8_t out[32]) {
+  for (int i = 0; i < 8; i++) {
+    const uint32_t w = std_form.v[7 - i];
+    out[4 * i] = (uint8_t)(w >> 24); out[4 * i + 1] = (uint8_t)(w >> 16); out[4 * i + 2] = (uint8_t)(w >> 8); out[4 * i + 3] = (uint8_t)w;
+  }
+}
+
+// a^((q + 1) / 4): the square root when a is a square (q = 3 mod 4)
+bool fq_sqrt(const Fq& a, Fq& root) {
+  uint32_t e[8];
+  uint64_t c = 1;
+  for (int i = 0; i < 8; i++) { c += kFqP[i]; e[i] = (uint32_t)c; c >>= 32; }
+  for (int i = 0; i < 8; i++) e[i] = (e[i] >> 2) | (i < 7 ? e[i + 1] << 30 : 0);
+  root = fp_pow(a, e);
+  return fp_eq(fp_sqr(root), a);
+}
+bool fq2_sqrt(const Fq2& a, Fq2& root) {
+  const Fq zero = fp_zero<FqParams>();
+  if (fp_is_zero(a.b)) {
+    Fq s;
+    if (fq_sqrt(a.a, s)) { root = Fq2{s, zero}; return true; }
+    if (fq_sqrt(fp_neg(a.a), s)) { root = Fq2{zero, s}; return true; }   // (s u)^2 = -s^2
+    return false;
+  }
+  Fq n;
+  if (!fq_sqrt(fp_add(fp_sqr(a.a), fp_sqr(a.b)), n)) return false;   // the norm of a square is a square
+  const Fq two_inv = fp_inv(fp_add(fp_one<FqParams>(), fp_one<FqParams>()));
+  Fq x0;
+  if (!fq_sqrt(fp_mul(fp_add(a.a, n), two_inv), x0) && !fq_sqrt(fp_mul(fp_sub(a.a, n), two_inv), x0)) return false;
+  const Fq x1 = fp_mul(a.b, fp_inv(fp_add(x0, x0)));
+  root = Fq2{x0, x1};
+  return Fq2Ops::eq(Fq2Ops::sqr(root), a);
+}
+// "negative": the standard value is above (q - 1) / 2; for Fq2 that of c1 unless c1 = 0
+bool fq_is_negative(const Fq& a_mont) {
+  uint32_t half[8];
+  for (int i = 0; i < 8; i++) half[i] = (kFqP[i] >> 1) | (i < 7 ? kFqP[i + 1] << 31 : 0);   // (q - 1) / 2, q odd
+  const Fq s = fp_from_mont(a_mont);
+  return !limbs_below(s.v, half) && memcmp(s.v, half, 32) != 0;
+}
+bool fq2_is_negative(const Fq2& a) { return fp_is_zero(a.b) ? fq_is_negative(a.a) : fq_is_negative(a.b); }
+
+// ChaCha20 block function as a word stream
+struct ChaCha {
+  uint32_t key[8];
+  uint64_t counter = 0;
+  uint32_t buf[16];
+  int have = 0;
+  static uint32_t rotl(uint32_t x, int n) { return (x << n) | (x >> (32 - n)); }
+  void refill() {
+    uint32_t s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
+    for (int i = 0; i < 8; i++) s[4 + i] = key[i];
+    s[12] = (uint32_t)counter; s[13] = (uint32_t)(counter >> 32); s[14] = 0; s[15] = 0;
+    uint32_t x[16];
+    memcpy(x, s, sizeof(x));
+    auto qr = [&](int a, int b, int c, int d) {
+      x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 16);
+      x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 12);
+      x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 8);
+      x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 7);
+    };
+    for (int r = 0; r < 10; r++) {
+      qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15);
+      qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14);
+    }
+    for (int i = 0; i < 16; i++) buf[i] = x[i] + s[i];
+    counter++;
+    have = 16;
+  }
+  uint32_t next_u32() {
+    if (!have) refill();
+    return buf[16 - have--];
+  }
+  uint64_t next_u64() { const uint64_t hi = next_u32(); return hi << 32 | next_u32(); }
+  // sum_i next_u64 2^(64 i) masked to 254 bits, redrawn until below the modulus
+  void next_below(const uint32_t mod[8], uint32_t out[8]) {
+    for (;;) {
+      for (int i = 0; i < 4; i++) { const uint64_t w = next_u64(); out[2 * i] = (uint32_t)w; out[2 * i + 1] = (uint32_t)(w >> 32); }
+      out[7] &= 0x3fffffffu;
+      if (limbs_below(out, mod)) return;
+    }
+  }
+};
+
+int os_random(uint8_t* out, size_t n) {
+  const int fd = open("/dev/urandom", O_RDONLY);
+  if (fd < 0) { set_error("cannot open /dev/urandom"); return G16_E_STATE; }
+  const bool ok = read(fd, out, n) == (ssize_t)n;
+  close(fd);
+  if (!ok) { set_error("short read from /dev/urandom"); return G16_E_STATE; }
+  return G16_OK;
+}
+
+template <class F> void mul_image(const uint8_t* lem, const Fr& k_std, uint8_t* out) {   // [k] P on the host, file images
+  Affine<F> p, r;
+  memcpy(&p, lem, sizeof(p));
+  XYZZ<F> acc;
+  xyzz_mul_scalar(acc, p, k_std.v);
+  xyzz_to_affine(r, acc);
+  memcpy(out, &r, sizeof(r));
+}
+
+}  // namespace
+
+void g1_uncompressed(const uint8_t lem[64], uint8_t out[64]) {
+  if (all_zero(lem, 64)) { memset(out, 0, 64); out[0] = 0x40; return; }
+  be32(fp_from_mont(fq_load(lem)), out);
+  be32(fp_from_mont(fq_load(lem + 32)), out + 32);
+}
+void g2_uncompressed(const uint8_t lem[128], uint8_t out[128]) {   // x.c1 | x.c0 | y.c1 | y.c0
+  if (all_zero(lem, 128)) { memset(out, 0, 128); out[0] = 0x40; return; }
+  be32(fp_from_mont(fq_load(lem + 32)), out);
+  be32(fp_from_mont(fq_load(lem)), out + 32);
+  be32(fp_from_mont(fq_load(lem + 96)), out + 64);
+  be32(fp_from_mont(fq_load(lem + 64)), out + 96);
+}
+
+void mpc_hash_pubkey(std::vector<uint8_t>& feed, const MpcRecord& r) {
+  const size_t at = feed.size();
+  feed.resize(at + 64 + 64 + 64 + 128 + 64);
+  uint8_t* q = feed.data() + at;
+  g1_uncompressed(r.delta_after(), q);
+  g1_uncompressed(r.g1_s(), q + 64);
+  g1_uncompressed(r.g1_sx(), q + 128);
+  g2_uncompressed(r.g2_spx(), q + 192);
+  memcpy(q + 320, r.transcript(), 64);
+}
+
+// The transcript's point on G2, ffjavascript's construction as far as it can be restated without the package: a
+// ChaCha20 word stream keyed with the first 32 transcript bytes (eight big-endian words), field elements drawn as four
+// 64-bit words (low word first, each word = first u32 * 2^32 + second u32) masked to 254 bits and redrawn until below
+// q, THE DRAWN VALUE TAKEN AS THE MONTGOMERY IMAGE; x = (c0, c1), then one bit `greatest`; both redrawn until
+// x^3 + b' is a square; y = the root that is negative exactly when `greatest`; the point times the cofactor 2q - r.
+// NOT CROSS-CHECKED AGAINST snarkjs (ffjavascript is not available to the tests): the twin in tests/zkey_mpc_ref.py is
+// written from the same description.  The whole derivation lives in this one function, so a correction is a one-place
+// change (and one in the twin).
+void hash_to_g2(const uint8_t transcript[64], G2Affine& out) {
+  ChaCha rng;
+  for (int i = 0; i < 8; i++)
+    rng.key[i] = (uint32_t)transcript[4 * i] << 24 | (uint32_t)transcript[4 * i + 1] << 16 | (uint32_t)transcript[4 * i + 2] << 8 |
+                 transcript[4 * i + 3];
+  G2Affine p;
+  for (;;) {
+    rng.next_below(kFqP, p.x.a.v);
+    rng.next_below(kFqP, p.x.b.v);
+    const bool greatest = rng.next_u32() & 1;
+    const Fq2 rhs = Fq2Ops::add(Fq2Ops::mul(Fq2Ops::sqr(p.x), p.x), twist_b());
+    if (!fq2_sqrt(rhs, p.y)) continue;
+    if (fq2_is_negative(p.y) != greatest) p.y = Fq2Ops::neg(p.y);
+    break;
+  }
+  uint32_t cof[8];   // 2q - r
+  {
+    int64_t c = 0;
+    for (int i = 0; i < 8; i++) {
+      c += 2 * (int64_t)kFqP[i] - (int64_t)kFrP[i];
+      cof[i] = (uint32_t)c;
+      c >>= 32;
+    }
+  }
+  G2XYZZ acc;
+  xyzz_mul_scalar(acc, p, cof);
+  xyzz_to_affine(out, acc);
+}
+
+int mpc_parse(const BinSection& s10, MpcSection& out) {
+  auto bad = []() { set_error("zkey: Invalid File format"); return G16_E_FORMAT; };
+  out = MpcSection{};
+  if (!s10.p || s10.size < 68) return bad();
+  out.cs_hash = s10.p;
+  const uint32_t n = rd32(s10.p + 64);
+  uint64_t pos = 68;
+  for (uint32_t i = 0; i < n; i++) {
+    if (s10.size - pos < kMpcRecordFixed) return bad();
+    const uint8_t* r = s10.p + pos;
+    const uint32_t plen = rd32(r + kMpcRecordFixed - 4);
+    if (s10.size - pos - kMpcRecordFixed < plen) return bad();
+    if (!g1_image_ok(r) || !g1_image_ok(r + 64) || !g1_image_ok(r + 128) || !g2_image_ok(r + 192)) return bad();
+    out.rec.push_back(MpcRecord{r, kMpcRecordFixed + plen});
+    pos += kMpcRecordFixed + plen;
+  }
+  if (pos != s10.size) return bad();
+  return G16_OK;
+}
+
+// ------------------------------------------------------------------ the key as both routes read it
+namespace {
+
+constexpr size_t kHdrDelta1 = 468, kHdrDelta2 = 532, kHdrEnd = 660;
+
+struct KeyView {
+  BinView f;
+  uint32_t nVars = 0, nPublic = 0, N = 0;
+  MpcSection mpc;
+};
+
+// exact_89: sections 8 and 9 must have the header's sizes (the verifier only needs whole points: a short section is a
+// verdict there, not a malformed file)
+int open_key(const uint8_t* zkey, size_t len, KeyView& k, bool exact_89) {
+  auto bad = []() { set_error("zkey: Invalid File format"); return G16_E_FORMAT; };
+  if (const int rc = bin_open(zkey, len, "zkey", 2, k.f)) return rc;
+  const BinSection& s1 = k.f.sec[1];
+  if (!s1.p) return bad();
+  if (s1.size < 4 || rd32(s1.p) != 1) { set_error("zkey file is not groth16"); return G16_E_FORMAT; }
+  const BinSection& s2 = k.f.sec[2];
+  if (!s2.p || s2.size < kHdrEnd || rd32(s2.p) != 32 || rd32(s2.p + 36) != 32) return bad();
+  if (!bin_is_field(s2.p, 36, kFqP) || !bin_is_field(s2.p + 36, 36, kFrP)) {
+    set_error("Curve not supported: zkey is not over bn128");
+    return G16_E_FORMAT;
+  }
+  k.nVars = rd32(s2.p + 72);
+  k.nPublic = rd32(s2.p + 76);
+  k.N = rd32(s2.p + 80);
+  if (k.N == 0 || (k.N & (k.N - 1)) || (uint64_t)k.nPublic + 1 > (uint64_t)k.nVars) return bad();
+  for (int id = 3; id <= 10; id++)
+    if (!k.f.sec[id].p) return bad();
+  const uint64_t nC = k.nVars - k.nPublic - 1;
+  const uint64_t want[10] = {0, 0, 0, ((uint64_t)k.nPublic + 1) * 64, 0, (uint64_t)k.nVars * 64, (uint64_t)k.nVars * 64,
+                             (uint64_t)k.nVars * 128, nC * 64, (uint64_t)k.N * 64};
+  for (int id = 3; id <= 9; id++) {
+    if (id == 4) continue;
+    if (id >= 8 && !exact_89 ? k.f.sec[id].size % 64 != 0 : k.f.sec[id].size != want[id]) return bad();
+  }
+  const BinSection& s4 = k.f.sec[4];
+  if (s4.size < 4 || (s4.size - 4) % 44 || (s4.size - 4) / 44 != rd32(s4.p)) return bad();
+  const uint8_t* h = s2.p;
+  if (!g1_image_ok(h + kHdrDelta1) || !g2_image_ok(h + kHdrDelta2) || all_zero(h + kHdrDelta1, 64) || all_zero(h + kHdrDelta2, 128))
+    return bad();
+  return mpc_parse(k.f.sec[10], k.mpc);
+}
+
+// csHash | hashPubKey of records [0, upto) | g1_s | g1_sx (uncompressed)  ->  the transcript of record `upto`
+void transcript_of(const MpcSection& m, size_t upto, const uint8_t* g1_s, const uint8_t* g1_sx, uint8_t out[64]) {
+  std::vector<uint8_t> feed(m.cs_hash, m.cs_hash + 64);
+  for (size_t i = 0; i < upto; i++) mpc_hash_pubkey(feed, m.rec[i]);
+  const size_t at = feed.size();
+  feed.resize(at + 128);
+  g1_uncompressed(g1_s, feed.data() + at);
+  g1_uncompressed(g1_sx, feed.data() + at + 64);
+  blake2b512(feed.data(), feed.size(), out);
+}
+
+bool scalar_ok(const uint8_t* s, Fr& out) {   // standard form, in [1, r)
+  memcpy(out.v, s, 32);
+  return !fp_is_zero(out) && fr_below_modulus(out.v);
+}
+
+double ms_since(const std::chrono::steady_clock::time_point& t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, const uint8_t* secret, int device, uint8_t** out,
+                    size_t* out_len, uint8_t contribution_hash[64]) {
+  const auto t0 = std::chrono::steady_clock::now();
+  KeyView k;
+  if (const int rc = open_key(zkey, zkey_len, k, true)) return rc;
+  Fr d, s;
+  if (secret) {
+    if (!scalar_ok(secret, d) || !scalar_ok(secret + 32, s)) { set_error("zkey contribute: the secret scalars must be in [1, r)"); return G16_E_ARG; }
+  } else {
+    for (Fr* x : {&d, &s})
+      for (;;) {
+        if (const int rc = os_random((uint8_t*)x->v, 32)) return rc;
+        x->v[7] &= 0x3fffffffu;
+        if (!fp_is_zero(*x) && fr_below_modulus(x->v)) break;
+      }
+  }
+  if (const int rc = require_hip_device("zkey contribute", device)) return rc;
+
+  // the record's name: at most 64 characters, and what one length byte can hold
+  std::string nm;
+  if (name) {
+    size_t chars = 0, i = 0;
+    const size_t len = strlen(name);
+    while (i < len && chars < 64) {
+      size_t j = i + 1;
+      while (j < len && ((uint8_t)name[j] & 0xc0) == 0x80) j++;
+      if (j > 255) break;
+      i = j;
+      chars++;
+    }
+    nm.assign(name, i);
+  }
+  const uint32_t plen = nm.empty() ? 0 : (uint32_t)(2 + nm.size());
+  const size_t rec_len = kMpcRecordFixed + plen;
+
+  // the image: every record of the input's table in its order, the first section 10 one record longer
+  struct Entry { uint32_t id; const uint8_t* p; uint64_t size; };
+  std::vector<Entry> table;
+  {
+    const uint32_t nsec = rd32(zkey + 8);
+    size_t pos = 12;   // (bin_open has walked and bounded this table)
+    for (uint32_t i = 0; i < nsec; i++) {
+      table.push_back(Entry{rd32(zkey + pos), zkey + pos + 12, rd64(zkey + pos + 4)});
+      pos += 12 + table.back().size;
+    }
+  }
+  size_t total = 12;
+  for (const Entry& e : table) total += 12 + e.size;
+  total += rec_len;
+  Buf z;
+  if (!z.reserve(total)) { set_error("zkey contribute: out of memory"); return G16_E_STATE; }
+  z.put(zkey, 12);
+  uint8_t* sp[16] = {};
+  for (const Entry& e : table) {
+    const bool first = e.id < 16 && e.p == k.f.sec[e.id].p;
+    z.u32(e.id);
+    z.u64(first && e.id == 10 ? e.size + rec_len : e.size);
+    uint8_t* q = z.skip(e.size);
+    if (first) sp[e.id] = q;
+    if (!(first && (e.id == 8 || e.id == 9))) memcpy(q, e.p, e.size);
+    if (first && e.id == 10) z.skip(rec_len);
+  }
+
+  // host: the contribution's points and the header's delta
+  uint8_t* rec = sp[10] + k.f.sec[10].size;
+  const uint8_t* hdr = k.f.sec[2].p;
+  {
+    G1Affine g1;   // (1, 2)
+    g1.x = fp_one<FqParams>();
+    g1.y = fp_add(g1.x, g1.x);
+    uint8_t* g1_s = rec + 64;
+    uint8_t* g1_sx = rec + 128;
+    mul_image<FqOps>((const uint8_t*)&g1, s, g1_s);
+    mul_image<FqOps>(g1_s, d, g1_sx);
+    uint8_t* tr = rec + 320;
+    transcript_of(k.mpc, k.mpc.rec.size(), g1_s, g1_sx, tr);
+    G2Affine sp2;
+    hash_to_g2(tr, sp2);
+    mul_image<Fq2Ops>((const uint8_t*)&sp2, d, rec + 192);
+    mul_image<FqOps>(hdr + kHdrDelta1, d, sp[2] + kHdrDelta1);
+    mul_image<Fq2Ops>(hdr + kHdrDelta2, d, sp[2] + kHdrDelta2);
+    memcpy(rec, sp[2] + kHdrDelta1, 64);   // deltaAfter
+    const uint32_t type = 0;
+    memcpy(rec + 384, &type, 4);
+    memcpy(rec + 388, &plen, 4);
+    if (plen) {
+      rec[392] = 1;
+      rec[393] = (uint8_t)nm.size();
+      memcpy(rec + 394, nm.data(), nm.size());
+    }
+    const uint32_t count = (uint32_t)k.mpc.rec.size() + 1;
+    memcpy(sp[10] + 64, &count, 4);
+    std::vector<uint8_t> feed;
+    mpc_hash_pubkey(feed, MpcRecord{rec, rec_len});
+    if (contribution_hash) blake2b512(feed.data(), feed.size(), contribution_hash);
+  }
+
+  // device: sections 8 and 9 times 1 / d
+  const Fr dinv = fp_from_mont(fp_inv(fp_to_mont(d)));
+  ZkeyScaleStats st[2];
+  int rc = zkey_scale_g1(device, k.f.sec[8].p, k.f.sec[8].size / 64, dinv, sp[8], &st[0]);
+  if (!rc) rc = zkey_scale_g1(device, k.f.sec[9].p, k.f.sec[9].size / 64, dinv, sp[9], &st[1]);
+  if (rc) { free(z.p); return rc; }
+  if (getenv("G16_TRACE_HOST"))
+    fprintf(stderr, "[g16] zkey contribute: points %llu; kernels %.3f ms, transfers %.3f ms, MSM 0.000 ms, pairings 0.000 ms; call %.3f ms\n",
+            (unsigned long long)(st[0].points + st[1].points), st[0].kern_ms + st[1].kern_ms, st[0].xfer_ms + st[1].xfer_ms, ms_since(t0));
+  z.give(out, out_len);
+  return G16_OK;
+}
+
+// ---- verify
+void pair_words(std::vector<uint8_t>& in, const uint8_t* g1_lem, const uint8_t* g2_lem) {   // g16_pairing_op's input
+  const size_t at = in.size();
+  in.resize(at + 192);
+  for (int i = 0; i < 2; i++) { const Fq v = fp_from_mont(fq_load(g1_lem + 32 * i)); memcpy(in.data() + at + 32 * i, v.v, 32); }
+  for (int i = 0; i < 4; i++) { const Fq v = fp_from_mont(fq_load(g2_lem + 32 * i)); memcpy(in.data() + at + 64 + 32 * i, v.v, 32); }
+}
+
+int verify_core(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_t zkey_len, int device, int* ok) {
+  const auto t0 = std::chrono::steady_clock::now();
+  *ok = 0;
+  KeyView a, b;   // a = init, b = the key under test
+  if (const int rc = open_key(init, init_len, a, true)) return rc;
+  if (const int rc = open_key(zkey, zkey_len, b, false)) return rc;
+  if (const int rc = require_hip_device("zkey verify", device)) return rc;
+  auto verdict = [&](const char* why) { set_error(why); return G16_OK; };
+
+  // 1. everything a contribution leaves alone
+  const uint8_t *ha = a.f.sec[2].p, *hb = b.f.sec[2].p;
+  if (a.nVars != b.nVars || a.nPublic != b.nPublic || a.N != b.N || memcmp(ha, hb, kHdrDelta1) != 0)
+    return verdict("zkey verify: the header differs from the initial key's (sizes, alpha, beta or gamma)");
+  for (int id = 3; id <= 7; id++)
+    if (a.f.sec[id].size != b.f.sec[id].size || memcmp(a.f.sec[id].p, b.f.sec[id].p, a.f.sec[id].size) != 0)
+      return verdict("zkey verify: sections 3 to 7 differ from the initial key's");
+  if (memcmp(a.mpc.cs_hash, b.mpc.cs_hash, 64) != 0) return verdict("zkey verify: the circuit hash differs from the initial key's");
+  // 2. the initial key's own records
+  if (b.mpc.rec.size() < a.mpc.rec.size()) return verdict("zkey verify: the contributions do not begin with the initial key's");
+  for (size_t i = 0; i < a.mpc.rec.size(); i++)
+    if (a.mpc.rec[i].len != b.mpc.rec[i].len || memcmp(a.mpc.rec[i].p, b.mpc.rec[i].p, a.mpc.rec[i].len) != 0)
+      return verdict("zkey verify: the contributions do not begin with the initial key's");
+  // 5 (lengths first: host checks before the device)
+  if (a.f.sec[8].size != b.f.sec[8].size || a.f.sec[9].size != b.f.sec[9].size)
+    return verdict("zkey verify: section 8 or 9 has not the initial key's length");
+
+  // 3. the chain: hashes on the host, the pairs of every same-ratio check collected for ONE device call
+  std::vector<uint8_t> pairs;        // 192 bytes each; check c compares pairing 2c with pairing 2c + 1
+  std::vector<const char*> reason;   // per check
+  auto same_ratio = [&](const uint8_t* g1a, const uint8_t* g1b, const uint8_t* g2c, const uint8_t* g2d, const char* why) {
+    if (all_zero(g1a, 64) || all_zero(g1b, 64) || all_zero(g2c, 128) || all_zero(g2d, 128)) return false;
+    pair_words(pairs, g1a, g2d);   // e(a, d) = e(b, c)
+    pair_words(pairs, g1b, g2c);
+    reason.push_back(why);
+    return true;
+  };
+  const char* inf_text = "zkey verify: a contribution holds the point at infinity";
+  const uint8_t* cur = ha + kHdrDelta1;
+  std::vector<G2Affine> g2_sp(b.mpc.rec.size());
+  for (size_t i = a.mpc.rec.size(); i < b.mpc.rec.size(); i++) {
+    const MpcRecord& r = b.mpc.rec[i];
+    uint8_t tr[64];
+    transcript_of(b.mpc, i, r.g1_s(), r.g1_sx(), tr);
+    if (memcmp(tr, r.transcript(), 64) != 0) return verdict("zkey verify: a contribution's transcript hash does not match");
+    hash_to_g2(tr, g2_sp[i]);
+    const uint8_t* sp2 = (const uint8_t*)&g2_sp[i];
+    if (!same_ratio(r.g1_s(), r.g1_sx(), sp2, r.g2_spx(), "zkey verify: a contribution's public key is not consistent")) return verdict(inf_text);
+    if (!same_ratio(cur, r.delta_after(), sp2, r.g2_spx(), "zkey verify: a contribution's delta does not continue the chain")) return verdict(inf_text);
+    cur = r.delta_after();
+  }
+  // 4. the header's delta
+  if (memcmp(cur, hb + kHdrDelta1, 64) != 0) return verdict("zkey verify: delta1 of the header is not the last contribution's");
+  if (!same_ratio(ha + kHdrDelta1, hb + kHdrDelta1, ha + kHdrDelta2, hb + kHdrDelta2, "zkey verify: delta2 does not match delta1"))
+    return verdict(inf_text);
+
+  // 5. sections 8 and 9: S = sum rho_i new_i, T = sum rho_i init_i, e(S, delta2) = e(T, delta2 of init)
+  const uint64_t n8 = a.f.sec[8].size / 64, n9 = a.f.sec[9].size / 64, n = n8 + n9;
+  double msm_ms = 0;
+  uint8_t S[64], T[64];   // standard form
+  {
+    std::vector<uint8_t> bases_new(n * 64), bases_init(n * 64), rho(n * 32);
+    memcpy(bases_init.data(), a.f.sec[8].p, n8 * 64);
+    memcpy(bases_init.data() + n8 * 64, a.f.sec[9].p, n9 * 64);
+    memcpy(bases_new.data(), b.f.sec[8].p, n8 * 64);
+    memcpy(bases_new.data() + n8 * 64, b.f.sec[9].p, n9 * 64);
+    for (uint64_t i = 0; i < n; i++) {
+      if (!g1_image_ok(bases_new.data() + i * 64)) { set_error("zkey: Invalid File format"); return G16_E_FORMAT; }
+      if (all_zero(bases_new.data() + i * 64, 64) != all_zero(bases_init.data() + i * 64, 64))
+        return verdict("zkey verify: sections 8 and 9 are not the initial key's scaled by 1 / delta");
+    }
+    ChaCha rng;   // fresh scalars: a ChaCha20 stream keyed from the OS CSPRNG
+    if (const int rc = os_random((uint8_t*)rng.key, 32)) return rc;
+    for (uint64_t i = 0; i < n; i++) rng.next_below(kFrP, (uint32_t*)(rho.data() + i * 32));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (const int rc = g16_g1_multiexp(device, bases_new.data(), rho.data(), n, 0, S)) return rc;
+    if (const int rc = g16_g1_multiexp(device, bases_init.data(), rho.data(), n, 0, T)) return rc;
+    msm_ms = ms_since(t1);
+  }
+  const bool s_inf = all_zero(S, 64);
+  if (!s_inf) {
+    if (all_zero(T, 64)) return verdict("zkey verify: sections 8 and 9 are not the initial key's scaled by 1 / delta");
+    const size_t at = pairs.size();
+    pairs.resize(at + 2 * 192);
+    memcpy(pairs.data() + at, S, 64);
+    memcpy(pairs.data() + at + 192, T, 64);
+    for (int i = 0; i < 4; i++) {
+      const Fq v = fp_from_mont(fq_load(hb + kHdrDelta2 + 32 * i)), w = fp_from_mont(fq_load(ha + kHdrDelta2 + 32 * i));
+      memcpy(pairs.data() + at + 64 + 32 * i, v.v, 32);
+      memcpy(pairs.data() + at + 192 + 64 + 32 * i, w.v, 32);
+    }
+    reason.push_back("zkey verify: sections 8 and 9 are not the initial key's scaled by 1 / delta");
+  } else if (n) {
+    return verdict("zkey verify: the combination of sections 8 and 9 is the point at infinity");
+  }
+  const auto t2 = std::chrono::steady_clock::now();
+  const uint32_t np = (uint32_t)(pairs.size() / 192);
+  std::vector<uint8_t> gt((size_t)np * 384);
+  if (np)
+    if (const int rc = g16_pairing_op(device, pairs.data(), np, gt.data())) return rc;
+  const double pair_ms = ms_since(t2);
+  if (getenv("G16_TRACE_HOST"))
+    fprintf(stderr, "[g16] zkey verify: points %llu; kernels 0.000 ms, transfers 0.000 ms, MSM %.3f ms, pairings %.3f ms (%u); call %.3f ms\n",
+            (unsigned long long)n, msm_ms, pair_ms, np, ms_since(t0));
+  for (size_t c = 0; c < reason.size(); c++)
+    if (memcmp(gt.data() + 2 * c * 384, gt.data() + (2 * c + 1) * 384, 384) != 0) return verdict(reason[c]);
+  set_error("");
+  *ok = 1;
+  return G16_OK;
+}
+
+}  // namespace
+}  // namespace g16
+
+using namespace g16;
+
+extern "C" int g16_blake2b512(const uint8_t* data, size_t len, uint8_t out[64]) {
+  if ((!data && len) || !out) { set_error("NULL argument"); return G16_E_ARG; }
+  blake2b512(data, len, out);
+  return G16_OK;
+}
+
+extern "C" int g16_zkey_hash_to_g2(const uint8_t transcript[64], uint8_t out[128]) {
+  if (!transcript || !out) { set_error("NULL argument"); return G16_E_ARG; }
+  G2Affine p;
+  hash_to_g2(transcript, p);
+  memcpy(out, &p, 128);
+  return G16_OK;
+}
+
+extern "C" int g16_zkey_contribute(const uint8_t* zkey, size_t zkey_len, const char* name, const uint8_t secret[64], int device,
+                                   uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]) {
+  if (!zkey || !out || !out_len) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("zkey contribute",
+                      [&]() { return contribute_core(zkey, zkey_len, name, secret, device, out, out_len, contribution_hash); });
+}
+
+extern "C" int g16_zkey_contribute_files(const char* in_path, const char* out_path, const char* name, const uint8_t secret[64],
+                                         int device, uint8_t contribution_hash[64]) {
+  if (!in_path || !out_path) { set_error("NULL argument"); return G16_E_ARG; }
+  return files_form(&in_path, 1, out_path, [&](const MappedFile* m, uint8_t** z, size_t* zl) {
+    return g16_zkey_contribute((const uint8_t*)m[0].p, m[0].len, name, secret, device, z, zl, contribution_hash);
+  });
+}
+
+extern "C" int g16_zkey_verify_from_init(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_t zkey_len, int device,
+                                         int* ok) {
+  if (!init || !zkey || !ok) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("zkey verify", [&]() { return verify_core(init, init_len, zkey, zkey_len, device, ok); });
+}
+
+extern "C" int g16_zkey_verify_from_init_files(const char* init_path, const char* zkey_path, int device, int* ok) {
+  if (!init_path || !zkey_path || !ok) { set_error("NULL argument"); return G16_E_ARG; }
+  MappedFile in[2];
+  if (const int rc = in[0].open_ro(init_path)) return rc;
+  if (const int rc = in[1].open_ro(zkey_path)) return rc;
+  return g16_zkey_verify_from_init((const uint8_t*)in[0].p, in[0].len, (const uint8_t*)in[1].p, in[1].len, device, ok);
+}

@@ -22,6 +22,9 @@
  *           plonkSetupFiles(r1csPath, ptauPath, zkeyPath, device, withLagrange) -> Promise<undefined>   (g16_plonk_setup_files)
  *           groth16SetupFiles(r1csPath, ptauPath, zkeyPath, device) -> Promise<undefined>   (g16_groth16_setup_files)
  *           ptauPrepareFiles(inPath, outPath, device) -> Promise<undefined>   (g16_ptau_prepare_files)
+ *           zkeyContributeFiles(inPath, outPath, name | null, secret Buffer(64) | null, device) -> Promise<Buffer(64)>
+ *                                                                              (g16_zkey_contribute_files: the hash)
+ *           zkeyVerifyFromInitFiles(initPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_from_init_files)
  */
 #include <node_api.h>
 #include <stdlib.h>
@@ -781,6 +784,103 @@ static napi_value js_ptau_prepare_files(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* zkey contribute / zkey verify frominit from / to files */
+typedef struct {
+  napi_async_work work;
+  napi_deferred deferred;
+  char a[1024], b[1024], name[512];
+  uint8_t secret[64], hash[64];
+  int has_name, has_secret, verify, device, rc, ok;
+  char err[512];
+} zjob_t;
+static void zjob_execute(napi_env env, void* data) {
+  zjob_t* j = (zjob_t*)data;
+  j->rc = j->verify ? g16_zkey_verify_from_init_files(j->a, j->b, j->device, &j->ok)
+                    : g16_zkey_contribute_files(j->a, j->b, j->has_name ? j->name : NULL, j->has_secret ? j->secret : NULL,
+                                                j->device, j->hash);
+  if (j->rc || (j->verify && !j->ok)) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
+}
+static void zjob_complete(napi_env env, napi_status status, void* data) {
+  zjob_t* j = (zjob_t*)data;
+  if (status != napi_ok || j->rc) {
+    napi_value msg, err;
+    napi_create_string_utf8(env, j->rc ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_reject_deferred(env, j->deferred, err);
+  } else if (j->verify) {
+    napi_value obj, ok, reason;
+    napi_create_object(env, &obj);
+    napi_get_boolean(env, j->ok != 0, &ok);
+    napi_create_string_utf8(env, j->ok ? "" : j->err, NAPI_AUTO_LENGTH, &reason);
+    napi_set_named_property(env, obj, "ok", ok);
+    napi_set_named_property(env, obj, "reason", reason);
+    napi_resolve_deferred(env, j->deferred, obj);
+  } else {
+    napi_value buf;
+    void* copy = NULL;
+    napi_create_buffer_copy(env, 64, j->hash, &copy, &buf);
+    napi_resolve_deferred(env, j->deferred, buf);
+  }
+  napi_delete_async_work(env, j->work);
+  free(j);
+}
+static napi_value zjob_start(napi_env env, zjob_t* j, const char* resource) {
+  napi_value promise, resname;
+  NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
+  NAPI_OK(napi_create_string_utf8(env, resource, NAPI_AUTO_LENGTH, &resname));
+  NAPI_OK(napi_create_async_work(env, NULL, resname, zjob_execute, zjob_complete, j, &j->work));
+  NAPI_OK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+static napi_value js_zkey_contribute_files(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) { napi_throw_type_error(env, NULL, "zkeyContributeFiles(inPath, outPath, name, secret, device)"); return NULL; }
+  zjob_t* j = (zjob_t*)calloc(1, sizeof(zjob_t));
+  size_t n = 0;
+  if (napi_get_value_string_utf8(env, argv[0], j->a, sizeof(j->a), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], j->b, sizeof(j->b), &n) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, "zkeyContributeFiles: two path strings expected");
+    return NULL;
+  }
+  if (argc > 2 && napi_get_value_string_utf8(env, argv[2], j->name, sizeof(j->name), &n) == napi_ok) j->has_name = 1;
+  bool is_buf = false;
+  if (argc > 3 && napi_is_buffer(env, argv[3], &is_buf) == napi_ok && is_buf) {
+    void* p = NULL;
+    size_t len = 0;
+    if (napi_get_buffer_info(env, argv[3], &p, &len) != napi_ok || len != 64) {
+      free(j);
+      napi_throw_type_error(env, NULL, "zkeyContributeFiles: the secret is a Buffer of 64 bytes (d | s) or null");
+      return NULL;
+    }
+    memcpy(j->secret, p, 64);
+    j->has_secret = 1;
+  }
+  int32_t v = 0;
+  if (argc > 4 && napi_get_value_int32(env, argv[4], &v) == napi_ok) j->device = v;
+  return zjob_start(env, j, "g16_zkey_contribute_files");
+}
+static napi_value js_zkey_verify_from_init_files(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) { napi_throw_type_error(env, NULL, "zkeyVerifyFromInitFiles(initPath, zkeyPath, device)"); return NULL; }
+  zjob_t* j = (zjob_t*)calloc(1, sizeof(zjob_t));
+  size_t n = 0;
+  if (napi_get_value_string_utf8(env, argv[0], j->a, sizeof(j->a), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], j->b, sizeof(j->b), &n) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, "zkeyVerifyFromInitFiles: two path strings expected");
+    return NULL;
+  }
+  j->verify = 1;
+  int32_t v = 0;
+  if (argc > 2 && napi_get_value_int32(env, argv[2], &v) == napi_ok) j->device = v;
+  return zjob_start(env, j, "g16_zkey_verify_from_init_files");
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"create", NULL, js_create, NULL, NULL, NULL, napi_default, NULL},
@@ -798,6 +898,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"plonkSetupFiles", NULL, js_plonk_setup_files, NULL, NULL, NULL, napi_default, NULL},
       {"groth16SetupFiles", NULL, js_groth16_setup_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauPrepareFiles", NULL, js_ptau_prepare_files, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyContributeFiles", NULL, js_zkey_contribute_files, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyVerifyFromInitFiles", NULL, js_zkey_verify_from_init_files, NULL, NULL, NULL, napi_default, NULL},
   };
   NAPI_OK(napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props));
   return exports;

@@ -4,6 +4,12 @@
 // /root/reference/Makefile:30-33).  Writes JSON.stringify(x, null, 1) like snarkjs.
 // And of `snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>` (alias `zkey new`; prepared ptau only).
 // And of `snarkjs powersoftau prepare phase2 <powersoftau.ptau> <new_powersoftau.ptau>` (alias `pt2`).
+// And of `snarkjs zkey contribute <old.zkey> <new.zkey> [--name=..] [-e=..]` (alias `zkc`): prints the contribution hash
+// as snarkjs does.  -e: THIS CLI's derivation of the secret from the text (index.js secretFromEntropy), not snarkjs's.
+// And of `snarkjs zkey verify frominit <init.zkey> <pot.ptau> <circuit.zkey>` (alias `zkvi`) and `snarkjs zkey verify
+// <circuit.r1cs> <pot.ptau> <circuit.zkey>` (alias `zkv`: runs the setup into a temporary file beside the zkey): prints
+// "[INFO]  snarkJS: ZKey Ok!" and exits 0, or "[ERROR] snarkJS: <reason>" and exits 1.  The ptau is read by the setup of
+// `zkv` only: section 9 is not recomputed from it, and csHash is not snarkjs's (see INTEGRATION.md 5b).
 // And of `snarkjs groth16 verify <verification_key.json> <public.json> <proof.json>` (groth16Verify [EXT]): prints
 // "[INFO]  snarkJS: OK!" and exits 0, or "[ERROR] snarkJS: Invalid proof" and exits 1.
 "use strict";
@@ -16,6 +22,45 @@ async function main(argv) {
     const { exportVerificationKey } = require("./index.js");
     const [zk, out = "verification_key.json"] = a.slice(3);
     fs.writeFileSync(out, JSON.stringify(exportVerificationKey(zk), null, 1), "utf-8");
+    return;
+  }
+  if ((a[0] === "zkey" && a[1] === "contribute") || a[0] === "zkc") {
+    const rest = a.slice(a[0] === "zkc" ? 1 : 2);
+    const opt = (long, short) => {
+      for (const x of rest) {
+        if (x.startsWith(`--${long}=`)) return x.slice(long.length + 3);
+        if (x.startsWith(`-${short}=`)) return x.slice(short.length + 2);
+      }
+      return undefined;
+    };
+    const pos = rest.filter((x) => !x.startsWith("-"));
+    if (pos.length < 2) { console.error("usage: cli.js zkey contribute <circuit_old.zkey> <circuit_new.zkey> [--name=..] [-e=..]"); process.exit(2); }
+    const { zKey, formatHash } = require("./index.js");
+    const hash = await zKey.contribute(pos[0], pos[1], opt("name", "n"), opt("entropy", "e"));
+    console.log(`[INFO]  snarkJS: Contribution Hash: \n${formatHash(hash)}`);
+    return;
+  }
+  if ((a[0] === "zkey" && a[1] === "verify") || a[0] === "zkv" || a[0] === "zkvi") {
+    let rest = a.slice(a[0] === "zkey" ? 2 : 1);
+    const frominit = a[0] === "zkvi" || rest[0] === "frominit";
+    if (rest[0] === "frominit") rest = rest.slice(1);
+    const pos = rest.filter((x) => !x.startsWith("-"));
+    if (pos.length < 3) { console.error("usage: cli.js zkey verify [frominit] <circuit.r1cs | init.zkey> <pot.ptau> <circuit.zkey>"); process.exit(2); }
+    const { zKey, newZKey } = require("./index.js");
+    let init = pos[0], tmp = null;
+    if (!frominit) {
+      tmp = `${pos[2]}.init.${process.pid}.tmp`;
+      init = tmp;
+    }
+    let res;
+    try {
+      if (tmp) await newZKey(pos[0], pos[1], tmp);
+      res = await zKey.verifyFromInit(init, pos[1], pos[2], { reason: true });
+    } finally {
+      if (tmp && fs.existsSync(tmp)) fs.unlinkSync(tmp);
+    }
+    if (!res.ok) throw new Error(res.reason);
+    console.log("[INFO]  snarkJS: ZKey Ok!");
     return;
   }
   if ((a[0] === "groth16" && a[1] === "setup") || (a[0] === "zkey" && a[1] === "new")) {

@@ -289,6 +289,48 @@ const powersOfTau = {
   },
 };
 
+// ------------------------------------------------------------------ zkey contribute / zkey verify
+// snarkjs: zKey.contribute(oldZkeyName, newZKeyName, name, entropy[, logger]) -> the 64-byte contribution hash.
+// entropy: a string (or Buffer), hashed with Blake2b-512 into the two secret scalars d | s -- each 32-byte half, read
+// little-endian, reduced mod r (0 becomes 1): THIS LIBRARY'S derivation, not snarkjs's (which seeds a ChaCha stream),
+// so the same text gives the same key here and another one there.  Absent: the OS CSPRNG.
+function secretFromEntropy(entropy) {
+  const h = require("crypto").createHash("blake2b512").update(entropy).digest();
+  const out = Buffer.alloc(64);
+  for (let k = 0; k < 2; k++) {
+    let v = leBig(h, 32 * k) % FR;
+    if (v === 0n) v = 1n;
+    for (let i = 0; i < 32; i++) { out[32 * k + i] = Number(v & 0xffn); v >>= 8n; }
+  }
+  return out;
+}
+async function contribute(oldZkeyName, newZkeyName, name, entropy, opts = {}) {
+  if (opts && typeof opts.debug === "function") opts = {};
+  const secret = entropy === undefined || entropy === null || entropy === "" ? null : secretFromEntropy(entropy);
+  return native().zkeyContributeFiles(String(oldZkeyName), String(newZkeyName), name ? String(name) : null, secret, opts.device | 0);
+}
+// snarkjs: zKey.verifyFromInit(initFileName, pTauFileName, zkeyFileName[, logger]) -> boolean.  The ptau argument is
+// accepted for the call shape and NOT opened: section 9 is not recomputed from the ceremony file.  opts.reason = true
+// returns {ok, reason} instead.
+async function verifyFromInit(initName, ptauName, zkeyName, opts = {}) {
+  if (opts && typeof opts.debug === "function") opts = {};
+  const res = await native().zkeyVerifyFromInitFiles(String(initName), String(zkeyName), opts.device | 0);
+  return opts.reason ? res : res.ok;
+}
+// snarkjs formatHash: four lines of four big-endian u32 in 8 hex digits, each line led by two tabs
+function formatHash(b) {
+  let s = "";
+  for (let i = 0; i < 4; i++) {
+    if (i > 0) s += "\n";
+    s += "\t\t";
+    for (let j = 0; j < 4; j++) {
+      if (j > 0) s += " ";
+      s += b.readUInt32BE(i * 16 + j * 4).toString(16).padStart(8, "0");
+    }
+  }
+  return s;
+}
+
 // ------------------------------------------------------------------ zkey export verificationkey (host-only: header reads)
 // snarkjs `zKey.exportVerificationKey(zkey)` / CLI `zkey export verificationkey <zkey> <vk.json>` -- the second line of
 // the reference's PLONK flow (/root/reference/Makefile:32).  Groth16 and PLONK keys; points leave Montgomery form here
@@ -370,4 +412,4 @@ const groth16 = {
   createProver,
 };
 
-module.exports = { groth16, plonk, powersOfTau, zKey: { exportVerificationKey, newZKey }, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
+module.exports = { groth16, plonk, powersOfTau, zKey: { exportVerificationKey, newZKey, contribute, verifyFromInit }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
