@@ -382,6 +382,79 @@ int g16_r1cs_setup_trapdoor(const uint8_t* r1cs, size_t r1cs_len, const uint8_t 
 int g16_ptau_synth(uint32_t power, const uint8_t tau_alpha_beta[3 * 32], int prepared, int device, uint8_t** ptau,
                    size_t* ptau_len);
 
+/* `snarkjs powersoftau new bn128 <power> pot_0000.ptau`: the .ptau v1 image (g16_free) of a ceremony nobody has
+ * contributed to: sections 1-7, every point of sections 2-6 the generator of its group (2: 2^(power+1) - 1 points of
+ * G1; 3: 2^power of G2; 4, 5: 2^power of G1; 6: one of G2), section 7 "no contributions" (four zero bytes).  Host only.
+ * The bytes are g16_ptau_synth(power, 1 | 1 | 1, prepared = 0)'s.  A power above 24: G16_E_ARG, the text names the limit. */
+int g16_ptau_new(uint32_t power, uint8_t** out, size_t* out_len);
+int g16_ptau_new_file(uint32_t power, const char* path);
+/* `snarkjs powersoftau contribute old.ptau new.ptau --name=.. -e=..`: one phase-1 contribution (g16_free).
+ * secret = tau | alpha | beta | s_tau | s_alpha | s_beta, six standard-form 32-byte LE scalars in [1, r) (anything else:
+ * G16_E_ARG), or NULL for the OS CSPRNG; the same inputs give the same bytes.  On `device` (there is no CPU path:
+ * G16_E_NOGPU; csrc/ptau_scale.hip, every lane forms its own scalar): point i of sections 2 and 3 <- [tau^i] point i,
+ * of section 4 <- [alpha tau^i], of section 5 <- [beta tau^i], section 6 <- [beta].  Section 1 byte for byte; section 7 =
+ * the old records and the new one; sections 12-15 of a prepared input are DROPPED (a contribution invalidates them),
+ * other section ids are not carried; the output order is 1..7.
+ * Section 7, snarkjs's powersoftau_utils.js layout as far as it can be restated without the package: u32 n, then n
+ * records, every point in the file's form (affine little-endian Montgomery):
+ *   tauG1 (64) | tauG2 (128) | alphaG1 (64) | betaG1 (64) | betaG2 (128) |
+ *   tau.g1_s | tau.g1_sx | alpha.g1_s | alpha.g1_sx | beta.g1_s | beta.g1_sx (64 each) |
+ *   tau.g2_spx | alpha.g2_spx | beta.g2_spx (128 each) |
+ *   partialHash (216) | nextChallenge (64) | u32 type = 0 | u32 paramsLen | params
+ * params as in g16_zkey_contribute (byte 1, byte len, the name cut to 64 characters and 255 bytes, or nothing).  tauG1,
+ * tauG2 = point 1 of the new sections 2, 3 (a power-0 file holds no point 1: there they are [tau] times the last
+ * record's, or times the generators); alphaG1, betaG1, betaG2 = point 0 of the new sections 4, 5, 6.
+ * Hashes.  challengeHash(state, prev) = Blake2b-512(prev | every point of sections 2, 3, 4, 5, 6 in that order,
+ * uncompressed big-endian standard form as in g16_zkey_contribute).  The challenge a contribution answers is the last
+ * record's nextChallenge, or -- no records -- challengeHash(the input file, Blake2b-512("")).  For key x (tau = 0,
+ * alpha = 1, beta = 2): g1_s = [s_x]G1, g1_sx = [x]g1_s, g2_sp = g16_zkey_hash_to_g2(Blake2b-512(challenge | byte x |
+ * g1_s | g1_sx uncompressed)), g2_spx = [x]g2_sp.  responseHash = Blake2b-512(challenge | the nine key points
+ * uncompressed, in record order) = contribution_hash (optional), what the CLI prints as "Contribution Hash";
+ * nextChallenge = challengeHash(new state, responseHash).
+ * DEPARTURES from snarkjs: it hashes a response file of COMPRESSED points and stores a hasher snapshot in partialHash;
+ * here the new points enter through nextChallenge only and partialHash is 216 zero bytes that nothing reads.  The layout
+ * and the powers are snarkjs's; its `powersoftau verify` is NOT claimed to accept this transcript.  NOT implemented:
+ * `powersoftau beacon`, and the challenge / response file exchange (export challenge, challenge contribute, import
+ * response).  The G2 derivation is NOT cross-checked against snarkjs.
+ * Checked before the device is touched: the container, curve and power texts of g16_ptau_prepare ("ptau: Invalid File
+ * format...", a power above 24: G16_E_ARG naming the limit); sections 2-6 present with exactly the sizes the power
+ * implies and a section 7 that parses (not shorter than its records say, no trailing bytes, every record point a valid
+ * image), else "ptau: Invalid File format"; "ptau contribute: the secret scalars must be in [1, r)". */
+int g16_ptau_contribute(const uint8_t* ptau, size_t ptau_len, const char* name /* or NULL */,
+                        const uint8_t secret[192] /* or NULL = OS CSPRNG */, int device, uint8_t** out, size_t* out_len,
+                        uint8_t contribution_hash[64]);
+/* the same from / to files: the input is mapped read-only and the output written in chunks */
+int g16_ptau_contribute_files(const char* in_path, const char* out_path, const char* name, const uint8_t secret[192],
+                              int device, uint8_t contribution_hash[64]);
+/* `snarkjs powersoftau verify pot.ptau`: is the file the generator file plus a chain of honest contributions (of THIS
+ * library's transcript, see above)?  G16_OK with *ok = 1 / 0; for 0 g16_last_error() holds the reason, one fixed text
+ * per check, each led by "ptau verify: ", in this order:
+ *   1. "the first point of section 2 or 3 is not the generator";
+ *   2. per record, from the generators on: "a contribution holds the point at infinity"; "a contribution's public key
+ *      is not consistent" (e(g1_s, g2_spx) != e(g1_sx, g2_sp) for one of its three keys); "a contribution's tauG1 /
+ *      alphaG1 / betaG1 does not continue the chain" (not the record before's by the ratio of its key); "a contribution's
+ *      tauG2 does not match its tauG1" (e(tauG1, G2) != e(G1, tauG2)), "... betaG2 does not match its betaG1".  g2_sp is
+ *      recomputed from the record's challenge: the generator file's for the first record, the nextChallenge of the
+ *      record before for every other.  nextChallenge itself can be recomputed only where the state it hashes is at hand,
+ *      that is for the last record (check 4); the first record's challenge is that of the generator file of this power;
+ *   3. "the file's points are not the last contribution's" (point 1 of sections 2 and 3 -- power >= 1 --, point 0 of
+ *      sections 4, 5, 6), or, without records, "a file without contributions is not the generator file";
+ *   4. "the last contribution's challenge hash does not match the file" (skipped without records);
+ *   5. the powers, with fresh random rho_i (ChaCha20 keyed from the OS CSPRNG): S1 = sum rho_i P_i, S2 = sum rho_i
+ *      P_(i+1), e(S1, tauG2) != e(S2, G2): "section 2 is not the powers of tau", "section 4 is not alpha times the powers
+ *      of tau", "section 5 is not beta times the powers of tau"; the G2 sums of section 3 against (G1, tauG1): "section 3
+ *      is not the powers of tau"; "the combination of section N is the point at infinity";
+ *   6. a prepared file: "the prepared sections 12 to 15 are not all present"; "the prepared sections are not the
+ *      transform of sections 2 to 5" (g16_ptau_prepare is run and compared byte for byte).
+ * A malformed file is G16_E_FORMAT, not a verdict: the container, the sizes, section 7, and a coordinate >= q or a point
+ * off its curve anywhere in sections 2-6.  A power above 24: G16_E_ARG.  The sums are MSMs (g16_g1_multiexp /
+ * g16_g2_multiexp), the pairings ONE g16_pairing_op call on `device` (G16_E_NOGPU). */
+int g16_ptau_verify(const uint8_t* ptau, size_t ptau_len, int device, int* ok);
+int g16_ptau_verify_file(const char* path, int device, int* ok);
+/* The CLI's rule for `-e=<text>` (NOT snarkjs's): h_j = Blake2b-512(text | byte j), j = 0, 1, 2; the first 32 bytes of
+ * h_j (little-endian, reduced mod r, zero mapped to 1) are key j (tau, alpha, beta), the last 32 bytes s_j. */
+int g16_ptau_secret_from_text(const char* text, uint8_t secret[192]);
+
 /* `snarkjs zkey contribute old.zkey new.zkey --name=.. -e=..`: one phase-2 contribution to a Groth16 .zkey (g16_free).
  * secret = d | s, two standard-form 32-byte LE scalars in [1, r) (anything else: G16_E_ARG), or NULL for the OS CSPRNG;
  * like g16_prove's explicit r, s the same inputs give the same bytes.  g1_s = [s]G1, g1_sx = [d]g1_s; transcript =

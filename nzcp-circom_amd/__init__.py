@@ -71,7 +71,9 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_groth16_setup_ptau", "g16_groth16_setup_files", "g16_r1cs_setup_trapdoor", "g16_ptau_synth",
            "g16_ptau_prepare", "g16_ptau_prepare_files",
            "g16_zkey_contribute", "g16_zkey_contribute_files", "g16_zkey_verify_from_init",
-           "g16_zkey_verify_from_init_files", "g16_blake2b512", "g16_zkey_hash_to_g2"]
+           "g16_zkey_verify_from_init_files", "g16_blake2b512", "g16_zkey_hash_to_g2",
+           "g16_ptau_new", "g16_ptau_new_file", "g16_ptau_contribute", "g16_ptau_contribute_files", "g16_ptau_verify",
+           "g16_ptau_verify_file", "g16_ptau_secret_from_text"]
 
 
 def load():
@@ -154,6 +156,13 @@ def load():
     lib.g16_zkey_contribute_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
     lib.g16_zkey_verify_from_init.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_int, C.POINTER(C.c_int)]
     lib.g16_zkey_verify_from_init_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_ptau_new.argtypes = [C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
+    lib.g16_ptau_new_file.argtypes = [C.c_uint32, C.c_char_p]
+    lib.g16_ptau_contribute.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
+    lib.g16_ptau_contribute_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
+    lib.g16_ptau_verify.argtypes = [C.c_char_p, sz, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_ptau_verify_file.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_ptau_secret_from_text.argtypes = [C.c_char_p, C.c_char_p]
     lib.g16_blake2b512.argtypes = [C.c_char_p, sz, C.c_char_p]
     lib.g16_zkey_hash_to_g2.argtypes = [C.c_char_p, C.c_char_p]
     lib.g16_r1cs_setup.argtypes = [C.c_char_p, sz, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
@@ -737,6 +746,44 @@ def ptau_prepare(ptau, device=0):
     z, zl = C.c_void_p(), C.c_size_t()
     _check(load().g16_ptau_prepare(ptau, len(ptau), device, C.byref(z), C.byref(zl)))
     return _take(z, zl)
+
+
+def ptau_new(power):
+    """`snarkjs powersoftau new bn128 <power>`: the .ptau bytes of a ceremony without contributions (host only)."""
+    z, zl = C.c_void_p(), C.c_size_t()
+    _check(load().g16_ptau_new(power, C.byref(z), C.byref(zl)))
+    return _take(z, zl)
+
+
+def ptau_contribute(ptau, name=None, secret=None, device=0):
+    """`snarkjs powersoftau contribute`: .ptau bytes -> (contributed .ptau bytes, 64-byte contribution hash).  secret:
+    (tau, alpha, beta, s_tau, s_alpha, s_beta), ints in [1, r), or None for the OS CSPRNG."""
+    blob = None
+    if secret is not None:
+        if len(secret) != 6:
+            raise ValueError("ptau_contribute: six secret scalars expected")
+        blob = b"".join(int(x).to_bytes(32, "little") for x in secret)
+    z, zl = C.c_void_p(), C.c_size_t()
+    h = C.create_string_buffer(64)
+    nm = None if name is None else name.encode("utf-8")
+    _check(load().g16_ptau_contribute(ptau, len(ptau), nm, blob, device, C.byref(z), C.byref(zl), h))
+    return _take(z, zl), h.raw
+
+
+def ptau_verify(ptau, device=0):
+    """`snarkjs powersoftau verify` -> (ok, reason): is the file the generator file plus a chain of honest contributions?
+    reason is empty when ok.  A malformed file raises G16Error(-2)."""
+    ok = C.c_int(0)
+    lib = load()
+    _check(lib.g16_ptau_verify(ptau, len(ptau), device, C.byref(ok)))
+    return bool(ok.value), ("" if ok.value else lib.g16_last_error().decode("utf-8", "replace"))
+
+
+def ptau_secret_from_text(text):
+    """The CLI's `-e=<text>` rule -> the six secret scalars (ints)."""
+    out = C.create_string_buffer(192)
+    _check(load().g16_ptau_secret_from_text(text.encode("utf-8"), out))
+    return tuple(int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(6))
 
 
 def zkey_contribute(zkey, name=None, d=None, s=None, device=0):

@@ -120,6 +120,21 @@ struct ZkeyScaleStats {
 };
 int zkey_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& k_std, uint8_t* out, ZkeyScaleStats* st);
 
+// ---------------------------------------------------------------- powersoftau contribute (ptau_scale.hip)
+// out[i] = [c k^(first + i)] in[i]: n affine Montgomery points of G1 / G2 (host, file layout; infinity = zero bytes in
+// and out), c and k standard form in [1, r), first + n <= 2^31; every lane forms its scalar on the device.  out_be
+// (optional, as large as out): the uncompressed big-endian standard-form image of every output point (G1: x | y; G2:
+// x.c1 | x.c0 | y.c1 | y.c0; infinity = zeros with bit 0x40 of byte 0).  In chunks over two streams.  No CPU path.
+struct PtauScaleStats {
+  float kern_ms = 0.f;   // device time of the kernels (scaling, conversion to affine, big-endian images), all chunks
+  float xfer_ms = 0.f;   // device time of the copies in and out
+  uint64_t points = 0;
+};
+int ptau_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& c_std, const Fr& k_std, uint64_t first, uint8_t* out,
+                  uint8_t* out_be, PtauScaleStats* st);
+int ptau_scale_g2(int device, const uint8_t* in, uint64_t n, const Fr& c_std, const Fr& k_std, uint64_t first, uint8_t* out,
+                  uint8_t* out_be, PtauScaleStats* st);
+
 // ---------------------------------------------------------------- NTT (ntt.hip)
 struct NttPass { int lo_bits, S, tb; };
 struct NttTables {

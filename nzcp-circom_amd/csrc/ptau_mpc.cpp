@@ -1,0 +1,574 @@
+// `snarkjs powersoftau new`, `powersoftau contribute` and `powersoftau verify` ([EXT] snarkjs 0.4.12 powersoftau_new.js,
+// powersoftau_contribute.js, powersoftau_verify.js, powersoftau_utils.js; keypair.js for the keys).
+//   new:        sections 1-7 with every point the generator (host only).
+//   contribute: point i of sections 2 / 3 <- [tau^i], 4 <- [alpha tau^i], 5 <- [beta tau^i], 6 <- [beta] (ptau_scale.hip,
+//               every lane forms its scalar on the device), one record more in section 7.
+//   verify:     the file is the generator file plus a chain of honest contributions -- the record walk (same-ratio
+//               pairing checks), the challenge hash of the file, one random linear combination per section for the
+//               powers (MSMs on the Pippenger operators, pairings on the verifier's device code) and, when the file is
+//               prepared, sections 12-15 against a fresh transform.
+// The record LAYOUT and the powers are snarkjs's.  The TRANSCRIPT is not: snarkjs hashes a challenge / response file
+// exchange of compressed points and stores a hasher snapshot in partialHash; here
+//   challengeHash(state, prev) = Blake2b-512(prev | every point of sections 2, 3, 4, 5, 6 in that order, uncompressed
+//                                big-endian standard form),
+// the first challenge is that of the file as it stands with prev = Blake2b-512(""), every later one the last record's
+// nextChallenge; for key x (tau = 0, alpha = 1, beta = 2) g1_s = [s_x]G1, g1_sx = [x]g1_s, g2_sp =
+// hash_to_g2(Blake2b-512(challenge | byte x | g1_s | g1_sx)), g2_spx = [x]g2_sp; responseHash = Blake2b-512(challenge |
+// the nine key points in record order); nextChallenge = challengeHash(new state, responseHash); partialHash is 216 zero
+// bytes that nothing reads.  snarkjs's `powersoftau verify` is NOT claimed to accept this transcript.  NOT here:
+// `powersoftau beacon` and the challenge / response file exchange (export challenge, challenge contribute, import
+// response).
+#include "ptau_mpc.h"
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <thread>
+
+#include "internal.h"
+#include "mapped_file.h"
+#include "ptau.h"
+#include "zkey_mpc.h"
+
+namespace g16 {
+
+int ptau_records_parse(const BinSection& s7, std::vector<PtauRecord>& out) {
+  out.clear();
+  if (!s7.p) return G16_OK;   // (no section 7: no contributions, as g16_ptau_prepare reads it)
+  if (s7.size < 4) return ptau_bad("Invalid File format");
+  const uint32_t n = rd32(s7.p);
+  uint64_t pos = 4;
+  for (uint32_t i = 0; i < n; i++) {
+    if (s7.size - pos < kPtauRecordFixed) return ptau_bad("Invalid File format");
+    const uint8_t* r = s7.p + pos;
+    const uint32_t plen = rd32(r + kPtauRecordFixed - 4);
+    if (s7.size - pos - kPtauRecordFixed < plen) return ptau_bad("Invalid File format");
+    const PtauRecord rec{r, kPtauRecordFixed + plen};
+    bool ok = mpc_g1_image_ok(rec.tau_g1()) && mpc_g2_image_ok(rec.tau_g2()) && mpc_g1_image_ok(rec.alpha_g1()) &&
+              mpc_g1_image_ok(rec.beta_g1()) && mpc_g2_image_ok(rec.beta_g2());
+    for (int x = 0; x < 3 && ok; x++) ok = mpc_g1_image_ok(rec.g1_s(x)) && mpc_g1_image_ok(rec.g1_sx(x)) && mpc_g2_image_ok(rec.g2_spx(x));
+    if (!ok) return ptau_bad("Invalid File format");
+    out.push_back(rec);
+    pos += rec.len;
+  }
+  if (pos != s7.size) return ptau_bad("Invalid File format");
+  return G16_OK;
+}
+
+namespace {
+
+constexpr uint32_t kPowerMax = 24;   // (what g16_ptau_prepare takes; the device arrays index with 32 bits)
+
+int power_above_limit(const char* route, uint32_t power) {
+  set_error(std::string(route) + ": power " + std::to_string(power) + " is above the supported limit of " + std::to_string(kPowerMax));
+  return G16_E_ARG;
+}
+
+double ms_since(const std::chrono::steady_clock::time_point& t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+bool all_zero(const uint8_t* p, size_t n) {
+  for (size_t i = 0; i < n; i++) if (p[i]) return false;
+  return true;
+}
+
+struct Gens { uint8_t g1[64], g2[128]; };
+const Gens& gens() {
+  static const Gens g = [] {
+    Gens o;
+    G1Affine a;   // (1, 2)
+    a.x = fp_one<FqParams>();
+    a.y = fp_add(a.x, a.x);
+    G2Affine b;
+    b.x.a = Fq{G16_G2X0}; b.x.b = Fq{G16_G2X1}; b.y.a = Fq{G16_G2Y0}; b.y.b = Fq{G16_G2Y1};
+    memcpy(o.g1, &a, 64);
+    memcpy(o.g2, &b, 128);
+    return o;
+  }();
+  return g;
+}
+
+// [lo, hi) of n items over at most 16 host threads
+template <class Fn> void par_for(uint64_t n, Fn fn) {
+  const unsigned hw = std::thread::hardware_concurrency();
+  const uint64_t nt = n < 8192 ? 1 : std::min<uint64_t>(16, hw ? hw : 1);
+  if (nt <= 1) { fn((uint64_t)0, n); return; }
+  std::vector<std::thread> th;
+  const uint64_t per = (n + nt - 1) / nt;
+  for (uint64_t t = 0; t < nt; t++) {
+    const uint64_t lo = t * per, hi = std::min(n, lo + per);
+    if (lo < hi) th.emplace_back([=]() { fn(lo, hi); });
+  }
+  for (auto& t : th) t.join();
+}
+
+// the ceremony as the two routes read it
+struct Ceremony {
+  PtauView pv;
+  uint64_t n = 0;          // 2^power
+  uint64_t cnt[7] = {};    // points of sections 2-6
+  std::vector<PtauRecord> rec;
+  static size_t psz(int id) { return id == 3 || id == 6 ? 128 : 64; }
+  size_t points_bytes() const {
+    size_t t = 0;
+    for (int id = 2; id <= 6; id++) t += cnt[id] * psz(id);
+    return t;
+  }
+};
+
+int open_ceremony(const uint8_t* ptau, size_t len, const char* route, Ceremony& c) {
+  if (const int rc = ptau_open(ptau, len, c.pv, /*tau_sections=*/false)) return rc;
+  if (c.pv.power > kPowerMax) return power_above_limit(route, c.pv.power);
+  c.n = (uint64_t)1 << c.pv.power;
+  c.cnt[2] = 2 * c.n - 1; c.cnt[3] = c.n; c.cnt[4] = c.n; c.cnt[5] = c.n; c.cnt[6] = 1;
+  for (int id = 2; id <= 6; id++)
+    if (!c.pv.sec[id].p || c.pv.sec[id].size != c.cnt[id] * Ceremony::psz(id)) return ptau_bad("Invalid File format");
+  return ptau_records_parse(c.pv.sec[7], c.rec);
+}
+
+// the uncompressed big-endian images of sections 2-6 (sec[id] = cnt[id] file images), behind each other at q
+void points_be_host(const uint8_t* const sec[7], const uint64_t cnt[7], uint8_t* q) {
+  for (int id = 2; id <= 6; id++) {
+    const uint8_t* s = sec[id];
+    if (Ceremony::psz(id) == 64) par_for(cnt[id], [=](uint64_t lo, uint64_t hi) { for (uint64_t i = lo; i < hi; i++) g1_uncompressed(s + i * 64, q + i * 64); });
+    else par_for(cnt[id], [=](uint64_t lo, uint64_t hi) { for (uint64_t i = lo; i < hi; i++) g2_uncompressed(s + i * 128, q + i * 128); });
+    q += cnt[id] * Ceremony::psz(id);
+  }
+}
+
+// Blake2b-512(challenge | byte key | g1_s | g1_sx uncompressed) -> the key's point on G2
+void key_g2_sp(const uint8_t challenge[64], int key, const uint8_t* g1_s, const uint8_t* g1_sx, G2Affine& sp) {
+  uint8_t feed[64 + 1 + 128], h[64];
+  memcpy(feed, challenge, 64);
+  feed[64] = (uint8_t)key;
+  g1_uncompressed(g1_s, feed + 65);
+  g1_uncompressed(g1_sx, feed + 129);
+  blake2b512(feed, sizeof(feed), h);
+  hash_to_g2(h, sp);
+}
+
+// Blake2b-512(challenge | the nine key points of a record, uncompressed, in record order)
+void response_hash(const uint8_t challenge[64], const PtauRecord& r, uint8_t out[64]) {
+  uint8_t feed[64 + 6 * 64 + 3 * 128];
+  memcpy(feed, challenge, 64);
+  for (int x = 0; x < 3; x++) {
+    g1_uncompressed(r.g1_s(x), feed + 64 + 128 * x);
+    g1_uncompressed(r.g1_sx(x), feed + 64 + 128 * x + 64);
+    g2_uncompressed(r.g2_spx(x), feed + 64 + 384 + 128 * x);
+  }
+  blake2b512(feed, sizeof(feed), out);
+}
+
+// the challenge of the generator file of this ceremony's size: what the first record's keys are bound to
+void generator_challenge(const Ceremony& c, uint8_t out[64]) {
+  std::vector<uint8_t> feed(64 + c.points_bytes());
+  blake2b512(nullptr, 0, feed.data());
+  uint8_t u1[64], u2[128];
+  g1_uncompressed(gens().g1, u1);
+  g2_uncompressed(gens().g2, u2);
+  uint8_t* q = feed.data() + 64;
+  for (int id = 2; id <= 6; id++)
+    for (uint64_t i = 0; i < c.cnt[id]; i++) {
+      if (Ceremony::psz(id) == 64) memcpy(q, u1, 64); else memcpy(q, u2, 128);
+      q += Ceremony::psz(id);
+    }
+  blake2b512(feed.data(), feed.size(), out);
+}
+
+bool scalar_ok(const uint8_t* s, Fr& out) {   // standard form, in [1, r)
+  memcpy(out.v, s, 32);
+  return !fp_is_zero(out) && fr_below_modulus(out.v);
+}
+
+int new_core(uint32_t power, uint8_t** out, size_t* out_len) {
+  if (power > kPowerMax) return power_above_limit("ptau new", power);
+  const uint64_t n = (uint64_t)1 << power;
+  const uint64_t sizes[16] = {0, 44, (2 * n - 1) * 64, n * 128, n * 64, n * 64, 128, 4};
+  static const int ids[7] = {1, 2, 3, 4, 5, 6, 7};
+  Buf z;
+  uint8_t* sp[16] = {};
+  if (!bin_layout(z, "ptau", 1, ids, 7, sizes, sp)) { set_error("ptau new: out of memory"); return G16_E_STATE; }
+  uint8_t* q = bin_put_field(sp[1], kFqP);
+  memcpy(q, &power, 4); memcpy(q + 4, &power, 4);
+  for (int id = 2; id <= 6; id++) {
+    const size_t psz = Ceremony::psz(id);
+    for (uint64_t i = 0; i < sizes[id] / psz; i++) memcpy(sp[id] + i * psz, psz == 64 ? gens().g1 : gens().g2, psz);
+  }
+  memset(sp[7], 0, 4);
+  z.give(out, out_len);
+  return G16_OK;
+}
+
+int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uint8_t* secret, int device, uint8_t** out,
+                    size_t* out_len, uint8_t contribution_hash[64]) {
+  const auto t0 = std::chrono::steady_clock::now();
+  Ceremony c;
+  if (const int rc = open_ceremony(ptau, len, "ptau contribute", c)) return rc;
+  Fr key[3], sk[3];   // tau, alpha, beta; s_tau, s_alpha, s_beta
+  if (secret) {
+    for (int x = 0; x < 3; x++)
+      if (!scalar_ok(secret + 32 * x, key[x]) || !scalar_ok(secret + 96 + 32 * x, sk[x])) {
+        set_error("ptau contribute: the secret scalars must be in [1, r)");
+        return G16_E_ARG;
+      }
+  } else {
+    for (Fr* x : {&key[0], &key[1], &key[2], &sk[0], &sk[1], &sk[2]})
+      for (;;) {
+        if (const int rc = mpc_os_random((uint8_t*)x->v, 32)) return rc;
+        x->v[7] &= 0x3fffffffu;
+        if (!fp_is_zero(*x) && fr_below_modulus(x->v)) break;
+      }
+  }
+  if (const int rc = require_hip_device("ptau contribute", device)) return rc;
+
+  const std::string params = mpc_name_params(name);
+  const uint32_t plen = (uint32_t)params.size();
+  const size_t rec_len = kPtauRecordFixed + plen;
+  static const uint8_t no_contributions[4] = {0, 0, 0, 0};
+  const uint8_t* old7 = c.pv.sec[7].p ? c.pv.sec[7].p : no_contributions;
+  const uint64_t old7_size = c.pv.sec[7].p ? c.pv.sec[7].size : 4;
+
+  uint64_t sizes[16] = {};
+  for (int id = 1; id <= 6; id++) sizes[id] = c.pv.sec[id].size;
+  sizes[7] = old7_size + rec_len;
+  static const int ids[7] = {1, 2, 3, 4, 5, 6, 7};
+  Buf z;
+  uint8_t* sp[16] = {};
+  if (!bin_layout(z, "ptau", 1, ids, 7, sizes, sp)) { set_error("ptau contribute: out of memory"); return G16_E_STATE; }
+  struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
+  memcpy(sp[1], c.pv.sec[1].p, sizes[1]);
+  memcpy(sp[7], old7, old7_size);
+  const uint32_t count = (uint32_t)c.rec.size() + 1;
+  memcpy(sp[7], &count, 4);
+  uint8_t* rec = sp[7] + old7_size;
+  memset(rec, 0, rec_len);   // (partialHash stays zero)
+  const PtauRecord R{rec, rec_len};
+
+  // the challenge this contribution answers
+  const auto th0 = std::chrono::steady_clock::now();
+  std::vector<uint8_t> feed(64 + c.points_bytes());
+  uint8_t challenge[64];
+  const uint8_t* in[7] = {};
+  for (int id = 2; id <= 6; id++) in[id] = c.pv.sec[id].p;
+  if (c.rec.empty()) {
+    blake2b512(nullptr, 0, feed.data());
+    points_be_host(in, c.cnt, feed.data() + 64);
+    blake2b512(feed.data(), feed.size(), challenge);
+  } else {
+    memcpy(challenge, c.rec.back().next_challenge(), 64);
+  }
+  // the three keys
+  for (int x = 0; x < 3; x++) {
+    uint8_t* g1_s = rec + kPtauKeysAt + 128 * x;
+    mpc_mul_g1(gens().g1, sk[x], g1_s);
+    mpc_mul_g1(g1_s, key[x], g1_s + 64);
+    G2Affine sp2;
+    key_g2_sp(challenge, x, g1_s, g1_s + 64, sp2);
+    mpc_mul_g2((const uint8_t*)&sp2, key[x], rec + 832 + 128 * x);
+  }
+  double hash_ms = ms_since(th0);
+
+  // device: the sections, and the big-endian images of the new points straight into the next challenge's feed
+  Fr one = fp_zero<FrParams>();
+  one.v[0] = 1;
+  PtauScaleStats st[5];
+  {
+    uint8_t* be = feed.data() + 64;
+    const Fr* cs[7] = {nullptr, nullptr, &one, &one, &key[1], &key[2], &key[2]};
+    int rc = G16_OK;
+    for (int id = 2; id <= 6 && !rc; id++) {
+      const Fr& k = id == 6 ? one : key[0];
+      rc = Ceremony::psz(id) == 64 ? ptau_scale_g1(device, in[id], c.cnt[id], *cs[id], k, 0, sp[id], be, &st[id - 2])
+                                   : ptau_scale_g2(device, in[id], c.cnt[id], *cs[id], k, 0, sp[id], be, &st[id - 2]);
+      be += c.cnt[id] * Ceremony::psz(id);
+    }
+    if (rc) return rc;
+  }
+
+  // the record: the state after this contribution.  tauG1 / tauG2 are point 1 of sections 2 / 3; a power-0 file holds
+  // no such point, there they continue the last record's (or the generators)
+  const auto th1 = std::chrono::steady_clock::now();
+  if (c.pv.power >= 1) {
+    memcpy(rec, sp[2] + 64, 64);
+    memcpy(rec + 64, sp[3] + 128, 128);
+  } else {
+    mpc_mul_g1(c.rec.empty() ? gens().g1 : c.rec.back().tau_g1(), key[0], rec);
+    mpc_mul_g2(c.rec.empty() ? gens().g2 : c.rec.back().tau_g2(), key[0], rec + 64);
+  }
+  memcpy(rec + 192, sp[4], 64);
+  memcpy(rec + 256, sp[5], 64);
+  memcpy(rec + 320, sp[6], 128);
+  uint8_t response[64];
+  response_hash(challenge, R, response);
+  if (contribution_hash) memcpy(contribution_hash, response, 64);
+  memcpy(feed.data(), response, 64);
+  blake2b512(feed.data(), feed.size(), rec + kPtauNextChallengeAt);
+  const uint32_t type = 0;
+  memcpy(rec + kPtauNextChallengeAt + 64, &type, 4);
+  memcpy(rec + kPtauNextChallengeAt + 68, &plen, 4);
+  if (plen) memcpy(rec + kPtauRecordFixed, params.data(), plen);
+  hash_ms += ms_since(th1);
+
+  if (getenv("G16_TRACE_HOST")) {
+    uint64_t g1 = 0, g2 = 0;
+    float k1 = 0, k2 = 0, xf = 0;
+    for (int id = 2; id <= 6; id++) {
+      const PtauScaleStats& s = st[id - 2];
+      if (Ceremony::psz(id) == 64) { g1 += s.points; k1 += s.kern_ms; } else { g2 += s.points; k2 += s.kern_ms; }
+      xf += s.xfer_ms;
+    }
+    fprintf(stderr,
+            "[g16] ptau contribute: points G1 %llu G2 %llu; kernels G1 %.3f ms G2 %.3f ms, transfers %.3f ms; host hashing %.3f ms "
+            "(big-endian images of the new points made on the device%s); call %.3f ms\n",
+            (unsigned long long)g1, (unsigned long long)g2, k1, k2, xf, hash_ms,
+            c.rec.empty() ? ", of the input on the host" : "", ms_since(t0));
+  }
+  guard.p = nullptr;
+  z.give(out, out_len);
+  return G16_OK;
+}
+
+int verify_core(const uint8_t* ptau, size_t len, int device, int* ok) {
+  const auto t0 = std::chrono::steady_clock::now();
+  *ok = 0;
+  Ceremony c;
+  if (const int rc = open_ceremony(ptau, len, "ptau verify", c)) return rc;
+  const uint8_t* sec[16] = {};
+  for (int id = 0; id < 16; id++) sec[id] = c.pv.sec[id].p;
+  {
+    std::atomic<bool> bad{false};
+    for (int id = 2; id <= 6; id++) {
+      const uint8_t* s = sec[id];
+      const bool g1 = Ceremony::psz(id) == 64;
+      par_for(c.cnt[id], [&, s, g1](uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo; i < hi && !bad.load(std::memory_order_relaxed); i++)
+          if (!(g1 ? mpc_g1_image_ok(s + i * 64) : mpc_g2_image_ok(s + i * 128))) bad = true;
+      });
+    }
+    if (bad) return ptau_bad("Invalid File format");
+  }
+  if (const int rc = require_hip_device("ptau verify", device)) return rc;
+  auto verdict = [&](const char* why) { set_error(why); return G16_OK; };
+  const Gens& G = gens();
+
+  // 1. the first powers
+  if (memcmp(sec[2], G.g1, 64) != 0 || memcmp(sec[3], G.g2, 128) != 0)
+    return verdict("ptau verify: the first point of section 2 or 3 is not the generator");
+
+  // 2. the record walk: hashes on the host, the pairs of every same-ratio check collected for ONE device call.  A
+  // record's keys are bound to its challenge: the generator file's for the first record, the nextChallenge of the
+  // record before for every other.  nextChallenge itself can only be recomputed where the state it hashes is at hand:
+  // for the last record, from the file (check 4)
+  std::vector<uint8_t> pairs;        // 192 bytes each; check k compares pairing 2k with pairing 2k + 1
+  std::vector<const char*> reason;   // per check
+  auto same_ratio = [&](const uint8_t* g1a, const uint8_t* g1b, const uint8_t* g2c, const uint8_t* g2d, const char* why) {
+    mpc_pair_words(pairs, g1a, g2d);   // e(a, d) = e(b, c)
+    mpc_pair_words(pairs, g1b, g2c);
+    reason.push_back(why);
+  };
+  const uint8_t* cur[3] = {G.g1, G.g1, G.g1};   // tauG1, alphaG1, betaG1 before the record
+  uint8_t challenge[64];
+  std::vector<G2Affine> g2_sp(3 * c.rec.size());
+  static const char* const chain_text[3] = {"ptau verify: a contribution's tauG1 does not continue the chain",
+                                            "ptau verify: a contribution's alphaG1 does not continue the chain",
+                                            "ptau verify: a contribution's betaG1 does not continue the chain"};
+  for (size_t i = 0; i < c.rec.size(); i++) {
+    const PtauRecord& r = c.rec[i];
+    bool inf = all_zero(r.tau_g1(), 64) || all_zero(r.tau_g2(), 128) || all_zero(r.alpha_g1(), 64) || all_zero(r.beta_g1(), 64) ||
+               all_zero(r.beta_g2(), 128);
+    for (int x = 0; x < 3; x++) inf = inf || all_zero(r.g1_s(x), 64) || all_zero(r.g1_sx(x), 64) || all_zero(r.g2_spx(x), 128);
+    if (inf) return verdict("ptau verify: a contribution holds the point at infinity");
+    if (i == 0) generator_challenge(c, challenge);
+    else memcpy(challenge, c.rec[i - 1].next_challenge(), 64);
+    const uint8_t* now[3] = {r.tau_g1(), r.alpha_g1(), r.beta_g1()};
+    for (int x = 0; x < 3; x++) {
+      G2Affine& sp = g2_sp[3 * i + x];
+      key_g2_sp(challenge, x, r.g1_s(x), r.g1_sx(x), sp);
+      same_ratio(r.g1_s(x), r.g1_sx(x), (const uint8_t*)&sp, r.g2_spx(x), "ptau verify: a contribution's public key is not consistent");
+      same_ratio(cur[x], now[x], (const uint8_t*)&sp, r.g2_spx(x), chain_text[x]);
+      cur[x] = now[x];
+    }
+    same_ratio(G.g1, r.tau_g1(), G.g2, r.tau_g2(), "ptau verify: a contribution's tauG2 does not match its tauG1");
+    same_ratio(G.g1, r.beta_g1(), G.g2, r.beta_g2(), "ptau verify: a contribution's betaG2 does not match its betaG1");
+  }
+
+  // 3, 4 (host): a failure here is reported after the walk's pairings, and spares the sums of check 5
+  const char* host_fail = nullptr;
+  if (c.rec.empty()) {
+    bool gen = true;
+    for (int id = 2; id <= 6 && gen; id++)
+      for (uint64_t i = 0; i < c.cnt[id] && gen; i++)
+        gen = Ceremony::psz(id) == 64 ? memcmp(sec[id] + i * 64, G.g1, 64) == 0 : memcmp(sec[id] + i * 128, G.g2, 128) == 0;
+    if (!gen) host_fail = "ptau verify: a file without contributions is not the generator file";
+  } else {
+    const PtauRecord& r = c.rec.back();
+    bool same = memcmp(r.alpha_g1(), sec[4], 64) == 0 && memcmp(r.beta_g1(), sec[5], 64) == 0 && memcmp(r.beta_g2(), sec[6], 128) == 0;
+    if (c.pv.power >= 1) same = same && memcmp(r.tau_g1(), sec[2] + 64, 64) == 0 && memcmp(r.tau_g2(), sec[3] + 128, 128) == 0;
+    if (!same) host_fail = "ptau verify: the file's points are not the last contribution's";
+    if (!host_fail) {
+      // (challenge = the last record's, from the walk)
+      std::vector<uint8_t> feed(64 + c.points_bytes());
+      response_hash(challenge, r, feed.data());
+      points_be_host(sec, c.cnt, feed.data() + 64);
+      uint8_t next[64];
+      blake2b512(feed.data(), feed.size(), next);
+      if (memcmp(next, r.next_challenge(), 64) != 0) host_fail = "ptau verify: the last contribution's challenge hash does not match the file";
+    }
+  }
+
+  // 5. the powers: with fresh random rho_i, S1 = sum rho_i P_i, S2 = sum rho_i P_(i+1) must have the ratio tau
+  double msm_ms = 0;
+  uint64_t msm_points = 0;
+  const char* inf_fail = nullptr;
+  if (!host_fail && c.pv.power >= 1) {
+    static const char* const power_text[6] = {nullptr, nullptr, "ptau verify: section 2 is not the powers of tau",
+                                              "ptau verify: section 3 is not the powers of tau",
+                                              "ptau verify: section 4 is not alpha times the powers of tau",
+                                              "ptau verify: section 5 is not beta times the powers of tau"};
+    static const char* const inf_text[6] = {nullptr, nullptr, "ptau verify: the combination of section 2 is the point at infinity",
+                                            "ptau verify: the combination of section 3 is the point at infinity",
+                                            "ptau verify: the combination of section 4 is the point at infinity",
+                                            "ptau verify: the combination of section 5 is the point at infinity"};
+    std::vector<uint8_t> rho((c.cnt[2] - 1) * 32);
+    if (const int rc = mpc_random_fr(rho.data(), c.cnt[2] - 1)) return rc;
+    const auto t1 = std::chrono::steady_clock::now();
+    uint8_t tau1[192], gen[192];   // (tauG1, tauG2) and (G1, G2) as pairing words
+    {
+      std::vector<uint8_t> w;
+      mpc_pair_words(w, sec[2] + 64, sec[3] + 128);
+      memcpy(tau1, w.data(), 192);
+      w.clear();
+      mpc_pair_words(w, G.g1, G.g2);
+      memcpy(gen, w.data(), 192);
+    }
+    for (int id = 2; id <= 5 && !inf_fail; id++) {
+      const uint64_t m = c.cnt[id] - 1;
+      uint8_t S1[128], S2[128];   // standard form
+      const size_t at = pairs.size();
+      if (id != 3) {
+        if (const int rc = g16_g1_multiexp(device, sec[id], rho.data(), m, 0, S1)) return rc;
+        if (const int rc = g16_g1_multiexp(device, sec[id] + 64, rho.data(), m, 0, S2)) return rc;
+        if (all_zero(S1, 64) || all_zero(S2, 64)) { inf_fail = inf_text[id]; break; }
+        pairs.resize(at + 2 * 192);
+        memcpy(pairs.data() + at, S1, 64);                    // e(S1, tauG2) = e(S2, G2)
+        memcpy(pairs.data() + at + 64, tau1 + 64, 128);
+        memcpy(pairs.data() + at + 192, S2, 64);
+        memcpy(pairs.data() + at + 192 + 64, gen + 64, 128);
+      } else {
+        if (const int rc = g16_g2_multiexp(device, sec[id], rho.data(), m, 0, S1)) return rc;
+        if (const int rc = g16_g2_multiexp(device, sec[id] + 128, rho.data(), m, 0, S2)) return rc;
+        if (all_zero(S1, 128) || all_zero(S2, 128)) { inf_fail = inf_text[id]; break; }
+        pairs.resize(at + 2 * 192);
+        memcpy(pairs.data() + at, tau1, 64);                  // e(tauG1, T1) = e(G1, T2)
+        memcpy(pairs.data() + at + 64, S1, 128);
+        memcpy(pairs.data() + at + 192, gen, 64);
+        memcpy(pairs.data() + at + 192 + 64, S2, 128);
+      }
+      reason.push_back(power_text[id]);
+      msm_points += 2 * m;
+    }
+    msm_ms = ms_since(t1);
+  }
+  const auto t2 = std::chrono::steady_clock::now();
+  const uint32_t np = (uint32_t)(pairs.size() / 192);
+  std::vector<uint8_t> gt((size_t)np * 384);
+  if (np)
+    if (const int rc = g16_pairing_op(device, pairs.data(), np, gt.data())) return rc;
+  const double pair_ms = ms_since(t2);
+  if (getenv("G16_TRACE_HOST"))
+    fprintf(stderr, "[g16] ptau verify: power %u, records %zu; MSM %.3f ms (%llu points), pairings %.3f ms (%u); call %.3f ms\n",
+            c.pv.power, c.rec.size(), msm_ms, (unsigned long long)msm_points, pair_ms, np, ms_since(t0));
+  // (a host failure has spared the sums: every pairing check is then the walk's, and comes first)
+  for (size_t k = 0; k < reason.size(); k++) {
+    if (memcmp(gt.data() + 2 * k * 384, gt.data() + (2 * k + 1) * 384, 384) != 0) return verdict(reason[k]);
+  }
+  if (host_fail) return verdict(host_fail);
+  if (inf_fail) return verdict(inf_fail);
+
+  // 6. a prepared file: sections 12-15 against a fresh transform of sections 2-5
+  int have = 0;
+  for (int id = 12; id <= 15; id++) have += sec[id] ? 1 : 0;
+  if (have) {
+    if (have != 4) return verdict("ptau verify: the prepared sections 12 to 15 are not all present");
+    uint8_t* prep = nullptr;
+    size_t prep_len = 0;
+    if (const int rc = g16_ptau_prepare(ptau, len, device, &prep, &prep_len)) return rc;
+    struct Free { uint8_t* p; ~Free() { free(p); } } guard{prep};
+    PtauView pp;
+    if (const int rc = ptau_open(prep, prep_len, pp, false)) return rc;
+    for (int id = 12; id <= 15; id++)
+      if (!pp.sec[id].p || pp.sec[id].size != c.pv.sec[id].size || memcmp(pp.sec[id].p, sec[id], pp.sec[id].size) != 0)
+        return verdict("ptau verify: the prepared sections are not the transform of sections 2 to 5");
+  }
+  set_error("");
+  *ok = 1;
+  return G16_OK;
+}
+
+}  // namespace
+}  // namespace g16
+
+using namespace g16;
+
+extern "C" int g16_ptau_new(uint32_t power, uint8_t** out, size_t* out_len) {
+  if (!out || !out_len) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("ptau new", [&]() { return new_core(power, out, out_len); });
+}
+
+extern "C" int g16_ptau_new_file(uint32_t power, const char* path) {
+  if (!path) { set_error("NULL argument"); return G16_E_ARG; }
+  uint8_t* z = nullptr;
+  size_t zl = 0;
+  if (const int rc = g16_ptau_new(power, &z, &zl)) return rc;
+  return write_key_file(path, z, zl);
+}
+
+extern "C" int g16_ptau_contribute(const uint8_t* ptau, size_t ptau_len, const char* name, const uint8_t secret[192], int device,
+                                   uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]) {
+  if (!ptau || !out || !out_len) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("ptau contribute",
+                      [&]() { return contribute_core(ptau, ptau_len, name, secret, device, out, out_len, contribution_hash); });
+}
+
+extern "C" int g16_ptau_contribute_files(const char* in_path, const char* out_path, const char* name, const uint8_t secret[192],
+                                         int device, uint8_t contribution_hash[64]) {
+  if (!in_path || !out_path) { set_error("NULL argument"); return G16_E_ARG; }
+  return files_form(&in_path, 1, out_path, [&](const MappedFile* m, uint8_t** z, size_t* zl) {
+    return g16_ptau_contribute((const uint8_t*)m[0].p, m[0].len, name, secret, device, z, zl, contribution_hash);
+  });
+}
+
+extern "C" int g16_ptau_verify(const uint8_t* ptau, size_t ptau_len, int device, int* ok) {
+  if (!ptau || !ok) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("ptau verify", [&]() { return verify_core(ptau, ptau_len, device, ok); });
+}
+
+extern "C" int g16_ptau_verify_file(const char* path, int device, int* ok) {
+  if (!path || !ok) { set_error("NULL argument"); return G16_E_ARG; }
+  MappedFile in;
+  if (const int rc = in.open_ro(path)) return rc;
+  return g16_ptau_verify((const uint8_t*)in.p, in.len, device, ok);
+}
+
+extern "C" int g16_ptau_secret_from_text(const char* text, uint8_t secret[192]) {
+  if (!text || !secret) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("ptau secret", [&]() {
+    const size_t n = strlen(text);
+    std::vector<uint8_t> feed(n + 1);
+    memcpy(feed.data(), text, n);
+    for (int j = 0; j < 3; j++) {
+      uint8_t h[64];
+      feed[n] = (uint8_t)j;
+      blake2b512(feed.data(), feed.size(), h);
+      for (int half = 0; half < 2; half++) {
+        Fr x;
+        memcpy(x.v, h + 32 * half, 32);
+        x = fp_from_mont(fp_to_mont(x));   // (reduces a value >= r)
+        if (fp_is_zero(x)) x.v[0] = 1;
+        memcpy(secret + 96 * half + 32 * j, x.v, 32);
+      }
+    }
+    return G16_OK;
+  });
+}

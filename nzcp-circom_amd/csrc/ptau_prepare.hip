@@ -18,7 +18,7 @@
 // digits) and the pos = 0 lanes, which need no product, are whole wavefronts that leave at once.  The strided point
 // accesses this costs do not matter: a product is ~3500 field multiplications on 128 / 256 bytes.
 //
-// The product is sp_full_kernel's (setup_ptau.hip) signed 3-bit fixed window -- digits -3..4, 254 doublings + at most
+// The product (pp_scalar_mul, scalar_mul.cuh) is sp_full_kernel's (setup_ptau.hip) signed 3-bit fixed window -- digits -3..4, 254 doublings + at most
 // 85 additions + 3 for the table [1..4]P -- over a projective base.  A lane's table lives in global memory, one slot
 // per lane of a fixed persistent grid (grid-stride loop), not in LDS: 4 x 256 B per G2 lane would cap a workgroup at
 // one wavefront.  Exact canonical arithmetic (fp.cuh / ec.cuh): the XYZZ formulas there are complete (infinity
@@ -32,12 +32,13 @@
 
 #include "ec.cuh"
 #include "internal.h"
+#include "scalar_mul.cuh"
 #include "setup_affine.cuh"
 
 namespace g16 {
 namespace {
 
-constexpr int kWin = 3, kTbl = 1 << (kWin - 1), kDigits = (254 + kWin - 1) / kWin;
+constexpr int kWin = 3, kTbl = 1 << (kWin - 1);
 constexpr int kMulBlock = 256;
 
 // element t of the block layout: block k = floor(log2(t + 1)), point j = t + 1 - 2^k
@@ -55,59 +56,6 @@ __global__ __launch_bounds__(256) void pp_load_kernel(const Affine<FC>* __restri
   if (i < nsrc) xyzz_from_affine(p, src[i]);
   else xyzz_set_inf(p);
   work[t] = p;
-}
-
-// acc = [k] base, k standard form < r (read where indexed: a private copy would go to scratch); tbl = the lane's
-// table slots, `stride` elements apart
-template <class FC>
-__device__ __forceinline__ void pp_scalar_mul(XYZZ<FC>& acc, const XYZZ<FC>& base, const uint32_t* __restrict__ k,
-                                              XYZZ<FC>* __restrict__ tbl, uint32_t stride) {
-  xyzz_set_inf(acc);
-  if (xyzz_is_inf(base)) return;
-  {
-    XYZZ<FC> t = base;
-    tbl[0] = t;
-    xyzz_dbl(t);
-    tbl[stride] = t;
-    for (int e = 2; e < kTbl; e++) {
-      xyzz_add(t, base);
-      tbl[(size_t)e * stride] = t;
-    }
-  }
-  // signed digits d_j in [-3, 4], k = sum d_j 2^(3j): a window above 4 becomes window - 8 and carries one into the
-  // next; k < 2^254, so the top window (bits 252-254) takes its carry without producing one
-  auto window = [&](int j) -> uint32_t {
-    const int pos = j * kWin;
-    uint64_t v = k[pos >> 5];
-    if ((pos >> 5) + 1 < 8) v |= (uint64_t)k[(pos >> 5) + 1] << 32;
-    return (uint32_t)(v >> (pos & 31)) & ((1u << kWin) - 1);
-  };
-  uint64_t carry_lo = 0, carry_hi = 0;   // (kDigits = 85 < 128)
-  {
-    uint32_t c = 0;
-    for (int j = 0; j < kDigits; j++) {
-      const uint32_t d = window(j) + c;
-      c = d > (uint32_t)kTbl ? 1u : 0u;
-      if (c) {
-        if (j < 64) carry_lo |= 1ull << j;
-        else carry_hi |= 1ull << (j - 64);
-      }
-    }
-  }
-  auto carry = [&](int j) -> uint32_t {
-    if (j < 0) return 0;
-    return (uint32_t)((j < 64 ? carry_lo >> j : carry_hi >> (j - 64)) & 1);
-  };
-  for (int j = kDigits - 1; j >= 0; j--) {
-    if (j != kDigits - 1)
-      for (int s = 0; s < kWin; s++) xyzz_dbl(acc);
-    const int d = (int)(window(j) + carry(j - 1)) - (int)(carry(j) << kWin);
-    if (d) {
-      XYZZ<FC> e = tbl[(size_t)((d < 0 ? -d : d) - 1) * stride];
-      if (d < 0) xyzz_neg(e);
-      xyzz_add(acc, e);
-    }
-  }
 }
 
 // Lane t of n (grid-stride).  s >= 1, the twiddle products of stage s: v = t + 2^s, block k = floor(log2 v) + 1,
@@ -134,7 +82,7 @@ __global__ __launch_bounds__(kMulBlock) void pp_mul_kernel(XYZZ<FC>* __restrict_
     }
     const XYZZ<FC> base = work[e];
     XYZZ<FC> acc;
-    pp_scalar_mul<FC>(acc, base, sc[si].v, tbl + gid, stride);
+    pp_scalar_mul<FC, kWin>(acc, base, sc[si].v, tbl + gid, stride);
     work[e] = acc;
   }
 }

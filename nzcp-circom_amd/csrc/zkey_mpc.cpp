@@ -214,6 +214,38 @@ template <class F> void mul_image(const uint8_t* lem, const Fr& k_std, uint8_t* 
 
 }  // namespace
 
+// the helpers above for the .ptau ceremony (ptau_mpc.cpp)
+bool mpc_g1_image_ok(const uint8_t* p) { return g1_image_ok(p); }
+bool mpc_g2_image_ok(const uint8_t* p) { return g2_image_ok(p); }
+void mpc_mul_g1(const uint8_t* lem, const Fr& k_std, uint8_t* out) { mul_image<FqOps>(lem, k_std, out); }
+void mpc_mul_g2(const uint8_t* lem, const Fr& k_std, uint8_t* out) { mul_image<Fq2Ops>(lem, k_std, out); }
+int mpc_os_random(uint8_t* out, size_t n) { return os_random(out, n); }
+int mpc_random_fr(uint8_t* out, uint64_t n) {
+  ChaCha rng;
+  if (const int rc = os_random((uint8_t*)rng.key, 32)) return rc;
+  for (uint64_t i = 0; i < n; i++) rng.next_below(kFrP, (uint32_t*)(out + i * 32));
+  return G16_OK;
+}
+// a record's params: byte 1, byte len, the name's UTF-8 bytes cut to 64 characters and to what one length byte can
+// hold; nothing without a name
+std::string mpc_name_params(const char* name) {
+  std::string nm;
+  if (name) {
+    size_t chars = 0, i = 0;
+    const size_t len = strlen(name);
+    while (i < len && chars < 64) {
+      size_t j = i + 1;
+      while (j < len && ((uint8_t)name[j] & 0xc0) == 0x80) j++;
+      if (j > 255) break;
+      i = j;
+      chars++;
+    }
+    nm.assign(name, i);
+  }
+  if (nm.empty()) return nm;
+  return std::string(1, (char)1) + std::string(1, (char)(uint8_t)nm.size()) + nm;
+}
+
 void g1_uncompressed(const uint8_t lem[64], uint8_t out[64]) {
   if (all_zero(lem, 64)) { memset(out, 0, 64); out[0] = 0x40; return; }
   be32(fp_from_mont(fq_load(lem)), out);
@@ -379,21 +411,8 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
   }
   if (const int rc = require_hip_device("zkey contribute", device)) return rc;
 
-  // the record's name: at most 64 characters, and what one length byte can hold
-  std::string nm;
-  if (name) {
-    size_t chars = 0, i = 0;
-    const size_t len = strlen(name);
-    while (i < len && chars < 64) {
-      size_t j = i + 1;
-      while (j < len && ((uint8_t)name[j] & 0xc0) == 0x80) j++;
-      if (j > 255) break;
-      i = j;
-      chars++;
-    }
-    nm.assign(name, i);
-  }
-  const uint32_t plen = nm.empty() ? 0 : (uint32_t)(2 + nm.size());
+  const std::string params = mpc_name_params(name);
+  const uint32_t plen = (uint32_t)params.size();
   const size_t rec_len = kMpcRecordFixed + plen;
 
   // the image: every record of the input's table in its order, the first section 10 one record longer
@@ -446,11 +465,7 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
     const uint32_t type = 0;
     memcpy(rec + 384, &type, 4);
     memcpy(rec + 388, &plen, 4);
-    if (plen) {
-      rec[392] = 1;
-      rec[393] = (uint8_t)nm.size();
-      memcpy(rec + 394, nm.data(), nm.size());
-    }
+    if (plen) memcpy(rec + 392, params.data(), plen);
     const uint32_t count = (uint32_t)k.mpc.rec.size() + 1;
     memcpy(sp[10] + 64, &count, 4);
     std::vector<uint8_t> feed;
@@ -472,13 +487,14 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
 }
 
 // ---- verify
-void pair_words(std::vector<uint8_t>& in, const uint8_t* g1_lem, const uint8_t* g2_lem) {   // g16_pairing_op's input
+}  // namespace
+void mpc_pair_words(std::vector<uint8_t>& in, const uint8_t* g1_lem, const uint8_t* g2_lem) {   // g16_pairing_op's input
   const size_t at = in.size();
   in.resize(at + 192);
   for (int i = 0; i < 2; i++) { const Fq v = fp_from_mont(fq_load(g1_lem + 32 * i)); memcpy(in.data() + at + 32 * i, v.v, 32); }
   for (int i = 0; i < 4; i++) { const Fq v = fp_from_mont(fq_load(g2_lem + 32 * i)); memcpy(in.data() + at + 64 + 32 * i, v.v, 32); }
 }
-
+namespace {
 int verify_core(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_t zkey_len, int device, int* ok) {
   const auto t0 = std::chrono::steady_clock::now();
   *ok = 0;
@@ -510,8 +526,8 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_
   std::vector<const char*> reason;   // per check
   auto same_ratio = [&](const uint8_t* g1a, const uint8_t* g1b, const uint8_t* g2c, const uint8_t* g2d, const char* why) {
     if (all_zero(g1a, 64) || all_zero(g1b, 64) || all_zero(g2c, 128) || all_zero(g2d, 128)) return false;
-    pair_words(pairs, g1a, g2d);   // e(a, d) = e(b, c)
-    pair_words(pairs, g1b, g2c);
+    mpc_pair_words(pairs, g1a, g2d);   // e(a, d) = e(b, c)
+    mpc_pair_words(pairs, g1b, g2c);
     reason.push_back(why);
     return true;
   };

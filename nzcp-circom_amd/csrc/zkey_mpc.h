@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 #include "binfile.h"
@@ -42,5 +43,16 @@ void g1_uncompressed(const uint8_t lem[64], uint8_t out[64]);
 void g2_uncompressed(const uint8_t lem[128], uint8_t out[128]);
 
 void hash_to_g2(const uint8_t transcript[64], G2Affine& out);
+
+// Shared with the .ptau ceremony (ptau_mpc.cpp).  File images are affine little-endian Montgomery, infinity = zeros.
+bool mpc_g1_image_ok(const uint8_t* p);   // coordinates below q and the point on its curve (infinity passes)
+bool mpc_g2_image_ok(const uint8_t* p);
+void mpc_mul_g1(const uint8_t* lem, const Fr& k_std, uint8_t* out);   // [k] P on the host
+void mpc_mul_g2(const uint8_t* lem, const Fr& k_std, uint8_t* out);
+int mpc_os_random(uint8_t* out, size_t n);
+int mpc_random_fr(uint8_t* out, uint64_t n);   // n fresh standard-form scalars below r: ChaCha20 keyed from the OS CSPRNG
+std::string mpc_name_params(const char* name);   // a record's params for a contribution's name (or NULL)
+// one pair of g16_pairing_op's input appended: six standard-form words
+void mpc_pair_words(std::vector<uint8_t>& in, const uint8_t* g1_lem, const uint8_t* g2_lem);
 
 }  // namespace g16

@@ -24,6 +24,10 @@
  *           ptauPrepareFiles(inPath, outPath, device) -> Promise<undefined>   (g16_ptau_prepare_files)
  *           zkeyContributeFiles(inPath, outPath, name | null, secret Buffer(64) | null, device) -> Promise<Buffer(64)>
  *                                                                              (g16_zkey_contribute_files: the hash)
+ *           ptauNewFile(power, outPath) -> Promise<undefined>                  (g16_ptau_new_file)
+ *           ptauContributeFiles(inPath, outPath, name | null, secret Buffer(192) | null, device) -> Promise<Buffer(64)>
+ *                                                                              (g16_ptau_contribute_files: the hash)
+ *           ptauVerifyFile(path, device) -> Promise<{ok, reason}>              (g16_ptau_verify_file)
  *           zkeyVerifyFromInitFiles(initPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_from_init_files)
  */
 #include <node_api.h>
@@ -881,6 +885,124 @@ static napi_value js_zkey_verify_from_init_files(napi_env env, napi_callback_inf
   return zjob_start(env, j, "g16_zkey_verify_from_init_files");
 }
 
+/* powersoftau new / contribute / verify from / to files */
+typedef struct {
+  napi_async_work work;
+  napi_deferred deferred;
+  char a[1024], b[1024], name[512];
+  uint8_t secret[192], hash[64];
+  int mode;   /* 0: g16_ptau_new_file(power, a); 1: g16_ptau_contribute_files(a, b, ..); 2: g16_ptau_verify_file(a) */
+  int has_name, has_secret, device, rc, ok;
+  uint32_t power;
+  char err[512];
+} tjob_t;
+static void tjob_execute(napi_env env, void* data) {
+  tjob_t* j = (tjob_t*)data;
+  if (j->mode == 0) j->rc = g16_ptau_new_file(j->power, j->a);
+  else if (j->mode == 1)
+    j->rc = g16_ptau_contribute_files(j->a, j->b, j->has_name ? j->name : NULL, j->has_secret ? j->secret : NULL, j->device, j->hash);
+  else j->rc = g16_ptau_verify_file(j->a, j->device, &j->ok);
+  if (j->rc || (j->mode == 2 && !j->ok)) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
+}
+static void tjob_complete(napi_env env, napi_status status, void* data) {
+  tjob_t* j = (tjob_t*)data;
+  if (status != napi_ok || j->rc) {
+    napi_value msg, err;
+    napi_create_string_utf8(env, j->rc ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_reject_deferred(env, j->deferred, err);
+  } else if (j->mode == 2) {
+    napi_value obj, ok, reason;
+    napi_create_object(env, &obj);
+    napi_get_boolean(env, j->ok != 0, &ok);
+    napi_create_string_utf8(env, j->ok ? "" : j->err, NAPI_AUTO_LENGTH, &reason);
+    napi_set_named_property(env, obj, "ok", ok);
+    napi_set_named_property(env, obj, "reason", reason);
+    napi_resolve_deferred(env, j->deferred, obj);
+  } else if (j->mode == 1) {
+    napi_value buf;
+    void* copy = NULL;
+    napi_create_buffer_copy(env, 64, j->hash, &copy, &buf);
+    napi_resolve_deferred(env, j->deferred, buf);
+  } else {
+    napi_value undef;
+    napi_get_undefined(env, &undef);
+    napi_resolve_deferred(env, j->deferred, undef);
+  }
+  napi_delete_async_work(env, j->work);
+  free(j);
+}
+static napi_value tjob_start(napi_env env, tjob_t* j, const char* resource) {
+  napi_value promise, resname;
+  NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
+  NAPI_OK(napi_create_string_utf8(env, resource, NAPI_AUTO_LENGTH, &resname));
+  NAPI_OK(napi_create_async_work(env, NULL, resname, tjob_execute, tjob_complete, j, &j->work));
+  NAPI_OK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+static napi_value js_ptau_new_file(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  tjob_t* j = (tjob_t*)calloc(1, sizeof(tjob_t));
+  size_t n = 0;
+  if (argc < 2 || napi_get_value_uint32(env, argv[0], &j->power) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], j->a, sizeof(j->a), &n) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, "ptauNewFile(power, outPath)");
+    return NULL;
+  }
+  j->mode = 0;
+  return tjob_start(env, j, "g16_ptau_new_file");
+}
+static napi_value js_ptau_contribute_files(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) { napi_throw_type_error(env, NULL, "ptauContributeFiles(inPath, outPath, name, secret, device)"); return NULL; }
+  tjob_t* j = (tjob_t*)calloc(1, sizeof(tjob_t));
+  size_t n = 0;
+  if (napi_get_value_string_utf8(env, argv[0], j->a, sizeof(j->a), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], j->b, sizeof(j->b), &n) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, "ptauContributeFiles: two path strings expected");
+    return NULL;
+  }
+  if (argc > 2 && napi_get_value_string_utf8(env, argv[2], j->name, sizeof(j->name), &n) == napi_ok) j->has_name = 1;
+  bool is_buf = false;
+  if (argc > 3 && napi_is_buffer(env, argv[3], &is_buf) == napi_ok && is_buf) {
+    void* p = NULL;
+    size_t len = 0;
+    if (napi_get_buffer_info(env, argv[3], &p, &len) != napi_ok || len != 192) {
+      free(j);
+      napi_throw_type_error(env, NULL, "ptauContributeFiles: the secret is a Buffer of 192 bytes (six scalars) or null");
+      return NULL;
+    }
+    memcpy(j->secret, p, 192);
+    j->has_secret = 1;
+  }
+  int32_t v = 0;
+  if (argc > 4 && napi_get_value_int32(env, argv[4], &v) == napi_ok) j->device = v;
+  j->mode = 1;
+  return tjob_start(env, j, "g16_ptau_contribute_files");
+}
+static napi_value js_ptau_verify_file(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  tjob_t* j = (tjob_t*)calloc(1, sizeof(tjob_t));
+  size_t n = 0;
+  if (argc < 1 || napi_get_value_string_utf8(env, argv[0], j->a, sizeof(j->a), &n) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, "ptauVerifyFile(path, device)");
+    return NULL;
+  }
+  int32_t v = 0;
+  if (argc > 1 && napi_get_value_int32(env, argv[1], &v) == napi_ok) j->device = v;
+  j->mode = 2;
+  return tjob_start(env, j, "g16_ptau_verify_file");
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"create", NULL, js_create, NULL, NULL, NULL, napi_default, NULL},
@@ -900,6 +1022,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"ptauPrepareFiles", NULL, js_ptau_prepare_files, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyContributeFiles", NULL, js_zkey_contribute_files, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerifyFromInitFiles", NULL, js_zkey_verify_from_init_files, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauNewFile", NULL, js_ptau_new_file, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauContributeFiles", NULL, js_ptau_contribute_files, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauVerifyFile", NULL, js_ptau_verify_file, NULL, NULL, NULL, napi_default, NULL},
   };
   NAPI_OK(napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props));
   return exports;

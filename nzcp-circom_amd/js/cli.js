@@ -4,6 +4,12 @@
 // /root/reference/Makefile:30-33).  Writes JSON.stringify(x, null, 1) like snarkjs.
 // And of `snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>` (alias `zkey new`; prepared ptau only).
 // And of `snarkjs powersoftau prepare phase2 <powersoftau.ptau> <new_powersoftau.ptau>` (alias `pt2`).
+// And of `snarkjs powersoftau new bn128 <power> <pot_0000.ptau>` (alias `ptn`), `snarkjs powersoftau contribute <old.ptau>
+// <new.ptau> [--name=..] [-e=..]` (alias `ptc`: prints the contribution hash as snarkjs does; -e: THIS CLI's derivation of
+// the six secret scalars, index.js ptauSecretFromEntropy, not snarkjs's) and `snarkjs powersoftau verify <pot.ptau>`
+// (alias `ptv`): prints "[INFO]  snarkJS: Powers of tau Ok!" and exits 0, or "[ERROR] snarkJS: <reason>" and exits 1.
+// The transcript hashes are this library's (INTEGRATION.md 5b): snarkjs's `powersoftau verify` is not claimed to accept
+// these files, nor this one snarkjs's.
 // And of `snarkjs zkey contribute <old.zkey> <new.zkey> [--name=..] [-e=..]` (alias `zkc`): prints the contribution hash
 // as snarkjs does.  -e: THIS CLI's derivation of the secret from the text (index.js secretFromEntropy), not snarkjs's.
 // And of `snarkjs zkey verify frominit <init.zkey> <pot.ptau> <circuit.zkey>` (alias `zkvi`) and `snarkjs zkey verify
@@ -69,6 +75,40 @@ async function main(argv) {
     if (pos.length < 3) { console.error("usage: cli.js groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>"); process.exit(2); }
     const { newZKey } = require("./index.js");
     await newZKey(pos[0], pos[1], pos[2]);
+    return;
+  }
+  if ((a[0] === "powersoftau" && a[1] === "new") || a[0] === "ptn") {
+    // snarkjs powersoftau new <curve> <power> [powersoftau_0000.ptau]   (alias: ptn)
+    const pos = a.slice(a[0] === "ptn" ? 1 : 2).filter((x) => !x.startsWith("-"));
+    if (pos.length < 3) { console.error("usage: cli.js powersoftau new bn128 <power> <powersoftau_0000.ptau>"); process.exit(2); }
+    if (!/^\d+$/.test(pos[1])) throw new Error(`powersoftau new: bad power ${pos[1]}`);
+    const { powersOfTau } = require("./index.js");
+    await powersOfTau.newAccumulator(pos[0], parseInt(pos[1], 10), pos[2]);
+    return;
+  }
+  if ((a[0] === "powersoftau" && a[1] === "contribute") || a[0] === "ptc") {
+    const rest = a.slice(a[0] === "ptc" ? 1 : 2);
+    const opt = (long, short) => {
+      for (const x of rest) {
+        if (x.startsWith(`--${long}=`)) return x.slice(long.length + 3);
+        if (x.startsWith(`-${short}=`)) return x.slice(short.length + 2);
+      }
+      return undefined;
+    };
+    const pos = rest.filter((x) => !x.startsWith("-"));
+    if (pos.length < 2) { console.error("usage: cli.js powersoftau contribute <powersoftau.ptau> <new_powersoftau.ptau> [--name=..] [-e=..]"); process.exit(2); }
+    const { powersOfTau, formatHash } = require("./index.js");
+    const hash = await powersOfTau.contribute(pos[0], pos[1], opt("name", "n"), opt("entropy", "e"));
+    console.log(`[INFO]  snarkJS: Contribution Hash: \n${formatHash(hash)}`);
+    return;
+  }
+  if ((a[0] === "powersoftau" && a[1] === "verify") || a[0] === "ptv") {
+    const pos = a.slice(a[0] === "ptv" ? 1 : 2).filter((x) => !x.startsWith("-"));
+    if (pos.length < 1) { console.error("usage: cli.js powersoftau verify <powersoftau.ptau>"); process.exit(2); }
+    const { powersOfTau } = require("./index.js");
+    const res = await powersOfTau.verify(pos[0], { reason: true });
+    if (!res.ok) throw new Error(res.reason);
+    console.log("[INFO]  snarkJS: Powers of tau Ok!");
     return;
   }
   if ((a[0] === "powersoftau" && a[1] === "prepare" && a[2] === "phase2") || a[0] === "pt2") {

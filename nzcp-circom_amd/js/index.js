@@ -287,7 +287,48 @@ const powersOfTau = {
     if (opts && typeof opts.debug === "function") opts = {};
     await native().ptauPrepareFiles(String(oldPtauName), String(newPtauName), opts.device | 0);
   },
+  // snarkjs: powersOfTau.newAccumulator(curve, power, fileName[, logger]) / CLI `powersoftau new bn128 <power> <file>`
+  // (alias `ptn`).  The curve is bn128: (power, fileName) here, or snarkjs's three arguments with "bn128" first.
+  async newAccumulator(...args) {
+    if (typeof args[0] === "string" && args.length >= 3) {
+      if (!["bn128", "bn254", "altbn128"].includes(args[0].toLowerCase())) throw new Error(`Curve not supported: ${args[0]}`);
+      args = args.slice(1);
+    }
+    const power = Number(args[0]);
+    if (!Number.isInteger(power) || power < 0) throw new Error("powersoftau new: the power is a non-negative integer");
+    await native().ptauNewFile(power, String(args[1]));
+  },
+  // snarkjs: powersOfTau.contribute(oldPtauFilename, newPTauFilename, name, entropy[, logger]) -> the 64-byte
+  // contribution hash / CLI `powersoftau contribute` (alias `ptc`).  entropy: a string (or Buffer) turned into the six
+  // secret scalars by ptauSecretFromEntropy -- THIS LIBRARY'S rule, not snarkjs's.  Absent: the OS CSPRNG.  The
+  // transcript (challenge and response hashes) is this library's too: see INTEGRATION.md 5b.
+  async contribute(oldPtauName, newPtauName, name, entropy, opts = {}) {
+    if (opts && typeof opts.debug === "function") opts = {};
+    const secret = entropy === undefined || entropy === null || entropy === "" ? null : ptauSecretFromEntropy(entropy);
+    return native().ptauContributeFiles(String(oldPtauName), String(newPtauName), name ? String(name) : null, secret, opts.device | 0);
+  },
+  // snarkjs: powersOfTau.verify(tauFilename[, logger]) -> boolean / CLI `powersoftau verify` (alias `ptv`).
+  // opts.reason = true returns {ok, reason} instead.
+  async verify(ptauName, opts = {}) {
+    if (opts && typeof opts.debug === "function") opts = {};
+    const res = await native().ptauVerifyFile(String(ptauName), opts.device | 0);
+    return opts.reason ? res : res.ok;
+  },
 };
+// tau | alpha | beta | s_tau | s_alpha | s_beta from a text: h_j = Blake2b-512(text | byte j), j = 0, 1, 2; the first
+// 32 bytes of h_j (little-endian, reduced mod r, 0 becomes 1) are key j, the last 32 bytes s_j (g16_ptau_secret_from_text)
+function ptauSecretFromEntropy(entropy) {
+  const out = Buffer.alloc(192);
+  for (let j = 0; j < 3; j++) {
+    const h = require("crypto").createHash("blake2b512").update(entropy).update(Buffer.from([j])).digest();
+    for (let half = 0; half < 2; half++) {
+      let v = leBig(h, 32 * half) % FR;
+      if (v === 0n) v = 1n;
+      for (let i = 0; i < 32; i++) { out[96 * half + 32 * j + i] = Number(v & 0xffn); v >>= 8n; }
+    }
+  }
+  return out;
+}
 
 // ------------------------------------------------------------------ zkey contribute / zkey verify
 // snarkjs: zKey.contribute(oldZkeyName, newZKeyName, name, entropy[, logger]) -> the 64-byte contribution hash.
