@@ -294,6 +294,23 @@ void g16_verifier_destroy(g16_verifier* v);
  * qy.c1, both on their curves, neither infinity) -> twelve standard-form words per pair: the pairing value the verifier
  * kernels compute, as the coefficients (c0, c1) of W^0..W^5 in the tower Fq12 = Fq2[W]/(W^6 - (9+u)). */
 int g16_pairing_op(int device, const uint8_t* in, uint32_t count, uint8_t* out);
+/* Layer tests of the point conversions of the challenge / response exchange (csrc/ptau_points.hip; the formats are
+ * described at g16_ptau_export_challenge).  group 1 = G1, 2 = G2; n points; host buffers.  *first_bad (optional) = the
+ * smallest index whose image is not a point, else -1 (the outputs are then not to be used); kernel_ms (optional) = the
+ * device time of the kernels.  G16_PTAU_CHUNK / G16_PTAU_LANES size the chunks and the grid as in ptau_scale.hip.
+ *   from_be:     uncompressed big-endian (64 / 128 bytes) -> the file form (affine little-endian Montgomery); bad: a
+ *                coordinate >= q, a point off its curve, bit 0x80, bit 0x40 with anything else set;
+ *   compress:    the file form -> x and the flags (32 / 64 bytes); first_bad is always -1;
+ *   decompress:  the inverse, and -- out_be, optional -- the uncompressed big-endian image of every point; bad: x >= q,
+ *                x^3 + b without a root, bit 0x40 with anything else set.
+ * g16_fq_sqrt_batch: square roots of n raw field elements in standard little-endian form (ext 0 = Fq, 32 bytes; 1 = Fq2,
+ * c0 | c1, 64 bytes; every word below q, else G16_E_ARG) by the decompression's routine: out[i] = a root of in[i] and
+ * has_root[i] = 1, or zeros and 0.  It reaches the Fq2 cases a curve point cannot (c1 = 0, a non-residue c0). */
+int g16_ptau_points_from_be(int group, const uint8_t* in, size_t n, int device, uint8_t* out, int64_t* first_bad, float* kernel_ms);
+int g16_ptau_points_compress(int group, const uint8_t* in, size_t n, int device, uint8_t* out, int64_t* first_bad, float* kernel_ms);
+int g16_ptau_points_decompress(int group, const uint8_t* in, size_t n, int device, uint8_t* out, uint8_t* out_be /* or NULL */,
+                               int64_t* first_bad, float* kernel_ms);
+int g16_fq_sqrt_batch(int ext, const uint8_t* in, size_t n, int device, uint8_t* out, uint8_t* has_root);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * PLONK prover on the device.  [EXT] snarkjs 0.4.12 plonk_prove.js `plonk.prove(zkey, wtns)` -- the
@@ -414,8 +431,8 @@ int g16_ptau_new_file(uint32_t power, const char* path);
  * DEPARTURES from snarkjs: it hashes a response file of COMPRESSED points and stores a hasher snapshot in partialHash;
  * here the new points enter through nextChallenge only and partialHash is 216 zero bytes that nothing reads.  The layout
  * and the powers are snarkjs's; its `powersoftau verify` is NOT claimed to accept this transcript.  NOT implemented:
- * `powersoftau beacon`, and the challenge / response file exchange (export challenge, challenge contribute, import
- * response).  The G2 derivation is NOT cross-checked against snarkjs.
+ * `powersoftau beacon`.  The challenge / response file exchange is g16_ptau_export_challenge and its neighbours below.
+ * The G2 derivation is NOT cross-checked against snarkjs.
  * Checked before the device is touched: the container, curve and power texts of g16_ptau_prepare ("ptau: Invalid File
  * format...", a power above 24: G16_E_ARG naming the limit); sections 2-6 present with exactly the sizes the power
  * implies and a section 7 that parses (not shorter than its records say, no trailing bytes, every record point a valid
@@ -451,6 +468,69 @@ int g16_ptau_contribute_files(const char* in_path, const char* out_path, const c
  * g16_g2_multiexp), the pairings ONE g16_pairing_op call on `device` (G16_E_NOGPU). */
 int g16_ptau_verify(const uint8_t* ptau, size_t ptau_len, int device, int* ok);
 int g16_ptau_verify_file(const char* path, int device, int* ok);
+/* The challenge / response file exchange of phase 1: how somebody who does not hold the .ptau contributes.  The
+ * coordinator exports a challenge, the contributor answers it with a response, the coordinator imports the response.
+ * File formats, snarkjs 0.4.12's (powersoftau_export_challenge.js, powersoftau_challenge_contribute.js,
+ * powersoftau_import.js) as far as they can be restated without ffjavascript, which is not available here; n = 2^power:
+ *   challenge file, 384 n + 128 bytes: prev (64) | the 2n - 1 points of section 2, the n of 3, of 4, of 5, the one of 6,
+ *     each uncompressed big-endian standard form (G1: x | y; G2: x.c1 | x.c0 | y.c1 | y.c0; infinity: zeros with bit 0x40
+ *     of byte 0).  prev = Blake2b-512("") for a file without records, else the last record's responseHash (not stored:
+ *     recomputed from the record's key points and the challenge it answered -- the nextChallenge of the record before,
+ *     or the generator file's challenge).  Blake2b-512(challenge file) = challengeHash(state, prev) of
+ *     g16_ptau_contribute: the challenge the next contribution answers.
+ *   response file, 192 n + 864 bytes: that challenge hash (64) | the same five runs of points COMPRESSED | the nine key
+ *     points uncompressed in record order (768: tau.g1_s, tau.g1_sx, alpha.g1_s, alpha.g1_sx, beta.g1_s, beta.g1_sx,
+ *     tau.g2_spx, alpha.g2_spx, beta.g2_spx).
+ *   compressed point: the big-endian x alone (G1: 32 bytes; G2: c1 | c0, 64); infinity: zeros with bit 0x40 of byte 0;
+ *     bit 0x80 of byte 0 set when y is "negative": in Fq y > (q - 1) / 2, in Fq2 that of c1, or of c0 when c1 = 0 (the
+ *     rule g16_zkey_hash_to_g2 uses).  q < 2^254 leaves both bits free.
+ * For the same old file, name and secret, import_response(old, challenge_contribute(export_challenge(old), secret),
+ * name) is g16_ptau_contribute(old, name, secret) byte for byte, with the same hash.
+ * DEPARTURES from snarkjs: the hash printed and returned by challenge contribute and import response is THIS library's
+ * responseHash = Blake2b-512(challenge | the nine key points), i.e. over the response's first 64 and last 768 bytes, not
+ * snarkjs's Blake2b-512 of the whole response file; partialHash stays zero; `powersoftau beacon` is not implemented.
+ *
+ * `snarkjs powersoftau export challenge pot.ptau challenge` (alias `ptec`): the challenge file (g16_free) and --
+ * optionally -- its Blake2b-512.  Host only (never G16_E_NOGPU); any power 0-24; the checks of g16_ptau_contribute on the
+ * input.  With records the hash must be the last record's nextChallenge, else G16_E_FORMAT "ptau export challenge: the
+ * file's points are not the last contribution's challenge". */
+int g16_ptau_export_challenge(const uint8_t* ptau, size_t ptau_len, uint8_t** out, size_t* out_len, uint8_t challenge_hash[64]);
+int g16_ptau_export_challenge_files(const char* ptau_path, const char* challenge_path, uint8_t challenge_hash[64]);
+/* `snarkjs powersoftau challenge contribute bn128 challenge response -e=..` (alias `ptcc`): the response file (g16_free)
+ * to a challenge file; secret as in g16_ptau_contribute.  The power comes from the size: (size - 128) / 384 must be a
+ * power of two up to 2^24, else G16_E_FORMAT "ptau challenge: Invalid File format"; a power-0 challenge (512 bytes) is
+ * G16_E_ARG, the text says so: its response would hold no point 1 for the import to take tauG1 from.  On `device` (no
+ * CPU path: G16_E_NOGPU; csrc/ptau_points.hip): every point from big-endian to the file form -- a coordinate >= q, a
+ * point off its curve, a set 0x80 bit or a 0x40 bit with anything else set is G16_E_FORMAT "ptau challenge contribute:
+ * point I of section S is not a point of the curve" for the first such point of the first such section --, scaled as
+ * g16_ptau_contribute scales the sections, compressed.  challenge = Blake2b-512(the input file); the keys are formed from
+ * it as in g16_ptau_contribute; contribution_hash (optional) = responseHash. */
+int g16_ptau_challenge_contribute(const uint8_t* challenge, size_t challenge_len, const uint8_t secret[192] /* or NULL */,
+                                  int device, uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]);
+int g16_ptau_challenge_contribute_files(const char* challenge_path, const char* response_path, const uint8_t secret[192],
+                                        int device, uint8_t contribution_hash[64]);
+/* `snarkjs powersoftau import response old.ptau response new.ptau --name=..` (alias `ptir`): old.ptau with the
+ * response's points and one record more (g16_free): sections 1..7, sections 12-15 of a prepared input dropped.
+ * Checked before the device is touched: everything g16_ptau_contribute checks on old.ptau; power >= 1 (power 0:
+ * G16_E_ARG); the response's size for that power (G16_E_FORMAT "ptau import response: Invalid File format"); its first
+ * 64 bytes = old.ptau's challenge (the last nextChallenge, or the first challenge computed on the host) -- otherwise the
+ * VERDICT "ptau import response: the response does not answer this file's challenge"; the nine key points valid images
+ * (G16_E_FORMAT "ptau import response: a key point is not a valid image").  On `device` (G16_E_NOGPU) every point is
+ * decompressed, y = sqrt(x^3 + b) with the sign the flag asks for: a 0x40 bit with any other bit set, x >= q or no root
+ * is G16_E_FORMAT "ptau import response: point I of section S is not a point of the curve"; the big-endian images for
+ * nextChallenge come from the same pass.  The record is built as g16_ptau_contribute builds it (tauG1 / tauG2 = point 1
+ * of the new sections 2 / 3, alphaG1 / betaG1 / betaG2 = point 0 of 4 / 5 / 6, the key points from the response,
+ * partialHash zero, nextChallenge = challengeHash(new state, responseHash), type 0, params from the name).  Before
+ * anything is written, check 2 of g16_ptau_verify is applied to the new record against the record before it (or the
+ * generators), its pairings in ONE g16_pairing_op call.  A failing check is a verdict as in g16_ptau_verify: G16_OK with
+ * *ok = 0, *out = NULL, nothing written, g16_last_error() = the text of that check led by "ptau import response: ".
+ * *ok = 1: the output is there and contribution_hash (optional) = responseHash.  The powers themselves (check 5) are
+ * left to g16_ptau_verify, as in snarkjs. */
+int g16_ptau_import_response(const uint8_t* ptau, size_t ptau_len, const uint8_t* response, size_t response_len,
+                             const char* name /* or NULL */, int device, uint8_t** out, size_t* out_len,
+                             uint8_t contribution_hash[64], int* ok);
+int g16_ptau_import_response_files(const char* ptau_path, const char* response_path, const char* out_path, const char* name,
+                                   int device, uint8_t contribution_hash[64], int* ok);
 /* The CLI's rule for `-e=<text>` (NOT snarkjs's): h_j = Blake2b-512(text | byte j), j = 0, 1, 2; the first 32 bytes of
  * h_j (little-endian, reduced mod r, zero mapped to 1) are key j (tau, alpha, beta), the last 32 bytes s_j. */
 int g16_ptau_secret_from_text(const char* text, uint8_t secret[192]);

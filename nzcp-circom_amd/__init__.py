@@ -73,7 +73,10 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_zkey_contribute", "g16_zkey_contribute_files", "g16_zkey_verify_from_init",
            "g16_zkey_verify_from_init_files", "g16_blake2b512", "g16_zkey_hash_to_g2",
            "g16_ptau_new", "g16_ptau_new_file", "g16_ptau_contribute", "g16_ptau_contribute_files", "g16_ptau_verify",
-           "g16_ptau_verify_file", "g16_ptau_secret_from_text"]
+           "g16_ptau_verify_file", "g16_ptau_secret_from_text",
+           "g16_ptau_export_challenge", "g16_ptau_export_challenge_files", "g16_ptau_challenge_contribute",
+           "g16_ptau_challenge_contribute_files", "g16_ptau_import_response", "g16_ptau_import_response_files",
+           "g16_ptau_points_from_be", "g16_ptau_points_compress", "g16_ptau_points_decompress", "g16_fq_sqrt_batch"]
 
 
 def load():
@@ -163,6 +166,19 @@ def load():
     lib.g16_ptau_verify.argtypes = [C.c_char_p, sz, C.c_int, C.POINTER(C.c_int)]
     lib.g16_ptau_verify_file.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     lib.g16_ptau_secret_from_text.argtypes = [C.c_char_p, C.c_char_p]
+    lib.g16_ptau_export_challenge.argtypes = [C.c_char_p, sz, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
+    lib.g16_ptau_export_challenge_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
+    lib.g16_ptau_challenge_contribute.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
+    lib.g16_ptau_challenge_contribute_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
+    lib.g16_ptau_import_response.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz),
+                                             C.c_char_p, C.POINTER(C.c_int)]
+    lib.g16_ptau_import_response_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                                   C.POINTER(C.c_int)]
+    i64p, f32p = C.POINTER(C.c_int64), C.POINTER(C.c_float)
+    lib.g16_ptau_points_from_be.argtypes = [C.c_int, C.c_char_p, sz, C.c_int, C.c_char_p, i64p, f32p]
+    lib.g16_ptau_points_compress.argtypes = [C.c_int, C.c_char_p, sz, C.c_int, C.c_char_p, i64p, f32p]
+    lib.g16_ptau_points_decompress.argtypes = [C.c_int, C.c_char_p, sz, C.c_int, C.c_char_p, C.c_char_p, i64p, f32p]
+    lib.g16_fq_sqrt_batch.argtypes = [C.c_int, C.c_char_p, sz, C.c_int, C.c_char_p, C.c_char_p]
     lib.g16_blake2b512.argtypes = [C.c_char_p, sz, C.c_char_p]
     lib.g16_zkey_hash_to_g2.argtypes = [C.c_char_p, C.c_char_p]
     lib.g16_r1cs_setup.argtypes = [C.c_char_p, sz, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
@@ -758,11 +774,7 @@ def ptau_new(power):
 def ptau_contribute(ptau, name=None, secret=None, device=0):
     """`snarkjs powersoftau contribute`: .ptau bytes -> (contributed .ptau bytes, 64-byte contribution hash).  secret:
     (tau, alpha, beta, s_tau, s_alpha, s_beta), ints in [1, r), or None for the OS CSPRNG."""
-    blob = None
-    if secret is not None:
-        if len(secret) != 6:
-            raise ValueError("ptau_contribute: six secret scalars expected")
-        blob = b"".join(int(x).to_bytes(32, "little") for x in secret)
+    blob = _ptau_secret_blob("ptau_contribute", secret)
     z, zl = C.c_void_p(), C.c_size_t()
     h = C.create_string_buffer(64)
     nm = None if name is None else name.encode("utf-8")
@@ -777,6 +789,95 @@ def ptau_verify(ptau, device=0):
     lib = load()
     _check(lib.g16_ptau_verify(ptau, len(ptau), device, C.byref(ok)))
     return bool(ok.value), ("" if ok.value else lib.g16_last_error().decode("utf-8", "replace"))
+
+
+def _ptau_secret_blob(route, secret):
+    if secret is None:
+        return None
+    if len(secret) != 6:
+        raise ValueError(route + ": six secret scalars expected")
+    return b"".join(int(x).to_bytes(32, "little") for x in secret)
+
+
+def ptau_export_challenge(ptau, with_hash=False):
+    """`snarkjs powersoftau export challenge`: .ptau bytes -> the challenge file's bytes (host only); with_hash: ->
+    (challenge file, its Blake2b-512: the challenge the next contribution answers)."""
+    z, zl = C.c_void_p(), C.c_size_t()
+    h = C.create_string_buffer(64)
+    _check(load().g16_ptau_export_challenge(ptau, len(ptau), C.byref(z), C.byref(zl), h))
+    out = _take(z, zl)
+    return (out, h.raw) if with_hash else out
+
+
+def ptau_challenge_contribute(challenge, secret=None, device=0):
+    """`snarkjs powersoftau challenge contribute`: challenge file bytes -> (response file bytes, 64-byte contribution
+    hash).  secret as in ptau_contribute."""
+    blob = _ptau_secret_blob("ptau_challenge_contribute", secret)
+    z, zl = C.c_void_p(), C.c_size_t()
+    h = C.create_string_buffer(64)
+    _check(load().g16_ptau_challenge_contribute(challenge, len(challenge), blob, device, C.byref(z), C.byref(zl), h))
+    return _take(z, zl), h.raw
+
+
+def ptau_import_response(ptau, response, name=None, device=0):
+    """`snarkjs powersoftau import response`: (.ptau bytes, response file bytes) -> (the new .ptau bytes, 64-byte
+    contribution hash).  A response that fails a check of its record is a verdict, not a malformed file: G16Error with
+    code 0 (G16_OK) and the check's text; nothing is returned."""
+    z, zl = C.c_void_p(), C.c_size_t()
+    h = C.create_string_buffer(64)
+    ok = C.c_int(0)
+    nm = None if name is None else name.encode("utf-8")
+    lib = load()
+    _check(lib.g16_ptau_import_response(ptau, len(ptau), response, len(response), nm, device, C.byref(z), C.byref(zl), h, C.byref(ok)))
+    if not ok.value:
+        raise G16Error(0, lib.g16_last_error().decode("utf-8", "replace"))
+    return _take(z, zl), h.raw
+
+
+def _ptau_points(fn, group, data, in_size, out_size, device, want_be=False):
+    """-> (output bytes, first bad index or -1, kernel ms[, big-endian images])."""
+    if group not in (1, 2) or len(data) % (in_size * group):
+        raise ValueError("ptau points: whole points of group 1 or 2 expected")
+    n = len(data) // (in_size * group)
+    out = C.create_string_buffer(max(1, n * out_size * group))
+    bad, ms = C.c_int64(-1), C.c_float(0)
+    if want_be is None:
+        _check(fn(group, data, n, device, out, C.byref(bad), C.byref(ms)))
+        return out.raw[:n * out_size * group], bad.value, ms.value
+    be = C.create_string_buffer(max(1, n * 64 * group)) if want_be else None
+    _check(fn(group, data, n, device, out, be, C.byref(bad), C.byref(ms)))
+    return out.raw[:n * out_size * group], bad.value, ms.value, (be.raw[:n * 64 * group] if want_be else None)
+
+
+def ptau_points_from_be(group, data, device=0):
+    """TEST-ONLY layer entry: uncompressed big-endian points -> (file-form bytes, first bad index or -1, kernel ms)."""
+    return _ptau_points(load().g16_ptau_points_from_be, group, data, 64, 64, device, None)
+
+
+def ptau_points_compress(group, data, device=0):
+    """TEST-ONLY layer entry: file-form points -> (compressed bytes, -1, kernel ms)."""
+    return _ptau_points(load().g16_ptau_points_compress, group, data, 64, 32, device, None)
+
+
+def ptau_points_decompress(group, data, device=0, want_be=True):
+    """TEST-ONLY layer entry: compressed points -> (file-form bytes, first bad index or -1, kernel ms, big-endian images)."""
+    return _ptau_points(load().g16_ptau_points_decompress, group, data, 32, 64, device, want_be)
+
+
+def fq_sqrt_batch(ext, values, device=0):
+    """TEST-ONLY layer entry: ints below q (ext 0) or pairs (c0, c1) (ext 1) -> [root or None] by the device routine."""
+    if ext:
+        data = b"".join(int(a).to_bytes(32, "little") + int(b).to_bytes(32, "little") for a, b in values)
+    else:
+        data = b"".join(int(a).to_bytes(32, "little") for a in values)
+    n, esz = len(values), 64 if ext else 32
+    out, has = C.create_string_buffer(max(1, n * esz)), C.create_string_buffer(max(1, n))
+    _check(load().g16_fq_sqrt_batch(1 if ext else 0, data, n, device, out, has))
+    res = []
+    for i in range(n):
+        w = [int.from_bytes(out.raw[i * esz + 32 * k:i * esz + 32 * k + 32], "little") for k in range(esz // 32)]
+        res.append(None if has.raw[i] == 0 else (tuple(w) if ext else w[0]))
+    return res
 
 
 def ptau_secret_from_text(text):

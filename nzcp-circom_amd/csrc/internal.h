@@ -135,6 +135,18 @@ int ptau_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& c_std, co
 int ptau_scale_g2(int device, const uint8_t* in, uint64_t n, const Fr& c_std, const Fr& k_std, uint64_t first, uint8_t* out,
                   uint8_t* out_be, PtauScaleStats* st);
 
+// ---------------------------------------------------------------- challenge / response points (ptau_points.hip)
+// n points of G1 (g2 = false) or G2 between the file form (affine little-endian Montgomery, 64 / 128 bytes, infinity =
+// zero bytes), the uncompressed big-endian standard form of the challenge file (as large) and the compressed form of
+// the response file (x alone with the sign and infinity flags, half as large); host buffers in and out, chunked like
+// ptau_scale.  *first_bad (optional) = the smallest index whose image is not a point (a coordinate >= q, a wrong flag,
+// off the curve, no root), else -1; the outputs of a section with a bad point are not to be used.  out_be (optional):
+// the uncompressed image of every decompressed point, from the same pass.  No CPU path (G16_E_NOGPU).
+int ptau_points_from_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, PtauScaleStats* st);
+int ptau_points_compress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, PtauScaleStats* st);
+int ptau_points_decompress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* out_be, int64_t* first_bad,
+                           PtauScaleStats* st);
+
 // ---------------------------------------------------------------- NTT (ntt.hip)
 struct NttPass { int lo_bits, S, tb; };
 struct NttTables {

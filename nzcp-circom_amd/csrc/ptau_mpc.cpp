@@ -16,8 +16,19 @@
 // hash_to_g2(Blake2b-512(challenge | byte x | g1_s | g1_sx)), g2_spx = [x]g2_sp; responseHash = Blake2b-512(challenge |
 // the nine key points in record order); nextChallenge = challengeHash(new state, responseHash); partialHash is 216 zero
 // bytes that nothing reads.  snarkjs's `powersoftau verify` is NOT claimed to accept this transcript.  NOT here:
-// `powersoftau beacon` and the challenge / response file exchange (export challenge, challenge contribute, import
-// response).
+// `powersoftau beacon`.
+// The challenge / response file exchange ([EXT] powersoftau_export_challenge.js, powersoftau_challenge_contribute.js,
+// powersoftau_import.js, restated without ffjavascript, which is not available here): the transcript above already IS
+// that of the files --
+//   challenge file = prev | every point of sections 2-6 uncompressed            (its Blake2b-512 = challengeHash)
+//   response file  = challenge hash | the same points compressed | the nine key points uncompressed
+//   export challenge:     host only; prev = Blake2b-512("") or the last record's responseHash, recomputed.
+//   challenge contribute: from-be, ptau_scale, compress on the device (ptau_points.hip), the keys as in contribute.
+//   import response:      decompress on the device (a square root per point), the record as contribute builds it, the
+//                         record checks of verify before anything is written.
+// import(old, contribute(export(old), secret), name) = contribute(old, name, secret) byte for byte.  DEPARTURE: the
+// hash printed and returned is responseHash (the response's first 64 and last 768 bytes), not snarkjs's Blake2b-512 of
+// the whole response file.
 #include "ptau_mpc.h"
 
 #include <algorithm>
@@ -149,14 +160,18 @@ void key_g2_sp(const uint8_t challenge[64], int key, const uint8_t* g1_s, const 
 }
 
 // Blake2b-512(challenge | the nine key points of a record, uncompressed, in record order)
-void response_hash(const uint8_t challenge[64], const PtauRecord& r, uint8_t out[64]) {
-  uint8_t feed[64 + 6 * 64 + 3 * 128];
-  memcpy(feed, challenge, 64);
+constexpr size_t kKeysBytes = 6 * 64 + 3 * 128;
+void keys_uncompressed(const PtauRecord& r, uint8_t out[kKeysBytes]) {   // (how a response file ends)
   for (int x = 0; x < 3; x++) {
-    g1_uncompressed(r.g1_s(x), feed + 64 + 128 * x);
-    g1_uncompressed(r.g1_sx(x), feed + 64 + 128 * x + 64);
-    g2_uncompressed(r.g2_spx(x), feed + 64 + 384 + 128 * x);
+    g1_uncompressed(r.g1_s(x), out + 128 * x);
+    g1_uncompressed(r.g1_sx(x), out + 128 * x + 64);
+    g2_uncompressed(r.g2_spx(x), out + 384 + 128 * x);
   }
+}
+void response_hash(const uint8_t challenge[64], const PtauRecord& r, uint8_t out[64]) {
+  uint8_t feed[64 + kKeysBytes];
+  memcpy(feed, challenge, 64);
+  keys_uncompressed(r, feed + 64);
   blake2b512(feed, sizeof(feed), out);
 }
 
@@ -179,6 +194,89 @@ void generator_challenge(const Ceremony& c, uint8_t out[64]) {
 bool scalar_ok(const uint8_t* s, Fr& out) {   // standard form, in [1, r)
   memcpy(out.v, s, 32);
   return !fp_is_zero(out) && fr_below_modulus(out.v);
+}
+
+// secret (tau | alpha | beta | s_tau | s_alpha | s_beta, or NULL for the OS CSPRNG) -> key[3], sk[3]
+int read_secret(const char* route, const uint8_t* secret, Fr key[3], Fr sk[3]) {
+  if (secret) {
+    for (int x = 0; x < 3; x++)
+      if (!scalar_ok(secret + 32 * x, key[x]) || !scalar_ok(secret + 96 + 32 * x, sk[x])) {
+        set_error(std::string(route) + ": the secret scalars must be in [1, r)");
+        return G16_E_ARG;
+      }
+    return G16_OK;
+  }
+  for (Fr* x : {&key[0], &key[1], &key[2], &sk[0], &sk[1], &sk[2]})
+    for (;;) {
+      if (const int rc = mpc_os_random((uint8_t*)x->v, 32)) return rc;
+      x->v[7] &= 0x3fffffffu;
+      if (!fp_is_zero(*x) && fr_below_modulus(x->v)) break;
+    }
+  return G16_OK;
+}
+
+// the nine key points of a record (rec = its first byte) for the challenge it answers
+void make_keys(const uint8_t challenge[64], const Fr key[3], const Fr sk[3], uint8_t* rec) {
+  for (int x = 0; x < 3; x++) {
+    uint8_t* g1_s = rec + kPtauKeysAt + 128 * x;
+    mpc_mul_g1(gens().g1, sk[x], g1_s);
+    mpc_mul_g1(g1_s, key[x], g1_s + 64);
+    G2Affine sp2;
+    key_g2_sp(challenge, x, g1_s, g1_s + 64, sp2);
+    mpc_mul_g2((const uint8_t*)&sp2, key[x], rec + 832 + 128 * x);
+  }
+}
+
+// Step 2 of the verifier for ONE record against the state before it (cur: tauG1, alphaG1, betaG1, advanced to the
+// record's): the infinity test, then eight same-ratio checks appended to pairs (check k compares pairing 2k with pairing
+// 2k + 1 of ONE g16_pairing_op call) with their texts in reason.  -> the infinity text, or nullptr.  g2_sp must outlive
+// the pairing call.  Shared by `verify` and `import response`, which differ in the texts' prefix alone.
+struct RecordTexts { const char* inf; const char* key; const char* chain[3]; const char* tau_g2; const char* beta_g2; };
+#define G16_RECORD_TEXTS(route)                                                                                      \
+  {route ": a contribution holds the point at infinity", route ": a contribution's public key is not consistent",    \
+   {route ": a contribution's tauG1 does not continue the chain", route ": a contribution's alphaG1 does not continue the chain", \
+    route ": a contribution's betaG1 does not continue the chain"},                                                  \
+   route ": a contribution's tauG2 does not match its tauG1", route ": a contribution's betaG2 does not match its betaG1"}
+const char* record_checks(const RecordTexts& t, const PtauRecord& r, const uint8_t* cur[3], const uint8_t challenge[64],
+                          G2Affine g2_sp[3], std::vector<uint8_t>& pairs, std::vector<const char*>& reason) {
+  bool inf = all_zero(r.tau_g1(), 64) || all_zero(r.tau_g2(), 128) || all_zero(r.alpha_g1(), 64) || all_zero(r.beta_g1(), 64) ||
+             all_zero(r.beta_g2(), 128);
+  for (int x = 0; x < 3; x++) inf = inf || all_zero(r.g1_s(x), 64) || all_zero(r.g1_sx(x), 64) || all_zero(r.g2_spx(x), 128);
+  if (inf) return t.inf;
+  auto same_ratio = [&](const uint8_t* g1a, const uint8_t* g1b, const uint8_t* g2c, const uint8_t* g2d, const char* why) {
+    mpc_pair_words(pairs, g1a, g2d);   // e(a, d) = e(b, c)
+    mpc_pair_words(pairs, g1b, g2c);
+    reason.push_back(why);
+  };
+  const Gens& G = gens();
+  const uint8_t* now[3] = {r.tau_g1(), r.alpha_g1(), r.beta_g1()};
+  for (int x = 0; x < 3; x++) {
+    key_g2_sp(challenge, x, r.g1_s(x), r.g1_sx(x), g2_sp[x]);
+    same_ratio(r.g1_s(x), r.g1_sx(x), (const uint8_t*)&g2_sp[x], r.g2_spx(x), t.key);
+    same_ratio(cur[x], now[x], (const uint8_t*)&g2_sp[x], r.g2_spx(x), t.chain[x]);
+    cur[x] = now[x];
+  }
+  same_ratio(G.g1, r.tau_g1(), G.g2, r.tau_g2(), t.tau_g2);
+  same_ratio(G.g1, r.beta_g1(), G.g2, r.beta_g2(), t.beta_g2);
+  return nullptr;
+}
+
+// The output image of a contribution: sections 1-7 framed, section 1 and the old records copied, the count raised;
+// -> where the new record (rec_len bytes) goes, or nullptr when the reservation failed
+uint8_t* layout_with_record(const Ceremony& c, size_t rec_len, Buf& z, uint8_t* sp[16]) {
+  static const uint8_t no_contributions[4] = {0, 0, 0, 0};
+  const uint8_t* old7 = c.pv.sec[7].p ? c.pv.sec[7].p : no_contributions;
+  const uint64_t old7_size = c.pv.sec[7].p ? c.pv.sec[7].size : 4;
+  uint64_t sizes[16] = {};
+  for (int id = 1; id <= 6; id++) sizes[id] = c.pv.sec[id].size;
+  sizes[7] = old7_size + rec_len;
+  static const int ids[7] = {1, 2, 3, 4, 5, 6, 7};
+  if (!bin_layout(z, "ptau", 1, ids, 7, sizes, sp)) return nullptr;
+  memcpy(sp[1], c.pv.sec[1].p, sizes[1]);
+  memcpy(sp[7], old7, old7_size);
+  const uint32_t count = (uint32_t)c.rec.size() + 1;
+  memcpy(sp[7], &count, 4);
+  return sp[7] + old7_size;
 }
 
 int new_core(uint32_t power, uint8_t** out, size_t* out_len) {
@@ -205,43 +303,18 @@ int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uin
   const auto t0 = std::chrono::steady_clock::now();
   Ceremony c;
   if (const int rc = open_ceremony(ptau, len, "ptau contribute", c)) return rc;
-  Fr key[3], sk[3];   // tau, alpha, beta; s_tau, s_alpha, s_beta
-  if (secret) {
-    for (int x = 0; x < 3; x++)
-      if (!scalar_ok(secret + 32 * x, key[x]) || !scalar_ok(secret + 96 + 32 * x, sk[x])) {
-        set_error("ptau contribute: the secret scalars must be in [1, r)");
-        return G16_E_ARG;
-      }
-  } else {
-    for (Fr* x : {&key[0], &key[1], &key[2], &sk[0], &sk[1], &sk[2]})
-      for (;;) {
-        if (const int rc = mpc_os_random((uint8_t*)x->v, 32)) return rc;
-        x->v[7] &= 0x3fffffffu;
-        if (!fp_is_zero(*x) && fr_below_modulus(x->v)) break;
-      }
-  }
+  Fr key[3], sk[3];
+  if (const int rc = read_secret("ptau contribute", secret, key, sk)) return rc;
   if (const int rc = require_hip_device("ptau contribute", device)) return rc;
 
   const std::string params = mpc_name_params(name);
   const uint32_t plen = (uint32_t)params.size();
   const size_t rec_len = kPtauRecordFixed + plen;
-  static const uint8_t no_contributions[4] = {0, 0, 0, 0};
-  const uint8_t* old7 = c.pv.sec[7].p ? c.pv.sec[7].p : no_contributions;
-  const uint64_t old7_size = c.pv.sec[7].p ? c.pv.sec[7].size : 4;
-
-  uint64_t sizes[16] = {};
-  for (int id = 1; id <= 6; id++) sizes[id] = c.pv.sec[id].size;
-  sizes[7] = old7_size + rec_len;
-  static const int ids[7] = {1, 2, 3, 4, 5, 6, 7};
   Buf z;
   uint8_t* sp[16] = {};
-  if (!bin_layout(z, "ptau", 1, ids, 7, sizes, sp)) { set_error("ptau contribute: out of memory"); return G16_E_STATE; }
+  uint8_t* rec = layout_with_record(c, rec_len, z, sp);
+  if (!rec) { set_error("ptau contribute: out of memory"); return G16_E_STATE; }
   struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
-  memcpy(sp[1], c.pv.sec[1].p, sizes[1]);
-  memcpy(sp[7], old7, old7_size);
-  const uint32_t count = (uint32_t)c.rec.size() + 1;
-  memcpy(sp[7], &count, 4);
-  uint8_t* rec = sp[7] + old7_size;
   memset(rec, 0, rec_len);   // (partialHash stays zero)
   const PtauRecord R{rec, rec_len};
 
@@ -258,15 +331,7 @@ int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uin
   } else {
     memcpy(challenge, c.rec.back().next_challenge(), 64);
   }
-  // the three keys
-  for (int x = 0; x < 3; x++) {
-    uint8_t* g1_s = rec + kPtauKeysAt + 128 * x;
-    mpc_mul_g1(gens().g1, sk[x], g1_s);
-    mpc_mul_g1(g1_s, key[x], g1_s + 64);
-    G2Affine sp2;
-    key_g2_sp(challenge, x, g1_s, g1_s + 64, sp2);
-    mpc_mul_g2((const uint8_t*)&sp2, key[x], rec + 832 + 128 * x);
-  }
+  make_keys(challenge, key, sk, rec);
   double hash_ms = ms_since(th0);
 
   // device: the sections, and the big-endian images of the new points straight into the next challenge's feed
@@ -329,6 +394,249 @@ int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uin
   return G16_OK;
 }
 
+// ------------------------------------------------------------------ the challenge / response exchange
+// `prev` of the challenge file: Blake2b-512("") without records, else the last record's responseHash -- not stored,
+// recomputed from its key points and the challenge IT answered
+void last_response_hash(const Ceremony& c, uint8_t out[64]) {
+  if (c.rec.empty()) { blake2b512(nullptr, 0, out); return; }
+  uint8_t answered[64];
+  if (c.rec.size() >= 2) memcpy(answered, c.rec[c.rec.size() - 2].next_challenge(), 64);
+  else generator_challenge(c, answered);
+  response_hash(answered, c.rec.back(), out);
+}
+
+int power_zero(const char* route) {
+  set_error(std::string(route) + ": power 0 is not supported (a power-0 response holds no point 1 to take tauG1 from)");
+  return G16_E_ARG;
+}
+
+int export_challenge_core(const uint8_t* ptau, size_t len, uint8_t** out, size_t* out_len, uint8_t challenge_hash[64]) {
+  Ceremony c;
+  if (const int rc = open_ceremony(ptau, len, "ptau export challenge", c)) return rc;
+  Buf z;
+  if (!z.reserve(64 + c.points_bytes())) { set_error("ptau export challenge: out of memory"); return G16_E_STATE; }
+  struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
+  last_response_hash(c, z.skip(64));
+  const uint8_t* in[7] = {};
+  for (int id = 2; id <= 6; id++) in[id] = c.pv.sec[id].p;
+  points_be_host(in, c.cnt, z.skip(c.points_bytes()));
+  uint8_t h[64];
+  blake2b512(z.p, z.len, h);
+  if (!c.rec.empty() && memcmp(h, c.rec.back().next_challenge(), 64) != 0) {
+    set_error("ptau export challenge: the file's points are not the last contribution's challenge");
+    return G16_E_FORMAT;
+  }
+  if (challenge_hash) memcpy(challenge_hash, h, 64);
+  guard.p = nullptr;
+  z.give(out, out_len);
+  return G16_OK;
+}
+
+int bad_point(const char* route, int64_t i, int id) {
+  set_error(std::string(route) + ": point " + std::to_string(i) + " of section " + std::to_string(id) + " is not a point of the curve");
+  return G16_E_FORMAT;
+}
+
+void trace_points(const char* route, const char* const stage[3], const PtauScaleStats st[5][3], double call_ms) {
+  if (!getenv("G16_TRACE_HOST")) return;
+  std::string kernels;
+  float xf = 0;
+  for (int j = 0; j < 3; j++) {
+    if (!stage[j]) continue;
+    float ms = 0;
+    for (int s = 0; s < 5; s++) { ms += st[s][j].kern_ms; xf += st[s][j].xfer_ms; }
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%s %.3f ms, ", stage[j], ms);
+    kernels += buf;
+  }
+  fprintf(stderr, "[g16] %s: kernels %stransfers %.3f ms; call %.3f ms\n", route, kernels.c_str(), xf, call_ms);
+}
+
+int challenge_contribute_core(const uint8_t* ch, size_t len, const uint8_t* secret, int device, uint8_t** out, size_t* out_len,
+                              uint8_t contribution_hash[64]) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint64_t n = len >= 128 + 384 && (len - 128) % 384 == 0 ? (len - 128) / 384 : 0;
+  if (n == 0 || (n & (n - 1)) || n > ((uint64_t)1 << kPowerMax)) {
+    set_error("ptau challenge: Invalid File format");
+    return G16_E_FORMAT;
+  }
+  if (n == 1) return power_zero("ptau challenge contribute");
+  Fr key[3], sk[3];
+  if (const int rc = read_secret("ptau challenge contribute", secret, key, sk)) return rc;
+  if (const int rc = require_hip_device("ptau challenge contribute", device)) return rc;
+
+  const uint64_t cnt[7] = {0, 0, 2 * n - 1, n, n, n, 1};
+  Buf z;
+  if (!z.reserve(192 * n + 864)) { set_error("ptau challenge contribute: out of memory"); return G16_E_STATE; }
+  struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
+  uint8_t challenge[64];
+  blake2b512(ch, len, challenge);
+  z.put(challenge, 64);
+  uint8_t rec[kPtauRecordFixed] = {};
+  make_keys(challenge, key, sk, rec);
+
+  // per section: big-endian -> file form (checked), scaled, compressed; three passes of the device over host buffers
+  Fr one = fp_zero<FrParams>();
+  one.v[0] = 1;
+  const Fr* cs[7] = {nullptr, nullptr, &one, &one, &key[1], &key[2], &key[2]};
+  std::vector<uint8_t> a(std::max<uint64_t>(cnt[2] * 64, n * 128)), b(a.size());
+  PtauScaleStats st[5][3];
+  const uint8_t* src = ch + 64;
+  for (int id = 2; id <= 6; id++) {
+    const size_t psz = Ceremony::psz(id);
+    const bool g2 = psz == 128;
+    int64_t bad = -1;
+    if (const int rc = ptau_points_from_be(device, g2, src, cnt[id], a.data(), &bad, &st[id - 2][0])) return rc;
+    if (bad >= 0) return bad_point("ptau challenge contribute", bad, id);
+    const Fr& k = id == 6 ? one : key[0];
+    if (const int rc = g2 ? ptau_scale_g2(device, a.data(), cnt[id], *cs[id], k, 0, b.data(), nullptr, &st[id - 2][1])
+                          : ptau_scale_g1(device, a.data(), cnt[id], *cs[id], k, 0, b.data(), nullptr, &st[id - 2][1]))
+      return rc;
+    if (const int rc = ptau_points_compress(device, g2, b.data(), cnt[id], z.skip(cnt[id] * psz / 2), &st[id - 2][2])) return rc;
+    src += cnt[id] * psz;
+  }
+  const PtauRecord R{rec, sizeof(rec)};
+  keys_uncompressed(R, z.skip(kKeysBytes));
+  if (contribution_hash) response_hash(challenge, R, contribution_hash);
+  static const char* const stages[3] = {"from-be", "scale", "compress"};
+  trace_points("ptau challenge contribute", stages, st, ms_since(t0));
+  guard.p = nullptr;
+  z.give(out, out_len);
+  return G16_OK;
+}
+
+// uncompressed big-endian standard form -> the file image; false for a flag other than a clean 0x40, a coordinate >= q
+// or a point off its curve
+bool image_from_be(const uint8_t* be, size_t psz, uint8_t* lem) {
+  if (be[0] & 0xc0) {
+    if (be[0] != 0x40 || !all_zero(be + 1, psz - 1)) return false;
+    memset(lem, 0, psz);
+    return true;
+  }
+  const int nc = (int)(psz / 32);
+  for (int c = 0; c < nc; c++) {
+    Fq s;
+    for (int i = 0; i < 8; i++) {
+      const uint8_t* w = be + 32 * c + 4 * (7 - i);
+      s.v[i] = (uint32_t)w[0] << 24 | (uint32_t)w[1] << 16 | (uint32_t)w[2] << 8 | w[3];
+    }
+    bool below = false;
+    for (int i = 7; i >= 0; i--)
+      if (s.v[i] != kFqP[i]) { below = s.v[i] < kFqP[i]; break; }
+    if (!below) return false;
+    s = fp_to_mont(s);
+    memcpy(lem + 32 * (nc == 2 ? c : c ^ 1), s.v, 32);
+  }
+  if (all_zero(lem, psz)) return false;   // (infinity is the flagged image alone)
+  return nc == 2 ? mpc_g1_image_ok(lem) : mpc_g2_image_ok(lem);
+}
+
+int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, size_t rlen, const char* name, int device,
+                         uint8_t** out, size_t* out_len, uint8_t contribution_hash[64], int* ok) {
+  const auto t0 = std::chrono::steady_clock::now();
+  *ok = 0;
+  *out = nullptr;
+  *out_len = 0;
+  Ceremony c;
+  if (const int rc = open_ceremony(ptau, len, "ptau import response", c)) return rc;
+  if (c.pv.power == 0) return power_zero("ptau import response");
+  if (rlen != 192 * c.n + 864) { set_error("ptau import response: Invalid File format"); return G16_E_FORMAT; }
+  auto verdict = [&](const char* why) { set_error(why); return G16_OK; };
+  const Gens& G = gens();
+
+  // the challenge the response must answer: the file's own
+  std::vector<uint8_t> feed(64 + c.points_bytes());
+  uint8_t challenge[64];
+  const uint8_t* in[7] = {};
+  for (int id = 2; id <= 6; id++) in[id] = c.pv.sec[id].p;
+  if (c.rec.empty()) {
+    blake2b512(nullptr, 0, feed.data());
+    points_be_host(in, c.cnt, feed.data() + 64);
+    blake2b512(feed.data(), feed.size(), challenge);
+  } else {
+    memcpy(challenge, c.rec.back().next_challenge(), 64);
+  }
+  if (memcmp(resp, challenge, 64) != 0) return verdict("ptau import response: the response does not answer this file's challenge");
+
+  const std::string params = mpc_name_params(name);
+  const uint32_t plen = (uint32_t)params.size();
+  const size_t rec_len = kPtauRecordFixed + plen;
+  std::vector<uint8_t> recbuf(rec_len, 0);   // (partialHash stays zero)
+  uint8_t* rec = recbuf.data();
+  const PtauRecord R{rec, rec_len};
+  {
+    const uint8_t* kp = resp + rlen - kKeysBytes;
+    bool good = true;
+    for (int x = 0; x < 3 && good; x++)
+      good = image_from_be(kp + 128 * x, 64, rec + kPtauKeysAt + 128 * x) && image_from_be(kp + 128 * x + 64, 64, rec + kPtauKeysAt + 128 * x + 64) &&
+             image_from_be(kp + 384 + 128 * x, 128, rec + 832 + 128 * x);
+    if (!good) { set_error("ptau import response: a key point is not a valid image"); return G16_E_FORMAT; }
+  }
+  if (const int rc = require_hip_device("ptau import response", device)) return rc;
+
+  Buf z;
+  uint8_t* sp[16] = {};
+  uint8_t* rec_out = layout_with_record(c, rec_len, z, sp);
+  if (!rec_out) { set_error("ptau import response: out of memory"); return G16_E_STATE; }
+  struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
+
+  // device: the sections, and the big-endian images of the new points straight into the next challenge's feed
+  PtauScaleStats st[5][3];
+  {
+    const uint8_t* src = resp + 64;
+    uint8_t* be = feed.data() + 64;
+    for (int id = 2; id <= 6; id++) {
+      const size_t psz = Ceremony::psz(id);
+      int64_t bad = -1;
+      if (const int rc = ptau_points_decompress(device, psz == 128, src, c.cnt[id], sp[id], be, &bad, &st[id - 2][2])) return rc;
+      if (bad >= 0) return bad_point("ptau import response", bad, id);
+      src += c.cnt[id] * psz / 2;
+      be += c.cnt[id] * psz;
+    }
+  }
+
+  // the record, as contribute builds it
+  memcpy(rec, sp[2] + 64, 64);
+  memcpy(rec + 64, sp[3] + 128, 128);
+  memcpy(rec + 192, sp[4], 64);
+  memcpy(rec + 256, sp[5], 64);
+  memcpy(rec + 320, sp[6], 128);
+  uint8_t response[64];
+  response_hash(challenge, R, response);
+  memcpy(feed.data(), response, 64);
+  blake2b512(feed.data(), feed.size(), rec + kPtauNextChallengeAt);
+  const uint32_t type = 0;
+  memcpy(rec + kPtauNextChallengeAt + 64, &type, 4);
+  memcpy(rec + kPtauNextChallengeAt + 68, &plen, 4);
+  if (plen) memcpy(rec + kPtauRecordFixed, params.data(), plen);
+
+  // step 2 of verify for this one record, against the record before it or the generators: ONE pairing call
+  {
+    static const RecordTexts texts = G16_RECORD_TEXTS("ptau import response");
+    const bool first = c.rec.empty();
+    const uint8_t* cur[3] = {first ? G.g1 : c.rec.back().tau_g1(), first ? G.g1 : c.rec.back().alpha_g1(),
+                             first ? G.g1 : c.rec.back().beta_g1()};
+    std::vector<uint8_t> pairs;
+    std::vector<const char*> reason;
+    G2Affine g2_sp[3];
+    if (const char* inf = record_checks(texts, R, cur, challenge, g2_sp, pairs, reason)) return verdict(inf);
+    const uint32_t np = (uint32_t)(pairs.size() / 192);
+    std::vector<uint8_t> gt((size_t)np * 384);
+    if (const int rc = g16_pairing_op(device, pairs.data(), np, gt.data())) return rc;
+    for (size_t k = 0; k < reason.size(); k++)
+      if (memcmp(gt.data() + 2 * k * 384, gt.data() + (2 * k + 1) * 384, 384) != 0) return verdict(reason[k]);
+  }
+  memcpy(rec_out, rec, rec_len);
+  if (contribution_hash) memcpy(contribution_hash, response, 64);
+  static const char* const stages[3] = {nullptr, nullptr, "decompress"};
+  trace_points("ptau import response", stages, st, ms_since(t0));
+  set_error("");
+  *ok = 1;
+  guard.p = nullptr;
+  z.give(out, out_len);
+  return G16_OK;
+}
+
 int verify_core(const uint8_t* ptau, size_t len, int device, int* ok) {
   const auto t0 = std::chrono::steady_clock::now();
   *ok = 0;
@@ -362,35 +670,14 @@ int verify_core(const uint8_t* ptau, size_t len, int device, int* ok) {
   // for the last record, from the file (check 4)
   std::vector<uint8_t> pairs;        // 192 bytes each; check k compares pairing 2k with pairing 2k + 1
   std::vector<const char*> reason;   // per check
-  auto same_ratio = [&](const uint8_t* g1a, const uint8_t* g1b, const uint8_t* g2c, const uint8_t* g2d, const char* why) {
-    mpc_pair_words(pairs, g1a, g2d);   // e(a, d) = e(b, c)
-    mpc_pair_words(pairs, g1b, g2c);
-    reason.push_back(why);
-  };
+  static const RecordTexts texts = G16_RECORD_TEXTS("ptau verify");
   const uint8_t* cur[3] = {G.g1, G.g1, G.g1};   // tauG1, alphaG1, betaG1 before the record
   uint8_t challenge[64];
   std::vector<G2Affine> g2_sp(3 * c.rec.size());
-  static const char* const chain_text[3] = {"ptau verify: a contribution's tauG1 does not continue the chain",
-                                            "ptau verify: a contribution's alphaG1 does not continue the chain",
-                                            "ptau verify: a contribution's betaG1 does not continue the chain"};
   for (size_t i = 0; i < c.rec.size(); i++) {
-    const PtauRecord& r = c.rec[i];
-    bool inf = all_zero(r.tau_g1(), 64) || all_zero(r.tau_g2(), 128) || all_zero(r.alpha_g1(), 64) || all_zero(r.beta_g1(), 64) ||
-               all_zero(r.beta_g2(), 128);
-    for (int x = 0; x < 3; x++) inf = inf || all_zero(r.g1_s(x), 64) || all_zero(r.g1_sx(x), 64) || all_zero(r.g2_spx(x), 128);
-    if (inf) return verdict("ptau verify: a contribution holds the point at infinity");
     if (i == 0) generator_challenge(c, challenge);
     else memcpy(challenge, c.rec[i - 1].next_challenge(), 64);
-    const uint8_t* now[3] = {r.tau_g1(), r.alpha_g1(), r.beta_g1()};
-    for (int x = 0; x < 3; x++) {
-      G2Affine& sp = g2_sp[3 * i + x];
-      key_g2_sp(challenge, x, r.g1_s(x), r.g1_sx(x), sp);
-      same_ratio(r.g1_s(x), r.g1_sx(x), (const uint8_t*)&sp, r.g2_spx(x), "ptau verify: a contribution's public key is not consistent");
-      same_ratio(cur[x], now[x], (const uint8_t*)&sp, r.g2_spx(x), chain_text[x]);
-      cur[x] = now[x];
-    }
-    same_ratio(G.g1, r.tau_g1(), G.g2, r.tau_g2(), "ptau verify: a contribution's tauG2 does not match its tauG1");
-    same_ratio(G.g1, r.beta_g1(), G.g2, r.beta_g2(), "ptau verify: a contribution's betaG2 does not match its betaG1");
+    if (const char* inf = record_checks(texts, c.rec[i], cur, challenge, &g2_sp[3 * i], pairs, reason)) return verdict(inf);
   }
 
   // 3, 4 (host): a failure here is reported after the walk's pairings, and spares the sums of check 5
@@ -537,6 +824,59 @@ extern "C" int g16_ptau_contribute_files(const char* in_path, const char* out_pa
   return files_form(&in_path, 1, out_path, [&](const MappedFile* m, uint8_t** z, size_t* zl) {
     return g16_ptau_contribute((const uint8_t*)m[0].p, m[0].len, name, secret, device, z, zl, contribution_hash);
   });
+}
+
+extern "C" int g16_ptau_export_challenge(const uint8_t* ptau, size_t ptau_len, uint8_t** out, size_t* out_len,
+                                         uint8_t challenge_hash[64]) {
+  if (!ptau || !out || !out_len) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("ptau export challenge", [&]() { return export_challenge_core(ptau, ptau_len, out, out_len, challenge_hash); });
+}
+
+extern "C" int g16_ptau_export_challenge_files(const char* ptau_path, const char* challenge_path, uint8_t challenge_hash[64]) {
+  if (!ptau_path || !challenge_path) { set_error("NULL argument"); return G16_E_ARG; }
+  return files_form(&ptau_path, 1, challenge_path, [&](const MappedFile* m, uint8_t** z, size_t* zl) {
+    return g16_ptau_export_challenge((const uint8_t*)m[0].p, m[0].len, z, zl, challenge_hash);
+  });
+}
+
+extern "C" int g16_ptau_challenge_contribute(const uint8_t* challenge, size_t challenge_len, const uint8_t secret[192], int device,
+                                             uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]) {
+  if (!challenge || !out || !out_len) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("ptau challenge contribute", [&]() {
+    return challenge_contribute_core(challenge, challenge_len, secret, device, out, out_len, contribution_hash);
+  });
+}
+
+extern "C" int g16_ptau_challenge_contribute_files(const char* challenge_path, const char* response_path, const uint8_t secret[192],
+                                                   int device, uint8_t contribution_hash[64]) {
+  if (!challenge_path || !response_path) { set_error("NULL argument"); return G16_E_ARG; }
+  return files_form(&challenge_path, 1, response_path, [&](const MappedFile* m, uint8_t** z, size_t* zl) {
+    return g16_ptau_challenge_contribute((const uint8_t*)m[0].p, m[0].len, secret, device, z, zl, contribution_hash);
+  });
+}
+
+extern "C" int g16_ptau_import_response(const uint8_t* ptau, size_t ptau_len, const uint8_t* response, size_t response_len,
+                                        const char* name, int device, uint8_t** out, size_t* out_len, uint8_t contribution_hash[64],
+                                        int* ok) {
+  if (!ptau || !response || !out || !out_len || !ok) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("ptau import response", [&]() {
+    return import_response_core(ptau, ptau_len, response, response_len, name, device, out, out_len, contribution_hash, ok);
+  });
+}
+
+extern "C" int g16_ptau_import_response_files(const char* ptau_path, const char* response_path, const char* out_path, const char* name,
+                                              int device, uint8_t contribution_hash[64], int* ok) {
+  if (!ptau_path || !response_path || !out_path || !ok) { set_error("NULL argument"); return G16_E_ARG; }
+  MappedFile old, resp;
+  if (const int rc = old.open_ro(ptau_path)) return rc;
+  if (const int rc = resp.open_ro(response_path)) return rc;
+  uint8_t* z = nullptr;
+  size_t zl = 0;
+  if (const int rc = g16_ptau_import_response((const uint8_t*)old.p, old.len, (const uint8_t*)resp.p, resp.len, name, device, &z, &zl,
+                                              contribution_hash, ok))
+    return rc;
+  if (!*ok) return G16_OK;   // a verdict: nothing is written, the text stays
+  return write_key_file(out_path, z, zl);
 }
 
 extern "C" int g16_ptau_verify(const uint8_t* ptau, size_t ptau_len, int device, int* ok) {

@@ -28,6 +28,13 @@
  *           ptauContributeFiles(inPath, outPath, name | null, secret Buffer(192) | null, device) -> Promise<Buffer(64)>
  *                                                                              (g16_ptau_contribute_files: the hash)
  *           ptauVerifyFile(path, device) -> Promise<{ok, reason}>              (g16_ptau_verify_file)
+ *           ptauExportChallengeFiles(ptauPath, challengePath) -> Promise<Buffer(64)>   (g16_ptau_export_challenge_files: the
+ *                                                                              challenge hash)
+ *           ptauChallengeContributeFiles(challengePath, responsePath, secret Buffer(192) | null, device) -> Promise<Buffer(64)>
+ *                                                                              (g16_ptau_challenge_contribute_files)
+ *           ptauImportResponseFiles(oldPath, responsePath, newPath, name | null, device) -> Promise<Buffer(64)>; a failed
+ *                                                                              check rejects with its text
+ *                                                                              (g16_ptau_import_response_files)
  *           zkeyVerifyFromInitFiles(initPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_from_init_files)
  */
 #include <node_api.h>
@@ -885,13 +892,16 @@ static napi_value js_zkey_verify_from_init_files(napi_env env, napi_callback_inf
   return zjob_start(env, j, "g16_zkey_verify_from_init_files");
 }
 
-/* powersoftau new / contribute / verify from / to files */
+/* powersoftau new / contribute / verify / export challenge / challenge contribute / import response from / to files */
 typedef struct {
   napi_async_work work;
   napi_deferred deferred;
-  char a[1024], b[1024], name[512];
+  char a[1024], b[1024], c[1024], name[512];
   uint8_t secret[192], hash[64];
-  int mode;   /* 0: g16_ptau_new_file(power, a); 1: g16_ptau_contribute_files(a, b, ..); 2: g16_ptau_verify_file(a) */
+  /* 0: g16_ptau_new_file(power, a); 1: g16_ptau_contribute_files(a, b, ..); 2: g16_ptau_verify_file(a);
+   * 3: g16_ptau_export_challenge_files(a, b); 4: g16_ptau_challenge_contribute_files(a, b, ..);
+   * 5: g16_ptau_import_response_files(a, c, b, ..) */
+  int mode;
   int has_name, has_secret, device, rc, ok;
   uint32_t power;
   char err[512];
@@ -901,14 +911,17 @@ static void tjob_execute(napi_env env, void* data) {
   if (j->mode == 0) j->rc = g16_ptau_new_file(j->power, j->a);
   else if (j->mode == 1)
     j->rc = g16_ptau_contribute_files(j->a, j->b, j->has_name ? j->name : NULL, j->has_secret ? j->secret : NULL, j->device, j->hash);
-  else j->rc = g16_ptau_verify_file(j->a, j->device, &j->ok);
-  if (j->rc || (j->mode == 2 && !j->ok)) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
+  else if (j->mode == 2) j->rc = g16_ptau_verify_file(j->a, j->device, &j->ok);
+  else if (j->mode == 3) j->rc = g16_ptau_export_challenge_files(j->a, j->b, j->hash);
+  else if (j->mode == 4) j->rc = g16_ptau_challenge_contribute_files(j->a, j->b, j->has_secret ? j->secret : NULL, j->device, j->hash);
+  else j->rc = g16_ptau_import_response_files(j->a, j->c, j->b, j->has_name ? j->name : NULL, j->device, j->hash, &j->ok);
+  if (j->rc || ((j->mode == 2 || j->mode == 5) && !j->ok)) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
 }
 static void tjob_complete(napi_env env, napi_status status, void* data) {
   tjob_t* j = (tjob_t*)data;
-  if (status != napi_ok || j->rc) {
+  if (status != napi_ok || j->rc || (j->mode == 5 && !j->ok)) {
     napi_value msg, err;
-    napi_create_string_utf8(env, j->rc ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
+    napi_create_string_utf8(env, status == napi_ok ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
     napi_create_error(env, NULL, msg, &err);
     napi_reject_deferred(env, j->deferred, err);
   } else if (j->mode == 2) {
@@ -919,7 +932,7 @@ static void tjob_complete(napi_env env, napi_status status, void* data) {
     napi_set_named_property(env, obj, "ok", ok);
     napi_set_named_property(env, obj, "reason", reason);
     napi_resolve_deferred(env, j->deferred, obj);
-  } else if (j->mode == 1) {
+  } else if (j->mode != 0) {
     napi_value buf;
     void* copy = NULL;
     napi_create_buffer_copy(env, 64, j->hash, &copy, &buf);
@@ -1002,6 +1015,68 @@ static napi_value js_ptau_verify_file(napi_env env, napi_callback_info info) {
   j->mode = 2;
   return tjob_start(env, j, "g16_ptau_verify_file");
 }
+/* (inPath, outPath[, third path]) of the challenge / response commands -> a job, or NULL after a thrown TypeError */
+static tjob_t* tjob_paths(napi_env env, napi_value* argv, size_t argc, size_t npaths, const char* usage) {
+  tjob_t* j = (tjob_t*)calloc(1, sizeof(tjob_t));
+  char* dst[3] = {j->a, j->b, j->c};
+  size_t n = 0;
+  bool ok = argc >= npaths;
+  for (size_t k = 0; k < npaths && ok; k++) ok = napi_get_value_string_utf8(env, argv[k], dst[k], 1024, &n) == napi_ok;
+  if (!ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  return j;
+}
+static napi_value js_ptau_export_challenge_files(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  tjob_t* j = tjob_paths(env, argv, argc, 2, "ptauExportChallengeFiles(ptauPath, challengePath)");
+  if (!j) return NULL;
+  j->mode = 3;
+  return tjob_start(env, j, "g16_ptau_export_challenge_files");
+}
+static napi_value js_ptau_challenge_contribute_files(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  tjob_t* j = tjob_paths(env, argv, argc, 2, "ptauChallengeContributeFiles(challengePath, responsePath, secret, device)");
+  if (!j) return NULL;
+  bool is_buf = false;
+  if (argc > 2 && napi_is_buffer(env, argv[2], &is_buf) == napi_ok && is_buf) {
+    void* p = NULL;
+    size_t len = 0;
+    if (napi_get_buffer_info(env, argv[2], &p, &len) != napi_ok || len != 192) {
+      free(j);
+      napi_throw_type_error(env, NULL, "ptauChallengeContributeFiles: the secret is a Buffer of 192 bytes (six scalars) or null");
+      return NULL;
+    }
+    memcpy(j->secret, p, 192);
+    j->has_secret = 1;
+  }
+  int32_t v = 0;
+  if (argc > 3 && napi_get_value_int32(env, argv[3], &v) == napi_ok) j->device = v;
+  j->mode = 4;
+  return tjob_start(env, j, "g16_ptau_challenge_contribute_files");
+}
+static napi_value js_ptau_import_response_files(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  /* (a = old, b = new, c = response: the job's field order, not the argument order) */
+  tjob_t* j = tjob_paths(env, argv, argc, 3, "ptauImportResponseFiles(oldPath, responsePath, newPath, name, device)");
+  if (!j) return NULL;
+  char tmp[1024];
+  memcpy(tmp, j->b, sizeof(tmp)); memcpy(j->b, j->c, sizeof(tmp)); memcpy(j->c, tmp, sizeof(tmp));
+  size_t n = 0;
+  if (argc > 3 && napi_get_value_string_utf8(env, argv[3], j->name, sizeof(j->name), &n) == napi_ok) j->has_name = 1;
+  int32_t v = 0;
+  if (argc > 4 && napi_get_value_int32(env, argv[4], &v) == napi_ok) j->device = v;
+  j->mode = 5;
+  return tjob_start(env, j, "g16_ptau_import_response_files");
+}
 
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
@@ -1025,6 +1100,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"ptauNewFile", NULL, js_ptau_new_file, NULL, NULL, NULL, napi_default, NULL},
       {"ptauContributeFiles", NULL, js_ptau_contribute_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauVerifyFile", NULL, js_ptau_verify_file, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauExportChallengeFiles", NULL, js_ptau_export_challenge_files, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauChallengeContributeFiles", NULL, js_ptau_challenge_contribute_files, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauImportResponseFiles", NULL, js_ptau_import_response_files, NULL, NULL, NULL, napi_default, NULL},
   };
   NAPI_OK(napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props));
   return exports;

@@ -8,6 +8,10 @@
 // <new.ptau> [--name=..] [-e=..]` (alias `ptc`: prints the contribution hash as snarkjs does; -e: THIS CLI's derivation of
 // the six secret scalars, index.js ptauSecretFromEntropy, not snarkjs's) and `snarkjs powersoftau verify <pot.ptau>`
 // (alias `ptv`): prints "[INFO]  snarkJS: Powers of tau Ok!" and exits 0, or "[ERROR] snarkJS: <reason>" and exits 1.
+// And of the challenge / response exchange: `snarkjs powersoftau export challenge <pot.ptau> <challenge>` (alias `ptec`:
+// prints the challenge hash), `snarkjs powersoftau challenge contribute bn128 <challenge> <response> [-e=..]` (alias
+// `ptcc`) and `snarkjs powersoftau import response <old.ptau> <response> <new.ptau> [--name=..]` (alias `ptir`); the last
+// two print the contribution hash, which is this library's responseHash and not snarkjs's hash of the response file.
 // The transcript hashes are this library's (INTEGRATION.md 5b): snarkjs's `powersoftau verify` is not claimed to accept
 // these files, nor this one snarkjs's.
 // And of `snarkjs zkey contribute <old.zkey> <new.zkey> [--name=..] [-e=..]` (alias `zkc`): prints the contribution hash
@@ -99,6 +103,35 @@ async function main(argv) {
     if (pos.length < 2) { console.error("usage: cli.js powersoftau contribute <powersoftau.ptau> <new_powersoftau.ptau> [--name=..] [-e=..]"); process.exit(2); }
     const { powersOfTau, formatHash } = require("./index.js");
     const hash = await powersOfTau.contribute(pos[0], pos[1], opt("name", "n"), opt("entropy", "e"));
+    console.log(`[INFO]  snarkJS: Contribution Hash: \n${formatHash(hash)}`);
+    return;
+  }
+  if ((a[0] === "powersoftau" && a[1] === "export" && a[2] === "challenge") || a[0] === "ptec") {
+    const pos = a.slice(a[0] === "ptec" ? 1 : 3).filter((x) => !x.startsWith("-"));
+    if (pos.length < 2) { console.error("usage: cli.js powersoftau export challenge <powersoftau.ptau> <challenge>"); process.exit(2); }
+    const { powersOfTau, formatHash } = require("./index.js");
+    const hash = await powersOfTau.exportChallenge(pos[0], pos[1]);
+    console.log(`[INFO]  snarkJS: Challenge Hash: \n${formatHash(hash)}`);
+    return;
+  }
+  if ((a[0] === "powersoftau" && a[1] === "challenge" && a[2] === "contribute") || a[0] === "ptcc") {
+    const rest = a.slice(a[0] === "ptcc" ? 1 : 3);
+    const entropy = rest.map((x) => (x.startsWith("--entropy=") ? x.slice(10) : x.startsWith("-e=") ? x.slice(3) : undefined)).find((x) => x !== undefined);
+    const pos = rest.filter((x) => !x.startsWith("-"));
+    if (pos.length < 3) { console.error("usage: cli.js powersoftau challenge contribute bn128 <challenge> <response> [-e=..]"); process.exit(2); }
+    if (!["bn128", "bn254", "altbn128"].includes(pos[0].toLowerCase())) throw new Error(`Curve not supported: ${pos[0]}`);
+    const { powersOfTau, formatHash } = require("./index.js");
+    const hash = await powersOfTau.challengeContribute(pos[1], pos[2], entropy);
+    console.log(`[INFO]  snarkJS: Contribution Hash: \n${formatHash(hash)}`);
+    return;
+  }
+  if ((a[0] === "powersoftau" && a[1] === "import" && a[2] === "response") || a[0] === "ptir") {
+    const rest = a.slice(a[0] === "ptir" ? 1 : 3);
+    const name = rest.map((x) => (x.startsWith("--name=") ? x.slice(7) : x.startsWith("-n=") ? x.slice(3) : undefined)).find((x) => x !== undefined);
+    const pos = rest.filter((x) => !x.startsWith("-"));
+    if (pos.length < 3) { console.error("usage: cli.js powersoftau import response <powersoftau_old.ptau> <response> <powersoftau_new.ptau> [--name=..]"); process.exit(2); }
+    const { powersOfTau, formatHash } = require("./index.js");
+    const hash = await powersOfTau.importResponse(pos[0], pos[1], pos[2], name);
     console.log(`[INFO]  snarkJS: Contribution Hash: \n${formatHash(hash)}`);
     return;
   }

@@ -314,6 +314,30 @@ const powersOfTau = {
     const res = await native().ptauVerifyFile(String(ptauName), opts.device | 0);
     return opts.reason ? res : res.ok;
   },
+  // The challenge / response file exchange: how somebody who does not hold the .ptau contributes (INTEGRATION.md 5b).
+  // snarkjs: powersOfTau.exportChallenge(pTauFilename, challengeFilename[, logger]) / CLI `powersoftau export
+  // challenge` (alias `ptec`) -> the 64-byte challenge hash.  Host only.
+  async exportChallenge(ptauName, challengeName) {
+    return native().ptauExportChallengeFiles(String(ptauName), String(challengeName));
+  },
+  // snarkjs: powersOfTau.challengeContribute(curve, challengeFilename, responseFileName, entropy[, logger]) / CLI
+  // `powersoftau challenge contribute bn128 <challenge> <response> [-e=..]` (alias `ptcc`) -> the 64-byte contribution
+  // hash (this library's responseHash, not snarkjs's hash of the response file).  The curve is bn128 and may be left out.
+  async challengeContribute(...args) {
+    if (args.length >= 3 && typeof args[0] === "string" && typeof args[2] === "string" && ["bn128", "bn254", "altbn128"].includes(args[0].toLowerCase())) args = args.slice(1);
+    const [challengeName, responseName, entropy] = args;
+    let opts = args[3] || {};
+    if (opts && typeof opts.debug === "function") opts = {};
+    const secret = entropy === undefined || entropy === null || entropy === "" ? null : ptauSecretFromEntropy(entropy);
+    return native().ptauChallengeContributeFiles(String(challengeName), String(responseName), secret, opts.device | 0);
+  },
+  // snarkjs: powersOfTau.importResponse(oldPtauFilename, contributionFilename, newPTauFilename, name, importPoints[,
+  // logger]) / CLI `powersoftau import response` (alias `ptir`) -> the 64-byte contribution hash.  A response that
+  // fails a check of its record rejects with that check's text and writes nothing.
+  async importResponse(oldPtauName, responseName, newPtauName, name, opts = {}) {
+    if (typeof opts !== "object" || opts === null || typeof opts.debug === "function") opts = {};
+    return native().ptauImportResponseFiles(String(oldPtauName), String(responseName), String(newPtauName), name ? String(name) : null, opts.device | 0);
+  },
 };
 // tau | alpha | beta | s_tau | s_alpha | s_beta from a text: h_j = Blake2b-512(text | byte j), j = 0, 1, 2; the first
 // 32 bytes of h_j (little-endian, reduced mod r, 0 becomes 1) are key j, the last 32 bytes s_j (g16_ptau_secret_from_text)
