@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 #include <functional>
 #include <new>
@@ -46,6 +47,13 @@ template <class Fn> int no_bad_alloc(const char* route, Fn fn) {   // no C++ exc
     set_error(std::string(route) + ": out of memory");
     return G16_E_STATE;
   }
+}
+
+inline uint32_t env_u32(const char* name) {   // a positive integer from the environment (at most 2^30), else 0
+  const char* e = getenv(name);
+  if (!e) return 0;
+  const long v = atol(e);
+  return v > 0 ? (uint32_t)(v < (1l << 30) ? v : 1l << 30) : 0;
 }
 
 // ---------------------------------------------------------------- sharded pipeline inside ONE process (prover.cpp -> multi.cpp)
@@ -110,30 +118,27 @@ struct PtauPrepareStats {
 int ptau_prepare_g1(int device, const uint8_t* src, uint64_t nsrc, int kmax, uint8_t* out, PtauPrepareStats* st);
 int ptau_prepare_g2(int device, const uint8_t* src, uint64_t nsrc, int kmax, uint8_t* out, PtauPrepareStats* st);
 
-// ---------------------------------------------------------------- zkey contribute (zkey_scale.hip)
-// out[i] = [k] in[i]: n affine Montgomery G1 points (host, file layout; infinity = zero bytes in and out) times ONE
-// scalar k (standard form, in [1, r)), in chunks over two streams.  No CPU path (G16_E_NOGPU).
-struct ZkeyScaleStats {
-  float kern_ms = 0.f;   // device time of the kernels (scaling + conversion to affine), all chunks
+// ---------------------------------------------------------------- the chunked point routes (chunk_pipeline.h)
+struct ChunkStats {
+  float kern_ms = 0.f;   // device time of a route's kernels (conversion to affine and big-endian images included), all chunks
   float xfer_ms = 0.f;   // device time of the copies in and out
   uint64_t points = 0;
 };
-int zkey_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& k_std, uint8_t* out, ZkeyScaleStats* st);
+
+// ---------------------------------------------------------------- zkey contribute (zkey_scale.hip)
+// out[i] = [k] in[i]: n affine Montgomery G1 points (host, file layout; infinity = zero bytes in and out) times ONE
+// scalar k (standard form, in [1, r)), in chunks over two streams.  No CPU path (G16_E_NOGPU).
+int zkey_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& k_std, uint8_t* out, ChunkStats* st);
 
 // ---------------------------------------------------------------- powersoftau contribute (ptau_scale.hip)
 // out[i] = [c k^(first + i)] in[i]: n affine Montgomery points of G1 / G2 (host, file layout; infinity = zero bytes in
 // and out), c and k standard form in [1, r), first + n <= 2^31; every lane forms its scalar on the device.  out_be
 // (optional, as large as out): the uncompressed big-endian standard-form image of every output point (G1: x | y; G2:
 // x.c1 | x.c0 | y.c1 | y.c0; infinity = zeros with bit 0x40 of byte 0).  In chunks over two streams.  No CPU path.
-struct PtauScaleStats {
-  float kern_ms = 0.f;   // device time of the kernels (scaling, conversion to affine, big-endian images), all chunks
-  float xfer_ms = 0.f;   // device time of the copies in and out
-  uint64_t points = 0;
-};
 int ptau_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& c_std, const Fr& k_std, uint64_t first, uint8_t* out,
-                  uint8_t* out_be, PtauScaleStats* st);
+                  uint8_t* out_be, ChunkStats* st);
 int ptau_scale_g2(int device, const uint8_t* in, uint64_t n, const Fr& c_std, const Fr& k_std, uint64_t first, uint8_t* out,
-                  uint8_t* out_be, PtauScaleStats* st);
+                  uint8_t* out_be, ChunkStats* st);
 
 // ---------------------------------------------------------------- challenge / response points (ptau_points.hip)
 // n points of G1 (g2 = false) or G2 between the file form (affine little-endian Montgomery, 64 / 128 bytes, infinity =
@@ -142,10 +147,10 @@ int ptau_scale_g2(int device, const uint8_t* in, uint64_t n, const Fr& c_std, co
 // ptau_scale.  *first_bad (optional) = the smallest index whose image is not a point (a coordinate >= q, a wrong flag,
 // off the curve, no root), else -1; the outputs of a section with a bad point are not to be used.  out_be (optional):
 // the uncompressed image of every decompressed point, from the same pass.  No CPU path (G16_E_NOGPU).
-int ptau_points_from_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, PtauScaleStats* st);
-int ptau_points_compress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, PtauScaleStats* st);
+int ptau_points_from_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, ChunkStats* st);
+int ptau_points_compress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st);
 int ptau_points_decompress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* out_be, int64_t* first_bad,
-                           PtauScaleStats* st);
+                           ChunkStats* st);
 
 // ---------------------------------------------------------------- NTT (ntt.hip)
 struct NttPass { int lo_bits, S, tb; };

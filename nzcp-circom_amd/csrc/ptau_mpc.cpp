@@ -298,6 +298,40 @@ int new_core(uint32_t power, uint8_t** out, size_t* out_len) {
   return G16_OK;
 }
 
+// The challenge this file poses: without records that of its points with prev = Blake2b-512(""), else the last record's
+// nextChallenge.  feed <- room for prev | the big-endian images of sections 2-6 (those of the file's points in the
+// first case), which the next challenge is hashed over
+void file_challenge(const Ceremony& c, std::vector<uint8_t>& feed, uint8_t challenge[64]) {
+  feed.resize(64 + c.points_bytes());
+  if (!c.rec.empty()) { memcpy(challenge, c.rec.back().next_challenge(), 64); return; }
+  const uint8_t* in[7] = {};
+  for (int id = 2; id <= 6; id++) in[id] = c.pv.sec[id].p;
+  blake2b512(nullptr, 0, feed.data());
+  points_be_host(in, c.cnt, feed.data() + 64);
+  blake2b512(feed.data(), feed.size(), challenge);
+}
+
+// The tail of a new record (rec: its keys in place) from the new sections sp[2 .. 6], whose big-endian images lie in
+// feed: the state after the contribution -- tauG1 / tauG2 are point 1 of sections 2 / 3, which a power-0 file does not
+// hold (the caller has set them) --, response <- responseHash, and the seal: nextChallenge, type and params
+void seal_record(const Ceremony& c, uint8_t* const sp[16], const uint8_t challenge[64], std::vector<uint8_t>& feed,
+                 const std::string& params, uint8_t* rec, uint8_t response[64]) {
+  if (c.pv.power >= 1) {
+    memcpy(rec, sp[2] + 64, 64);
+    memcpy(rec + 64, sp[3] + 128, 128);
+  }
+  memcpy(rec + 192, sp[4], 64);
+  memcpy(rec + 256, sp[5], 64);
+  memcpy(rec + 320, sp[6], 128);
+  response_hash(challenge, PtauRecord{rec, kPtauRecordFixed + params.size()}, response);
+  memcpy(feed.data(), response, 64);
+  blake2b512(feed.data(), feed.size(), rec + kPtauNextChallengeAt);
+  const uint32_t type = 0, plen = (uint32_t)params.size();
+  memcpy(rec + kPtauNextChallengeAt + 64, &type, 4);
+  memcpy(rec + kPtauNextChallengeAt + 68, &plen, 4);
+  if (plen) memcpy(rec + kPtauRecordFixed, params.data(), plen);
+}
+
 int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uint8_t* secret, int device, uint8_t** out,
                     size_t* out_len, uint8_t contribution_hash[64]) {
   const auto t0 = std::chrono::steady_clock::now();
@@ -308,78 +342,55 @@ int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uin
   if (const int rc = require_hip_device("ptau contribute", device)) return rc;
 
   const std::string params = mpc_name_params(name);
-  const uint32_t plen = (uint32_t)params.size();
-  const size_t rec_len = kPtauRecordFixed + plen;
+  const size_t rec_len = kPtauRecordFixed + params.size();
   Buf z;
   uint8_t* sp[16] = {};
   uint8_t* rec = layout_with_record(c, rec_len, z, sp);
   if (!rec) { set_error("ptau contribute: out of memory"); return G16_E_STATE; }
   struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
   memset(rec, 0, rec_len);   // (partialHash stays zero)
-  const PtauRecord R{rec, rec_len};
 
   // the challenge this contribution answers
   const auto th0 = std::chrono::steady_clock::now();
-  std::vector<uint8_t> feed(64 + c.points_bytes());
+  std::vector<uint8_t> feed;
   uint8_t challenge[64];
-  const uint8_t* in[7] = {};
-  for (int id = 2; id <= 6; id++) in[id] = c.pv.sec[id].p;
-  if (c.rec.empty()) {
-    blake2b512(nullptr, 0, feed.data());
-    points_be_host(in, c.cnt, feed.data() + 64);
-    blake2b512(feed.data(), feed.size(), challenge);
-  } else {
-    memcpy(challenge, c.rec.back().next_challenge(), 64);
-  }
+  file_challenge(c, feed, challenge);
   make_keys(challenge, key, sk, rec);
   double hash_ms = ms_since(th0);
 
   // device: the sections, and the big-endian images of the new points straight into the next challenge's feed
   Fr one = fp_zero<FrParams>();
   one.v[0] = 1;
-  PtauScaleStats st[5];
+  ChunkStats st[5];
   {
     uint8_t* be = feed.data() + 64;
     const Fr* cs[7] = {nullptr, nullptr, &one, &one, &key[1], &key[2], &key[2]};
     int rc = G16_OK;
     for (int id = 2; id <= 6 && !rc; id++) {
       const Fr& k = id == 6 ? one : key[0];
-      rc = Ceremony::psz(id) == 64 ? ptau_scale_g1(device, in[id], c.cnt[id], *cs[id], k, 0, sp[id], be, &st[id - 2])
-                                   : ptau_scale_g2(device, in[id], c.cnt[id], *cs[id], k, 0, sp[id], be, &st[id - 2]);
+      rc = Ceremony::psz(id) == 64 ? ptau_scale_g1(device, c.pv.sec[id].p, c.cnt[id], *cs[id], k, 0, sp[id], be, &st[id - 2])
+                                   : ptau_scale_g2(device, c.pv.sec[id].p, c.cnt[id], *cs[id], k, 0, sp[id], be, &st[id - 2]);
       be += c.cnt[id] * Ceremony::psz(id);
     }
     if (rc) return rc;
   }
 
-  // the record: the state after this contribution.  tauG1 / tauG2 are point 1 of sections 2 / 3; a power-0 file holds
-  // no such point, there they continue the last record's (or the generators)
+  // the record; in a power-0 file tauG1 / tauG2 continue the last record's (or the generators)
   const auto th1 = std::chrono::steady_clock::now();
-  if (c.pv.power >= 1) {
-    memcpy(rec, sp[2] + 64, 64);
-    memcpy(rec + 64, sp[3] + 128, 128);
-  } else {
+  if (c.pv.power == 0) {
     mpc_mul_g1(c.rec.empty() ? gens().g1 : c.rec.back().tau_g1(), key[0], rec);
     mpc_mul_g2(c.rec.empty() ? gens().g2 : c.rec.back().tau_g2(), key[0], rec + 64);
   }
-  memcpy(rec + 192, sp[4], 64);
-  memcpy(rec + 256, sp[5], 64);
-  memcpy(rec + 320, sp[6], 128);
   uint8_t response[64];
-  response_hash(challenge, R, response);
+  seal_record(c, sp, challenge, feed, params, rec, response);
   if (contribution_hash) memcpy(contribution_hash, response, 64);
-  memcpy(feed.data(), response, 64);
-  blake2b512(feed.data(), feed.size(), rec + kPtauNextChallengeAt);
-  const uint32_t type = 0;
-  memcpy(rec + kPtauNextChallengeAt + 64, &type, 4);
-  memcpy(rec + kPtauNextChallengeAt + 68, &plen, 4);
-  if (plen) memcpy(rec + kPtauRecordFixed, params.data(), plen);
   hash_ms += ms_since(th1);
 
   if (getenv("G16_TRACE_HOST")) {
     uint64_t g1 = 0, g2 = 0;
     float k1 = 0, k2 = 0, xf = 0;
     for (int id = 2; id <= 6; id++) {
-      const PtauScaleStats& s = st[id - 2];
+      const ChunkStats& s = st[id - 2];
       if (Ceremony::psz(id) == 64) { g1 += s.points; k1 += s.kern_ms; } else { g2 += s.points; k2 += s.kern_ms; }
       xf += s.xfer_ms;
     }
@@ -437,7 +448,7 @@ int bad_point(const char* route, int64_t i, int id) {
   return G16_E_FORMAT;
 }
 
-void trace_points(const char* route, const char* const stage[3], const PtauScaleStats st[5][3], double call_ms) {
+void trace_points(const char* route, const char* const stage[3], const ChunkStats st[5][3], double call_ms) {
   if (!getenv("G16_TRACE_HOST")) return;
   std::string kernels;
   float xf = 0;
@@ -480,7 +491,7 @@ int challenge_contribute_core(const uint8_t* ch, size_t len, const uint8_t* secr
   one.v[0] = 1;
   const Fr* cs[7] = {nullptr, nullptr, &one, &one, &key[1], &key[2], &key[2]};
   std::vector<uint8_t> a(std::max<uint64_t>(cnt[2] * 64, n * 128)), b(a.size());
-  PtauScaleStats st[5][3];
+  ChunkStats st[5][3];
   const uint8_t* src = ch + 64;
   for (int id = 2; id <= 6; id++) {
     const size_t psz = Ceremony::psz(id);
@@ -545,22 +556,13 @@ int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, s
   const Gens& G = gens();
 
   // the challenge the response must answer: the file's own
-  std::vector<uint8_t> feed(64 + c.points_bytes());
+  std::vector<uint8_t> feed;
   uint8_t challenge[64];
-  const uint8_t* in[7] = {};
-  for (int id = 2; id <= 6; id++) in[id] = c.pv.sec[id].p;
-  if (c.rec.empty()) {
-    blake2b512(nullptr, 0, feed.data());
-    points_be_host(in, c.cnt, feed.data() + 64);
-    blake2b512(feed.data(), feed.size(), challenge);
-  } else {
-    memcpy(challenge, c.rec.back().next_challenge(), 64);
-  }
+  file_challenge(c, feed, challenge);
   if (memcmp(resp, challenge, 64) != 0) return verdict("ptau import response: the response does not answer this file's challenge");
 
   const std::string params = mpc_name_params(name);
-  const uint32_t plen = (uint32_t)params.size();
-  const size_t rec_len = kPtauRecordFixed + plen;
+  const size_t rec_len = kPtauRecordFixed + params.size();
   std::vector<uint8_t> recbuf(rec_len, 0);   // (partialHash stays zero)
   uint8_t* rec = recbuf.data();
   const PtauRecord R{rec, rec_len};
@@ -581,7 +583,7 @@ int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, s
   struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
 
   // device: the sections, and the big-endian images of the new points straight into the next challenge's feed
-  PtauScaleStats st[5][3];
+  ChunkStats st[5][3];
   {
     const uint8_t* src = resp + 64;
     uint8_t* be = feed.data() + 64;
@@ -596,19 +598,8 @@ int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, s
   }
 
   // the record, as contribute builds it
-  memcpy(rec, sp[2] + 64, 64);
-  memcpy(rec + 64, sp[3] + 128, 128);
-  memcpy(rec + 192, sp[4], 64);
-  memcpy(rec + 256, sp[5], 64);
-  memcpy(rec + 320, sp[6], 128);
   uint8_t response[64];
-  response_hash(challenge, R, response);
-  memcpy(feed.data(), response, 64);
-  blake2b512(feed.data(), feed.size(), rec + kPtauNextChallengeAt);
-  const uint32_t type = 0;
-  memcpy(rec + kPtauNextChallengeAt + 64, &type, 4);
-  memcpy(rec + kPtauNextChallengeAt + 68, &plen, 4);
-  if (plen) memcpy(rec + kPtauRecordFixed, params.data(), plen);
+  seal_record(c, sp, challenge, feed, params, rec, response);
 
   // step 2 of verify for this one record, against the record before it or the generators: ONE pairing call
   {

@@ -32,27 +32,25 @@
 // (uniform across the wavefront); there is no table indexed by a runtime value.  Which of the two roots is stored is
 // fixed by the flag, so the bytes do not depend on the route.
 //
-// One driver for all stages (points_device): chunks of kChunk points (G16_PTAU_CHUNK) through two buffer sets and two
-// streams, the copies of chunk c + 1 (up) and c - 1 (down) running while chunk c computes, as scale_device does; the
+// One driver for all stages (points_device): chunks (G16_PTAU_CHUNK) through the pipeline of chunk_pipeline.h; the
 // grid is G16_PTAU_LANES lanes (whole wavefronts) or one lane per point of the chunk, grid-stride.  A stage is a
 // functor that launches its kernel on (in, out, out2).
 // As built for gfx950 (the compiler's resource usage; DESIGN.md 3.7f has the table): 0 B scratch in every kernel.
 // Measured on one MI355X at power 20 (tools/ptau_challenge_bench.py, kernel events): decompress G1 4.6 ns,
 // G2 9.6 - 9.7 ns per point against ptau_scale's 46.7 - 47.1 / 197.6 - 199.4 ns per product in the same process.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
 #include <algorithm>
-#include <vector>
 
+#include "chunk_pipeline.h"
 #include "ec.cuh"
 #include "internal.h"
+#include "ptau_be.cuh"
 
 namespace g16 {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr uint32_t kChunk = 1u << 18;        // points per chunk
 constexpr uint32_t kNoBad = 0xffffffffu;     // the device word while every point is good
 
 // (q - 3) / 4 and (q - 1) / 2 as limbs, from the modulus
@@ -140,28 +138,6 @@ __device__ __forceinline__ bool fq_below_q(const Fq& s) { return limbs_below(s.v
 __device__ __forceinline__ bool fq_negative(const Fq& s) { return limbs_below(QC::K.half, s.v); }   // s > (q - 1) / 2
 __device__ __forceinline__ bool y_negative(const Fq& ys) { return fq_negative(ys); }
 __device__ __forceinline__ bool y_negative(const Fq2& ys) { return fp_is_zero(ys.b) ? fq_negative(ys.a) : fq_negative(ys.b); }
-
-// a point as NC coordinates of Fq in the file's order (x.c0, x.c1, y.c0, y.c1 on G2); the big-endian images hold c1
-// ahead of c0
-template <int NC> __device__ __forceinline__ int be_slot(int c) { return NC == 2 ? c : c ^ 1; }
-__device__ __forceinline__ Fq load_be(const uint32_t* p) {   // (every coordinate lies on a 32-byte boundary)
-  const uint4 hi = reinterpret_cast<const uint4*>(p)[0], lo = reinterpret_cast<const uint4*>(p)[1];
-  const uint32_t w[8] = {hi.x, hi.y, hi.z, hi.w, lo.x, lo.y, lo.z, lo.w};
-  Fq s;
-#pragma unroll
-  for (int k = 0; k < 8; k++) s.v[7 - k] = __builtin_bswap32(w[k]);
-  return s;
-}
-__device__ __forceinline__ void store_be(uint32_t* p, const Fq& s) {
-  uint32_t w[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) w[k] = __builtin_bswap32(s.v[7 - k]);
-  reinterpret_cast<uint4*>(p)[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  reinterpret_cast<uint4*>(p)[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-__device__ __forceinline__ void store_inf(uint32_t* p, int words) {
-  for (int w = 0; w < words; w++) p[w] = w == 0 ? 0x40u : 0u;   // (byte 0 of the little-endian word)
-}
 
 template <class FC> __device__ __forceinline__ typename FC::T curve_b();
 template <> __device__ __forceinline__ Fq curve_b<FqOps>() {
@@ -325,131 +301,39 @@ __global__ __launch_bounds__(kBlock) void fq_sqrt_kernel(const typename FC::T* _
   }
 }
 
-uint32_t env_u32(const char* name) {
-  const char* e = getenv(name);
-  if (!e) return 0;
-  const long v = atol(e);
-  return v > 0 ? (uint32_t)std::min<long>(v, 1l << 30) : 0;
-}
-
 // n items of in_sz bytes (host) through launch(grid, block, stream, d_in, d_out, d_out2, cnt, base, d_bad) into out
 // (out_sz bytes each) and -- when out2 -- out2 (out2_sz each); *first_bad = the device word after the last chunk, or -1
 template <class Launch>
 int points_device(const char* what, int device, const uint8_t* in, size_t in_sz, uint64_t n, uint8_t* out, size_t out_sz,
-                  uint8_t* out2, size_t out2_sz, int64_t* first_bad, PtauScaleStats* st, Launch launch) {
+                  uint8_t* out2, size_t out2_sz, int64_t* first_bad, ChunkStats* st, Launch launch) {
   if (first_bad) *first_bad = -1;
-  if (st) *st = PtauScaleStats{};
+  if (st) *st = ChunkStats{};
   if (n >= ((uint64_t)1 << 31)) { set_error(std::string(what) + ": more than 2^31 items"); return G16_E_ARG; }
   if (const int rc = require_hip_device(what, device)) return rc;
   if (n == 0) return G16_OK;
   G16_HIP(hipSetDevice(device));
+  const ChunkPlan plan = chunk_plan("G16_PTAU_CHUNK", "G16_PTAU_LANES", n, 0);
 
-  uint32_t chunk = env_u32("G16_PTAU_CHUNK");
-  if (!chunk) chunk = kChunk;
-  chunk = (uint32_t)std::min<uint64_t>(chunk, n);
-  uint32_t lanes = env_u32("G16_PTAU_LANES"), block = kBlock;
-  if (lanes) {
-    lanes = (lanes + 63) / 64 * 64;
-    if (lanes % kBlock) block = 64;
-  }
-  const uint64_t nchunks = (n + chunk - 1) / chunk;
-
-  uint8_t* d_in[2] = {nullptr, nullptr};
-  uint8_t* d_out[2] = {nullptr, nullptr};
-  uint8_t* d_out2[2] = {nullptr, nullptr};
-  uint32_t* d_bad = nullptr;
+  DeviceBuf<uint32_t> bad;
   uint32_t h_bad = kNoBad;
-  hipStream_t cst = nullptr, xst = nullptr;   // compute, copies
-  hipEvent_t ev_up[2] = {}, ev_k[2] = {}, ev_down[2] = {};
-  std::vector<hipEvent_t> tk(2 * nchunks, nullptr), tx(4 * nchunks, nullptr);   // timing: kernel / copy begin-end pairs
-  int rc = G16_OK;
-  auto fail = [&](hipError_t e) {
-    if (e == hipSuccess) return false;
-    set_error(std::string(what) + " (device): " + hipGetErrorString(e));
-    rc = G16_E_HIP;
-    return true;
-  };
-  auto upload = [&](uint64_t c) {
-    const int b = (int)(c & 1);
-    const uint64_t lo = c * chunk, cnt = std::min<uint64_t>(chunk, n - lo);
-    // the buffer's last reader (the kernel of chunk c - 2) has finished
-    if (c >= 2 && fail(hipStreamWaitEvent(xst, ev_k[b], 0))) return false;
-    if (fail(hipEventRecord(tx[4 * c], xst))) return false;
-    if (fail(hipMemcpyAsync(d_in[b], in + lo * in_sz, cnt * in_sz, hipMemcpyHostToDevice, xst))) return false;
-    if (fail(hipEventRecord(tx[4 * c + 1], xst))) return false;
-    return !fail(hipEventRecord(ev_up[b], xst));
-  };
-  do {
-    if (fail(hipStreamCreateWithFlags(&cst, hipStreamNonBlocking)) || fail(hipStreamCreateWithFlags(&xst, hipStreamNonBlocking))) break;
-    bool bad = false;
-    for (int b = 0; b < 2 && !bad; b++)
-      bad = fail(hipEventCreateWithFlags(&ev_up[b], hipEventDisableTiming)) ||
-            fail(hipEventCreateWithFlags(&ev_k[b], hipEventDisableTiming)) ||
-            fail(hipEventCreateWithFlags(&ev_down[b], hipEventDisableTiming));
-    for (auto& e : tk) if (!bad) bad = fail(hipEventCreate(&e));
-    for (auto& e : tx) if (!bad) bad = fail(hipEventCreate(&e));
-    if (bad) break;
-    const int nbuf = nchunks > 1 ? 2 : 1;
-    for (int b = 0; b < nbuf && !bad; b++) {
-      bad = fail(hipMalloc(&d_in[b], (size_t)chunk * in_sz)) || fail(hipMalloc(&d_out[b], (size_t)chunk * out_sz));
-      if (!bad && out2) bad = fail(hipMalloc(&d_out2[b], (size_t)chunk * out2_sz));
-    }
-    if (bad) break;
-    if (fail(hipMalloc(&d_bad, sizeof(uint32_t)))) break;
-    if (fail(hipMemcpyAsync(d_bad, &h_bad, sizeof(uint32_t), hipMemcpyHostToDevice, cst))) break;
-    if (!upload(0)) break;
-    for (uint64_t c = 0; c < nchunks; c++) {
-      const int b = (int)(c & 1);
-      const uint64_t lo = c * chunk;
-      const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, n - lo);
-      if (c + 1 < nchunks && !upload(c + 1)) break;
-      if (fail(hipStreamWaitEvent(cst, ev_up[b], 0))) break;
-      if (c >= 2 && fail(hipStreamWaitEvent(cst, ev_down[b], 0))) break;   // d_out[b], d_out2[b] have been copied out
-      if (fail(hipEventRecord(tk[2 * c], cst))) break;
-      uint32_t grid = (cnt + block - 1) / block;
-      if (lanes) grid = std::min(grid, lanes / block);
-      launch(grid, block, cst, d_in[b], d_out[b], d_out2[b], cnt, (uint32_t)lo, d_bad);
-      if (fail(hipGetLastError())) break;
-      if (fail(hipEventRecord(tk[2 * c + 1], cst)) || fail(hipEventRecord(ev_k[b], cst))) break;
-      if (fail(hipStreamWaitEvent(xst, ev_k[b], 0))) break;
-      if (fail(hipEventRecord(tx[4 * c + 2], xst))) break;
-      if (fail(hipMemcpyAsync(out + lo * out_sz, d_out[b], (size_t)cnt * out_sz, hipMemcpyDeviceToHost, xst))) break;
-      if (out2 && fail(hipMemcpyAsync(out2 + lo * out2_sz, d_out2[b], (size_t)cnt * out2_sz, hipMemcpyDeviceToHost, xst))) break;
-      if (fail(hipEventRecord(tx[4 * c + 3], xst)) || fail(hipEventRecord(ev_down[b], xst))) break;
-    }
-    if (rc) break;
-    if (fail(hipStreamSynchronize(xst)) || fail(hipStreamSynchronize(cst))) break;
-    if (fail(hipMemcpy(&h_bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost))) break;
-    if (first_bad && h_bad != kNoBad) *first_bad = (int64_t)h_bad;
-    if (st) {
-      for (uint64_t c = 0; c < nchunks; c++) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, tk[2 * c], tk[2 * c + 1]) == hipSuccess) st->kern_ms += ms;
-        for (int h = 0; h < 2; h++)
-          if (hipEventElapsedTime(&ms, tx[4 * c + 2 * h], tx[4 * c + 2 * h + 1]) == hipSuccess) st->xfer_ms += ms;
-      }
-      st->points = n;
-    }
-  } while (false);
-  if (xst) (void)hipStreamSynchronize(xst);
-  if (cst) (void)hipStreamSynchronize(cst);
-  for (int b = 0; b < 2; b++) {
-    hipEvent_t evs[3] = {ev_up[b], ev_k[b], ev_down[b]};
-    for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-    if (d_in[b]) (void)hipFree(d_in[b]);
-    if (d_out[b]) (void)hipFree(d_out[b]);
-    if (d_out2[b]) (void)hipFree(d_out2[b]);
+  ChunkPipeline pipe(what);
+  if (!pipe.open(n, plan.chunk, in_sz, out_sz, out2 ? out2_sz : 0) || pipe.fail(bad.alloc(1)) ||
+      pipe.fail(hipMemcpyAsync(bad.p, &h_bad, sizeof(uint32_t), hipMemcpyHostToDevice, pipe.stream())))
+    return pipe.rc();
+  const int rc = pipe.run(in, out, out2, st, [&](hipStream_t s, const uint8_t* i, uint8_t* o, uint8_t* o2, uint32_t cnt, uint64_t lo) {
+    launch(plan.grid(cnt), plan.block, s, i, o, o2, cnt, (uint32_t)lo, bad.p);
+  });
+  if (rc) return rc;
+  if (pipe.fail(hipMemcpy(&h_bad, bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost))) {
+    if (st) *st = ChunkStats{};
+    return pipe.rc();
   }
-  for (hipEvent_t e : tk) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : tx) if (e) (void)hipEventDestroy(e);
-  if (d_bad) (void)hipFree(d_bad);
-  if (xst) (void)hipStreamDestroy(xst);
-  if (cst) (void)hipStreamDestroy(cst);
-  return rc;
+  if (first_bad && h_bad != kNoBad) *first_bad = (int64_t)h_bad;
+  return G16_OK;
 }
 
 template <class FC>
-int from_be(int device, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, PtauScaleStats* st) {
+int from_be(int device, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, ChunkStats* st) {
   constexpr size_t PSZ = sizeof(Affine<FC>);
   return points_device("ptau points from-be", device, in, PSZ, n, out, PSZ, nullptr, 0, first_bad, st,
                        [](uint32_t grid, uint32_t block, hipStream_t s, const uint8_t* i, uint8_t* o, uint8_t*, uint32_t cnt,
@@ -457,14 +341,14 @@ int from_be(int device, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* fi
                          ptau_from_be_kernel<FC><<<grid, block, 0, s>>>((const uint32_t*)i, (Affine<FC>*)o, cnt, base, bad);
                        });
 }
-template <class FC> int compress(int device, const uint8_t* in, uint64_t n, uint8_t* out, PtauScaleStats* st) {
+template <class FC> int compress(int device, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st) {
   constexpr size_t PSZ = sizeof(Affine<FC>);
   return points_device("ptau points compress", device, in, PSZ, n, out, PSZ / 2, nullptr, 0, nullptr, st,
                        [](uint32_t grid, uint32_t block, hipStream_t s, const uint8_t* i, uint8_t* o, uint8_t*, uint32_t cnt, uint32_t,
                           uint32_t*) { ptau_compress_kernel<FC><<<grid, block, 0, s>>>((const Affine<FC>*)i, (uint32_t*)o, cnt); });
 }
 template <class FC>
-int decompress(int device, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* out_be, int64_t* first_bad, PtauScaleStats* st) {
+int decompress(int device, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* out_be, int64_t* first_bad, ChunkStats* st) {
   constexpr size_t PSZ = sizeof(Affine<FC>);
   return points_device("ptau points decompress", device, in, PSZ / 2, n, out, PSZ, out_be, PSZ, first_bad, st,
                        [](uint32_t grid, uint32_t block, hipStream_t s, const uint8_t* i, uint8_t* o, uint8_t* o2, uint32_t cnt,
@@ -483,14 +367,14 @@ template <class FC> int sqrt_batch(int device, const uint8_t* in, uint64_t n, ui
 
 }  // namespace
 
-int ptau_points_from_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, PtauScaleStats* st) {
+int ptau_points_from_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, ChunkStats* st) {
   return g2 ? from_be<Fq2Ops>(device, in, n, out, first_bad, st) : from_be<FqOps>(device, in, n, out, first_bad, st);
 }
-int ptau_points_compress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, PtauScaleStats* st) {
+int ptau_points_compress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st) {
   return g2 ? compress<Fq2Ops>(device, in, n, out, st) : compress<FqOps>(device, in, n, out, st);
 }
 int ptau_points_decompress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* out_be, int64_t* first_bad,
-                           PtauScaleStats* st) {
+                           ChunkStats* st) {
   return g2 ? decompress<Fq2Ops>(device, in, n, out, out_be, first_bad, st) : decompress<FqOps>(device, in, n, out, out_be, first_bad, st);
 }
 
@@ -509,7 +393,7 @@ bool layer_args(const char* what, int group, const void* in, const void* out) {
 extern "C" int g16_ptau_points_from_be(int group, const uint8_t* in, size_t n, int device, uint8_t* out, int64_t* first_bad,
                                        float* kernel_ms) {
   if (!layer_args("ptau points from-be", group, in, out)) return G16_E_ARG;
-  PtauScaleStats st;
+  ChunkStats st;
   const int rc = ptau_points_from_be(device, group == 2, in, n, out, first_bad, &st);
   if (kernel_ms) *kernel_ms = st.kern_ms;
   return rc;
@@ -518,7 +402,7 @@ extern "C" int g16_ptau_points_compress(int group, const uint8_t* in, size_t n, 
                                         float* kernel_ms) {
   if (!layer_args("ptau points compress", group, in, out)) return G16_E_ARG;
   if (first_bad) *first_bad = -1;   // (every file image has a compressed form)
-  PtauScaleStats st;
+  ChunkStats st;
   const int rc = ptau_points_compress(device, group == 2, in, n, out, &st);
   if (kernel_ms) *kernel_ms = st.kern_ms;
   return rc;
@@ -526,7 +410,7 @@ extern "C" int g16_ptau_points_compress(int group, const uint8_t* in, size_t n, 
 extern "C" int g16_ptau_points_decompress(int group, const uint8_t* in, size_t n, int device, uint8_t* out, uint8_t* out_be,
                                           int64_t* first_bad, float* kernel_ms) {
   if (!layer_args("ptau points decompress", group, in, out)) return G16_E_ARG;
-  PtauScaleStats st;
+  ChunkStats st;
   const int rc = ptau_points_decompress(device, group == 2, in, n, out, out_be, first_bad, &st);
   if (kernel_ms) *kernel_ms = st.kern_ms;
   return rc;

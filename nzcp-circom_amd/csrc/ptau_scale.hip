@@ -37,18 +37,16 @@
 // are handled: tau = 1, tau = r - 1 or a root of unity need no argument), and the affine result is unique: the bytes
 // equal the host's and the oracle's.
 //
-// A section of any size runs in chunks of kChunk points (G16_PTAU_CHUNK) through two buffer sets, as zkey_scale_g1
-// does: the copies of chunk c + 1 (up) and c - 1 (down) go over a second stream while chunk c computes.  A chunk
-// carries its `first`.
+// A section of any size runs in chunks (G16_PTAU_CHUNK) through the pipeline of chunk_pipeline.h.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
 #include <algorithm>
-#include <vector>
 
 #include "binfile.h"
+#include "chunk_pipeline.h"
 #include "ec.cuh"
 #include "internal.h"
+#include "ptau_be.cuh"
 #include "scalar_mul.cuh"
 #include "setup_affine.cuh"
 
@@ -57,7 +55,6 @@ namespace {
 
 constexpr int kWin = 5;   // G16_PTAU_WINDOW = 3 / 4 / 5 overrides it
 constexpr int kScaleBlock = 256;
-constexpr uint32_t kChunk = 1u << 18;   // points per chunk (G1: 16 MB up, 32 MB XYZZ, 16 + 16 MB down)
 
 template <class FC, int W>
 __global__ __launch_bounds__(kScaleBlock) void ptau_scale_kernel(const Affine<FC>* __restrict__ in, XYZZ<FC>* __restrict__ work,
@@ -85,8 +82,8 @@ __global__ __launch_bounds__(kScaleBlock) void ptau_scale_kernel(const Affine<FC
   }
 }
 
-// affine file image -> uncompressed big-endian standard form: 32-byte coordinates x | y (G1), x.c1 | x.c0 | y.c1 | y.c0
-// (G2); infinity = zeros with bit 0x40 of byte 0
+// affine file image -> uncompressed big-endian standard form (ptau_be.cuh); the inverse of ptau_from_be_kernel
+// (ptau_points.hip)
 template <class FC>
 __global__ __launch_bounds__(256) void ptau_be_kernel(const Affine<FC>* __restrict__ in, uint32_t* __restrict__ out, uint32_t n) {
   constexpr int NC = sizeof(Affine<FC>) / 32;
@@ -96,20 +93,11 @@ __global__ __launch_bounds__(256) void ptau_be_kernel(const Affine<FC>* __restri
   const Fq* co = reinterpret_cast<const Fq*>(&p);
   uint32_t* o = out + (size_t)i * NC * 8;
   if (aff_is_inf(p)) {
-    for (int w = 0; w < NC * 8; w++) o[w] = w == 0 ? 0x40u : 0u;   // (byte 0 of the little-endian word)
+    store_inf(o, NC * 8);
     return;
   }
-  for (int c = 0; c < NC; c++) {
-    const Fq s = fp_from_mont(co[NC == 2 ? c : c ^ 1]);
-    for (int w = 0; w < 8; w++) o[c * 8 + w] = __builtin_bswap32(s.v[7 - w]);
-  }
-}
-
-uint32_t env_u32(const char* name) {
-  const char* e = getenv(name);
-  if (!e) return 0;
-  const long v = atol(e);
-  return v > 0 ? (uint32_t)std::min<long>(v, 1l << 30) : 0;
+#pragma unroll
+  for (int c = 0; c < NC; c++) store_be(o + c * 8, fp_from_mont(co[be_slot<NC>(c)]));
 }
 
 template <class FC, int W>
@@ -120,7 +108,7 @@ void launch_scale(uint32_t grid, uint32_t block, hipStream_t st, const Affine<FC
 
 template <class FC>
 int scale_device(int device, const uint8_t* in, uint64_t n, const Fr& c_std, const Fr& k_std, uint64_t first, uint8_t* out,
-                 uint8_t* out_be, PtauScaleStats* st) {
+                 uint8_t* out_be, ChunkStats* st) {
   constexpr size_t PSZ = sizeof(Affine<FC>);
   if (fp_is_zero(c_std) || !fr_below_modulus(c_std.v) || fp_is_zero(k_std) || !fr_below_modulus(k_std.v)) {
     set_error("ptau scale: a multiplier is not in [1, r)");
@@ -128,143 +116,45 @@ int scale_device(int device, const uint8_t* in, uint64_t n, const Fr& c_std, con
   }
   if (first + n > ((uint64_t)1 << 31)) { set_error("ptau scale: exponent range above 2^31"); return G16_E_ARG; }
   if (const int rc = require_hip_device("ptau scale", device)) return rc;
-  if (st) *st = PtauScaleStats{};
+  if (st) *st = ChunkStats{};
   if (n == 0) return G16_OK;
   G16_HIP(hipSetDevice(device));
   hipDeviceProp_t prop;
   G16_HIP(hipGetDeviceProperties(&prop, device));
   int win = (int)env_u32("G16_PTAU_WINDOW");
   if (win < 3 || win > 5) win = kWin;
-  const int ntbl = 1 << (win - 1);
   const Fr c_mont = fp_to_mont(c_std), k_mont = fp_to_mont(k_std);
+  const ChunkPlan plan = chunk_plan("G16_PTAU_CHUNK", "G16_PTAU_LANES", n, (uint32_t)std::max(prop.multiProcessorCount, 1) * 4 * kScaleBlock);
 
-  // chunk and persistent grid (both overridable, so that a small test runs several chunks and grid-stride passes)
-  uint32_t chunk = env_u32("G16_PTAU_CHUNK");
-  if (!chunk) chunk = kChunk;
-  chunk = (uint32_t)std::min<uint64_t>(chunk, n);
-  const uint32_t lanes_cap = (uint32_t)std::max(prop.multiProcessorCount, 1) * 4 * kScaleBlock;
-  uint32_t lanes = env_u32("G16_PTAU_LANES");
-  uint32_t block = kScaleBlock;
-  if (lanes) {
-    lanes = std::min((lanes + 63) / 64 * 64, lanes_cap);
-    if (lanes % kScaleBlock) block = 64;
-  } else {
-    lanes = lanes_cap;
-  }
-  lanes = std::min(lanes, (chunk + block - 1) / block * block);
-  const uint32_t blocks = lanes / block;
-  const uint64_t nchunks = (n + chunk - 1) / chunk;
-
-  Affine<FC>* d_in[2] = {nullptr, nullptr};
-  Affine<FC>* d_aff[2] = {nullptr, nullptr};
-  uint32_t* d_be[2] = {nullptr, nullptr};
-  XYZZ<FC>* d_work = nullptr;
-  XYZZ<FC>* d_tbl = nullptr;
-  Fr* d_sc = nullptr;
-  hipStream_t cst = nullptr, xst = nullptr;   // compute, copies
-  hipEvent_t ev_up[2] = {}, ev_k[2] = {}, ev_down[2] = {};
-  std::vector<hipEvent_t> tk(2 * nchunks, nullptr), tx(4 * nchunks, nullptr);   // timing: kernel / copy begin-end pairs
-  int rc = G16_OK;
-  auto fail = [&](hipError_t e) {
-    if (e == hipSuccess) return false;
-    set_error(std::string("ptau scale (device): ") + hipGetErrorString(e));
-    rc = G16_E_HIP;
-    return true;
-  };
-  auto upload = [&](uint64_t c) {
-    const int b = (int)(c & 1);
-    const uint64_t lo = c * chunk, cnt = std::min<uint64_t>(chunk, n - lo);
-    // the buffer's last reader (the kernel of chunk c - 2) has finished
-    if (c >= 2 && fail(hipStreamWaitEvent(xst, ev_k[b], 0))) return false;
-    if (fail(hipEventRecord(tx[4 * c], xst))) return false;
-    if (fail(hipMemcpyAsync(d_in[b], in + lo * PSZ, cnt * PSZ, hipMemcpyHostToDevice, xst))) return false;
-    if (fail(hipEventRecord(tx[4 * c + 1], xst))) return false;
-    return !fail(hipEventRecord(ev_up[b], xst));
-  };
-  do {
-    if (fail(hipStreamCreateWithFlags(&cst, hipStreamNonBlocking)) || fail(hipStreamCreateWithFlags(&xst, hipStreamNonBlocking))) break;
-    bool bad = false;
-    for (int b = 0; b < 2 && !bad; b++)
-      bad = fail(hipEventCreateWithFlags(&ev_up[b], hipEventDisableTiming)) ||
-            fail(hipEventCreateWithFlags(&ev_k[b], hipEventDisableTiming)) ||
-            fail(hipEventCreateWithFlags(&ev_down[b], hipEventDisableTiming));
-    for (auto& e : tk) if (!bad) bad = fail(hipEventCreate(&e));
-    for (auto& e : tx) if (!bad) bad = fail(hipEventCreate(&e));
-    if (bad) break;
-    const int nbuf = nchunks > 1 ? 2 : 1;
-    for (int b = 0; b < nbuf && !bad; b++) {
-      bad = fail(hipMalloc(&d_in[b], (size_t)chunk * PSZ)) || fail(hipMalloc(&d_aff[b], (size_t)chunk * PSZ));
-      if (!bad && out_be) bad = fail(hipMalloc(&d_be[b], (size_t)chunk * PSZ));
-    }
-    if (bad) break;
-    if (fail(hipMalloc(&d_work, (size_t)chunk * sizeof(XYZZ<FC>)))) break;
-    if (fail(hipMalloc(&d_tbl, (size_t)lanes * ntbl * sizeof(XYZZ<FC>)))) break;
-    if (fail(hipMalloc(&d_sc, (size_t)lanes * sizeof(Fr)))) break;
-    if (!upload(0)) break;
-    for (uint64_t c = 0; c < nchunks; c++) {
-      const int b = (int)(c & 1);
-      const uint64_t lo = c * chunk;
-      const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, n - lo);
-      if (c + 1 < nchunks && !upload(c + 1)) break;
-      if (fail(hipStreamWaitEvent(cst, ev_up[b], 0))) break;
-      if (c >= 2 && fail(hipStreamWaitEvent(cst, ev_down[b], 0))) break;   // d_aff[b], d_be[b] have been copied out
-      if (fail(hipEventRecord(tk[2 * c], cst))) break;
-      const uint32_t grid = std::min(blocks, (cnt + block - 1) / block);
-      const uint32_t cfirst = (uint32_t)(first + lo);
-      int nbits = 0;
-      while (nbits < 32 && ((uint64_t)cfirst + cnt - 1) >> nbits) nbits++;
-      if (win == 3) launch_scale<FC, 3>(grid, block, cst, d_in[b], d_work, cnt, cfirst, c_mont, k_mont, nbits, d_sc, d_tbl);
-      else if (win == 4) launch_scale<FC, 4>(grid, block, cst, d_in[b], d_work, cnt, cfirst, c_mont, k_mont, nbits, d_sc, d_tbl);
-      else launch_scale<FC, 5>(grid, block, cst, d_in[b], d_work, cnt, cfirst, c_mont, k_mont, nbits, d_sc, d_tbl);
-      setup_to_affine_kernel<FC><<<((cnt + kBatch - 1) / kBatch + 255) / 256, 256, 0, cst>>>(d_work, d_aff[b], cnt);
-      if (out_be) ptau_be_kernel<FC><<<(cnt + 255) / 256, 256, 0, cst>>>(d_aff[b], d_be[b], cnt);
-      if (fail(hipGetLastError())) break;
-      if (fail(hipEventRecord(tk[2 * c + 1], cst)) || fail(hipEventRecord(ev_k[b], cst))) break;
-      if (fail(hipStreamWaitEvent(xst, ev_k[b], 0))) break;
-      if (fail(hipEventRecord(tx[4 * c + 2], xst))) break;
-      if (fail(hipMemcpyAsync(out + lo * PSZ, d_aff[b], (size_t)cnt * PSZ, hipMemcpyDeviceToHost, xst))) break;
-      if (out_be && fail(hipMemcpyAsync(out_be + lo * PSZ, d_be[b], (size_t)cnt * PSZ, hipMemcpyDeviceToHost, xst))) break;
-      if (fail(hipEventRecord(tx[4 * c + 3], xst)) || fail(hipEventRecord(ev_down[b], xst))) break;
-    }
-    if (rc) break;
-    if (fail(hipStreamSynchronize(xst)) || fail(hipStreamSynchronize(cst))) break;
-    if (st) {
-      for (uint64_t c = 0; c < nchunks; c++) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, tk[2 * c], tk[2 * c + 1]) == hipSuccess) st->kern_ms += ms;
-        for (int h = 0; h < 2; h++)
-          if (hipEventElapsedTime(&ms, tx[4 * c + 2 * h], tx[4 * c + 2 * h + 1]) == hipSuccess) st->xfer_ms += ms;
-      }
-      st->points = n;
-    }
-  } while (false);
-  if (xst) (void)hipStreamSynchronize(xst);
-  if (cst) (void)hipStreamSynchronize(cst);
-  for (int b = 0; b < 2; b++) {
-    hipEvent_t evs[3] = {ev_up[b], ev_k[b], ev_down[b]};
-    for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-    if (d_in[b]) (void)hipFree(d_in[b]);
-    if (d_aff[b]) (void)hipFree(d_aff[b]);
-    if (d_be[b]) (void)hipFree(d_be[b]);
-  }
-  for (hipEvent_t e : tk) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : tx) if (e) (void)hipEventDestroy(e);
-  if (d_work) (void)hipFree(d_work);
-  if (d_tbl) (void)hipFree(d_tbl);
-  if (d_sc) (void)hipFree(d_sc);
-  if (xst) (void)hipStreamDestroy(xst);
-  if (cst) (void)hipStreamDestroy(cst);
-  return rc;
+  DeviceBuf<XYZZ<FC>> work, tbl;
+  DeviceBuf<Fr> sc;
+  ChunkPipeline pipe("ptau scale");
+  if (!pipe.open(n, plan.chunk, PSZ, PSZ, out_be ? PSZ : 0) || pipe.fail(work.alloc(plan.chunk)) ||
+      pipe.fail(tbl.alloc((size_t)plan.lanes << (win - 1))) || pipe.fail(sc.alloc(plan.lanes)))
+    return pipe.rc();
+  return pipe.run(in, out, out_be, st, [&](hipStream_t s, const uint8_t* d_in, uint8_t* d_out, uint8_t* d_be, uint32_t cnt, uint64_t lo) {
+    const Affine<FC>* pts = (const Affine<FC>*)d_in;
+    Affine<FC>* aff = (Affine<FC>*)d_out;
+    const uint32_t grid = plan.grid(cnt), block = plan.block;
+    const uint32_t cfirst = (uint32_t)(first + lo);   // a chunk carries its `first`
+    int nbits = 0;
+    while (nbits < 32 && ((uint64_t)cfirst + cnt - 1) >> nbits) nbits++;
+    if (win == 3) launch_scale<FC, 3>(grid, block, s, pts, work.p, cnt, cfirst, c_mont, k_mont, nbits, sc.p, tbl.p);
+    else if (win == 4) launch_scale<FC, 4>(grid, block, s, pts, work.p, cnt, cfirst, c_mont, k_mont, nbits, sc.p, tbl.p);
+    else launch_scale<FC, 5>(grid, block, s, pts, work.p, cnt, cfirst, c_mont, k_mont, nbits, sc.p, tbl.p);
+    setup_to_affine_kernel<FC><<<((cnt + kBatch - 1) / kBatch + 255) / 256, 256, 0, s>>>(work.p, aff, cnt);
+    if (d_be) ptau_be_kernel<FC><<<(cnt + 255) / 256, 256, 0, s>>>(aff, (uint32_t*)d_be, cnt);
+  });
 }
 
 }  // namespace
 
 int ptau_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& c_std, const Fr& k_std, uint64_t first, uint8_t* out,
-                  uint8_t* out_be, PtauScaleStats* st) {
+                  uint8_t* out_be, ChunkStats* st) {
   return scale_device<FqOps>(device, in, n, c_std, k_std, first, out, out_be, st);
 }
 int ptau_scale_g2(int device, const uint8_t* in, uint64_t n, const Fr& c_std, const Fr& k_std, uint64_t first, uint8_t* out,
-                  uint8_t* out_be, PtauScaleStats* st) {
+                  uint8_t* out_be, ChunkStats* st) {
   return scale_device<Fq2Ops>(device, in, n, c_std, k_std, first, out, out_be, st);
 }
 

@@ -475,7 +475,7 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
 
   // device: sections 8 and 9 times 1 / d
   const Fr dinv = fp_from_mont(fp_inv(fp_to_mont(d)));
-  ZkeyScaleStats st[2];
+  ChunkStats st[2];
   int rc = zkey_scale_g1(device, k.f.sec[8].p, k.f.sec[8].size / 64, dinv, sp[8], &st[0]);
   if (!rc) rc = zkey_scale_g1(device, k.f.sec[9].p, k.f.sec[9].size / 64, dinv, sp[9], &st[1]);
   if (rc) { free(z.p); return rc; }

@@ -28,15 +28,13 @@
 // are handled), so no argument about k or the order of the inputs is needed, and the affine result is unique: the
 // bytes equal the host's and the oracle's.
 //
-// A section of any size runs in chunks of kChunk points through two buffer sets: the copies of chunk c + 1 (up) and
-// c - 1 (down) go over a second stream while chunk c computes, and the device never holds more than two chunks.
+// A section of any size runs in chunks (G16_CONTRIBUTE_CHUNK) through the pipeline of chunk_pipeline.h.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
 #include <algorithm>
-#include <vector>
 
 #include "binfile.h"
+#include "chunk_pipeline.h"
 #include "ec.cuh"
 #include "internal.h"
 #include "setup_affine.cuh"
@@ -49,7 +47,6 @@ constexpr int kWinMax = 5;
 constexpr int table_entries(int w) { return 1 << (w - 2); }   // entries e = 0 .. hold (2e + 1) P
 constexpr int kMaxDigits = 256;
 constexpr int kScaleBlock = 256;
-constexpr uint32_t kChunk = 1u << 18;             // points per chunk: 16 MB up, 32 MB XYZZ, 16 MB down
 
 struct ScaleDigits {
   int32_t top;                 // position of the highest non-zero digit (always positive)
@@ -127,138 +124,38 @@ __global__ __launch_bounds__(kScaleBlock) void zkey_scale_kernel(const G1Affine*
   }
 }
 
-uint32_t env_u32(const char* name) {
-  const char* e = getenv(name);
-  if (!e) return 0;
-  const long v = atol(e);
-  return v > 0 ? (uint32_t)std::min<long>(v, 1l << 30) : 0;
-}
-
 }  // namespace
 
-int zkey_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& k_std, uint8_t* out, ZkeyScaleStats* st) {
+int zkey_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& k_std, uint8_t* out, ChunkStats* st) {
   if (fp_is_zero(k_std) || !fr_below_modulus(k_std.v)) { set_error("zkey scale: the multiplier is not in [1, r)"); return G16_E_ARG; }
   if (const int rc = require_hip_device("zkey scale", device)) return rc;
-  if (st) *st = ZkeyScaleStats{};
+  if (st) *st = ChunkStats{};
   if (n == 0) return G16_OK;
   G16_HIP(hipSetDevice(device));
   hipDeviceProp_t prop;
   G16_HIP(hipGetDeviceProperties(&prop, device));
   int win = (int)env_u32("G16_CONTRIBUTE_WINDOW");
   if (win < 3 || win > kWinMax) win = kWin;
-  const int ntbl = table_entries(win);
   ScaleDigits dg;
   recode(k_std, win, dg);
+  const ChunkPlan plan = chunk_plan("G16_CONTRIBUTE_CHUNK", "G16_CONTRIBUTE_LANES", n,
+                                    (uint32_t)std::max(prop.multiProcessorCount, 1) * 4 * kScaleBlock);
 
-  // chunk and persistent grid (both overridable, so that a small test runs several chunks and grid-stride passes)
-  uint32_t chunk = env_u32("G16_CONTRIBUTE_CHUNK");
-  if (!chunk) chunk = kChunk;
-  chunk = (uint32_t)std::min<uint64_t>(chunk, n);
-  const uint32_t lanes_cap = (uint32_t)std::max(prop.multiProcessorCount, 1) * 4 * kScaleBlock;
-  uint32_t lanes = env_u32("G16_CONTRIBUTE_LANES");
-  uint32_t block = kScaleBlock;
-  if (lanes) {
-    lanes = std::min((lanes + 63) / 64 * 64, lanes_cap);
-    if (lanes % kScaleBlock) block = 64;
-  } else {
-    lanes = lanes_cap;
-  }
-  lanes = std::min(lanes, (chunk + block - 1) / block * block);
-  const uint32_t blocks = lanes / block;
-  const uint64_t nchunks = (n + chunk - 1) / chunk;
-
-  G1Affine* d_in[2] = {nullptr, nullptr};
-  G1Affine* d_aff[2] = {nullptr, nullptr};
-  G1XYZZ* d_work = nullptr;
-  G1XYZZ* d_tbl = nullptr;
-  int8_t* d_digits = nullptr;
-  hipStream_t cst = nullptr, xst = nullptr;   // compute, copies
-  hipEvent_t ev_up[2] = {}, ev_k[2] = {}, ev_down[2] = {};
-  std::vector<hipEvent_t> tk(2 * nchunks, nullptr), tx(4 * nchunks, nullptr);   // timing: kernel / copy begin-end pairs
-  int rc = G16_OK;
-  auto fail = [&](hipError_t e) {
-    if (e == hipSuccess) return false;
-    set_error(std::string("zkey scale (device): ") + hipGetErrorString(e));
-    rc = G16_E_HIP;
-    return true;
-  };
-  auto upload = [&](uint64_t c) {
-    const int b = (int)(c & 1);
-    const uint64_t lo = c * chunk, cnt = std::min<uint64_t>(chunk, n - lo);
-    // the buffer's last reader (the kernel of chunk c - 2) has finished
-    if (c >= 2 && fail(hipStreamWaitEvent(xst, ev_k[b], 0))) return false;
-    if (fail(hipEventRecord(tx[4 * c], xst))) return false;
-    if (fail(hipMemcpyAsync(d_in[b], in + lo * 64, cnt * 64, hipMemcpyHostToDevice, xst))) return false;
-    if (fail(hipEventRecord(tx[4 * c + 1], xst))) return false;
-    return !fail(hipEventRecord(ev_up[b], xst));
-  };
-  do {
-    if (fail(hipStreamCreateWithFlags(&cst, hipStreamNonBlocking)) || fail(hipStreamCreateWithFlags(&xst, hipStreamNonBlocking))) break;
-    bool bad = false;
-    for (int b = 0; b < 2 && !bad; b++)
-      bad = fail(hipEventCreateWithFlags(&ev_up[b], hipEventDisableTiming)) ||
-            fail(hipEventCreateWithFlags(&ev_k[b], hipEventDisableTiming)) ||
-            fail(hipEventCreateWithFlags(&ev_down[b], hipEventDisableTiming));
-    for (auto& e : tk) if (!bad) bad = fail(hipEventCreate(&e));
-    for (auto& e : tx) if (!bad) bad = fail(hipEventCreate(&e));
-    if (bad) break;
-    const int nbuf = nchunks > 1 ? 2 : 1;
-    for (int b = 0; b < nbuf && !bad; b++)
-      bad = fail(hipMalloc(&d_in[b], (size_t)chunk * sizeof(G1Affine))) || fail(hipMalloc(&d_aff[b], (size_t)chunk * sizeof(G1Affine)));
-    if (bad) break;
-    if (fail(hipMalloc(&d_work, (size_t)chunk * sizeof(G1XYZZ)))) break;
-    if (fail(hipMalloc(&d_tbl, (size_t)lanes * ntbl * sizeof(G1XYZZ)))) break;
-    if (fail(hipMalloc(&d_digits, sizeof(dg.d)))) break;
-    if (fail(hipMemcpyAsync(d_digits, dg.d, sizeof(dg.d), hipMemcpyHostToDevice, xst))) break;   // (before ev_up of chunk 0)
-    if (!upload(0)) break;
-    for (uint64_t c = 0; c < nchunks; c++) {
-      const int b = (int)(c & 1);
-      const uint64_t lo = c * chunk;
-      const uint32_t cnt = (uint32_t)std::min<uint64_t>(chunk, n - lo);
-      if (c + 1 < nchunks && !upload(c + 1)) break;
-      if (fail(hipStreamWaitEvent(cst, ev_up[b], 0))) break;
-      if (c >= 2 && fail(hipStreamWaitEvent(cst, ev_down[b], 0))) break;   // d_aff[b] has been copied out
-      if (fail(hipEventRecord(tk[2 * c], cst))) break;
-      const uint32_t grid = std::min(blocks, (cnt + block - 1) / block);
-      if (win == 3) zkey_scale_kernel<3><<<grid, block, 0, cst>>>(d_in[b], d_work, cnt, d_digits, dg.top, d_tbl);
-      else if (win == 5) zkey_scale_kernel<5><<<grid, block, 0, cst>>>(d_in[b], d_work, cnt, d_digits, dg.top, d_tbl);
-      else zkey_scale_kernel<4><<<grid, block, 0, cst>>>(d_in[b], d_work, cnt, d_digits, dg.top, d_tbl);
-      setup_to_affine_kernel<FqOps><<<((cnt + kBatch - 1) / kBatch + 255) / 256, 256, 0, cst>>>(d_work, d_aff[b], cnt);
-      if (fail(hipGetLastError())) break;
-      if (fail(hipEventRecord(tk[2 * c + 1], cst)) || fail(hipEventRecord(ev_k[b], cst))) break;
-      if (fail(hipStreamWaitEvent(xst, ev_k[b], 0))) break;
-      if (fail(hipEventRecord(tx[4 * c + 2], xst))) break;
-      if (fail(hipMemcpyAsync(out + lo * 64, d_aff[b], (size_t)cnt * 64, hipMemcpyDeviceToHost, xst))) break;
-      if (fail(hipEventRecord(tx[4 * c + 3], xst)) || fail(hipEventRecord(ev_down[b], xst))) break;
-    }
-    if (rc) break;
-    if (fail(hipStreamSynchronize(xst)) || fail(hipStreamSynchronize(cst))) break;
-    if (st) {
-      for (uint64_t c = 0; c < nchunks; c++) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, tk[2 * c], tk[2 * c + 1]) == hipSuccess) st->kern_ms += ms;
-        for (int h = 0; h < 2; h++)
-          if (hipEventElapsedTime(&ms, tx[4 * c + 2 * h], tx[4 * c + 2 * h + 1]) == hipSuccess) st->xfer_ms += ms;
-      }
-      st->points = n;
-    }
-  } while (false);
-  if (xst) (void)hipStreamSynchronize(xst);
-  if (cst) (void)hipStreamSynchronize(cst);
-  for (int b = 0; b < 2; b++) {
-    hipEvent_t evs[3] = {ev_up[b], ev_k[b], ev_down[b]};
-    for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-    if (d_in[b]) (void)hipFree(d_in[b]);
-    if (d_aff[b]) (void)hipFree(d_aff[b]);
-  }
-  for (hipEvent_t e : tk) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : tx) if (e) (void)hipEventDestroy(e);
-  if (d_work) (void)hipFree(d_work);
-  if (d_tbl) (void)hipFree(d_tbl);
-  if (d_digits) (void)hipFree(d_digits);
-  if (xst) (void)hipStreamDestroy(xst);
-  if (cst) (void)hipStreamDestroy(cst);
-  return rc;
+  DeviceBuf<G1XYZZ> work, tbl;
+  DeviceBuf<int8_t> digits;
+  ChunkPipeline pipe("zkey scale");
+  if (!pipe.open(n, plan.chunk, sizeof(G1Affine), sizeof(G1Affine), 0) || pipe.fail(work.alloc(plan.chunk)) ||
+      pipe.fail(tbl.alloc((size_t)plan.lanes * table_entries(win))) || pipe.fail(digits.alloc(sizeof(dg.d))) ||
+      pipe.fail(hipMemcpyAsync(digits.p, dg.d, sizeof(dg.d), hipMemcpyHostToDevice, pipe.stream())))
+    return pipe.rc();
+  return pipe.run(in, out, nullptr, st, [&](hipStream_t s, const uint8_t* d_in, uint8_t* d_out, uint8_t*, uint32_t cnt, uint64_t) {
+    const G1Affine* pts = (const G1Affine*)d_in;
+    const uint32_t grid = plan.grid(cnt), block = plan.block;
+    if (win == 3) zkey_scale_kernel<3><<<grid, block, 0, s>>>(pts, work.p, cnt, digits.p, dg.top, tbl.p);
+    else if (win == 5) zkey_scale_kernel<5><<<grid, block, 0, s>>>(pts, work.p, cnt, digits.p, dg.top, tbl.p);
+    else zkey_scale_kernel<4><<<grid, block, 0, s>>>(pts, work.p, cnt, digits.p, dg.top, tbl.p);
+    setup_to_affine_kernel<FqOps><<<((cnt + kBatch - 1) / kBatch + 255) / 256, 256, 0, s>>>(work.p, (G1Affine*)d_out, cnt);
+  });
 }
 
 }  // namespace g16

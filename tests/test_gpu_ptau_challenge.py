@@ -67,14 +67,19 @@ def points():
     return out
 
 
-@pytest.mark.parametrize("small", [False, True], ids=["default", "chunk37_lanes64"])
+@pytest.mark.parametrize("env,count", [({}, 603), ({"G16_PTAU_CHUNK": "37", "G16_PTAU_LANES": "64"}, 603),
+                                       ({"G16_PTAU_CHUNK": "603"}, 603), ({"G16_PTAU_CHUNK": "201"}, 603),
+                                       ({"G16_PTAU_CHUNK": "302"}, 603), ({"G16_PTAU_CHUNK": "1"}, 5)],
+                         ids=["default", "chunk37_lanes64", "chunk603", "chunk201", "chunk302", "first5_chunk1"])
 @pytest.mark.parametrize("group", [1, 2])
-def test_compress_then_decompress_is_the_identity_and_the_twin(amd, points, group, small, monkeypatch):
-    """603 points: with chunks of 37 on 64 lanes, 16 full chunks and a tail of 11, every chunk ending mid-wavefront."""
-    if small:
-        monkeypatch.setenv("G16_PTAU_CHUNK", "37")
-        monkeypatch.setenv("G16_PTAU_LANES", "64")
-    p = points[group]
+def test_compress_then_decompress_is_the_identity_and_the_twin(amd, points, group, env, count, monkeypatch):
+    """603 points: with chunks of 37 on 64 lanes, 16 full chunks and a tail of 11, every chunk ending mid-wavefront.  The
+    chunk-count edges of the two buffer sets: chunks of 603, one full chunk on a single set; of 201, three full chunks
+    without a tail, the first reuse of set 0; of 302, two chunks (302 + 301) and no reuse; the first five points one to
+    a chunk, every set reused twice."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    p = {k: v[:count] for k, v in points[group].items()}
     lem = b"".join(p["lem"])
     comp, bad, _ = amd.ptau_points_compress(group, lem)
     assert bad == -1 and comp == b"".join(p["comp"])

@@ -75,10 +75,12 @@ def default_runs(amd):
     return {p: amd.ptau_contribute(amd.ptau_new(p), "x", _secret(60 + p), device=0) for p in (6, 12)}
 
 
-@pytest.mark.parametrize("window", [3, 4, 5])
-def test_small_chunks_and_grids_change_no_byte(amd, default_runs, monkeypatch, window):
-    """Power 6, chunks of 37 points on 64 lanes: section 2's 127 points end a chunk mid-wavefront (127 = 3 x 37 + 16)."""
-    monkeypatch.setenv("G16_PTAU_CHUNK", "37")
+@pytest.mark.parametrize("window,chunk", [(3, 37), (4, 37), (5, 37), (5, 64), (5, 32)], ids=["3", "4", "5", "5-chunk64", "5-chunk32"])
+def test_small_chunks_and_grids_change_no_byte(amd, default_runs, monkeypatch, window, chunk):
+    """Power 6, chunks of 37 points on 64 lanes: section 2's 127 points end a chunk mid-wavefront (127 = 3 x 37 + 16).
+    Chunks of 64 and of 32: the 64 points of sections 3-5 are exactly one and exactly two full chunks, section 2 is
+    64 + 63 and 3 x 32 + 31."""
+    monkeypatch.setenv("G16_PTAU_CHUNK", str(chunk))
     monkeypatch.setenv("G16_PTAU_LANES", "64")
     monkeypatch.setenv("G16_PTAU_WINDOW", str(window))
     assert amd.ptau_contribute(amd.ptau_new(6), "x", _secret(66), device=0) == default_runs[6]

@@ -137,11 +137,13 @@ def test_unused_private_wire_stays_infinity(amd):
 
 
 @pytest.mark.parametrize("env", [{"G16_CONTRIBUTE_LANES": "192"},
-                                 {"G16_CONTRIBUTE_LANES": "64", "G16_CONTRIBUTE_CHUNK": "200"}],
-                         ids=["lanes192", "lanes64_chunk200"])
+                                 {"G16_CONTRIBUTE_LANES": "64", "G16_CONTRIBUTE_CHUNK": "200"},
+                                 {"G16_CONTRIBUTE_LANES": "64", "G16_CONTRIBUTE_CHUNK": "243"}],
+                         ids=["lanes192", "lanes64_chunk200", "lanes64_chunk243"])
 def test_grid_stride_passes_and_chunks_give_the_same_bytes(amd, monkeypatch, env):
     """486 + 512 points on 192 lanes: six grid-stride passes with a ragged tail; on 64 lanes in chunks of 200 points:
-    three chunks per section over the two buffer sets, the last one short."""
+    three chunks per section over the two buffer sets, the last one short; in chunks of 243: section 8 is exactly two full
+    chunks, section 9 two and a tail of 26."""
     c = _case(amd, "large")
     whole, _ = amd.zkey_contribute(c["init"], "first", D1, S, device=0)
     for k, v in env.items():
