@@ -591,6 +591,45 @@ int g16_plonk_verifier_create(const uint8_t* vkey, size_t vkey_len, int device, 
 int g16_plonk_verify_batch(g16_plonk_verifier* v, const g16_plonk_proof* proofs, const uint8_t* pubs, size_t count, uint8_t* ok);
 void g16_plonk_verifier_destroy(g16_plonk_verifier* v);
 
+/* `snarkjs wtns check <circuit.r1cs> <witness.wtns>` of later snarkjs releases (the pinned 0.4.12 has none, so nothing here
+ * is compared with snarkjs; the oracle is big-integer arithmetic over the R1CS): does the witness w satisfy
+ * (A_i.w)(B_i.w) = C_i.w in Fr for every constraint row i, and if not, where does it break?  bn128 only.
+ * One checker = one .r1cs (iden3 v1, what g16_r1cs_setup reads; here a file with 0 constraints is accepted and every
+ * witness of the right length passes), its three matrices resident on `device` (csrc/wtns_check.hip: one launch forms the
+ * three sparse row sums of every row and writes only the verdict), or device = -1: host threads (at most 16), the route
+ * that needs no GPU.  A device >= 0 without one: G16_E_NOGPU.  Not thread-safe: one call at a time per checker.
+ * AN UNSATISFIED WITNESS IS A VERDICT, NOT AN ERROR: G16_OK, constraint = the lowest failing row, n_failed = how many rows
+ * fail, a, b, c = the standard-form little-endian values A.w, B.w, C.w of that row, and g16_last_error() =
+ * "wtns check: constraint I is not satisfied (N in all)" (the convention of g16_ptau_verify).  Every failing row a device
+ * run reports is recomputed on the host, which fills a, b, c; should the host find that row satisfied the call returns
+ * G16_E_STATE and says so: a device verdict is never reported unconfirmed.
+ * A MALFORMED INPUT IS AN ERROR (G16_E_FORMAT), checked before the device is touched: for the .r1cs the texts of
+ * g16_r1cs_setup ("r1cs: ..."); for the witness those of g16_prove -- "wtns: Invalid File format", "Version not
+ * supported", "wtns: Missing section N", "Curve of the witness does not match the curve of the proving key", "Invalid
+ * witness length. Circuit: X, witness: Y", "wtns: signal K is not reduced modulo the scalar field" -- and "wtns check:
+ * signal 0 is not 1".
+ * g16_wtns_check_batch: `count` witnesses of one circuit, one verdict each.  A malformed witness fails the whole call, its
+ * text led by "witness K: " (the lowest such K); with unsatisfied witnesses g16_last_error() is the verdict text of the
+ * first of them, led the same way.  On the device the batch runs in chunks of several witnesses per launch; a witness
+ * takes 72 bytes per wire there (its 32-byte words and their 40-byte Montgomery images), a chunk as many witnesses as
+ * 256 MB hold, at least one and at most 1024 -- the device memory of a checker does not grow with `count`.
+ * G16_WTNS_CHECK_CHUNK=<witnesses> (read at create) overrides the chunk size.
+ * g16_wtns_check_files: both files mapped read-only, a checker made for the one call.
+ * g16_r1cs_checker_timings: device time of the last call's uploads and of its kernels, all chunks (zero on the host route). */
+typedef struct g16_r1cs_checker g16_r1cs_checker;
+typedef struct {
+  int64_t constraint;           /* -1: every constraint holds */
+  uint32_t n_failed;
+  uint8_t a[32], b[32], c[32];  /* standard-form LE values of row `constraint`; zero when it is -1 */
+} g16_wtns_verdict;
+int g16_r1cs_checker_create(const uint8_t* r1cs, size_t len, int device /* -1 = host threads */, g16_r1cs_checker** out);
+int g16_wtns_check(g16_r1cs_checker* k, const uint8_t* wtns, size_t len, g16_wtns_verdict* out);
+int g16_wtns_check_batch(g16_r1cs_checker* k, const uint8_t* const* wtns, const size_t* lens, size_t count,
+                         g16_wtns_verdict* out);
+int g16_wtns_check_files(const char* r1cs_path, const char* wtns_path, int device, g16_wtns_verdict* out);
+int g16_r1cs_checker_timings(const g16_r1cs_checker* k, float ms[2]);
+void g16_r1cs_checker_destroy(g16_r1cs_checker* k);
+
 #ifdef __cplusplus
 }
 #endif

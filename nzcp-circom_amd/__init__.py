@@ -43,6 +43,11 @@ class PlonkProof(C.Structure):
                 [("Wxi", C.c_uint8 * 64), ("Wxiw", C.c_uint8 * 64)])
 
 
+class WtnsVerdictC(C.Structure):
+    _fields_ = [("constraint", C.c_int64), ("n_failed", C.c_uint32), ("a", C.c_uint8 * 32), ("b", C.c_uint8 * 32),
+                ("c", C.c_uint8 * 32)]
+
+
 class Info(C.Structure):
     _fields_ = [("n_vars", C.c_uint32), ("n_public", C.c_uint32), ("domain_size", C.c_uint32),
                 ("n_coefs", C.c_uint32), ("n_a", C.c_uint32), ("n_b1", C.c_uint32),
@@ -76,7 +81,9 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_ptau_verify_file", "g16_ptau_secret_from_text",
            "g16_ptau_export_challenge", "g16_ptau_export_challenge_files", "g16_ptau_challenge_contribute",
            "g16_ptau_challenge_contribute_files", "g16_ptau_import_response", "g16_ptau_import_response_files",
-           "g16_ptau_points_from_be", "g16_ptau_points_compress", "g16_ptau_points_decompress", "g16_fq_sqrt_batch"]
+           "g16_ptau_points_from_be", "g16_ptau_points_compress", "g16_ptau_points_decompress", "g16_fq_sqrt_batch",
+           "g16_r1cs_checker_create", "g16_wtns_check", "g16_wtns_check_batch", "g16_wtns_check_files",
+           "g16_r1cs_checker_timings", "g16_r1cs_checker_destroy"]
 
 
 def load():
@@ -179,6 +186,13 @@ def load():
     lib.g16_ptau_points_compress.argtypes = [C.c_int, C.c_char_p, sz, C.c_int, C.c_char_p, i64p, f32p]
     lib.g16_ptau_points_decompress.argtypes = [C.c_int, C.c_char_p, sz, C.c_int, C.c_char_p, C.c_char_p, i64p, f32p]
     lib.g16_fq_sqrt_batch.argtypes = [C.c_int, C.c_char_p, sz, C.c_int, C.c_char_p, C.c_char_p]
+    lib.g16_r1cs_checker_create.argtypes = [C.c_char_p, sz, C.c_int, C.POINTER(vp)]
+    lib.g16_wtns_check.argtypes = [vp, C.c_char_p, sz, C.POINTER(WtnsVerdictC)]
+    lib.g16_wtns_check_batch.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.POINTER(WtnsVerdictC)]
+    lib.g16_wtns_check_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(WtnsVerdictC)]
+    lib.g16_r1cs_checker_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.g16_r1cs_checker_destroy.argtypes = [vp]
+    lib.g16_r1cs_checker_destroy.restype = None
     lib.g16_blake2b512.argtypes = [C.c_char_p, sz, C.c_char_p]
     lib.g16_zkey_hash_to_g2.argtypes = [C.c_char_p, C.c_char_p]
     lib.g16_r1cs_setup.argtypes = [C.c_char_p, sz, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
@@ -317,6 +331,84 @@ class Prover:
         return {"upload_ms": t.upload_ms, "qap_ms": t.qap_ms, "ntt_ms": t.ntt_ms,
                 "msm_ms": list(t.msm_ms), "tail_ms": t.tail_ms, "total_ms": t.total_ms,
                 "msm_accum_kernel_ms": list(t.msm_accum_kernel_ms)}
+
+
+class WtnsVerdict:
+    """Verdict of a witness check: ok; constraint = the lowest failing row (-1: none); n_failed = how many rows fail;
+    a, b, c = the values A.w, B.w, C.w of that row (ints; 0 when ok); reason = the library's text for a failure."""
+
+    def __init__(self, v, reason=""):
+        self.constraint, self.n_failed = int(v.constraint), int(v.n_failed)
+        self.ok = self.constraint < 0
+        self.a, self.b, self.c = (int.from_bytes(bytes(x), "little") for x in (v.a, v.b, v.c))
+        self.reason = "" if self.ok else reason
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("ok", "constraint", "n_failed", "a", "b", "c")}
+
+    def __repr__(self):
+        return f"WtnsVerdict({self.as_dict()})"
+
+
+def _verdict_text(v):
+    return f"wtns check: constraint {v.constraint} is not satisfied ({v.n_failed} in all)"
+
+
+class R1csChecker:
+    """Resident .r1cs for witness checks (g16_wtns_check): device = a HIP device ordinal, or -1 = host threads."""
+
+    def __init__(self, r1cs, device=0):
+        lib = load()
+        if isinstance(r1cs, (str, os.PathLike)):
+            with open(r1cs, "rb") as f:
+                r1cs = f.read()
+        self._h = C.c_void_p()
+        _check(lib.g16_r1cs_checker_create(r1cs, len(r1cs), device, C.byref(self._h)))
+
+    @staticmethod
+    def _bytes(wtns):
+        if isinstance(wtns, (str, os.PathLike)):
+            with open(wtns, "rb") as f:
+                return f.read()
+        return bytes(wtns)
+
+    def check(self, wtns):
+        """-> WtnsVerdict; a malformed witness raises G16Error with g16_prove's texts."""
+        wtns = self._bytes(wtns)
+        v = WtnsVerdictC()
+        _check(load().g16_wtns_check(self._h, wtns, len(wtns), C.byref(v)))
+        return WtnsVerdict(v, _verdict_text(v))
+
+    def check_batch(self, wtns_list):
+        """One verdict per witness; a malformed witness K fails the whole call ("witness K: ...")."""
+        ws = [self._bytes(w) for w in wtns_list]
+        n = len(ws)
+        ptrs = (C.c_char_p * max(1, n))(*ws)
+        lens = (C.c_size_t * max(1, n))(*[len(w) for w in ws])
+        out = (WtnsVerdictC * max(1, n))()
+        _check(load().g16_wtns_check_batch(self._h, ptrs, lens, n, out))
+        return [WtnsVerdict(out[i], _verdict_text(out[i])) for i in range(n)]
+
+    def timings(self):
+        ms = (C.c_float * 2)()
+        _check(load().g16_r1cs_checker_timings(self._h, ms))
+        return {"upload_ms": ms[0], "kernel_ms": ms[1]}
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            load().g16_r1cs_checker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+def wtns_check(r1cs, wtns, device=0):
+    """`snarkjs wtns check circuit.r1cs witness.wtns` (later snarkjs; bytes or paths) -> WtnsVerdict."""
+    k = R1csChecker(r1cs, device)
+    try:
+        return k.check(wtns)
+    finally:
+        k.close()
 
 
 class MultiProver:

@@ -55,7 +55,7 @@ Buf write_r1cs(const Circuit& c, uint32_t n_pub_out, uint32_t n_pub_in) {
 // iden3 r1cs v1: section 1 header {n8, prime, nWires, nPubOut, nPubIn, nPrvIn, nLabels u64,
 // nConstraints}, section 2 constraints: A, B, C each {nTerms u32, nTerms x (wireId u32, coef n8 LE)}.
 // nPublic of the zkey = nPubOut + nPubIn ([EXT] r1csfile 0.0.35, pin /root/reference/yarn.lock:909-917).
-int read_r1cs(const uint8_t* buf, size_t len, Circuit& c) {
+int read_r1cs(const uint8_t* buf, size_t len, Circuit& c, bool allow_empty) {
   auto bad = [](const char* why) { set_error(std::string("r1cs: ") + why); return G16_E_FORMAT; };
   BinView f;
   BinFault why;
@@ -73,7 +73,7 @@ int read_r1cs(const uint8_t* buf, size_t len, Circuit& c) {
   memcpy(&nPrvIn, s1 + 48, 4); memcpy(&nCons, s1 + 60, 4);
   (void)nPrvIn;
   c.n = nWires; c.p = nPubOut + nPubIn; c.m = nCons;
-  if (c.n < c.p + 1 || c.m == 0 || (uint64_t)nPubOut + nPubIn >= nWires) return bad("inconsistent header");
+  if (c.n < c.p + 1 || (c.m == 0 && !allow_empty) || (uint64_t)nPubOut + nPubIn >= nWires) return bad("inconsistent header");
   // an untrusted header must not size the allocations: every constraint takes >= 12 bytes of section 2, and a wire
   // that appears nowhere still has its 8-byte entry in the wire map (section 3) when the file carries one
   if ((uint64_t)nCons * 12 > l2) return bad("constraint count exceeds the constraint section");

@@ -70,7 +70,8 @@ struct Circuit {
 };
 
 int g16_domain_log(const Circuit& c);   // smallest L with 2^L >= m + p + 1
-int read_r1cs(const uint8_t* buf, size_t len, Circuit& c);
+// (allow_empty: a file without constraints is read, for the witness checker; every setup route refuses it)
+int read_r1cs(const uint8_t* buf, size_t len, Circuit& c, bool allow_empty = false);
 Buf write_r1cs(const Circuit& c, uint32_t n_pub_out, uint32_t n_pub_in);
 Buf write_wtns(const std::vector<FrM>& w);   // w in Montgomery form
 

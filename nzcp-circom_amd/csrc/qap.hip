@@ -11,8 +11,7 @@
 // (coef * 2^522), and the sums are lazy (fr29.cuh).
 #include <stdlib.h>
 
-#include "fr29.cuh"
-#include "internal.h"
+#include "qap_rows.cuh"
 
 namespace g16 {
 
@@ -23,32 +22,6 @@ __device__ __forceinline__ void qap_set_prio() {
   if (p == 1) __builtin_amdgcn_s_setprio(1);
   else if (p == 2) __builtin_amdgcn_s_setprio(2);
   else if (p >= 3) __builtin_amdgcn_s_setprio(3);
-}
-
-// One matrix as the kernel sees it, and the sum of one row's records [k0, k1) taken with stride `step` from lane offset `lane`:
-// the +-1 records add or subtract the Montgomery image of their witness word (a 40-byte gather and nine limb additions instead
-// of a repack and a 229-instruction product: r03, 79 % of the records), the general ones multiply.  Lazy sums: an added term is
-// below 1.1r, a subtracted one adds 2r - x <= 2r; a weak reduction (-> 1.0001r) whenever seven units have gone in keeps the
-// sum below 1 + 6 * 1.1 + 2 = 9.6r < 16r.
-struct QapMat { const uint32_t *rp, *mid, *vptr, *col; const F29* val; };
-__device__ __forceinline__ F29 qap_row_sum(const QapMat& M, uint32_t c, uint32_t lane, uint32_t step,
-                                            const Fr* __restrict__ w, const F29* __restrict__ wm) {
-  F29 s = f29_zero();
-  uint32_t cnt = 0;
-  const uint32_t k0 = M.rp[c], km = M.mid[c], k1 = M.rp[c + 1];
-  for (uint32_t k = k0 + lane; k < km; k += step) {
-    const uint32_t ci = M.col[k];
-    const F29 x = wm[ci & 0x7fffffffu];
-    if (ci >> 31) { s = fr29_sub<2>(s, x); cnt += 2; }
-    else { s = fr29_add(s, x); cnt += 1; }
-    if (cnt >= 7) { s = fr29_weak_reduce(s); cnt = 0; }
-  }
-  const uint32_t vp = M.vptr[c];
-  for (uint32_t k = km + lane; k < k1; k += step) {
-    s = fr29_add(s, fr29_mul(M.val[vp + (k - km)], fr29_repack(w[M.col[k]])));
-    if (++cnt >= 7) { s = fr29_weak_reduce(s); cnt = 0; }
-  }
-  return s;
 }
 
 __device__ __forceinline__ void qap_eval_rows(uint32_t block, const QapMat& A, const QapMat& B, const Fr* __restrict__ w,
@@ -63,13 +36,6 @@ __device__ __forceinline__ void qap_eval_rows(uint32_t block, const QapMat& A, c
   cc[c] = fr29_mul(sa, sb);
 }
 
-__device__ __forceinline__ F29 f29_shfl_xor(const F29& v, int mask) {
-  F29 r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.l[i] = (uint32_t)__shfl_xor((int)v.l[i], mask, 64);
-  r.pad_ = 0;
-  return r;
-}
 // GW lanes per long row (GW = 64: a wavefront; GW = 8: eight rows per wavefront): lanes stride over the row's records,
 // partial sums meet in a log2(GW)-step __shfl_xor tree (weak-reduced on the way so they stay below 16r).
 // The real NZCP circuit has 48 k rows of 17-32 terms (and a single B term) beside its 2.5 k rows of 65-356 terms: with a

@@ -28,6 +28,8 @@
  *           ptauContributeFiles(inPath, outPath, name | null, secret Buffer(192) | null, device) -> Promise<Buffer(64)>
  *                                                                              (g16_ptau_contribute_files: the hash)
  *           ptauVerifyFile(path, device) -> Promise<{ok, reason}>              (g16_ptau_verify_file)
+ *           wtnsCheckFiles(r1csPath, wtnsPath, device) -> Promise<{constraint, nFailed, a, b, c}>  (g16_wtns_check_files;
+ *               constraint -1 = every constraint holds; a, b, c: Buffers of 32 bytes, little-endian)
  *           ptauExportChallengeFiles(ptauPath, challengePath) -> Promise<Buffer(64)>   (g16_ptau_export_challenge_files: the
  *                                                                              challenge hash)
  *           ptauChallengeContributeFiles(challengePath, responsePath, secret Buffer(192) | null, device) -> Promise<Buffer(64)>
@@ -1078,6 +1080,68 @@ static napi_value js_ptau_import_response_files(napi_env env, napi_callback_info
   return tjob_start(env, j, "g16_ptau_import_response_files");
 }
 
+/* wtns check from files: the verdict of g16_wtns_check_files (an unsatisfied witness resolves, a malformed file rejects) */
+typedef struct {
+  napi_async_work work;
+  napi_deferred deferred;
+  char a[1024], b[1024];
+  int device, rc;
+  g16_wtns_verdict v;
+  char err[512];
+} wjob_t;
+static void wjob_execute(napi_env env, void* data) {
+  wjob_t* j = (wjob_t*)data;
+  j->rc = g16_wtns_check_files(j->a, j->b, j->device, &j->v);
+  if (j->rc) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
+}
+static void wjob_complete(napi_env env, napi_status status, void* data) {
+  wjob_t* j = (wjob_t*)data;
+  if (status != napi_ok || j->rc) {
+    napi_value msg, err;
+    napi_create_string_utf8(env, status == napi_ok ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_reject_deferred(env, j->deferred, err);
+  } else {
+    napi_value obj, v;
+    napi_create_object(env, &obj);
+    napi_create_int64(env, j->v.constraint, &v);
+    napi_set_named_property(env, obj, "constraint", v);
+    napi_create_uint32(env, j->v.n_failed, &v);
+    napi_set_named_property(env, obj, "nFailed", v);
+    const uint8_t* vals[3] = {j->v.a, j->v.b, j->v.c};
+    const char* names[3] = {"a", "b", "c"};
+    for (int k = 0; k < 3; k++) {
+      void* copy = NULL;
+      napi_create_buffer_copy(env, 32, vals[k], &copy, &v);
+      napi_set_named_property(env, obj, names[k], v);
+    }
+    napi_resolve_deferred(env, j->deferred, obj);
+  }
+  napi_delete_async_work(env, j->work);
+  free(j);
+}
+static napi_value js_wtns_check_files(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  wjob_t* j = (wjob_t*)calloc(1, sizeof(wjob_t));
+  size_t n = 0;
+  if (argc < 2 || napi_get_value_string_utf8(env, argv[0], j->a, sizeof(j->a), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], j->b, sizeof(j->b), &n) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, "wtnsCheckFiles(r1csPath, wtnsPath, device)");
+    return NULL;
+  }
+  int32_t v = 0;
+  if (argc > 2 && napi_get_value_int32(env, argv[2], &v) == napi_ok) j->device = v;
+  napi_value promise, resname;
+  NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
+  NAPI_OK(napi_create_string_utf8(env, "g16_wtns_check_files", NAPI_AUTO_LENGTH, &resname));
+  NAPI_OK(napi_create_async_work(env, NULL, resname, wjob_execute, wjob_complete, j, &j->work));
+  NAPI_OK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"create", NULL, js_create, NULL, NULL, NULL, napi_default, NULL},
@@ -1103,6 +1167,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"ptauExportChallengeFiles", NULL, js_ptau_export_challenge_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauChallengeContributeFiles", NULL, js_ptau_challenge_contribute_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauImportResponseFiles", NULL, js_ptau_import_response_files, NULL, NULL, NULL, napi_default, NULL},
+      {"wtnsCheckFiles", NULL, js_wtns_check_files, NULL, NULL, NULL, napi_default, NULL},
   };
   NAPI_OK(napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props));
   return exports;

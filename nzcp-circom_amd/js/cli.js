@@ -22,6 +22,11 @@
 // `zkv` only: section 9 is not recomputed from it, and csHash is not snarkjs's (see INTEGRATION.md 5b).
 // And of `snarkjs groth16 verify <verification_key.json> <public.json> <proof.json>` (groth16Verify [EXT]): prints
 // "[INFO]  snarkJS: OK!" and exits 0, or "[ERROR] snarkJS: Invalid proof" and exits 1.
+// And of `snarkjs wtns check <circuit.r1cs> <witness.wtns>` (alias `wchk`) of LATER snarkjs releases -- the pinned 0.4.12
+// has none: prints "WITNESS IS CORRECT" and exits 0, or "[ERROR] snarkJS: WITNESS CHECKING FAILED", the lowest failing
+// constraint, how many fail and its three values A.w, B.w, C.w, and exits 1.  [--device n]: a GPU ordinal, -1 = host
+// threads.  `[groth16] prove ... --check <circuit.r1cs>` runs the same check first and stops with the same report and
+// exit status 1 before anything is written.  These texts are modelled on later snarkjs and not compared with it.
 "use strict";
 const fs = require("fs");
 const { groth16 } = require("./index.js");
@@ -32,6 +37,21 @@ async function main(argv) {
     const { exportVerificationKey } = require("./index.js");
     const [zk, out = "verification_key.json"] = a.slice(3);
     fs.writeFileSync(out, JSON.stringify(exportVerificationKey(zk), null, 1), "utf-8");
+    return;
+  }
+  if ((a[0] === "wtns" && a[1] === "check") || a[0] === "wchk") {
+    const rest = a.slice(a[0] === "wchk" ? 1 : 2);
+    const pos = [];
+    let device = 0;
+    for (let i = 0; i < rest.length; i++) {
+      if (rest[i] === "--device") device = parseInt(rest[++i], 10);
+      else if (!rest[i].startsWith("--")) pos.push(rest[i]);
+    }
+    if (pos.length < 2) { console.error("usage: cli.js wtns check <circuit.r1cs> <witness.wtns> [--device n]"); process.exit(2); }
+    const { wtns, wtnsCheckReport } = require("./index.js");
+    const v = await wtns.check(pos[0], pos[1], { device });
+    if (!v.ok) throw new Error(wtnsCheckReport(v));
+    console.log("WITNESS IS CORRECT");
     return;
   }
   if ((a[0] === "zkey" && a[1] === "contribute") || a[0] === "zkc") {
@@ -194,13 +214,19 @@ async function main(argv) {
     if (a[i] === "--r") opts.r = a[++i];
     else if (a[i] === "--s") opts.s = a[++i];
     else if (a[i] === "--device") opts.device = parseInt(a[++i], 10);
+    else if (a[i] === "--check") opts.check = a[++i];
     else pos.push(a[i]);
   }
   if (pos.length < 2) {
-    console.error("usage: cli.js [groth16] prove <circuit.zkey> <witness.wtns> [proof.json] [public.json] [--r dec --s dec --device n]");
+    console.error("usage: cli.js [groth16] prove <circuit.zkey> <witness.wtns> [proof.json] [public.json] [--r dec --s dec --device n --check circuit.r1cs]");
     process.exit(2);
   }
   const [zkey, wtns, proofFile = "proof.json", publicFile = "public.json"] = pos;
+  if (opts.check) {   // the witness against its circuit first: a bad one stops here, nothing is written
+    const { wtns: wt, wtnsCheckReport } = require("./index.js");
+    const v = await wt.check(opts.check, wtns, { device: opts.device });
+    if (!v.ok) throw new Error(wtnsCheckReport(v));
+  }
   const { proof, publicSignals } = await groth16.prove(zkey, wtns, opts);
   fs.writeFileSync(proofFile, JSON.stringify(proof, null, 1), "utf-8");
   fs.writeFileSync(publicFile, JSON.stringify(publicSignals, null, 1), "utf-8");

@@ -10,6 +10,7 @@
 // given the same blinding (r, s).  Errors are thrown Errors with snarkjs's messages.
 // groth16.verify(vk, publicSignals, proof) is snarkjs's too (GPU pairing check, csrc/verify.hip); createVerifier(vk)
 // keeps the key resident and verifies batches, one verdict per proof.
+// wtns.check(r1cs, wtns) is later snarkjs's witness check (csrc/wtns_check.hip): {ok, constraint, nFailed, a, b, c}.
 // Extensions (not in snarkjs): opts = {r, s, device, devices, windowBits}; groth16.createProver() keeps the
 // proving key resident in HBM across proofs; prover.proveBatch(wtnsList); createProver(zkey, {devices: [0, 1, ...]})
 // shards ONE proof over several GPUs of the node (BASELINE config 4: MSM point ranges + the A/B/C evaluation split
@@ -453,6 +454,25 @@ function exportVerificationKey(zkey) {
   throw new Error("zkey: unknown protocol");
 }
 
+// ------------------------------------------------------------------ wtns check
+// Later snarkjs releases: wtns.check(r1csFilename, wtnsFilename[, logger]) -> boolean / CLI `wtns check` (alias `wchk`);
+// the pinned 0.4.12 has none, and nothing here is compared with snarkjs.  Resolves to {ok, constraint, nFailed, a, b, c}:
+// constraint = the lowest failing row (-1: none), nFailed = how many rows fail, a, b, c = the values A.w, B.w, C.w of
+// that row as decimal strings ("0" when ok).  A malformed file rejects with the library's text.  opts.device: a GPU
+// ordinal (default 0) or -1 = host threads.
+const wtns = {
+  async check(r1csName, wtnsName, opts = {}) {
+    if (opts && typeof opts.debug === "function") opts = {};
+    const device = opts.device === undefined || opts.device === null ? 0 : opts.device | 0;
+    const v = await native().wtnsCheckFiles(String(r1csName), String(wtnsName), device);
+    return { ok: v.constraint < 0, constraint: v.constraint, nFailed: v.nFailed, a: dec(v.a, 0), b: dec(v.b, 0), c: dec(v.c, 0) };
+  },
+};
+// what the CLI prints for a failed check (modelled on later snarkjs, not compared with it)
+function wtnsCheckReport(v) {
+  return `WITNESS CHECKING FAILED\nconstraint ${v.constraint} is not satisfied (${v.nFailed} in all)\na = ${v.a}\nb = ${v.b}\nc = ${v.c}`;
+}
+
 const groth16 = {
   // snarkjs: groth16.verify(vk_verifier, publicSignals, proof[, logger]) -> boolean
   async verify(vk, publicSignals, proof, opts = {}) {
@@ -477,4 +497,4 @@ const groth16 = {
   createProver,
 };
 
-module.exports = { groth16, plonk, powersOfTau, zKey: { exportVerificationKey, newZKey, contribute, verifyFromInit }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
+module.exports = { groth16, plonk, powersOfTau, wtns, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, verifyFromInit }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
