@@ -219,17 +219,37 @@ def test_plonk_verifier_verdicts_equal_oracle(amd, n, p, m, seed):
     t["eval_b"] = str(int(t["eval_b"]) + b.R)      # evaluation given as value + r: reduced, still valid
     if int(t["eval_b"]) < (1 << 256):
         cases.append((pub0, t))
+    # every field matters: the evaluations, commitments and public signals the cases above leave alone.  A proof with
+    # one of them changed is rejected by the soundness of the protocol (no run of any code says so); on the small
+    # shape the oracle is asked about four of them as well.
+    sound = []
+    for key in ("eval_c", "eval_b", "eval_s1"):
+        t = copy.deepcopy(pr0)
+        t[key] = str((int(t[key]) + 1) % b.R)
+        sound.append((pub0, t))
+    for key in ("C", "T3", "B", "T1"):
+        t = copy.deepcopy(pr0)
+        assert t[key] != cases[1][1][key]
+        t[key] = list(cases[1][1][key])           # a valid point of another proof
+        sound.append((pub0, t))
+    for j in (range(p - 1) if p <= 5 else (0, 255, 256, p - 2)):
+        bad = list(pub0)
+        bad[j] = str((int(bad[j]) + 1) % b.R)
+        sound.append((bad, pr0))
     ver = amd.PlonkVerifier(_vk_json(zk))
-    got = ver.verify_batch(cases)
+    got = ver.verify_batch(cases + sound)
 
     def oracle(ps, po):
         try:
             return pk.verify(vk, [int(x) % b.R for x in ps], pk.proof_from_obj(po))
         except Exception:
             return False
-    exp = [oracle(ps, po) for ps, po in cases]
+    exp = [oracle(ps, po) for ps, po in cases] + [False] * len(sound)
     assert got == exp
+    if p == 5:
+        assert [oracle(ps, po) for ps, po in (sound[0], sound[1], sound[3], sound[4])] == [False] * 4
     assert got[:3] == [True, True, True] and not any(got[3:13])
+    assert not any(got[len(cases):]) and len(sound) == 7 + 4
     assert ver.verify(pub0, pr0) is True and ver.verify(pub0[:-1], pr0) is False
     t = copy.deepcopy(pr0)
     t["C"][1] = str(int(t["C"][1]) + b.Q)          # non-canonical coordinate: rejected (the oracle would reduce it)
@@ -239,6 +259,62 @@ def test_plonk_verifier_verdicts_equal_oracle(amd, n, p, m, seed):
     gp, gpub = prover.prove(f.write_wtns(w))
     prover.close()
     assert ver.verify(gpub, gp) is True
+    ver.close()
+
+
+@pytest.mark.parametrize("n,p,m,seed", [(24, 0, 12, 5), (24, 1, 12, 6)])
+def test_plonk_verifier_without_and_with_one_public_signal(amd, n, p, m, seed):
+    """nPublic = 0 (no Lagrange term of a public input, L_1 still needed) and 1: one valid proof, accepted by the oracle
+    as well, and the same proof with one evaluation + 1, rejected by the soundness of the protocol."""
+    import copy
+    rows, w = synth.make(n, p, m, seed)
+    zk = pk.setup(n, p, rows, tau=0xfeed + seed)
+    rng = synth.Xoshiro(seed + 3)
+    pr, pub = pk.prove(zk, w, {i: rng.rand_fr() for i in range(1, 10)})
+    assert len(pub) == p and pk.verify(pk.vkey(zk), [int(x) for x in pub], pr)
+    pub, po = [str(x) for x in pub], pk.proof_obj(pr)
+    cases = [(pub, po)]
+    for key in ("eval_a", "eval_r"):
+        t = copy.deepcopy(po)
+        t[key] = str((int(t[key]) + 1) % b.R)
+        cases.append((pub, t))
+    if p:
+        cases.append(([str((int(pub[0]) + 1) % b.R)], po))
+    cases.append((pub, po))
+    ver = amd.PlonkVerifier(_vk_json(zk))
+    got = ver.verify_batch(cases)
+    ver.close()
+    assert got == [True] + [False] * (len(cases) - 2) + [True]
+
+
+def test_plonk_batch_of_65_with_known_bad_indices(amd):
+    """65 proofs (3 distinct ones repeated), tampered at indices 0, 63 and 64: the tails of pv_terms_kernel (20 lanes per
+    proof: 1300 lanes, the last wavefront partial) and of the sum, Miller and final kernels (one full wavefront and one
+    lane).  The three proofs are the oracle prover's for valid witnesses; a tampered one is rejected by soundness."""
+    import copy
+    n, p, m, seed = 24, 2, 12, 1
+    rows, w = synth.make(n, p, m, seed)
+    zk = pk.setup(n, p, rows, tau=0xfeed + seed)
+    rng = synth.Xoshiro(seed + 3)
+    base = []
+    for k in range(3):
+        wk = w if k == 0 else synth.make(n, p, m, seed, 500 + k)[1]
+        pr, pub = pk.prove(zk, wk, {i: rng.rand_fr() for i in range(1, 10)})
+        base.append(([str(x) for x in pub], pk.proof_obj(pr)))
+    items = [base[i % 3] for i in range(65)]
+    for i, key in ((0, "eval_zw"), (63, "Z"), (64, "eval_c")):
+        pub, po = items[i]
+        t = copy.deepcopy(po)
+        if key == "Z":
+            t[key] = list(base[(i + 1) % 3][1][key])
+            assert t[key] != po[key]
+        else:
+            t[key] = str((int(t[key]) + 1) % b.R)
+        items[i] = (pub, t)
+    ver = amd.PlonkVerifier(_vk_json(zk))
+    got = ver.verify_batch(items)
+    assert got == [i not in (0, 63, 64) for i in range(65)]
+    assert ver.verify_batch(items[1:63]) == [True] * 62        # a smaller batch on the grown scratch
     ver.close()
 
 

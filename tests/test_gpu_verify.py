@@ -11,6 +11,7 @@ import bn254 as b
 import formats as f
 import groth16 as g
 import synth
+import verify_exponent_ref as ve
 from test_cpu_pairing import oracle_value, tower_to_poly
 
 pytestmark = pytest.mark.gpu
@@ -45,6 +46,76 @@ def test_pairing_value_on_device_equals_oracle(amd):
     a, c = rng.randrange(1, b.R), rng.randrange(1, b.R)
     v = amd.pairing_op([(b.G1.mul(b.G1_GEN, a), b.G2.mul(b.G2_GEN, c)), (b.G1.mul(b.G1_GEN, a * c % b.R), b.G2_GEN)] * 32)
     assert all(x == v[0] for x in v)
+
+
+def test_pairing_identities_between_device_values(amd):
+    """Identities every pairing satisfies, between values the device computed (compared through tower_to_poly with
+    oracle/bn254.py's Fq12 product; no Python Miller loop): e(-P, Q) e(P, Q) = 1, additivity in either argument,
+    e(P, Q)^r = 1 and e(P, Q) != 1."""
+    rng = random.Random(0x9a1)
+    p1, p2, q1, q2 = (rng.randrange(1, b.R) for _ in range(4))
+    P1, P2, P12 = ve.g1_points([p1, p2, p1 + p2])
+    Q1, Q2, Q12 = ve.g2_points([q1, q2, q1 + q2])
+    pairs = [(P1, Q1), (b.G1.neg(P1), Q1), (P2, Q1), (P12, Q1), (P1, Q2), (P1, Q12)]
+    e, e_neg, e_p2, e_p12, e_q2, e_q12 = (tower_to_poly(v) for v in amd.pairing_op(pairs))
+    assert e != b.F12_ONE and e_neg != e
+    assert b.f12_mul(e_neg, e) == b.F12_ONE
+    assert b.f12_mul(e, e_p2) == e_p12
+    assert b.f12_mul(e, e_q2) == e_q12
+    assert b.f12_pow(e, b.R) == b.F12_ONE
+    assert b.f12_pow(e_q12, b.R) == b.F12_ONE
+
+
+def test_pairing_op_grid_tails(amd):
+    """1, 63, 65 and 130 pairs drawn from 5 distinct ones: a partial wavefront alone, beside one and two full ones; every
+    output is the value the same pair has in a 5-pair call."""
+    rng = random.Random(0x7a1)
+    five = list(zip(ve.g1_points([rng.randrange(1, b.R) for _ in range(5)]), ve.g2_points([rng.randrange(1, b.R) for _ in range(5)])))
+    ref = amd.pairing_op(five)
+    assert len({tuple(v) for v in ref}) == 5
+    for count in (1, 63, 65, 130):
+        pick = [rng.randrange(5) for _ in range(count)]
+        pick[0], pick[-1] = count % 5, (count + 3) % 5
+        got = amd.pairing_op([five[k] for k in pick])
+        assert len(got) == count
+        assert [i for i in range(count) if got[i] != ref[pick[i]]] == []
+
+
+def test_precomputed_line_miller_loop_agrees_with_the_on_the_fly_loop(amd):
+    """g2_precompute + miller_loop_pre (gamma2, delta2) have no operator: they are pinned by verdict, beside the
+    on-the-fly miller_loop, on one G2 point Q = g G2 and a known k, B = k Q, A = a G1.
+      key "gamma"  gamma2 = Q; the signals are solved so that vk_x = k A, and C so that e(C, delta2) e(alpha1, beta2) = 1.
+                   What is left of the product is  miller_loop(-A, k Q) [factor 0] * miller_loop_pre(k A, Q) [factor 1],
+                   one after the final exponentiation iff the two loops agree.
+      key "delta"  delta2 = Q; C = k A, and the signals are solved so that e(vk_x, gamma2) e(alpha1, beta2) = 1.
+                   What is left is  miller_loop(-A, k Q) [factor 0] * miller_loop_pre(k A, Q) [factor 2].
+    k = 1 (B = Q itself), 2, r - 1 (B = -Q) and random; the neighbours B = (k + 1) Q are rejected.  Expected verdicts
+    are verify_exponent_ref.accepts()."""
+    rng = random.Random(0x11e)
+    ics = [rng.randrange(1, b.R) for _ in range(3)]
+    alpha, beta, g, other, a = (rng.randrange(1, b.R) for _ in range(5))
+    head = [rng.randrange(1 << 256)]
+    for which in ("gamma", "delta"):
+        ks = (ics, alpha, beta, g, other) if which == "gamma" else (ics, alpha, beta, other, g)
+        key, _ = ve.make_key(*ks)
+        cases = []
+        for k in (1, 2, b.R - 1, rng.randrange(1, b.R)):
+            if which == "gamma":
+                pub = head + [ve.solve_last_signal(ks, head, k * a % b.R)]
+                c = -alpha * beta * pow(other, -1, b.R) % b.R
+            else:
+                pub = head + [ve.solve_last_signal(ks, head, ve.x_without_a_and_c(ks))]
+                c = k * a % b.R
+            assert c == ve.solve_c(ks, a, k * g % b.R, pub)
+            cases += [(a, k * g % b.R, c, pub), (a, (k + 1) * g % b.R, c, pub)]
+        exp = [ve.accepts(ks, *case) for case in cases]
+        assert exp == [True, False] * 4
+        ve.g1_points([x for ca, _, cc, _ in cases for x in (ca, cc)])
+        ve.g2_points([cb for _, cb, _, _ in cases])
+        ver = amd.Verifier(key, 2, montgomery=True, device=0)
+        got = ver.verify_batch([([str(x) for x in pub], ve.proof_obj(ca, cb, cc)) for ca, cb, cc, pub in cases])
+        ver.close()
+        assert got == exp, which
 
 
 @pytest.mark.parametrize("n,p,m,seed", [(150, 6, 120, 2), (900, 513, 380, 24)])
