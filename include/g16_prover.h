@@ -558,8 +558,8 @@ int g16_zkey_contribute(const uint8_t* zkey, size_t zkey_len, const char* name /
 /* the same from / to files: the input is mapped read-only and the key is written in chunks */
 int g16_zkey_contribute_files(const char* in_path, const char* out_path, const char* name,
                               const uint8_t secret[64], int device, uint8_t contribution_hash[64]);
-/* `snarkjs zkey verify frominit init.zkey pot.ptau circuit.zkey` without the ptau leg (section 9 is not recomputed from
- * a ceremony file): is `zkey` the key `init` plus a chain of honest contributions?  G16_OK with *ok = 1 / 0; for 0
+/* `snarkjs zkey verify frominit init.zkey pot.ptau circuit.zkey` without the ptau leg (section 9 is not checked against
+ * a ceremony file; g16_zkey_verify_from_init_ptau below is the route with it): is `zkey` the key `init` plus a chain of honest contributions?  G16_OK with *ok = 1 / 0; for 0
  * g16_last_error() holds the reason, one fixed text per check, each led by "zkey verify: ":
  *   "the header differs from the initial key's (sizes, alpha, beta or gamma)", "sections 3 to 7 differ from the initial
  *   key's", "the circuit hash differs from the initial key's", "the contributions do not begin with the initial key's",
@@ -575,6 +575,40 @@ int g16_zkey_contribute_files(const char* in_path, const char* out_path, const c
 int g16_zkey_verify_from_init(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_t zkey_len,
                               int device, int* ok);
 int g16_zkey_verify_from_init_files(const char* init_path, const char* zkey_path, int device, int* ok);
+/* `snarkjs zkey verify frominit init.zkey pot.ptau circuit.zkey` WITH the ptau leg (snarkjs sectionHasSameRatioH): every
+ * check above, then section 9 of `zkey` against the ceremony file.  N = the key's domain, P_j = point j of the ptau's
+ * section 2, H_i = point i of the key's section 9, w = the primitive 2N-th root.  Drawn: u_0 .. u_(N-2) in Fr (ChaCha20
+ * keyed from the OS CSPRNG), u_(N-1) = 0.  rho_i = 2 sum_k u_k w^((2i+1) k), S = sum rho_i H_i, T = sum_(k <= N-2) u_k
+ * (P_k - P_(k+N)); accepted iff e(S, delta2 of zkey) = e(T, G2 generator), or S and T are both the point at infinity (the
+ * tau = 1 ceremony of g16_ptau_new: every P_j is the generator, so T is infinity, and the H points are infinity or sum to
+ * it); exactly one of them at infinity is a rejection.  The
+ * combination lies on the hyperplane sum rho_i w^(2i+1) = 0 -- the one the prover's scalars lie on -- where the two
+ * forms of the H basis agree: the full Lagrange block, and the block `prepare phase2` computes from the 2N - 1 points
+ * section 2 holds at N = 2^power.  The device forms rho / 2N (g16_zkey_h_scalars) and the host multiplies S by 2N.
+ * The ptau may be prepared or not: ONLY section 2 is read (its first 2N - 1 points).  The leg ties the key to those
+ * points; whether the file is a sound ceremony is g16_ptau_verify's question.
+ * Checked before the device is touched, after the two keys: the ptau's container, header and curve ("ptau: Invalid
+ * File format (bn128 powers of tau expected)" / "ptau: Invalid File format", G16_E_FORMAT); a power below log2 N is the
+ * verdict "zkey verify: the ptau is too small for this key"; a section 2 with fewer than 2N - 1 points, a coordinate
+ * >= q or a point off the curve among them is "ptau: Invalid File format".  The leg's verdict, after the checks above:
+ * "zkey verify: section 9 is not the ceremony's H basis scaled by 1 / delta".  One NTT of size N and two MSMs (N and
+ * 2N - 1 points, the ptau's read where they lie) on `device`; its pair joins the one pairing call. */
+int g16_zkey_verify_from_init_ptau(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_t ptau_len,
+                                   const uint8_t* zkey, size_t zkey_len, int device, int* ok);
+int g16_zkey_verify_from_init_ptau_files(const char* init_path, const char* ptau_path, const char* zkey_path, int device,
+                                         int* ok);
+/* `snarkjs zkey verify circuit.r1cs pot.ptau circuit.zkey`: g16_groth16_setup_ptau(r1cs, ptau) in memory (its errors and
+ * texts; the ptau must be prepared; no temporary file), then g16_zkey_verify_from_init_ptau against that key. */
+int g16_zkey_verify_r1cs(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len, const uint8_t* zkey,
+                         size_t zkey_len, int device, int* ok);
+int g16_zkey_verify_r1cs_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device, int* ok);
+/* Layer operator of the ptau leg (beside g16_fr_fft): both scalar vectors as the device forms them from one upload of u.
+ * u = N = 2^log_n standard-form LE scalars below r (not checked) with u[N-1] = 0 (else G16_E_ARG); log_n in [1, 27].
+ *   rho_out[i] = (1 / N) sum_k u[k] w^((2i+1) k)   (N x 32 bytes: the check's rho_i / 2N -- the NTT's coset table carries
+ *                                                   the 1 / N, the host multiplies the point S by 2N instead)
+ *   t_out      = u[0..N-2] | 0 | -u[0..N-2] mod r  ((2N - 1) x 32 bytes)
+ * so that 2N sum rho_out[i] H_i = sum t_out[j] P_j.  Standard form out. */
+int g16_zkey_h_scalars(int device, const uint8_t* u, uint32_t log_n, uint8_t* rho_out, uint8_t* t_out);
 /* Layer operators of the two routes above, host only.  Blake2b-512 (RFC 7693, unkeyed); the transcript's point on G2
  * (ChaCha20 keyed with the first 32 bytes, x drawn as the Montgomery image, cofactor 2q - r; affine LE Montgomery). */
 int g16_blake2b512(const uint8_t* data, size_t len, uint8_t out[64]);

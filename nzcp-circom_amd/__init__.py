@@ -77,6 +77,8 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_ptau_prepare", "g16_ptau_prepare_files",
            "g16_zkey_contribute", "g16_zkey_contribute_files", "g16_zkey_verify_from_init",
            "g16_zkey_verify_from_init_files", "g16_blake2b512", "g16_zkey_hash_to_g2",
+           "g16_zkey_verify_from_init_ptau", "g16_zkey_verify_from_init_ptau_files", "g16_zkey_verify_r1cs",
+           "g16_zkey_verify_r1cs_files", "g16_zkey_h_scalars",
            "g16_ptau_new", "g16_ptau_new_file", "g16_ptau_contribute", "g16_ptau_contribute_files", "g16_ptau_verify",
            "g16_ptau_verify_file", "g16_ptau_secret_from_text",
            "g16_ptau_export_challenge", "g16_ptau_export_challenge_files", "g16_ptau_challenge_contribute",
@@ -166,6 +168,11 @@ def load():
     lib.g16_zkey_contribute_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
     lib.g16_zkey_verify_from_init.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_int, C.POINTER(C.c_int)]
     lib.g16_zkey_verify_from_init_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_zkey_verify_from_init_ptau.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, sz, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_zkey_verify_from_init_ptau_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_zkey_verify_r1cs.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, sz, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_zkey_verify_r1cs_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_zkey_h_scalars.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_char_p, C.c_char_p]
     lib.g16_ptau_new.argtypes = [C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
     lib.g16_ptau_new_file.argtypes = [C.c_uint32, C.c_char_p]
     lib.g16_ptau_contribute.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
@@ -992,13 +999,38 @@ def zkey_contribute(zkey, name=None, d=None, s=None, device=0):
     return _take(z, zl), h.raw
 
 
-def zkey_verify_from_init(init, zkey, device=0):
-    """`snarkjs zkey verify frominit` without the ptau leg -> (ok, reason): is `zkey` the key `init` plus a chain of
-    honest contributions?  reason is empty when ok.  A malformed file raises G16Error(-2)."""
+def zkey_verify_from_init(init, zkey, device=0, ptau=None):
+    """`snarkjs zkey verify frominit` -> (ok, reason): is `zkey` the key `init` plus a chain of honest contributions?
+    reason is empty when ok.  ptau = .ptau bytes (prepared or not): the ptau leg as well -- section 9 of `zkey` is the H
+    basis of that ceremony's section 2 scaled by 1 / delta; None: without the leg.  A malformed file raises
+    G16Error(-2)."""
     ok = C.c_int(0)
     lib = load()
-    _check(lib.g16_zkey_verify_from_init(init, len(init), zkey, len(zkey), device, C.byref(ok)))
+    if ptau is None:
+        _check(lib.g16_zkey_verify_from_init(init, len(init), zkey, len(zkey), device, C.byref(ok)))
+    else:
+        _check(lib.g16_zkey_verify_from_init_ptau(init, len(init), ptau, len(ptau), zkey, len(zkey), device, C.byref(ok)))
     return bool(ok.value), ("" if ok.value else lib.g16_last_error().decode("utf-8", "replace"))
+
+
+def zkey_verify_r1cs(r1cs, ptau, zkey, device=0):
+    """`snarkjs zkey verify c.r1cs pot.ptau c.zkey` -> (ok, reason): the initial key is set up again from the .r1cs and
+    the prepared .ptau in memory, then zkey_verify_from_init with the ptau leg."""
+    ok = C.c_int(0)
+    lib = load()
+    _check(lib.g16_zkey_verify_r1cs(r1cs, len(r1cs), ptau, len(ptau), zkey, len(zkey), device, C.byref(ok)))
+    return bool(ok.value), ("" if ok.value else lib.g16_last_error().decode("utf-8", "replace"))
+
+
+def zkey_h_scalars(u, log_n, device=0):
+    """TEST-ONLY layer entry of the ptau leg: u = 2^log_n ints below r with u[-1] = 0 -> (rho, t), lists of ints, as the
+    device forms them: rho[i] = (1 / N) sum_k u[k] w^((2i+1) k), t = u[:N-1] | 0 | -u[:N-1] mod r."""
+    n = 1 << log_n
+    if len(u) != n:
+        raise ValueError("zkey_h_scalars: 2^log_n values expected")
+    rho, t = C.create_string_buffer(n * 32), C.create_string_buffer((2 * n - 1) * 32)
+    _check(load().g16_zkey_h_scalars(device, b"".join(_le32(x) for x in u), log_n, rho, t))
+    return tuple([int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)] for raw in (rho.raw, t.raw))
 
 
 def blake2b512(data):

@@ -130,6 +130,20 @@ struct ChunkStats {
 // scalar k (standard form, in [1, r)), in chunks over two streams.  No CPU path (G16_E_NOGPU).
 int zkey_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& k_std, uint8_t* out, ChunkStats* st);
 
+// ---------------------------------------------------------------- the ptau leg of zkey verify (zkey_verify_h.hip)
+// u = N = 2^log_n standard-form scalars below r with u[N-1] = 0 (host), uploaded once; both scalar vectors are formed
+// on the device (rho: N, t: 2N - 1, see the unit's header for the constant 1 / 2N that rho keeps) and feed two MSMs:
+// S = sum rho[i] sec9[i], T = sum t[j] tau_g1[j] (affine standard form, zero bytes = infinity).  sec9 = N and tau_g1 =
+// 2N - 1 affine Montgomery G1 points in file layout (host; read where they lie).  log_n in [1, 27].  No CPU path.
+struct ZkeyHStats {
+  float ntt_ms = 0.f;   // device time: tables, twist, transform, export, the t kernel
+  float msm_ms = 0.f;   // host wall time of the two MSMs
+};
+int zkey_verify_h(int device, const uint8_t* u, int log_n, const uint8_t* sec9, const uint8_t* tau_g1, uint8_t S[64],
+                  uint8_t T[64], ZkeyHStats* stats);
+// g16_g1_multiexp with the scalars already on the current device (ops.hip)
+int g1_multiexp_device(const uint8_t* bases, const Fr* d_scalars, size_t n, int window_bits, uint8_t out[64]);
+
 // ---------------------------------------------------------------- powersoftau contribute (ptau_scale.hip)
 // out[i] = [c k^(first + i)] in[i]: n affine Montgomery points of G1 / G2 (host, file layout; infinity = zero bytes in
 // and out), c and k standard form in [1, r), first + n <= 2^31; every lane forms its scalar on the device.  out_be

@@ -94,28 +94,23 @@ static int ec_add_impl(int device, const uint8_t* a, const uint8_t* b, uint8_t* 
   return G16_OK;
 }
 
+// the scalars (standard form) lie on the current device
 template <class F>
-static int multiexp_impl(int device, int curve, const uint8_t* bases, const uint8_t* scalars, size_t n,
-                         int window_bits, uint8_t* out) {
-  int rc = dev_check(device);
-  if (rc) return rc;
+static int multiexp_device(int curve, const uint8_t* bases, const Fr* d_scalars, size_t n, int window_bits, uint8_t* out) {
   if (n >= 0x7fffffffu) { set_error("multiexp: too many points"); return G16_E_ARG; }
   MsmGroup m;
   MsmConfig cfg;
   cfg.c = window_bits;
   MsmWorkspace* ws = nullptr;
-  DevBuf ds;
   hipStream_t st = nullptr;
   MsmSectionIn sec;
   if (curve == 2) sec.bases2_host = bases; else sec.bases_host = bases;
   sec.n_total = (uint32_t)n;
-  rc = msm_group_create(m, &sec, 1, cfg);
+  int rc = msm_group_create(m, &sec, 1, cfg);
   if (!rc) rc = msm_workspace_create(&ws, m);
-  if (!rc) rc = ds.alloc(n * 32);
-  if (!rc && hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy failed"); rc = G16_E_HIP; }
   if (!rc && hipStreamCreate(&st) != hipSuccess) { set_error("hipStreamCreate failed"); rc = G16_E_HIP; }
   MsmResult res;
-  if (!rc) rc = msm_launch(m, ws, (const Fr*)ds.p, st, st);
+  if (!rc) rc = msm_launch(m, ws, d_scalars, st, st);
   if (!rc) rc = msm_collect(m, ws, &res);
   if (!rc) {
     XYZZ<F> total;
@@ -128,6 +123,22 @@ static int multiexp_impl(int device, int curve, const uint8_t* bases, const uint
   msm_workspace_destroy(ws);
   msm_group_destroy(m);
   return rc;
+}
+
+template <class F>
+static int multiexp_impl(int device, int curve, const uint8_t* bases, const uint8_t* scalars, size_t n,
+                         int window_bits, uint8_t* out) {
+  int rc = dev_check(device);
+  if (rc) return rc;
+  if (n >= 0x7fffffffu) { set_error("multiexp: too many points"); return G16_E_ARG; }
+  DevBuf ds;
+  if ((rc = ds.alloc(n * 32))) return rc;
+  if (hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy failed"); return G16_E_HIP; }
+  return multiexp_device<F>(curve, bases, (const Fr*)ds.p, n, window_bits, out);
+}
+
+int g1_multiexp_device(const uint8_t* bases, const Fr* d_scalars, size_t n, int window_bits, uint8_t out[64]) {
+  return multiexp_device<FqOps>(1, bases, d_scalars, n, window_bits, out);
 }
 
 static int fft_impl(int device, uint8_t* buf, size_t n, bool inverse) {

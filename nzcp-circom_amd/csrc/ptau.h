@@ -1,4 +1,5 @@
-// The .ptau reader of the three routes that take a ceremony file (PLONK setup, Groth16 setup, prepare phase2).
+// The .ptau reader of the routes that take a ceremony file (PLONK setup, Groth16 setup, prepare phase2, and the ptau leg
+// of zkey verify, which opens with ptau_open and reads section 2 alone).
 #pragma once
 #include "binfile.h"
 

@@ -4,9 +4,12 @@
 //               section 10; everything else byte for byte.
 //   verify:     the key is the initial key plus a chain of honest contributions -- the hash chain and the same-ratio
 //               pairing checks of every record, and one random linear combination over sections 8 and 9 (two MSMs on
-//               the G1 Pippenger, pairings on the verifier's device code).
+//               the G1 Pippenger, pairings on the verifier's device code); with a .ptau also the ptau leg (snarkjs
+//               sectionHasSameRatioH): section 9 is the H basis of THAT ceremony's section 2 scaled by 1 / delta
+//               (zkey_verify_h.hip).  The leg reads section 2 only; whether the file is a sound ceremony is
+//               `powersoftau verify`'s question.
 // NOT here, on purpose: `zkey beacon`; the real csHash of `zkey new` (section 10 of this library's _0000 keys holds 64
-// zero bytes, and the chain is hashed from whatever section 10 holds); the ptau-based recomputation of section 9.
+// zero bytes, and the chain is hashed from whatever section 10 holds).
 // Because csHash is not snarkjs's, `snarkjs zkey verify` rejects these keys: the file LAYOUT and the proofs are
 // compatible, snarkjs's ceremony verifier is not claimed.
 #include "zkey_mpc.h"
@@ -18,6 +21,7 @@
 
 #include "internal.h"
 #include "mapped_file.h"
+#include "ptau.h"
 
 namespace g16 {
 
@@ -495,14 +499,28 @@ void mpc_pair_words(std::vector<uint8_t>& in, const uint8_t* g1_lem, const uint8
   for (int i = 0; i < 4; i++) { const Fq v = fp_from_mont(fq_load(g2_lem + 32 * i)); memcpy(in.data() + at + 64 + 32 * i, v.v, 32); }
 }
 namespace {
-int verify_core(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_t zkey_len, int device, int* ok) {
+// ptau != nullptr: the ptau leg as well (step 6): section 9 of the key under test against the first 2N - 1 points of
+// the ceremony's section 2 -- prepared or not, no other section of the ptau is read
+int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_t ptau_len, const uint8_t* zkey, size_t zkey_len,
+                int device, int* ok) {
   const auto t0 = std::chrono::steady_clock::now();
   *ok = 0;
   KeyView a, b;   // a = init, b = the key under test
   if (const int rc = open_key(init, init_len, a, true)) return rc;
   if (const int rc = open_key(zkey, zkey_len, b, false)) return rc;
-  if (const int rc = require_hip_device("zkey verify", device)) return rc;
   auto verdict = [&](const char* why) { set_error(why); return G16_OK; };
+  PtauView pv;
+  int L = 0;   // log2 of the domain of the key under test
+  while (((uint32_t)1 << L) < b.N) L++;
+  if (ptau) {
+    if (const int rc = ptau_open(ptau, ptau_len, pv, /*tau_sections=*/false)) return rc;
+    if ((int)pv.power < L) return verdict("zkey verify: the ptau is too small for this key");
+    const uint64_t m = 2 * (uint64_t)b.N - 1;
+    if (!pv.sec[2].p || pv.sec[2].size / 64 < m) return ptau_bad("Invalid File format");
+    for (uint64_t j = 0; j < m; j++)
+      if (!g1_image_ok(pv.sec[2].p + j * 64)) return ptau_bad("Invalid File format");
+  }
+  if (const int rc = require_hip_device("zkey verify", device)) return rc;
 
   // 1. everything a contribution leaves alone
   const uint8_t *ha = a.f.sec[2].p, *hb = b.f.sec[2].p;
@@ -589,15 +607,49 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_
   } else if (n) {
     return verdict("zkey verify: the combination of sections 8 and 9 is the point at infinity");
   }
+  // 6. the ptau leg: S = sum rho_i new9_i, T = sum t_j tauG1_j with both scalar vectors formed on the device from one
+  // draw u (zkey_verify_h.hip; rho keeps 1 / 2N, so S is multiplied by 2N here): e(2N S, delta2) = e(T, G2), or both
+  // sums the point at infinity (the tau = 1 ceremony).  A domain of one point has no H relation to check.
+  ZkeyHStats hst;
+  const bool leg = ptau && L >= 1;
+  if (leg) {
+    const char* h_text = "zkey verify: section 9 is not the ceremony's H basis scaled by 1 / delta";
+    std::vector<uint8_t> u((size_t)b.N * 32, 0);   // u[N-1] = 0
+    ChaCha rng;
+    if (const int rc = os_random((uint8_t*)rng.key, 32)) return rc;
+    for (uint32_t k = 0; k + 1 < b.N; k++) rng.next_below(kFrP, (uint32_t*)(u.data() + (size_t)k * 32));
+    uint8_t Sh[64], Th[64];   // standard form
+    if (const int rc = zkey_verify_h(device, u.data(), L, b.f.sec[9].p, pv.sec[2].p, Sh, Th, &hst)) return rc;
+    const bool sh_inf = all_zero(Sh, 64);
+    if (sh_inf != all_zero(Th, 64)) return verdict(h_text);
+    if (!sh_inf) {
+      G1Affine s, t, s2n;
+      s.x = fp_to_mont(fq_load(Sh)); s.y = fp_to_mont(fq_load(Sh + 32));
+      t.x = fp_to_mont(fq_load(Th)); t.y = fp_to_mont(fq_load(Th + 32));
+      Fr two_n = fp_zero<FrParams>();
+      two_n.v[0] = 2 * b.N;   // L <= 27
+      mul_image<FqOps>((const uint8_t*)&s, two_n, (uint8_t*)&s2n);
+      const G2Affine g2{Fq2{Fq{G16_G2X0}, Fq{G16_G2X1}}, Fq2{Fq{G16_G2Y0}, Fq{G16_G2Y1}}};
+      mpc_pair_words(pairs, (const uint8_t*)&s2n, hb + kHdrDelta2);
+      mpc_pair_words(pairs, (const uint8_t*)&t, (const uint8_t*)&g2);
+      reason.push_back(h_text);
+    }
+  }
   const auto t2 = std::chrono::steady_clock::now();
   const uint32_t np = (uint32_t)(pairs.size() / 192);
   std::vector<uint8_t> gt((size_t)np * 384);
   if (np)
     if (const int rc = g16_pairing_op(device, pairs.data(), np, gt.data())) return rc;
   const double pair_ms = ms_since(t2);
-  if (getenv("G16_TRACE_HOST"))
-    fprintf(stderr, "[g16] zkey verify: points %llu; kernels 0.000 ms, transfers 0.000 ms, MSM %.3f ms, pairings %.3f ms (%u); call %.3f ms\n",
-            (unsigned long long)n, msm_ms, pair_ms, np, ms_since(t0));
+  if (getenv("G16_TRACE_HOST")) {
+    if (leg)
+      fprintf(stderr, "[g16] zkey verify: points %llu; kernels 0.000 ms, transfers 0.000 ms, MSM %.3f ms, pairings %.3f ms (%u); "
+              "ptau leg: points %llu, NTT %.3f ms, MSM %.3f ms; call %.3f ms\n",
+              (unsigned long long)n, msm_ms, pair_ms, np, 3 * (unsigned long long)b.N - 1, hst.ntt_ms, hst.msm_ms, ms_since(t0));
+    else
+      fprintf(stderr, "[g16] zkey verify: points %llu; kernels 0.000 ms, transfers 0.000 ms, MSM %.3f ms, pairings %.3f ms (%u); call %.3f ms\n",
+              (unsigned long long)n, msm_ms, pair_ms, np, ms_since(t0));
+  }
   for (size_t c = 0; c < reason.size(); c++)
     if (memcmp(gt.data() + 2 * c * 384, gt.data() + (2 * c + 1) * 384, 384) != 0) return verdict(reason[c]);
   set_error("");
@@ -642,7 +694,7 @@ extern "C" int g16_zkey_contribute_files(const char* in_path, const char* out_pa
 extern "C" int g16_zkey_verify_from_init(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_t zkey_len, int device,
                                          int* ok) {
   if (!init || !zkey || !ok) { set_error("NULL argument"); return G16_E_ARG; }
-  return no_bad_alloc("zkey verify", [&]() { return verify_core(init, init_len, zkey, zkey_len, device, ok); });
+  return no_bad_alloc("zkey verify", [&]() { return verify_core(init, init_len, nullptr, 0, zkey, zkey_len, device, ok); });
 }
 
 extern "C" int g16_zkey_verify_from_init_files(const char* init_path, const char* zkey_path, int device, int* ok) {
@@ -651,4 +703,46 @@ extern "C" int g16_zkey_verify_from_init_files(const char* init_path, const char
   if (const int rc = in[0].open_ro(init_path)) return rc;
   if (const int rc = in[1].open_ro(zkey_path)) return rc;
   return g16_zkey_verify_from_init((const uint8_t*)in[0].p, in[0].len, (const uint8_t*)in[1].p, in[1].len, device, ok);
+}
+
+extern "C" int g16_zkey_verify_from_init_ptau(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_t ptau_len,
+                                              const uint8_t* zkey, size_t zkey_len, int device, int* ok) {
+  if (!init || !ptau || !zkey || !ok) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("zkey verify", [&]() { return verify_core(init, init_len, ptau, ptau_len, zkey, zkey_len, device, ok); });
+}
+
+extern "C" int g16_zkey_verify_from_init_ptau_files(const char* init_path, const char* ptau_path, const char* zkey_path,
+                                                    int device, int* ok) {
+  if (!init_path || !ptau_path || !zkey_path || !ok) { set_error("NULL argument"); return G16_E_ARG; }
+  MappedFile in[3];
+  if (const int rc = in[0].open_ro(init_path)) return rc;
+  if (const int rc = in[1].open_ro(ptau_path)) return rc;
+  if (const int rc = in[2].open_ro(zkey_path)) return rc;
+  return g16_zkey_verify_from_init_ptau((const uint8_t*)in[0].p, in[0].len, (const uint8_t*)in[1].p, in[1].len,
+                                        (const uint8_t*)in[2].p, in[2].len, device, ok);
+}
+
+// `snarkjs zkey verify c.r1cs pot.ptau c.zkey`: the initial key is set up again in memory (g16_groth16_setup_ptau, which
+// needs the prepared sections), then the route above
+extern "C" int g16_zkey_verify_r1cs(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len,
+                                    const uint8_t* zkey, size_t zkey_len, int device, int* ok) {
+  if (!r1cs || !ptau || !zkey || !ok) { set_error("NULL argument"); return G16_E_ARG; }
+  *ok = 0;
+  uint8_t* init = nullptr;
+  size_t init_len = 0;
+  if (const int rc = g16_groth16_setup_ptau(r1cs, r1cs_len, ptau, ptau_len, device, &init, &init_len)) return rc;
+  const int rc = g16_zkey_verify_from_init_ptau(init, init_len, ptau, ptau_len, zkey, zkey_len, device, ok);
+  free(init);
+  return rc;
+}
+
+extern "C" int g16_zkey_verify_r1cs_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device,
+                                          int* ok) {
+  if (!r1cs_path || !ptau_path || !zkey_path || !ok) { set_error("NULL argument"); return G16_E_ARG; }
+  MappedFile in[3];
+  if (const int rc = in[0].open_ro(r1cs_path)) return rc;
+  if (const int rc = in[1].open_ro(ptau_path)) return rc;
+  if (const int rc = in[2].open_ro(zkey_path)) return rc;
+  return g16_zkey_verify_r1cs((const uint8_t*)in[0].p, in[0].len, (const uint8_t*)in[1].p, in[1].len, (const uint8_t*)in[2].p,
+                              in[2].len, device, ok);
 }

@@ -38,6 +38,8 @@
  *                                                                              check rejects with its text
  *                                                                              (g16_ptau_import_response_files)
  *           zkeyVerifyFromInitFiles(initPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_from_init_files)
+ *           zkeyVerifyFromInitPtauFiles(initPath, ptauPath, zkeyPath, device) -> Promise<{ok, reason}>   (..._from_init_ptau_files)
+ *           zkeyVerifyR1csFiles(r1csPath, ptauPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_r1cs_files)
  */
 #include <node_api.h>
 #include <stdlib.h>
@@ -801,14 +803,16 @@ static napi_value js_ptau_prepare_files(napi_env env, napi_callback_info info) {
 typedef struct {
   napi_async_work work;
   napi_deferred deferred;
-  char a[1024], b[1024], name[512];
+  char a[1024], b[1024], c[1024], name[512];
   uint8_t secret[64], hash[64];
-  int has_name, has_secret, verify, device, rc, ok;
+  int has_name, has_secret, verify, device, rc, ok;   /* verify: 1 = a init, b zkey; 2 = a init, c ptau, b zkey; 3 = a r1cs, c ptau, b zkey */
   char err[512];
 } zjob_t;
 static void zjob_execute(napi_env env, void* data) {
   zjob_t* j = (zjob_t*)data;
-  j->rc = j->verify ? g16_zkey_verify_from_init_files(j->a, j->b, j->device, &j->ok)
+  j->rc = j->verify == 3 ? g16_zkey_verify_r1cs_files(j->a, j->c, j->b, j->device, &j->ok)
+          : j->verify == 2 ? g16_zkey_verify_from_init_ptau_files(j->a, j->c, j->b, j->device, &j->ok)
+          : j->verify ? g16_zkey_verify_from_init_files(j->a, j->b, j->device, &j->ok)
                     : g16_zkey_contribute_files(j->a, j->b, j->has_name ? j->name : NULL, j->has_secret ? j->secret : NULL,
                                                 j->device, j->hash);
   if (j->rc || (j->verify && !j->ok)) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
@@ -892,6 +896,33 @@ static napi_value js_zkey_verify_from_init_files(napi_env env, napi_callback_inf
   int32_t v = 0;
   if (argc > 2 && napi_get_value_int32(env, argv[2], &v) == napi_ok) j->device = v;
   return zjob_start(env, j, "g16_zkey_verify_from_init_files");
+}
+/* zkeyVerifyFromInitPtauFiles(initPath, ptauPath, zkeyPath, device) / zkeyVerifyR1csFiles(r1csPath, ptauPath, zkeyPath, device) */
+static napi_value zkey_verify_three(napi_env env, napi_callback_info info, int mode, const char* usage, const char* resource) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  zjob_t* j = (zjob_t*)calloc(1, sizeof(zjob_t));
+  size_t n = 0;
+  if (argc < 3 || napi_get_value_string_utf8(env, argv[0], j->a, sizeof(j->a), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], j->c, sizeof(j->c), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[2], j->b, sizeof(j->b), &n) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  j->verify = mode;
+  int32_t v = 0;
+  if (argc > 3 && napi_get_value_int32(env, argv[3], &v) == napi_ok) j->device = v;
+  return zjob_start(env, j, resource);
+}
+static napi_value js_zkey_verify_from_init_ptau_files(napi_env env, napi_callback_info info) {
+  return zkey_verify_three(env, info, 2, "zkeyVerifyFromInitPtauFiles(initPath, ptauPath, zkeyPath, device): three path strings expected",
+                           "g16_zkey_verify_from_init_ptau_files");
+}
+static napi_value js_zkey_verify_r1cs_files(napi_env env, napi_callback_info info) {
+  return zkey_verify_three(env, info, 3, "zkeyVerifyR1csFiles(r1csPath, ptauPath, zkeyPath, device): three path strings expected",
+                           "g16_zkey_verify_r1cs_files");
 }
 
 /* powersoftau new / contribute / verify / export challenge / challenge contribute / import response from / to files */
@@ -1161,6 +1192,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"ptauPrepareFiles", NULL, js_ptau_prepare_files, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyContributeFiles", NULL, js_zkey_contribute_files, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerifyFromInitFiles", NULL, js_zkey_verify_from_init_files, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyVerifyFromInitPtauFiles", NULL, js_zkey_verify_from_init_ptau_files, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyVerifyR1csFiles", NULL, js_zkey_verify_r1cs_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauNewFile", NULL, js_ptau_new_file, NULL, NULL, NULL, napi_default, NULL},
       {"ptauContributeFiles", NULL, js_ptau_contribute_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauVerifyFile", NULL, js_ptau_verify_file, NULL, NULL, NULL, napi_default, NULL},

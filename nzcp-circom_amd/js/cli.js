@@ -17,9 +17,10 @@
 // And of `snarkjs zkey contribute <old.zkey> <new.zkey> [--name=..] [-e=..]` (alias `zkc`): prints the contribution hash
 // as snarkjs does.  -e: THIS CLI's derivation of the secret from the text (index.js secretFromEntropy), not snarkjs's.
 // And of `snarkjs zkey verify frominit <init.zkey> <pot.ptau> <circuit.zkey>` (alias `zkvi`) and `snarkjs zkey verify
-// <circuit.r1cs> <pot.ptau> <circuit.zkey>` (alias `zkv`: runs the setup into a temporary file beside the zkey): prints
-// "[INFO]  snarkJS: ZKey Ok!" and exits 0, or "[ERROR] snarkJS: <reason>" and exits 1.  The ptau is read by the setup of
-// `zkv` only: section 9 is not recomputed from it, and csHash is not snarkjs's (see INTEGRATION.md 5b).
+// <circuit.r1cs> <pot.ptau> <circuit.zkey>` (alias `zkv`: the setup runs in memory, no file is written): prints
+// "[INFO]  snarkJS: ZKey Ok!" and exits 0, or "[ERROR] snarkJS: <reason>" and exits 1.  Both open the ptau and run the
+// ptau leg: section 9 of the key against the ceremony file's section 2.  [--skip-ptau]: without the leg (`zkv` then runs
+// the setup into a temporary file beside the zkey).  csHash is not snarkjs's (see INTEGRATION.md 5b).
 // And of `snarkjs groth16 verify <verification_key.json> <public.json> <proof.json>` (groth16Verify [EXT]): prints
 // "[INFO]  snarkJS: OK!" and exits 0, or "[ERROR] snarkJS: Invalid proof" and exits 1.
 // And of `snarkjs wtns check <circuit.r1cs> <witness.wtns>` (alias `wchk`) of LATER snarkjs releases -- the pinned 0.4.12
@@ -75,19 +76,22 @@ async function main(argv) {
     const frominit = a[0] === "zkvi" || rest[0] === "frominit";
     if (rest[0] === "frominit") rest = rest.slice(1);
     const pos = rest.filter((x) => !x.startsWith("-"));
-    if (pos.length < 3) { console.error("usage: cli.js zkey verify [frominit] <circuit.r1cs | init.zkey> <pot.ptau> <circuit.zkey>"); process.exit(2); }
+    if (pos.length < 3) { console.error("usage: cli.js zkey verify [frominit] <circuit.r1cs | init.zkey> <pot.ptau> <circuit.zkey> [--skip-ptau]"); process.exit(2); }
     const { zKey, newZKey } = require("./index.js");
-    let init = pos[0], tmp = null;
-    if (!frominit) {
-      tmp = `${pos[2]}.init.${process.pid}.tmp`;
-      init = tmp;
-    }
+    const skipPtau = rest.includes("--skip-ptau");
     let res;
-    try {
-      if (tmp) await newZKey(pos[0], pos[1], tmp);
-      res = await zKey.verifyFromInit(init, pos[1], pos[2], { reason: true });
-    } finally {
-      if (tmp && fs.existsSync(tmp)) fs.unlinkSync(tmp);
+    if (frominit) {
+      res = await zKey.verifyFromInit(pos[0], pos[1], pos[2], { reason: true, ptau: !skipPtau });
+    } else if (!skipPtau) {
+      res = await zKey.verifyFromR1cs(pos[0], pos[1], pos[2], { reason: true });
+    } else {
+      const tmp = `${pos[2]}.init.${process.pid}.tmp`;
+      try {
+        await newZKey(pos[0], pos[1], tmp);
+        res = await zKey.verifyFromInit(tmp, pos[1], pos[2], { reason: true, ptau: false });
+      } finally {
+        if (fs.existsSync(tmp)) fs.unlinkSync(tmp);
+      }
     }
     if (!res.ok) throw new Error(res.reason);
     console.log("[INFO]  snarkJS: ZKey Ok!");

@@ -375,12 +375,22 @@ async function contribute(oldZkeyName, newZkeyName, name, entropy, opts = {}) {
   const secret = entropy === undefined || entropy === null || entropy === "" ? null : secretFromEntropy(entropy);
   return native().zkeyContributeFiles(String(oldZkeyName), String(newZkeyName), name ? String(name) : null, secret, opts.device | 0);
 }
-// snarkjs: zKey.verifyFromInit(initFileName, pTauFileName, zkeyFileName[, logger]) -> boolean.  The ptau argument is
-// accepted for the call shape and NOT opened: section 9 is not recomputed from the ceremony file.  opts.reason = true
-// returns {ok, reason} instead.
+// snarkjs: zKey.verifyFromInit(initFileName, pTauFileName, zkeyFileName[, logger]) -> boolean.  The ptau (prepared or
+// not) is opened and the ptau leg runs: section 9 of the key is the H basis of that file's section 2 scaled by 1 / delta.
+// opts.ptau === false: without the leg, the ptau argument is then not opened.  opts.reason = true returns {ok, reason}
+// instead.
 async function verifyFromInit(initName, ptauName, zkeyName, opts = {}) {
   if (opts && typeof opts.debug === "function") opts = {};
-  const res = await native().zkeyVerifyFromInitFiles(String(initName), String(zkeyName), opts.device | 0);
+  const res = opts.ptau === false
+    ? await native().zkeyVerifyFromInitFiles(String(initName), String(zkeyName), opts.device | 0)
+    : await native().zkeyVerifyFromInitPtauFiles(String(initName), String(ptauName), String(zkeyName), opts.device | 0);
+  return opts.reason ? res : res.ok;
+}
+// snarkjs: zKey.verifyFromR1cs(r1csFileName, pTauFileName, zkeyFileName[, logger]) -> boolean.  The initial key is set
+// up again from the .r1cs and the prepared ptau in memory (no file is written), then verifyFromInit with the ptau leg.
+async function verifyFromR1cs(r1csName, ptauName, zkeyName, opts = {}) {
+  if (opts && typeof opts.debug === "function") opts = {};
+  const res = await native().zkeyVerifyR1csFiles(String(r1csName), String(ptauName), String(zkeyName), opts.device | 0);
   return opts.reason ? res : res.ok;
 }
 // snarkjs formatHash: four lines of four big-endian u32 in 8 hex digits, each line led by two tabs
@@ -497,4 +507,4 @@ const groth16 = {
   createProver,
 };
 
-module.exports = { groth16, plonk, powersOfTau, wtns, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, verifyFromInit }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
+module.exports = { groth16, plonk, powersOfTau, wtns, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, verifyFromInit, verifyFromR1cs }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
