@@ -8,23 +8,14 @@
 //   copy stream     wait ev_k[b]   download c -> ev_down[b]
 // and the upload of chunk c + 1 is enqueued ahead of the kernels of chunk c.  Both streams are drained before run()
 // returns and before anything is freed.  What a stage needs beyond the buffers (tables, digits, a result word) stays
-// with its caller: a DeviceBuf each, declared AHEAD of the pipeline so that it outlives the streams, written and read
-// over stream() before and after run().
+// with its caller: a DeviceBuf each, declared AHEAD of the pipeline (device_job.h: the pipeline owns the streams),
+// written and read over stream() before and after run().
 #pragma once
 #include <algorithm>
 
 #include "internal.h"
 
 namespace g16 {
-
-template <class T> struct DeviceBuf {
-  T* p = nullptr;
-  DeviceBuf() = default;
-  DeviceBuf(const DeviceBuf&) = delete;
-  DeviceBuf& operator=(const DeviceBuf&) = delete;
-  ~DeviceBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)); }
-};
 
 // Chunk size and grid of a run over n items, both overridable so that a small test runs several chunks and grid-stride
 // passes: chunk = G16_<..>_CHUNK or 2^18 items; lanes = G16_<..>_LANES rounded up to whole wavefronts (workgroups of 64
@@ -47,9 +38,9 @@ inline ChunkPlan chunk_plan(const char* chunk_env, const char* lanes_env, uint64
   return p;
 }
 
-class ChunkPipeline {
+class ChunkPipeline : public DeviceJob {   // fail(): also for the caller's own calls
  public:
-  explicit ChunkPipeline(const char* route) : route_(route) {}
+  explicit ChunkPipeline(const char* route) : DeviceJob(route) {}
   ChunkPipeline(const ChunkPipeline&) = delete;
   ChunkPipeline& operator=(const ChunkPipeline&) = delete;
   ~ChunkPipeline() {
@@ -62,13 +53,6 @@ class ChunkPipeline {
     for (hipStream_t s : {xst_, cst_}) if (s) (void)hipStreamDestroy(s);
   }
   hipStream_t stream() const { return cst_; }   // the compute stream
-  int rc() const { return rc_; }
-  bool fail(hipError_t e) {   // "<route> (device): <hip error string>"; also for the caller's own calls
-    if (e == hipSuccess) return false;
-    set_error(std::string(route_) + " (device): " + hipGetErrorString(e));
-    rc_ = G16_E_HIP;
-    return true;
-  }
   // streams, events and buffers: n > 0 items of in_sz bytes, out_sz bytes out each and -- when out2_sz -- as many into out2
   bool open(uint64_t n, uint32_t chunk, size_t in_sz, size_t out_sz, size_t out2_sz) {
     n_ = n; chunk_ = chunk; in_sz_ = in_sz; out_sz_ = out_sz; out2_sz_ = out2_sz;
@@ -90,7 +74,7 @@ class ChunkPipeline {
     bool ok = upload(in, 0);
     for (uint64_t c = 0; ok && c < nchunks_; c++) ok = (c + 1 == nchunks_ || upload(in, c + 1)) && chunk(c, out, out2, launch);
     if (ok) ok = !fail(hipStreamSynchronize(xst_)) && !fail(hipStreamSynchronize(cst_));
-    if (!ok) { drain(); return rc_; }
+    if (!ok) { drain(); return rc; }
     for (uint64_t c = 0; st && c < nchunks_; c++) {
       float ms = 0.f;
       for (int h = 0; h < 3; h++)
@@ -123,10 +107,8 @@ class ChunkPipeline {
     return !fail(hipEventRecord(te_[6 * c + 5], xst_)) && !fail(hipEventRecord(ev_down_[b], xst_));
   }
 
-  const char* route_;
   uint64_t n_ = 0, nchunks_ = 0;
   uint32_t chunk_ = 0;
-  int rc_ = G16_OK;
   size_t in_sz_ = 0, out_sz_ = 0, out2_sz_ = 0;
   hipStream_t cst_ = nullptr, xst_ = nullptr;   // compute, copies
   hipEvent_t ev_up_[2] = {}, ev_k_[2] = {}, ev_down_[2] = {};

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/g16_prover.h"
+#include "device_job.h"
 #include "ec.cuh"
 #include "fq29.cuh"
 
@@ -30,16 +31,6 @@ const char* get_error();
     }                                                                                      \
   } while (0)
 
-// the device check of the routes without a CPU path; called after every input check
-inline int require_hip_device(const char* route, int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error(std::string(route) + ": no HIP device (there is no CPU path)");
-    return G16_E_NOGPU;
-  }
-  if (device < 0 || device >= ndev) { set_error(std::string(route) + ": bad device ordinal"); return G16_E_ARG; }
-  return G16_OK;
-}
 template <class Fn> int no_bad_alloc(const char* route, Fn fn) {   // no C++ exception crosses the C ABI
   try {
     return fn();
@@ -178,6 +169,11 @@ struct NttTables {
 };
 int ntt_tables_create(NttTables& t, int L, hipStream_t st);
 void ntt_tables_destroy(NttTables& t);
+struct NttTablesOwned : NttTables {   // a one-shot route's tables (device_job.h: declared ahead of the stream)
+  NttTablesOwned() = default;
+  NttTablesOwned(const NttTablesOwned&) = delete;
+  ~NttTablesOwned() { ntt_tables_destroy(*this); }
+};
 // Batched in-place transforms over `nvec` vectors (device pointers in host array vecs).
 // dif_inverse: natural in -> bit-reversed out with w^-1 (no scaling);  dit_forward: bit-reversed
 // in -> natural out with w.
@@ -319,6 +315,13 @@ int msm_workspace_create(MsmWorkspace** ws, const MsmGroup& g);
 static constexpr int kMsmPrioHighest = -1000;
 void msm_set_aux_stream_priority(int prio);
 void msm_workspace_destroy(MsmWorkspace* ws);
+struct MsmJob {   // a one-shot route's group and workspace (device_job.h: declared ahead of the stream)
+  MsmGroup g;
+  MsmWorkspace* ws = nullptr;
+  MsmJob() = default;
+  MsmJob(const MsmJob&) = delete;
+  ~MsmJob() { msm_workspace_destroy(ws); msm_group_destroy(g); }
+};
 // Per-section results of one launch: XYZZ sums in the canonical Montgomery(2^256) image.
 struct MsmResult {
   G1XYZZ g1[kMsmMaxSections];

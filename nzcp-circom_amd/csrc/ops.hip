@@ -45,22 +45,13 @@ __global__ void ec_add_kernel(const Affine<F>* a, const Affine<F>* b, XYZZ<F>* o
   out[i] = twice;
 }
 
-static int dev_check(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    set_error("no HIP device available: libg16hip has no CPU fallback");
-    return G16_E_NOGPU;
-  }
-  if (device < 0 || device >= n) { set_error("device ordinal out of range"); return G16_E_ARG; }
+static int select_device(int device) {
+  if (const int rc = require_hip_device(device, "no HIP device available: libg16hip has no CPU fallback",
+                                        "device ordinal out of range"))
+    return rc;
   G16_HIP(hipSetDevice(device));
   return G16_OK;
 }
-
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { G16_HIP(hipMalloc(&p, bytes ? bytes : 16)); return G16_OK; }
-};
 
 template <class F> static void to_std_bytes(uint8_t* out, const Affine<F>& p);
 template <> void to_std_bytes<FqOps>(uint8_t* out, const G1Affine& p) {
@@ -74,18 +65,17 @@ template <> void to_std_bytes<Fq2Ops>(uint8_t* out, const G2Affine& p) {
 
 template <class F>
 static int ec_add_impl(int device, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n) {
-  int rc = dev_check(device);
-  if (rc) return rc;
-  DevBuf da, db, dout;
+  if (const int rc = select_device(device)) return rc;
+  DeviceJob job("ec add");
+  DeviceBuf<Affine<F>> da, db;
+  DeviceBuf<XYZZ<F>> dout;
   const size_t ab = n * sizeof(Affine<F>), ob = n * sizeof(XYZZ<F>);
-  if ((rc = da.alloc(ab)) || (rc = db.alloc(ab)) || (rc = dout.alloc(ob))) return rc;
-  G16_HIP(hipMemcpy(da.p, a, ab, hipMemcpyHostToDevice));
-  G16_HIP(hipMemcpy(db.p, b, ab, hipMemcpyHostToDevice));
-  ec_add_kernel<F><<<(unsigned)((n + 63) / 64), 64>>>((const Affine<F>*)da.p, (const Affine<F>*)db.p,
-                                                      (XYZZ<F>*)dout.p, n);
-  G16_HIP(hipGetLastError());
+  if (job.fail(da.alloc(n)) || job.fail(db.alloc(n)) || job.fail(dout.alloc(n)) ||
+      job.fail(hipMemcpy(da.p, a, ab, hipMemcpyHostToDevice)) || job.fail(hipMemcpy(db.p, b, ab, hipMemcpyHostToDevice)))
+    return job.rc;
+  ec_add_kernel<F><<<(unsigned)((n + 63) / 64), 64>>>(da.p, db.p, dout.p, n);
   std::vector<XYZZ<F>> h(n);
-  G16_HIP(hipMemcpy(h.data(), dout.p, ob, hipMemcpyDeviceToHost));
+  if (job.fail(hipGetLastError()) || job.fail(hipMemcpy(h.data(), dout.p, ob, hipMemcpyDeviceToHost))) return job.rc;
   for (size_t i = 0; i < n; i++) {
     Affine<F> r;
     xyzz_to_affine(r, h[i]);
@@ -98,43 +88,36 @@ static int ec_add_impl(int device, const uint8_t* a, const uint8_t* b, uint8_t* 
 template <class F>
 static int multiexp_device(int curve, const uint8_t* bases, const Fr* d_scalars, size_t n, int window_bits, uint8_t* out) {
   if (n >= 0x7fffffffu) { set_error("multiexp: too many points"); return G16_E_ARG; }
-  MsmGroup m;
+  DeviceJob job("multiexp");
+  MsmJob msm;
+  DeviceStream st;
   MsmConfig cfg;
   cfg.c = window_bits;
-  MsmWorkspace* ws = nullptr;
-  hipStream_t st = nullptr;
   MsmSectionIn sec;
   if (curve == 2) sec.bases2_host = bases; else sec.bases_host = bases;
   sec.n_total = (uint32_t)n;
-  int rc = msm_group_create(m, &sec, 1, cfg);
-  if (!rc) rc = msm_workspace_create(&ws, m);
-  if (!rc && hipStreamCreate(&st) != hipSuccess) { set_error("hipStreamCreate failed"); rc = G16_E_HIP; }
+  int rc = msm_group_create(msm.g, &sec, 1, cfg);
+  if (rc || (rc = msm_workspace_create(&msm.ws, msm.g))) return rc;
+  if (job.fail(st.create())) return job.rc;
   MsmResult res;
-  if (!rc) rc = msm_launch(m, ws, d_scalars, st, st);
-  if (!rc) rc = msm_collect(m, ws, &res);
-  if (!rc) {
-    XYZZ<F> total;
-    memcpy(&total, curve == 2 ? (const void*)&res.g2 : (const void*)&res.g1[0], sizeof(total));
-    Affine<F> r;
-    xyzz_to_affine(r, total);
-    to_std_bytes<F>(out, r);
-  }
-  if (st) (void)hipStreamDestroy(st);
-  msm_workspace_destroy(ws);
-  msm_group_destroy(m);
-  return rc;
+  if ((rc = msm_launch(msm.g, msm.ws, d_scalars, st, st)) || (rc = msm_collect(msm.g, msm.ws, &res))) return rc;
+  XYZZ<F> total;
+  memcpy(&total, curve == 2 ? (const void*)&res.g2 : (const void*)&res.g1[0], sizeof(total));
+  Affine<F> r;
+  xyzz_to_affine(r, total);
+  to_std_bytes<F>(out, r);
+  return G16_OK;
 }
 
 template <class F>
 static int multiexp_impl(int device, int curve, const uint8_t* bases, const uint8_t* scalars, size_t n,
                          int window_bits, uint8_t* out) {
-  int rc = dev_check(device);
-  if (rc) return rc;
+  if (const int rc = select_device(device)) return rc;
   if (n >= 0x7fffffffu) { set_error("multiexp: too many points"); return G16_E_ARG; }
-  DevBuf ds;
-  if ((rc = ds.alloc(n * 32))) return rc;
-  if (hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy failed"); return G16_E_HIP; }
-  return multiexp_device<F>(curve, bases, (const Fr*)ds.p, n, window_bits, out);
+  DeviceJob job("multiexp");
+  DeviceBuf<Fr> ds;
+  if (job.fail(ds.alloc(n)) || job.fail(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice))) return job.rc;
+  return multiexp_device<F>(curve, bases, ds.p, n, window_bits, out);
 }
 
 int g1_multiexp_device(const uint8_t* bases, const Fr* d_scalars, size_t n, int window_bits, uint8_t out[64]) {
@@ -142,39 +125,33 @@ int g1_multiexp_device(const uint8_t* bases, const Fr* d_scalars, size_t n, int 
 }
 
 static int fft_impl(int device, uint8_t* buf, size_t n, bool inverse) {
-  int rc = dev_check(device);
+  int rc = select_device(device);
   if (rc) return rc;
   int L = 0;
   while (((size_t)1 << L) < n) L++;
   if (n == 0 || ((size_t)1 << L) != n) { set_error("fft: size must be a power of two"); return G16_E_ARG; }
-  NttTables t;
-  DevBuf dx, dy;
-  hipStream_t st = nullptr;
-  G16_HIP(hipStreamCreate(&st));
-  rc = ntt_tables_create(t, L, st);
-  if (!rc) rc = dx.alloc(n * 32);
-  if (!rc) rc = dy.alloc(n * 32);
-  if (!rc && hipMemcpyAsync(dx.p, buf, n * 32, hipMemcpyHostToDevice, st) != hipSuccess) { set_error("hipMemcpy failed"); rc = G16_E_HIP; }
-  // dx: canonical image (in, then out); dz: the lazy working vector
-  DevBuf dz;
-  if (!rc) rc = dz.alloc(n * sizeof(F29));
-  F29* vz[1] = {(F29*)dz.p};
-  if (!rc) {
-    if (inverse) {
-      rc = ntt_import(t, (const Fr*)dx.p, (F29*)dz.p, false, st);
-      if (!rc) rc = ntt_dif_inverse(t, vz, 1, st);
-      if (!rc) rc = ntt_export(t, (const F29*)dz.p, (Fr*)dy.p, true, true, st);
-    } else {
-      rc = ntt_import(t, (const Fr*)dx.p, (F29*)dz.p, true, st);
-      if (!rc) rc = ntt_dit_forward(t, vz, 1, st);
-      if (!rc) rc = ntt_export(t, (const F29*)dz.p, (Fr*)dy.p, false, false, st);
-    }
+  DeviceJob job("fft");
+  NttTablesOwned t;
+  DeviceBuf<Fr> dx, dy;   // the canonical image in and out
+  DeviceBuf<F29> dz;      // the lazy working vector
+  DeviceStream st;
+  if (job.fail(st.create())) return job.rc;
+  if ((rc = ntt_tables_create(t, L, st))) return rc;
+  if (job.fail(dx.alloc(n)) || job.fail(dy.alloc(n)) || job.fail(hipMemcpyAsync(dx.p, buf, n * 32, hipMemcpyHostToDevice, st)) ||
+      job.fail(dz.alloc(n)))
+    return job.rc;
+  F29* vz[1] = {dz.p};
+  if (inverse) {
+    if ((rc = ntt_import(t, dx.p, dz.p, false, st)) || (rc = ntt_dif_inverse(t, vz, 1, st)) ||
+        (rc = ntt_export(t, dz.p, dy.p, true, true, st)))
+      return rc;
+  } else {
+    if ((rc = ntt_import(t, dx.p, dz.p, true, st)) || (rc = ntt_dit_forward(t, vz, 1, st)) ||
+        (rc = ntt_export(t, dz.p, dy.p, false, false, st)))
+      return rc;
   }
-  if (!rc && hipMemcpyAsync(buf, dy.p, n * 32, hipMemcpyDeviceToHost, st) != hipSuccess) { set_error("hipMemcpy failed"); rc = G16_E_HIP; }
-  if (hipStreamSynchronize(st) != hipSuccess && !rc) { set_error("stream sync failed"); rc = G16_E_HIP; }
-  ntt_tables_destroy(t);
-  (void)hipStreamDestroy(st);
-  return rc;
+  if (job.fail(hipMemcpyAsync(buf, dy.p, n * 32, hipMemcpyDeviceToHost, st)) || job.fail(hipStreamSynchronize(st))) return job.rc;
+  return G16_OK;
 }
 
 
@@ -243,17 +220,16 @@ int g16_fr_fft(int device, uint8_t* buf, size_t n) { return fft_impl(device, buf
 int g16_fr_ifft(int device, uint8_t* buf, size_t n) { return fft_impl(device, buf, n, true); }
 
 int g16_field_op(int device, int field, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n) {
-  int rc = dev_check(device);
-  if (rc) return rc;
-  DevBuf da, db, dout;
-  if ((rc = da.alloc(n * 32)) || (rc = db.alloc(n * 32)) || (rc = dout.alloc(n * 32))) return rc;
-  G16_HIP(hipMemcpy(da.p, a, n * 32, hipMemcpyHostToDevice));
-  G16_HIP(hipMemcpy(db.p, b, n * 32, hipMemcpyHostToDevice));
+  if (const int rc = select_device(device)) return rc;
+  DeviceJob job("field op");
+  DeviceBuf<Fr> da, db, dout;   // (Fq images have the same layout)
+  if (job.fail(da.alloc(n)) || job.fail(db.alloc(n)) || job.fail(dout.alloc(n)) ||
+      job.fail(hipMemcpy(da.p, a, n * 32, hipMemcpyHostToDevice)) || job.fail(hipMemcpy(db.p, b, n * 32, hipMemcpyHostToDevice)))
+    return job.rc;
   const unsigned nb = (unsigned)((n + 255) / 256);
-  if (field == 0) field_op_kernel<FrParams><<<nb, 256>>>((const Fr*)da.p, (const Fr*)db.p, (Fr*)dout.p, n, op);
+  if (field == 0) field_op_kernel<FrParams><<<nb, 256>>>(da.p, db.p, dout.p, n, op);
   else field_op_kernel<FqParams><<<nb, 256>>>((const Fq*)da.p, (const Fq*)db.p, (Fq*)dout.p, n, op);
-  G16_HIP(hipGetLastError());
-  G16_HIP(hipMemcpy(out, dout.p, n * 32, hipMemcpyDeviceToHost));
+  if (job.fail(hipGetLastError()) || job.fail(hipMemcpy(out, dout.p, n * 32, hipMemcpyDeviceToHost))) return job.rc;
   return G16_OK;
 }
 
@@ -276,45 +252,40 @@ int g16_g2_multiexp(int device, const uint8_t* bases, const uint8_t* scalars, si
 
 int g16_f29_op(int device, int field, int op, const uint8_t* a, const uint8_t* b, const uint8_t* c, const uint8_t* d,
                uint8_t* out, size_t n) {
-  int rc = dev_check(device);
+  int rc = select_device(device);
   if (rc) return rc;
   if (!a || !out || op < 0 || op > 11 || (op == 10 && field != 0)) { set_error("g16_f29_op: bad argument"); return G16_E_ARG; }
-  DevBuf dv[4], dout;
+  DeviceJob job("f29 op");
+  DeviceBuf<F29> dv[4], dout;
   const uint8_t* src[4] = {a, b ? b : a, c ? c : a, d ? d : a};
   const size_t bytes = n * sizeof(F29);
-  for (int k = 0; k < 4; k++) {
-    if ((rc = dv[k].alloc(bytes))) return rc;
-    G16_HIP(hipMemcpy(dv[k].p, src[k], bytes, hipMemcpyHostToDevice));
-  }
-  if ((rc = dout.alloc(bytes))) return rc;
+  for (int k = 0; k < 4; k++)
+    if (job.fail(dv[k].alloc(n)) || job.fail(hipMemcpy(dv[k].p, src[k], bytes, hipMemcpyHostToDevice))) return job.rc;
+  if (job.fail(dout.alloc(n))) return job.rc;
   const unsigned nb = (unsigned)((n + 255) / 256);
-  if (field == 0)
-    f29_op_kernel<Fr29C><<<nb, 256>>>((const F29*)dv[0].p, (const F29*)dv[1].p, (const F29*)dv[2].p, (const F29*)dv[3].p, (F29*)dout.p, n, op);
-  else
-    f29_op_kernel<Fq29C><<<nb, 256>>>((const F29*)dv[0].p, (const F29*)dv[1].p, (const F29*)dv[2].p, (const F29*)dv[3].p, (F29*)dout.p, n, op);
-  G16_HIP(hipGetLastError());
-  G16_HIP(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+  if (field == 0) f29_op_kernel<Fr29C><<<nb, 256>>>(dv[0].p, dv[1].p, dv[2].p, dv[3].p, dout.p, n, op);
+  else f29_op_kernel<Fq29C><<<nb, 256>>>(dv[0].p, dv[1].p, dv[2].p, dv[3].p, dout.p, n, op);
+  if (job.fail(hipGetLastError()) || job.fail(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost))) return job.rc;
   return G16_OK;
 }
 
 int g16_x29_op(int device, int curve, int op, const uint8_t* acc, const uint8_t* q, uint8_t* out, uint8_t* flags, size_t n) {
-  int rc = dev_check(device);
+  int rc = select_device(device);
   if (rc) return rc;
   if (!acc || !out || op < 0 || op > 4 || (op != 3 && !q)) { set_error("g16_x29_op: bad argument"); return G16_E_ARG; }
   const size_t coord = curve == 2 ? sizeof(F29x2) : sizeof(F29);
   const size_t ab = n * 4 * coord, qb = n * (op == 2 ? 4 : 2) * coord;
-  DevBuf da, dq, dout, dfl;
-  if ((rc = da.alloc(ab)) || (rc = dq.alloc(qb)) || (rc = dout.alloc(ab)) || (rc = dfl.alloc(n))) return rc;
-  G16_HIP(hipMemcpy(da.p, acc, ab, hipMemcpyHostToDevice));
-  if (q) G16_HIP(hipMemcpy(dq.p, q, qb, hipMemcpyHostToDevice));
+  DeviceJob job("x29 op");
+  DeviceBuf<uint8_t> da, dq, dout, dfl;
+  if (job.fail(da.alloc(ab)) || job.fail(dq.alloc(qb)) || job.fail(dout.alloc(ab)) || job.fail(dfl.alloc(n)) ||
+      job.fail(hipMemcpy(da.p, acc, ab, hipMemcpyHostToDevice)) || (q && job.fail(hipMemcpy(dq.p, q, qb, hipMemcpyHostToDevice))))
+    return job.rc;
   const unsigned nb = (unsigned)((n + 63) / 64);
-  if (curve == 2)
-    x29_op_kernel<Fq2x29Ops><<<nb, 64>>>((const G2XYZZ29*)da.p, dq.p, (G2XYZZ29*)dout.p, (uint8_t*)dfl.p, n, op);
-  else
-    x29_op_kernel<Fq29Ops><<<nb, 64>>>((const G1XYZZ29*)da.p, dq.p, (G1XYZZ29*)dout.p, (uint8_t*)dfl.p, n, op);
-  G16_HIP(hipGetLastError());
-  G16_HIP(hipMemcpy(out, dout.p, ab, hipMemcpyDeviceToHost));
-  if (flags) G16_HIP(hipMemcpy(flags, dfl.p, n, hipMemcpyDeviceToHost));
+  if (curve == 2) x29_op_kernel<Fq2x29Ops><<<nb, 64>>>((const G2XYZZ29*)da.p, dq.p, (G2XYZZ29*)dout.p, dfl.p, n, op);
+  else x29_op_kernel<Fq29Ops><<<nb, 64>>>((const G1XYZZ29*)da.p, dq.p, (G1XYZZ29*)dout.p, dfl.p, n, op);
+  if (job.fail(hipGetLastError()) || job.fail(hipMemcpy(out, dout.p, ab, hipMemcpyDeviceToHost)) ||
+      (flags && job.fail(hipMemcpy(flags, dfl.p, n, hipMemcpyDeviceToHost))))
+    return job.rc;
   return G16_OK;
 }
 

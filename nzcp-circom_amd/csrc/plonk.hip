@@ -1110,46 +1110,30 @@ int plonk_prove_impl(g16_plonk* P, const uint8_t* wtns, size_t wlen, const uint8
 // coefficients and the 4N evaluations, written back to back at out[k] (5N words)
 namespace g16 {
 int plonk_setup_polys(int device, int L, const Fr* const evals[8], uint8_t* const out[8]) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("plonk setup: no HIP device (the transforms run on the GPU)"); return G16_E_NOGPU; }
-  if (device < 0 || device >= ndev) { set_error("plonk setup: bad device ordinal"); return G16_E_ARG; }
+  if (const int rc = require_hip_device(device, "plonk setup: no HIP device (the transforms run on the GPU)",
+                                        "plonk setup: bad device ordinal"))
+    return rc;
   G16_HIP(hipSetDevice(device));
   const size_t N = (size_t)1 << L, n4 = N * 4;
-  NttTables tn, t4;
-  hipStream_t st = nullptr;
-  FrM *d_ev = nullptr, *d_co = nullptr, *d_ext = nullptr;
-  F29* d_lazy = nullptr;
+  DeviceJob job("plonk setup");
+  NttTablesOwned tn, t4;
+  DeviceBuf<FrM> d_ev, d_co, d_ext;
+  DeviceBuf<F29> d_lazy;
+  DeviceStream st;
   int rc = G16_OK;
-  auto fail = [&](hipError_t e) {
-    if (e == hipSuccess) return false;
-    set_error(std::string("plonk setup: ") + hipGetErrorString(e));
-    rc = G16_E_HIP;
-    return true;
-  };
-  do {
-    if (fail(hipStreamCreate(&st))) break;
-    if ((rc = ntt_tables_create(tn, L, st))) break;
-    if ((rc = ntt_tables_create(t4, L + 2, st))) break;
-    if (fail(hipMalloc(&d_ev, N * 32)) || fail(hipMalloc(&d_co, N * 32)) || fail(hipMalloc(&d_ext, n4 * 32)) ||
-        fail(hipMalloc(&d_lazy, n4 * sizeof(F29)))) break;
-    for (int k = 0; k < 8 && rc == G16_OK; k++) {
-      if (fail(hipMemcpyAsync(d_ev, evals[k], N * 32, hipMemcpyHostToDevice, st))) break;
-      if ((rc = do_ifft(tn, d_ev, d_co, d_lazy, st))) break;
-      k_pad4<<<nblk(n4), 256, 0, st>>>(d_co, (uint32_t)N, d_ext);
-      if ((rc = do_fft(t4, d_ext, d_ext, d_lazy, st))) break;
-      if (fail(hipGetLastError())) break;
-      if (fail(hipMemcpyAsync(out[k], d_co, N * 32, hipMemcpyDeviceToHost, st))) break;
-      if (fail(hipMemcpyAsync(out[k] + N * 32, d_ext, n4 * 32, hipMemcpyDeviceToHost, st))) break;
-      if (fail(hipStreamSynchronize(st))) break;
-    }
-  } while (false);
-  if (st) (void)hipStreamSynchronize(st);
-  void* bufs[] = {d_ev, d_co, d_ext, d_lazy};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  ntt_tables_destroy(tn);
-  ntt_tables_destroy(t4);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  if (job.fail(st.create())) return job.rc;
+  if ((rc = ntt_tables_create(tn, L, st)) || (rc = ntt_tables_create(t4, L + 2, st))) return rc;
+  if (job.fail(d_ev.alloc(N)) || job.fail(d_co.alloc(N)) || job.fail(d_ext.alloc(n4)) || job.fail(d_lazy.alloc(n4))) return job.rc;
+  for (int k = 0; k < 8; k++) {
+    if (job.fail(hipMemcpyAsync(d_ev.p, evals[k], N * 32, hipMemcpyHostToDevice, st))) return job.rc;
+    if ((rc = do_ifft(tn, d_ev.p, d_co.p, d_lazy.p, st))) return rc;
+    k_pad4<<<nblk(n4), 256, 0, st>>>(d_co.p, (uint32_t)N, d_ext.p);
+    if ((rc = do_fft(t4, d_ext.p, d_ext.p, d_lazy.p, st))) return rc;
+    if (job.fail(hipGetLastError()) || job.fail(hipMemcpyAsync(out[k], d_co.p, N * 32, hipMemcpyDeviceToHost, st)) ||
+        job.fail(hipMemcpyAsync(out[k] + N * 32, d_ext.p, n4 * 32, hipMemcpyDeviceToHost, st)) || job.fail(hipStreamSynchronize(st)))
+      return job.rc;
+  }
+  return G16_OK;
 }
 }  // namespace g16
 
@@ -1157,44 +1141,33 @@ int plonk_setup_polys(int device, int L, const Fr* const evals[8], uint8_t* cons
 // first N powers; coefs[k] = N Montgomery words on the host, out = 8 affine Montgomery points
 namespace g16 {
 int plonk_setup_commit(int device, const uint8_t* tau_g1, uint32_t N, const uint8_t* const coefs[8], uint8_t* out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("plonk setup: no HIP device"); return G16_E_NOGPU; }
-  if (device < 0 || device >= ndev) { set_error("plonk setup: bad device ordinal"); return G16_E_ARG; }
+  if (const int rc = require_hip_device(device, "plonk setup: no HIP device", "plonk setup: bad device ordinal")) return rc;
   G16_HIP(hipSetDevice(device));
-  MsmGroup grp;
-  MsmWorkspace* ws = nullptr;
+  DeviceJob job("plonk setup");
+  MsmJob msm;
+  DeviceBuf<FrM> d_co;
+  DeviceBuf<Fr> d_sc;
+  DeviceStream st;
   MsmSectionIn sec;
   sec.bases_host = tau_g1;
   sec.n_total = N;
   MsmConfig cfg;
   cfg.dense = true;
-  int rc = msm_group_create(grp, &sec, 1, cfg);
-  if (!rc && grp.n != N) { set_error("ptau: a power of tau is the point at infinity"); rc = G16_E_FORMAT; }
-  if (!rc) rc = msm_workspace_create(&ws, grp);
-  hipStream_t st = nullptr;
-  FrM* d_co = nullptr;
-  Fr* d_sc = nullptr;
-  if (!rc && (hipStreamCreate(&st) != hipSuccess || hipMalloc(&d_co, (size_t)N * 32) != hipSuccess ||
-              hipMalloc(&d_sc, (size_t)N * 32) != hipSuccess)) { set_error("plonk setup: HIP allocation failed"); rc = G16_E_HIP; }
-  for (int k = 0; k < 8 && !rc; k++) {
-    if (hipMemcpyAsync(d_co, coefs[k], (size_t)N * 32, hipMemcpyHostToDevice, st) != hipSuccess) { set_error("plonk setup: upload failed"); rc = G16_E_HIP; break; }
-    k_from_mont_pad<<<nblk(N), 256, 0, st>>>(d_co, N, d_sc, N);
-    rc = msm_launch(grp, ws, d_sc, st, st);
+  int rc = msm_group_create(msm.g, &sec, 1, cfg);
+  if (rc) return rc;
+  if (msm.g.n != N) { set_error("ptau: a power of tau is the point at infinity"); return G16_E_FORMAT; }
+  if ((rc = msm_workspace_create(&msm.ws, msm.g))) return rc;
+  if (job.fail(st.create()) || job.fail(d_co.alloc(N)) || job.fail(d_sc.alloc(N))) return job.rc;
+  for (int k = 0; k < 8; k++) {
+    if (job.fail(hipMemcpyAsync(d_co.p, coefs[k], (size_t)N * 32, hipMemcpyHostToDevice, st))) return job.rc;
+    k_from_mont_pad<<<nblk(N), 256, 0, st>>>(d_co.p, N, d_sc.p, N);
     MsmResult res;
-    if (!rc) rc = msm_collect(grp, ws, &res);
-    if (!rc) {
-      G1Affine a;
-      xyzz_to_affine(a, res.g1[0]);
-      memcpy(out + (size_t)k * 64, &a, 64);
-    }
+    if ((rc = msm_launch(msm.g, msm.ws, d_sc.p, st, st)) || (rc = msm_collect(msm.g, msm.ws, &res))) return rc;
+    G1Affine a;
+    xyzz_to_affine(a, res.g1[0]);
+    memcpy(out + (size_t)k * 64, &a, 64);
   }
-  if (st) (void)hipStreamSynchronize(st);
-  if (d_co) (void)hipFree(d_co);
-  if (d_sc) (void)hipFree(d_sc);
-  if (ws) msm_workspace_destroy(ws);
-  msm_group_destroy(grp);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  return G16_OK;
 }
 }  // namespace g16
 

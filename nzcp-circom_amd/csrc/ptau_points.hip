@@ -319,14 +319,14 @@ int points_device(const char* what, int device, const uint8_t* in, size_t in_sz,
   ChunkPipeline pipe(what);
   if (!pipe.open(n, plan.chunk, in_sz, out_sz, out2 ? out2_sz : 0) || pipe.fail(bad.alloc(1)) ||
       pipe.fail(hipMemcpyAsync(bad.p, &h_bad, sizeof(uint32_t), hipMemcpyHostToDevice, pipe.stream())))
-    return pipe.rc();
+    return pipe.rc;
   const int rc = pipe.run(in, out, out2, st, [&](hipStream_t s, const uint8_t* i, uint8_t* o, uint8_t* o2, uint32_t cnt, uint64_t lo) {
     launch(plan.grid(cnt), plan.block, s, i, o, o2, cnt, (uint32_t)lo, bad.p);
   });
   if (rc) return rc;
   if (pipe.fail(hipMemcpy(&h_bad, bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost))) {
     if (st) *st = ChunkStats{};
-    return pipe.rc();
+    return pipe.rc;
   }
   if (first_bad && h_bad != kNoBad) *first_bad = (int64_t)h_bad;
   return G16_OK;

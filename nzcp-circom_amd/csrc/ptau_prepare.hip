@@ -119,12 +119,7 @@ int prepare_device(int device, const uint8_t* src, uint64_t nsrc, int kmax, uint
   if (kmax < 0 || kmax > 26) { set_error("ptau prepare: bad block count"); return G16_E_ARG; }
   const uint32_t total = (2u << kmax) - 1;   // points of blocks 0 .. kmax
   if (nsrc == 0 || nsrc > ((uint64_t)1 << kmax)) { set_error("ptau prepare: bad source length"); return G16_E_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("ptau prepare: no HIP device (there is no CPU path)");
-    return G16_E_NOGPU;
-  }
-  if (device < 0 || device >= ndev) { set_error("ptau prepare: bad device ordinal"); return G16_E_ARG; }
+  if (const int rc = require_hip_device("ptau prepare", device)) return rc;
   G16_HIP(hipSetDevice(device));
   hipDeviceProp_t prop;
   G16_HIP(hipGetDeviceProperties(&prop, device));
@@ -148,68 +143,47 @@ int prepare_device(int device, const uint8_t* src, uint64_t nsrc, int kmax, uint
   const uint32_t mul_blocks = std::min(grid_cap, (max_mul + kMulBlock - 1) / kMulBlock);
   const size_t mul_lanes = (size_t)mul_blocks * kMulBlock;
 
-  Affine<FC>*d_src = nullptr, *d_aff = nullptr;
-  XYZZ<FC>*d_work = nullptr, *d_tbl = nullptr;
-  Fr* d_sc = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = G16_OK;
-  auto fail = [&](hipError_t e) {
-    if (e == hipSuccess) return false;
-    set_error(std::string("ptau prepare (device): ") + hipGetErrorString(e));
-    rc = G16_E_HIP;
-    return true;
-  };
-  float kern_ms = 0.f;
+  DeviceJob job("ptau prepare");
+  DeviceBuf<Affine<FC>> d_src, d_aff;
+  DeviceBuf<XYZZ<FC>> d_work, d_tbl;
+  DeviceBuf<Fr> d_sc;
+  DeviceTimer timer;
+  DeviceStream st;
   uint64_t muls = 0, adds = 0;
-  do {
-    if (fail(hipStreamCreate(&st))) break;
-    if (fail(hipEventCreate(&e0)) || fail(hipEventCreate(&e1))) break;
-    if (fail(hipMalloc(&d_src, nsrc * sizeof(Affine<FC>)))) break;
-    if (fail(hipMalloc(&d_work, (size_t)total * sizeof(XYZZ<FC>)))) break;
-    if (fail(hipMalloc(&d_aff, (size_t)total * sizeof(Affine<FC>)))) break;
-    if (fail(hipMalloc(&d_tbl, mul_lanes * kTbl * sizeof(XYZZ<FC>)))) break;
-    if (fail(hipMalloc(&d_sc, sc.size() * sizeof(Fr)))) break;
-    if (fail(hipMemcpyAsync(d_src, src, nsrc * sizeof(Affine<FC>), hipMemcpyHostToDevice, st))) break;
-    if (fail(hipMemcpyAsync(d_sc, sc.data(), sc.size() * sizeof(Fr), hipMemcpyHostToDevice, st))) break;
-    if (fail(hipEventRecord(e0, st))) break;
-    pp_load_kernel<FC><<<(total + 255) / 256, 256, 0, st>>>(d_src, (uint32_t)nsrc, total, d_work);
-    for (int s = 0; s < kmax; s++) {
-      const uint32_t n = (1u << kmax) - (1u << s);   // butterflies of stage s over blocks s + 1 .. kmax
-      if (s >= 1) {
-        pp_mul_kernel<FC><<<std::min(mul_blocks, (n + kMulBlock - 1) / kMulBlock), kMulBlock, 0, st>>>(d_work, d_sc, n, s,
-                                                                                                       kmax - 1 - s, d_tbl);
-        for (int k = s + 1; k <= kmax; k++) muls += ((uint64_t)1 << (k - 1)) - ((uint64_t)1 << (k - 1 - s));
-      }
-      pp_bfly_kernel<FC><<<(n + 255) / 256, 256, 0, st>>>(d_work, n, s);
-      adds += 2 * (uint64_t)n;
+  if (job.fail(st.create()) || job.fail(timer.create()) || job.fail(d_src.alloc(nsrc)) || job.fail(d_work.alloc(total)) ||
+      job.fail(d_aff.alloc(total)) || job.fail(d_tbl.alloc(mul_lanes * kTbl)) || job.fail(d_sc.alloc(sc.size())) ||
+      job.fail(hipMemcpyAsync(d_src.p, src, nsrc * sizeof(Affine<FC>), hipMemcpyHostToDevice, st)) ||
+      job.fail(hipMemcpyAsync(d_sc.p, sc.data(), sc.size() * sizeof(Fr), hipMemcpyHostToDevice, st)) || job.fail(timer.start(st)))
+    return job.rc;
+  pp_load_kernel<FC><<<(total + 255) / 256, 256, 0, st>>>(d_src.p, (uint32_t)nsrc, total, d_work.p);
+  for (int s = 0; s < kmax; s++) {
+    const uint32_t n = (1u << kmax) - (1u << s);   // butterflies of stage s over blocks s + 1 .. kmax
+    if (s >= 1) {
+      pp_mul_kernel<FC><<<std::min(mul_blocks, (n + kMulBlock - 1) / kMulBlock), kMulBlock, 0, st>>>(d_work.p, d_sc.p, n, s,
+                                                                                                     kmax - 1 - s, d_tbl.p);
+      for (int k = s + 1; k <= kmax; k++) muls += ((uint64_t)1 << (k - 1)) - ((uint64_t)1 << (k - 1 - s));
     }
-    if (kmax >= 1) {
-      const uint32_t n = total - 1;
-      pp_mul_kernel<FC><<<std::min(mul_blocks, (n + kMulBlock - 1) / kMulBlock), kMulBlock, 0, st>>>(d_work, d_sc + ntw, n, -1, 0,
-                                                                                                     d_tbl);
-      muls += n;
-    }
-    const uint32_t nb = (total + kBatch - 1) / kBatch;
-    setup_to_affine_kernel<FC><<<(nb + 255) / 256, 256, 0, st>>>(d_work, d_aff, total);
-    if (fail(hipGetLastError())) break;
-    if (fail(hipEventRecord(e1, st))) break;
-    if (fail(hipMemcpyAsync(out, d_aff, (size_t)total * sizeof(Affine<FC>), hipMemcpyDeviceToHost, st))) break;
-    if (fail(hipStreamSynchronize(st))) break;
-    (void)hipEventElapsedTime(&kern_ms, e0, e1);
-  } while (false);
-  if (st) (void)hipStreamSynchronize(st);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  void* bufs[] = {d_src, d_work, d_aff, d_tbl, d_sc};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (st) (void)hipStreamDestroy(st);
-  if (rc == G16_OK && stats) {
-    stats->kern_ms = kern_ms;
+    pp_bfly_kernel<FC><<<(n + 255) / 256, 256, 0, st>>>(d_work.p, n, s);
+    adds += 2 * (uint64_t)n;
+  }
+  if (kmax >= 1) {
+    const uint32_t n = total - 1;
+    pp_mul_kernel<FC><<<std::min(mul_blocks, (n + kMulBlock - 1) / kMulBlock), kMulBlock, 0, st>>>(d_work.p, d_sc.p + ntw, n, -1, 0,
+                                                                                                   d_tbl.p);
+    muls += n;
+  }
+  const uint32_t nb = (total + kBatch - 1) / kBatch;
+  setup_to_affine_kernel<FC><<<(nb + 255) / 256, 256, 0, st>>>(d_work.p, d_aff.p, total);
+  if (job.fail(hipGetLastError()) || job.fail(timer.stop(st)) ||
+      job.fail(hipMemcpyAsync(out, d_aff.p, (size_t)total * sizeof(Affine<FC>), hipMemcpyDeviceToHost, st)) ||
+      job.fail(hipStreamSynchronize(st)))
+    return job.rc;
+  if (stats) {
+    stats->kern_ms = timer.ms();
     stats->muls = muls;
     stats->adds = adds;
   }
-  return rc;
+  return G16_OK;
 }
 
 }  // namespace

@@ -131,7 +131,7 @@ int scale_device(int device, const uint8_t* in, uint64_t n, const Fr& c_std, con
   ChunkPipeline pipe("ptau scale");
   if (!pipe.open(n, plan.chunk, PSZ, PSZ, out_be ? PSZ : 0) || pipe.fail(work.alloc(plan.chunk)) ||
       pipe.fail(tbl.alloc((size_t)plan.lanes << (win - 1))) || pipe.fail(sc.alloc(plan.lanes)))
-    return pipe.rc();
+    return pipe.rc;
   return pipe.run(in, out, out_be, st, [&](hipStream_t s, const uint8_t* d_in, uint8_t* d_out, uint8_t* d_be, uint32_t cnt, uint64_t lo) {
     const Affine<FC>* pts = (const Affine<FC>*)d_in;
     Affine<FC>* aff = (Affine<FC>*)d_out;

@@ -48,67 +48,43 @@ __global__ __launch_bounds__(256) void setup_fixed_mul_kernel(const Affine<FC>* 
 template <class FC>
 int fixed_mul_device(int device, const Affine<FC>* h_tbl, int wb, int nwin, const Fr* ks_mont, size_t n, uint8_t* out) {
   if (n == 0) return G16_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("setup: no HIP device (g16_setup_device selected the GPU path)");
-    return G16_E_NOGPU;
-  }
-  if (device < 0 || device >= ndev) { set_error("setup: bad device ordinal"); return G16_E_ARG; }
+  if (const int rc = require_hip_device(device, "setup: no HIP device (g16_setup_device selected the GPU path)",
+                                        "setup: bad device ordinal"))
+    return rc;
   G16_HIP(hipSetDevice(device));
   const size_t tbl_n = (size_t)nwin * (((size_t)1 << wb) - 1);
   const size_t chunk = n < ((size_t)1 << 20) ? n : ((size_t)1 << 20);
-  Affine<FC>* d_tbl = nullptr;
-  Fr* d_k = nullptr;
-  XYZZ<FC>* d_acc = nullptr;
-  Affine<FC>* d_aff = nullptr;
-  hipStream_t st = nullptr;
-  int rc = G16_OK;
-  auto fail = [&](hipError_t e) {
-    if (e == hipSuccess) return false;
-    set_error(std::string("setup (device): ") + hipGetErrorString(e));
-    rc = G16_E_HIP;
-    return true;
-  };
   static const bool trace = getenv("G16_TRACE_HOST") != nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  DeviceJob job("setup");
+  DeviceBuf<Affine<FC>> d_tbl, d_aff;
+  DeviceBuf<Fr> d_k;
+  DeviceBuf<XYZZ<FC>> d_acc;
+  DeviceTimer timer;
+  DeviceStream st;
   float kern_ms = 0.f;
-  do {
-    if (fail(hipStreamCreate(&st))) break;
-    if (trace && (fail(hipEventCreate(&e0)) || fail(hipEventCreate(&e1)))) break;
-    if (fail(hipMalloc(&d_tbl, tbl_n * sizeof(Affine<FC>)))) break;
-    if (fail(hipMalloc(&d_k, chunk * sizeof(Fr)))) break;
-    if (fail(hipMalloc(&d_acc, chunk * sizeof(XYZZ<FC>)))) break;
-    if (fail(hipMalloc(&d_aff, chunk * sizeof(Affine<FC>)))) break;
-    if (fail(hipMemcpyAsync(d_tbl, h_tbl, tbl_n * sizeof(Affine<FC>), hipMemcpyHostToDevice, st))) break;
-    for (size_t base = 0; base < n && rc == G16_OK; base += chunk) {
-      const uint32_t cnt = (uint32_t)(base + chunk < n ? chunk : n - base);
-      if (fail(hipMemcpyAsync(d_k, ks_mont + base, (size_t)cnt * sizeof(Fr), hipMemcpyHostToDevice, st))) break;
-      if (trace) (void)hipEventRecord(e0, st);
-      setup_fixed_mul_kernel<FC><<<(cnt + 255) / 256, 256, 0, st>>>(d_tbl, wb, nwin, d_k, cnt, d_acc);
-      const uint32_t nb = (cnt + kBatch - 1) / kBatch;
-      setup_to_affine_kernel<FC><<<(nb + 255) / 256, 256, 0, st>>>(d_acc, d_aff, cnt);
-      if (trace) (void)hipEventRecord(e1, st);
-      if (fail(hipGetLastError())) break;
-      if (fail(hipMemcpyAsync(out + base * sizeof(Affine<FC>), d_aff, (size_t)cnt * sizeof(Affine<FC>),
-                              hipMemcpyDeviceToHost, st))) break;
-      if (fail(hipStreamSynchronize(st))) break;
-      if (trace) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        kern_ms += ms;
-      }
-    }
-  } while (false);
-  if (trace && rc == G16_OK)
+  if (job.fail(st.create()) || (trace && job.fail(timer.create())) || job.fail(d_tbl.alloc(tbl_n)) || job.fail(d_k.alloc(chunk)) ||
+      job.fail(d_acc.alloc(chunk)) || job.fail(d_aff.alloc(chunk)) ||
+      job.fail(hipMemcpyAsync(d_tbl.p, h_tbl, tbl_n * sizeof(Affine<FC>), hipMemcpyHostToDevice, st)))
+    return job.rc;
+  for (size_t base = 0; base < n; base += chunk) {
+    const uint32_t cnt = (uint32_t)(base + chunk < n ? chunk : n - base);
+    if (job.fail(hipMemcpyAsync(d_k.p, ks_mont + base, (size_t)cnt * sizeof(Fr), hipMemcpyHostToDevice, st))) return job.rc;
+    if (trace) (void)timer.start(st);
+    setup_fixed_mul_kernel<FC><<<(cnt + 255) / 256, 256, 0, st>>>(d_tbl.p, wb, nwin, d_k.p, cnt, d_acc.p);
+    const uint32_t nb = (cnt + kBatch - 1) / kBatch;
+    setup_to_affine_kernel<FC><<<(nb + 255) / 256, 256, 0, st>>>(d_acc.p, d_aff.p, cnt);
+    if (trace) (void)timer.stop(st);
+    if (job.fail(hipGetLastError()) ||
+        job.fail(hipMemcpyAsync(out + base * sizeof(Affine<FC>), d_aff.p, (size_t)cnt * sizeof(Affine<FC>),
+                                hipMemcpyDeviceToHost, st)) ||
+        job.fail(hipStreamSynchronize(st)))
+      return job.rc;
+    if (trace) kern_ms += timer.ms();
+  }
+  if (trace)
     fprintf(stderr, "[g16 setup] %s fixed-base: %zu scalars, kernels %.3f ms (%.1f M points/s)\n",
             sizeof(Affine<FC>) == 64 ? "G1" : "G2", n, kern_ms, kern_ms > 0 ? n / kern_ms / 1e3 : 0.0);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamSynchronize(st);
-  void* bufs[] = {d_tbl, d_k, d_acc, d_aff};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  return G16_OK;
 }
 
 }  // namespace

@@ -303,12 +303,7 @@ template <class FC>
 int sparse_device(int device, const uint8_t* const* seg, const size_t* seg_n, int nseg, const SparseTerms& t,
                   uint8_t* out, SparseStats* stats) {
   const uint64_t nout = t.start.size() - 1;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("groth16 setup: no HIP device (there is no CPU path)");
-    return G16_E_NOGPU;
-  }
-  if (device < 0 || device >= ndev) { set_error("groth16 setup: bad device ordinal"); return G16_E_ARG; }
+  if (const int rc = require_hip_device("groth16 setup", device)) return rc;
   if (nout == 0) return G16_OK;
   G16_HIP(hipSetDevice(device));
   uint64_t nbases = 0;
@@ -336,119 +331,92 @@ int sparse_device(int device, const uint8_t* const* seg, const size_t* seg_n, in
     return G16_E_ARG;
   }
   const uint64_t max_slots = 2 * ((max_terms + kChunk - 1) / kChunk) + 2;
-  Affine<FC>* d_bases = nullptr;
-  uint32_t *d_keys = nullptr, *d_refs = nullptr, *d_sb = nullptr, *d_fb = nullptr, *d_pk[2] = {nullptr, nullptr};
-  uint64_t* d_sm = nullptr;
-  Fr* d_fk = nullptr;
-  XYZZ<FC>*d_prod = nullptr, *d_out = nullptr, *d_pv[2] = {nullptr, nullptr};
-  Affine<FC>* d_aff = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = G16_OK;
-  auto fail = [&](hipError_t e) {
-    if (e == hipSuccess) return false;
-    set_error(std::string("groth16 setup (device): ") + hipGetErrorString(e));
-    rc = G16_E_HIP;
-    return true;
-  };
+  DeviceJob job("groth16 setup");
+  DeviceBuf<Affine<FC>> d_bases, d_aff;
+  DeviceBuf<uint32_t> d_keys, d_refs, d_sb, d_fb, d_pk[2];
+  DeviceBuf<uint64_t> d_sm;
+  DeviceBuf<Fr> d_fk;
+  DeviceBuf<XYZZ<FC>> d_prod, d_out, d_pv[2];
+  DeviceTimer timer;
+  DeviceStream st;
   float kern_ms = 0.f;
   HostPiece hp;
   SparseStats local;
-  do {
-    if (fail(hipStreamCreate(&st))) break;
-    if (fail(hipEventCreate(&e0)) || fail(hipEventCreate(&e1))) break;
-    if (fail(hipMalloc(&d_bases, std::max<uint64_t>(nbases, 1) * sizeof(Affine<FC>)))) break;
-    if (fail(hipMalloc(&d_keys, std::max<uint64_t>(max_terms, 1) * 4))) break;
-    if (fail(hipMalloc(&d_refs, std::max<uint64_t>(max_terms, 1) * 4))) break;
-    if (fail(hipMalloc(&d_sb, std::max<uint64_t>(max_terms, 1) * 4))) break;
-    if (fail(hipMalloc(&d_sm, std::max<uint64_t>(max_terms, 1) * 8))) break;
-    if (fail(hipMalloc(&d_prod, std::max<uint64_t>(max_terms, 1) * sizeof(XYZZ<FC>)))) break;
-    for (int k = 0; k < 2; k++) {
-      if (fail(hipMalloc(&d_pk[k], max_slots * 4))) break;
-      if (fail(hipMalloc(&d_pv[k], max_slots * sizeof(XYZZ<FC>)))) break;
+  if (job.fail(st.create()) || job.fail(timer.create()) || job.fail(d_bases.alloc(nbases)) || job.fail(d_keys.alloc(max_terms)) ||
+      job.fail(d_refs.alloc(max_terms)) || job.fail(d_sb.alloc(max_terms)) || job.fail(d_sm.alloc(max_terms)) ||
+      job.fail(d_prod.alloc(max_terms)))
+    return job.rc;
+  for (int k = 0; k < 2; k++)
+    if (job.fail(d_pk[k].alloc(max_slots)) || job.fail(d_pv[k].alloc(max_slots))) return job.rc;
+  if (job.fail(d_out.alloc(nout)) || job.fail(d_aff.alloc(nout)) ||
+      job.fail(hipMemsetAsync(d_out.p, 0, nout * sizeof(XYZZ<FC>), st)))   // zz = 0: infinity (empty sums)
+    return job.rc;
+  {
+    uint64_t off = 0;
+    for (int s = 0; s < nseg; s++) {
+      if (seg_n[s] && job.fail(hipMemcpyAsync(d_bases.p + off, seg[s], seg_n[s] * sizeof(Affine<FC>), hipMemcpyHostToDevice, st)))
+        return job.rc;
+      off += seg_n[s];
     }
-    if (rc) break;
-    if (fail(hipMalloc(&d_out, nout * sizeof(XYZZ<FC>)))) break;
-    if (fail(hipMalloc(&d_aff, nout * sizeof(Affine<FC>)))) break;
-    if (fail(hipMemsetAsync(d_out, 0, nout * sizeof(XYZZ<FC>), st))) break;   // zz = 0: infinity (empty sums)
-    {
-      uint64_t off = 0;
-      for (int s = 0; s < nseg && !rc; s++) {
-        if (seg_n[s] && fail(hipMemcpyAsync(d_bases + off, seg[s], seg_n[s] * sizeof(Affine<FC>), hipMemcpyHostToDevice, st))) break;
-        off += seg_n[s];
-      }
+  }
+  size_t fcap = 0;
+  for (size_t k = 0; k + 1 < cuts.size(); k++) {
+    if (!build_piece(t, cuts[k], cuts[k + 1], nbases, hp, local)) {
+      set_error("groth16 setup: term refers to a point outside the uploaded blocks");
+      return G16_E_ARG;
     }
-    if (rc) break;
-    size_t fcap = 0;
-    for (size_t k = 0; k + 1 < cuts.size() && !rc; k++) {
-      if (!build_piece(t, cuts[k], cuts[k + 1], nbases, hp, local)) {
-        set_error("groth16 setup: term refers to a point outside the uploaded blocks");
-        rc = G16_E_ARG;
-        break;
-      }
-      const uint32_t n = (uint32_t)hp.keys.size();
-      const uint32_t ns = (uint32_t)hp.sbase.size(), nf = (uint32_t)hp.fbase.size();
-      if (n == 0) continue;
-      if (nf > fcap) {
-        if (d_fb) (void)hipFree(d_fb);
-        if (d_fk) (void)hipFree(d_fk);
-        d_fb = nullptr; d_fk = nullptr;
-        fcap = nf;
-        if (fail(hipMalloc(&d_fb, fcap * 4)) || fail(hipMalloc(&d_fk, fcap * sizeof(Fr)))) break;
-      }
-      if (fail(hipMemcpyAsync(d_keys, hp.keys.data(), (size_t)n * 4, hipMemcpyHostToDevice, st))) break;
-      if (fail(hipMemcpyAsync(d_refs, hp.refs.data(), (size_t)n * 4, hipMemcpyHostToDevice, st))) break;
-      if (ns && (fail(hipMemcpyAsync(d_sb, hp.sbase.data(), (size_t)ns * 4, hipMemcpyHostToDevice, st)) ||
-                 fail(hipMemcpyAsync(d_sm, hp.smag.data(), (size_t)ns * 8, hipMemcpyHostToDevice, st)))) break;
-      if (nf && (fail(hipMemcpyAsync(d_fb, hp.fbase.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st)) ||
-                 fail(hipMemcpyAsync(d_fk, hp.fk.data(), (size_t)nf * sizeof(Fr), hipMemcpyHostToDevice, st)))) break;
-      if (fail(hipEventRecord(e0, st))) break;
-      if (ns) sp_short_kernel<FC><<<(ns + 255) / 256, 256, 0, st>>>(d_bases, d_sb, d_sm, ns, d_prod);
-      if (nf) sp_full_kernel<FC><<<(nf + kFullBlock - 1) / kFullBlock, kFullBlock, 0, st>>>(d_bases, d_fb, d_fk, nf, d_prod + ns);
-      // level 0, then the partials until one chunk holds them all
-      uint32_t chunks = (n + kChunk - 1) / kChunk;
-      sp_reduce_kernel<FC, true><<<(chunks + 255) / 256, 256, 0, st>>>(d_keys, d_refs, d_bases, d_prod, n, d_out, d_pk[0], d_pv[0]);
-      int cur = 0;
-      while (chunks > 1) {
-        const uint32_t m = 2 * chunks;
-        chunks = (m + kChunk - 1) / kChunk;
-        sp_reduce_kernel<FC, false><<<(chunks + 255) / 256, 256, 0, st>>>(d_pk[cur], nullptr, d_bases, d_pv[cur], m, d_out,
-                                                                          d_pk[cur ^ 1], d_pv[cur ^ 1]);
-        cur ^= 1;
-      }
-      if (fail(hipGetLastError())) break;
-      if (fail(hipEventRecord(e1, st))) break;
-      if (fail(hipStreamSynchronize(st))) break;
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      kern_ms += ms;
+    const uint32_t n = (uint32_t)hp.keys.size();
+    const uint32_t ns = (uint32_t)hp.sbase.size(), nf = (uint32_t)hp.fbase.size();
+    if (n == 0) continue;
+    if (nf > fcap) {   // (the stream is idle: every piece ends with a wait)
+      d_fb.reset();
+      d_fk.reset();
+      fcap = nf;
+      if (job.fail(d_fb.alloc(fcap)) || job.fail(d_fk.alloc(fcap))) return job.rc;
     }
-    if (rc) break;
-    if (fail(hipEventRecord(e0, st))) break;
-    const uint64_t nb = (nout + kBatch - 1) / kBatch;
-    setup_to_affine_kernel<FC><<<(unsigned)((nb + 255) / 256), 256, 0, st>>>(d_out, d_aff, (uint32_t)nout);
-    if (fail(hipGetLastError())) break;
-    if (fail(hipEventRecord(e1, st))) break;
-    if (fail(hipMemcpyAsync(out, d_aff, nout * sizeof(Affine<FC>), hipMemcpyDeviceToHost, st))) break;
-    if (fail(hipStreamSynchronize(st))) break;
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    kern_ms += ms;
-  } while (false);
-  if (st) (void)hipStreamSynchronize(st);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  void* bufs[] = {d_bases, d_keys, d_refs, d_sb, d_sm, d_fb, d_fk, d_prod, d_pk[0], d_pk[1], d_pv[0], d_pv[1], d_out, d_aff};
-  for (void* p : bufs) if (p) (void)hipFree(p);
-  if (st) (void)hipStreamDestroy(st);
-  if (rc == G16_OK && stats) {
+    if (job.fail(hipMemcpyAsync(d_keys.p, hp.keys.data(), (size_t)n * 4, hipMemcpyHostToDevice, st)) ||
+        job.fail(hipMemcpyAsync(d_refs.p, hp.refs.data(), (size_t)n * 4, hipMemcpyHostToDevice, st)))
+      return job.rc;
+    if (ns && (job.fail(hipMemcpyAsync(d_sb.p, hp.sbase.data(), (size_t)ns * 4, hipMemcpyHostToDevice, st)) ||
+               job.fail(hipMemcpyAsync(d_sm.p, hp.smag.data(), (size_t)ns * 8, hipMemcpyHostToDevice, st))))
+      return job.rc;
+    if (nf && (job.fail(hipMemcpyAsync(d_fb.p, hp.fbase.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st)) ||
+               job.fail(hipMemcpyAsync(d_fk.p, hp.fk.data(), (size_t)nf * sizeof(Fr), hipMemcpyHostToDevice, st))))
+      return job.rc;
+    if (job.fail(timer.start(st))) return job.rc;
+    if (ns) sp_short_kernel<FC><<<(ns + 255) / 256, 256, 0, st>>>(d_bases.p, d_sb.p, d_sm.p, ns, d_prod.p);
+    if (nf) sp_full_kernel<FC><<<(nf + kFullBlock - 1) / kFullBlock, kFullBlock, 0, st>>>(d_bases.p, d_fb.p, d_fk.p, nf, d_prod.p + ns);
+    // level 0, then the partials until one chunk holds them all
+    uint32_t chunks = (n + kChunk - 1) / kChunk;
+    sp_reduce_kernel<FC, true><<<(chunks + 255) / 256, 256, 0, st>>>(d_keys.p, d_refs.p, d_bases.p, d_prod.p, n, d_out.p, d_pk[0].p,
+                                                                     d_pv[0].p);
+    int cur = 0;
+    while (chunks > 1) {
+      const uint32_t m = 2 * chunks;
+      chunks = (m + kChunk - 1) / kChunk;
+      sp_reduce_kernel<FC, false><<<(chunks + 255) / 256, 256, 0, st>>>(d_pk[cur].p, nullptr, d_bases.p, d_pv[cur].p, m, d_out.p,
+                                                                        d_pk[cur ^ 1].p, d_pv[cur ^ 1].p);
+      cur ^= 1;
+    }
+    if (job.fail(hipGetLastError()) || job.fail(timer.stop(st)) || job.fail(hipStreamSynchronize(st))) return job.rc;
+    kern_ms += timer.ms();
+  }
+  if (job.fail(timer.start(st))) return job.rc;
+  const uint64_t nb = (nout + kBatch - 1) / kBatch;
+  setup_to_affine_kernel<FC><<<(unsigned)((nb + 255) / 256), 256, 0, st>>>(d_out.p, d_aff.p, (uint32_t)nout);
+  if (job.fail(hipGetLastError()) || job.fail(timer.stop(st)) ||
+      job.fail(hipMemcpyAsync(out, d_aff.p, nout * sizeof(Affine<FC>), hipMemcpyDeviceToHost, st)) ||
+      job.fail(hipStreamSynchronize(st)))
+    return job.rc;
+  kern_ms += timer.ms();
+  if (stats) {
     stats->pm1 += local.pm1;
     stats->shorts += local.shorts;
     stats->full += local.full;
     stats->zero += local.zero;
     stats->kern_ms += kern_ms;
   }
-  return rc;
+  return G16_OK;
 }
 
 }  // namespace

@@ -383,24 +383,17 @@ extern "C" void g16_verifier_destroy(g16_verifier* V) { delete V; }
 // each -> the 12 standard-form words of the pairing value the verifier kernels compute.
 extern "C" int g16_pairing_op(int device, const uint8_t* in, uint32_t count, uint8_t* out) {
   if (!in || !out) { set_error("NULL argument"); return G16_E_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device"); return G16_E_NOGPU; }
-  if (device < 0 || device >= ndev) { set_error("bad device ordinal"); return G16_E_ARG; }
+  if (const int rc = require_hip_device(device, "no HIP device", "bad device ordinal")) return rc;
   if (count == 0) return G16_OK;
   G16_HIP(hipSetDevice(device));
   PairingConsts pc;
   pairing_consts_init(pc);
-  uint32_t *d_in = nullptr, *d_out = nullptr;
-  G16_HIP(hipMalloc(&d_in, (size_t)count * 192));
-  if (hipMalloc(&d_out, (size_t)count * 384) != hipSuccess) { (void)hipFree(d_in); set_error("hipMalloc"); return G16_E_HIP; }
-  int rc = G16_OK;
-  if (hipMemcpy(d_in, in, (size_t)count * 192, hipMemcpyHostToDevice) != hipSuccess) rc = G16_E_HIP;
-  if (!rc) {
-    verify_pairing_op_kernel<<<(count + 63) / 64, 64>>>(d_in, count, pc, d_out);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(out, d_out, (size_t)count * 384, hipMemcpyDeviceToHost) != hipSuccess) rc = G16_E_HIP;
-  }
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
-  if (rc) set_error("pairing operator: HIP error");
-  return rc;
+  DeviceJob job("pairing operator");
+  DeviceBuf<uint32_t> d_in, d_out;
+  if (job.fail(d_in.alloc((size_t)count * 48)) || job.fail(d_out.alloc((size_t)count * 96)) ||
+      job.fail(hipMemcpy(d_in.p, in, (size_t)count * 192, hipMemcpyHostToDevice)))
+    return job.rc;
+  verify_pairing_op_kernel<<<(count + 63) / 64, 64>>>(d_in.p, count, pc, d_out.p);
+  if (job.fail(hipGetLastError()) || job.fail(hipMemcpy(out, d_out.p, (size_t)count * 384, hipMemcpyDeviceToHost))) return job.rc;
+  return G16_OK;
 }

@@ -147,7 +147,7 @@ int zkey_scale_g1(int device, const uint8_t* in, uint64_t n, const Fr& k_std, ui
   if (!pipe.open(n, plan.chunk, sizeof(G1Affine), sizeof(G1Affine), 0) || pipe.fail(work.alloc(plan.chunk)) ||
       pipe.fail(tbl.alloc((size_t)plan.lanes * table_entries(win))) || pipe.fail(digits.alloc(sizeof(dg.d))) ||
       pipe.fail(hipMemcpyAsync(digits.p, dg.d, sizeof(dg.d), hipMemcpyHostToDevice, pipe.stream())))
-    return pipe.rc();
+    return pipe.rc;
   return pipe.run(in, out, nullptr, st, [&](hipStream_t s, const uint8_t* d_in, uint8_t* d_out, uint8_t*, uint32_t cnt, uint64_t) {
     const G1Affine* pts = (const G1Affine*)d_in;
     const uint32_t grid = plan.grid(cnt), block = plan.block;

@@ -31,45 +31,31 @@ __global__ __launch_bounds__(256) void zkey_h_t_kernel(const Fr* __restrict__ u,
 }
 
 namespace {
-struct HJob {
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  NttTables tab;
-  Fr *d_u = nullptr, *d_rho = nullptr, *d_t = nullptr;
-  F29* d_z = nullptr;
-  ~HJob() {
-    ntt_tables_destroy(tab);
-    for (void* p : {(void*)d_u, (void*)d_rho, (void*)d_t, (void*)d_z})
-      if (p) (void)hipFree(p);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (st) (void)hipStreamDestroy(st);
-  }
+struct HJob {   // (device_job.h: the stream last)
+  NttTablesOwned tab;
+  DeviceBuf<Fr> d_u, d_rho, d_t;
+  DeviceBuf<F29> d_z;
+  DeviceTimer timer;
+  DeviceStream st;
   // u (host, N x 32 bytes) -> d_rho (N) and d_t (2N - 1), waited for; *ms = device time of tables, transform and kernel
   int form(int device, const uint8_t* u, int L, float* ms) {
     if (L < 1 || L > 27) { set_error("zkey h scalars: log_n out of range (need 1..27)"); return G16_E_ARG; }
     if (const int rc = require_hip_device("zkey h scalars", device)) return rc;
     G16_HIP(hipSetDevice(device));
     const size_t N = (size_t)1 << L;
-    G16_HIP(hipStreamCreate(&st));
-    for (hipEvent_t& e : ev) G16_HIP(hipEventCreate(&e));
-    G16_HIP(hipMalloc(&d_u, N * sizeof(Fr)));
-    G16_HIP(hipMalloc(&d_rho, N * sizeof(Fr)));
-    G16_HIP(hipMalloc(&d_t, (2 * N - 1) * sizeof(Fr)));
-    G16_HIP(hipMalloc(&d_z, N * sizeof(F29)));
-    G16_HIP(hipMemcpyAsync(d_u, u, N * sizeof(Fr), hipMemcpyHostToDevice, st));
-    G16_HIP(hipEventRecord(ev[0], st));
-    if (const int rc = ntt_tables_create(tab, L, st)) return rc;
-    F29* vz[1] = {d_z};
-    if (const int rc = ntt_import(tab, d_u, d_z, /*bitrev=*/true, st)) return rc;
-    if (const int rc = ntt_coset_scale(tab, vz, 1, st)) return rc;
-    if (const int rc = ntt_dit_forward(tab, vz, 1, st)) return rc;
-    if (const int rc = ntt_export(tab, d_z, d_rho, /*bitrev=*/false, /*scale_ninv=*/false, st)) return rc;
-    zkey_h_t_kernel<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(d_u, d_t, (uint32_t)N);
-    G16_HIP(hipGetLastError());
-    G16_HIP(hipEventRecord(ev[1], st));
-    G16_HIP(hipStreamSynchronize(st));
-    if (ms) G16_HIP(hipEventElapsedTime(ms, ev[0], ev[1]));
+    DeviceJob job("zkey h scalars");
+    if (job.fail(st.create()) || job.fail(timer.create()) || job.fail(d_u.alloc(N)) || job.fail(d_rho.alloc(N)) ||
+        job.fail(d_t.alloc(2 * N - 1)) || job.fail(d_z.alloc(N)) ||
+        job.fail(hipMemcpyAsync(d_u.p, u, N * sizeof(Fr), hipMemcpyHostToDevice, st)) || job.fail(timer.start(st)))
+      return job.rc;
+    F29* vz[1] = {d_z.p};
+    int rc = ntt_tables_create(tab, L, st);
+    if (rc || (rc = ntt_import(tab, d_u.p, d_z.p, /*bitrev=*/true, st)) || (rc = ntt_coset_scale(tab, vz, 1, st)) ||
+        (rc = ntt_dit_forward(tab, vz, 1, st)) || (rc = ntt_export(tab, d_z.p, d_rho.p, /*bitrev=*/false, /*scale_ninv=*/false, st)))
+      return rc;
+    zkey_h_t_kernel<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(d_u.p, d_t.p, (uint32_t)N);
+    if (job.fail(hipGetLastError()) || job.fail(timer.stop(st)) || job.fail(hipStreamSynchronize(st))) return job.rc;
+    if (ms) *ms = timer.ms();
     return G16_OK;
   }
 };
@@ -82,8 +68,8 @@ int zkey_verify_h(int device, const uint8_t* u, int log_n, const uint8_t* sec9, 
   if (const int rc = job.form(device, u, log_n, &ntt_ms)) return rc;
   const size_t N = (size_t)1 << log_n;
   const auto t0 = std::chrono::steady_clock::now();
-  if (const int rc = g1_multiexp_device(sec9, job.d_rho, N, 0, S)) return rc;
-  if (const int rc = g1_multiexp_device(tau_g1, job.d_t, 2 * N - 1, 0, T)) return rc;
+  if (const int rc = g1_multiexp_device(sec9, job.d_rho.p, N, 0, S)) return rc;
+  if (const int rc = g1_multiexp_device(tau_g1, job.d_t.p, 2 * N - 1, 0, T)) return rc;
   if (stats) {
     stats->ntt_ms = ntt_ms;
     stats->msm_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -103,7 +89,7 @@ extern "C" int g16_zkey_h_scalars(int device, const uint8_t* u, uint32_t log_n, 
     if (u[(N - 1) * 32 + i]) { set_error("zkey h scalars: u[N-1] must be zero"); return G16_E_ARG; }
   HJob job;
   if (const int rc = job.form(device, u, (int)log_n, nullptr)) return rc;
-  G16_HIP(hipMemcpy(rho_out, job.d_rho, N * sizeof(Fr), hipMemcpyDeviceToHost));
-  G16_HIP(hipMemcpy(t_out, job.d_t, (2 * N - 1) * sizeof(Fr), hipMemcpyDeviceToHost));
+  G16_HIP(hipMemcpy(rho_out, job.d_rho.p, N * sizeof(Fr), hipMemcpyDeviceToHost));
+  G16_HIP(hipMemcpy(t_out, job.d_t.p, (2 * N - 1) * sizeof(Fr), hipMemcpyDeviceToHost));
   return G16_OK;
 }

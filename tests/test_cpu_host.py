@@ -126,6 +126,48 @@ def test_no_cpu_fallback(amd):
     assert len(amd.synth_setup(150, 6, 120, 2, 2)[0]) > 0
 
 
+def test_no_device_texts_of_the_one_shot_routes(amd):
+    """The one-shot device routes name themselves in their own words when there is no HIP device: code -4 and the whole
+    text, route by route."""
+    import torch
+    import plonk as pk
+    if torch.cuda.is_available():
+        pytest.skip("GPU present: covered by the -m gpu tests")
+    r1cs = f.write_r1cs(24, 2, 0, synth.gen_circuit(24, 2, 12, 1)[1])   # 12 + 2 + 1 rows: domain 2^4
+
+    def trapdoor_setup():
+        amd.setup_device(0)
+        try:
+            amd.synth_setup(150, 6, 120, 2, 2)   # (batches of fewer than 64 scalars stay on the host threads)
+        finally:
+            amd.setup_device(-1)
+    ops = "no HIP device available: libg16hip has no CPU fallback"
+    g1 = bytes(64)
+    routes = [
+        (trapdoor_setup, "setup: no HIP device (g16_setup_device selected the GPU path)"),
+        (lambda: amd.groth16_setup_ptau(r1cs, amd.ptau_synth(4, 5, 6, 7, device=-1), device=0),
+         "groth16 setup: no HIP device (there is no CPU path)"),
+        (lambda: amd.ptau_prepare(amd.ptau_synth(3, 5, 6, 7, prepared=False, device=-1), device=0),
+         "ptau prepare: no HIP device (there is no CPU path)"),
+        (lambda: amd.plonk_setup(r1cs, 1, device=0), "plonk setup: no HIP device (the transforms run on the GPU)"),
+        (lambda: amd.plonk_setup_ptau(r1cs, pk.write_ptau(6, 777), device=0),
+         "plonk setup: no HIP device (the transforms run on the GPU)"),
+        (lambda: amd.pairing_op([((1, 2), ((1, 0), (2, 0)))] * 2), "no HIP device"),
+        (lambda: amd.fr_fft(bytes(8 * 32)), ops),
+        (lambda: amd.fr_fft(bytes(8 * 32), inverse=True), ops),
+        (lambda: amd.multiexp(1, g1 * 3, bytes(3 * 32)), ops),
+        (lambda: amd.multiexp(2, bytes(3 * 128), bytes(3 * 32)), ops),
+        (lambda: amd.ec_add(1, g1, g1), ops),
+        (lambda: amd.ec_add(2, bytes(128), bytes(128)), ops),
+        (lambda: amd.zkey_h_scalars([3, 0], 1), "zkey h scalars: no HIP device (there is no CPU path)"),
+        (lambda: amd.zkey_h_scalars([3, 1, 4, 1, 5, 9, 2, 0], 3), "zkey h scalars: no HIP device (there is no CPU path)"),
+    ]
+    for call, text in routes:
+        with pytest.raises(amd.G16Error) as e:
+            call()
+        assert e.value.code == -4 and str(e.value) == text, (str(e.value), text)
+
+
 @pytest.mark.parametrize("n,p,m,seed", [(24, 2, 12, 1), (200, 7, 160, 13)])
 def test_r1cs_setup_equals_synth_setup(amd, n, p, m, seed):
     """the .r1cs reader + trapdoor setup.  The synthetic circuit written as an iden3
