@@ -22,15 +22,21 @@ def plan(L, tile_log_max=10, min_tb=2):
     return tl, passes
 
 
+def tile_gidx(t, tl, lo_bits, S, tb):
+    """tile t of a pass -> the map from a tile element to its index in the vector (ntt_pass_kernel's base and gidx)."""
+    tile, T = 1 << tl, 1 << tb
+    if lo_bits == 0:
+        base = t * tile
+    else:
+        per = (1 << lo_bits) >> tb
+        base = ((t // per) << (lo_bits + S)) + (t % per) * T
+    return lambda e: base + ((e >> tb) << lo_bits) + (e & (T - 1))
+
+
 def run_pass(x, tw, L, tl, lo_bits, S, tb, dif):
-    N, tile, T = 1 << L, 1 << tl, 1 << tb
+    N, tile = 1 << L, 1 << tl
     for t in range(N // tile):
-        if lo_bits == 0:
-            base = t * tile
-        else:
-            per = (1 << lo_bits) >> tb
-            base = ((t // per) << (lo_bits + S)) + (t % per) * T
-        gidx = lambda e: base + ((e >> tb) << lo_bits) + (e & (T - 1))  # noqa: E731
+        gidx = tile_gidx(t, tl, lo_bits, S, tb)
         lds = [x[gidx(e)] for e in range(tile)]
         for k in range(S):
             st = S - 1 - k if dif else k
