@@ -664,6 +664,51 @@ int g16_wtns_check_files(const char* r1cs_path, const char* wtns_path, int devic
 int g16_r1cs_checker_timings(const g16_r1cs_checker* k, float ms[2]);
 void g16_r1cs_checker_destroy(g16_r1cs_checker* k);
 
+/* ---- wtns calculate / groth16 fullprove: the witness computed from a recorded PROGRAM (csrc/witness_program.h) -------------
+ * A witness program is a tape of how every wire of a natively built circuit follows from earlier wires -- six kinds of op
+ * (INPUT, QUAD, BITS, INV0, ISZ, CHECK) sorted by dependency level -- recorded once by the native builders, independent
+ * of any input; it takes the place of circom's .wasm calculator for these circuits and runs no .wasm.
+ * g16_nzcp_witness_program: the program of NZCPPubIdentity(params) (the parameter checks of g16_nzcp_circuit_setup); its
+ * inputs are toBeSigned (8 * MaxToBeSignedBytes words, a bit each, MSB first per byte, zero beyond the length) and
+ * toBeSignedLen, which g16_nzcp_inputs fills from the ToBeSigned bytes (out_words: 8 * max_bytes + 1 words).  The
+ * calculator trusts the toBeSigned words to be bits, as the builder's bytes are; other values give a witness that
+ * g16_wtns_check refuses.
+ * g16_nzcp_gadget_program: ONE template of the library (the names of g16_nzcp_gadget); its private inputs are the input
+ * words, in g16_nzcp_gadget's order (sha256Var: the length in bits, then the 512 << blockSpace message BITS), its output
+ * values the wires g16_wtns_calc_outputs lists.  Both images are g16_free'd; building takes seconds at the full size, so
+ * callers keep the image.
+ * g16_wtns_calc_create: the image is validated COMPLETELY on the host before any device is touched (every wire defined
+ * exactly once, every term reading a wire of a strictly lower level, every index and the level index in range):
+ * G16_E_FORMAT and "witness program: ..." otherwise.  device >= 0: the program resident there (csrc/wtns_calc.hip, one
+ * workgroup per witness, a barrier per level); device = -1: host threads (at most 16, one witness each).  Not thread-safe.
+ * g16_wtns_calc: `count` witnesses; inputs = count * n_inputs canonical 32-byte little-endian words (a word >= r:
+ * G16_E_FORMAT, "witness I: input NAME[J] is not reduced modulo the scalar field"); out_bodies (or NULL) = count * n_wires
+ * words, the body of a .wtns each; status[i] = the lowest violated check of witness i, or 0xffffffff.  A VIOLATED CHECK IS A
+ * VERDICT: the call succeeds; g16_wtns_calc_check_text words it (the builder's text for that constraint; NULL out of
+ * range).  On the device a batch runs in chunks of as many witnesses as 4 GiB hold at 32 bytes per wire, at most 1024
+ * (G16_WTNS_CALC_CHUNK=<witnesses>, read at create, overrides); only the status words come back unless out_bodies asks.
+ * g16_wtns_calc_wtns: the .wtns image of one witness (g16_free); with a violated check *wtns stays NULL.
+ * g16_wtns_calc_info: n_wires, n_public, n_inputs, levels, outputs, named inputs.  g16_wtns_calc_input: the name, first
+ * word and count of named input i.  g16_wtns_calc_timings: device ms of the last call's upload, kernels and download.
+ * g16_stage_inputs: the witness evaluated on the prover's stream INTO slot `slot` of the prover, only the public signals
+ * copied back; g16_prove_staged then works unchanged.  Refused with a text: a calculator on another device or on the host
+ * route, a program whose wire or public counts differ from the key's, a prover between g16_shard_begin and _end.  With a
+ * violated check the call succeeds, *status names it and the slot is left unstaged. */
+typedef struct g16_wtns_calculator g16_wtns_calculator;
+int g16_nzcp_witness_program(const uint32_t params[7], uint8_t** prog, size_t* len);
+int g16_nzcp_gadget_program(const char* name, const uint32_t* params, uint32_t nparams, uint8_t** prog, size_t* len);
+int g16_nzcp_inputs(const uint8_t* tbs, uint32_t len, uint32_t max_bytes, uint8_t* out_words);
+int g16_wtns_calc_create(const uint8_t* prog, size_t len, int device /* -1 = host threads */, g16_wtns_calculator** out);
+int g16_wtns_calc(g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, size_t count, uint8_t* out_bodies, uint32_t* status);
+const char* g16_wtns_calc_check_text(const g16_wtns_calculator* h, uint32_t k);
+int g16_wtns_calc_wtns(g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, uint32_t* status, uint8_t** wtns, size_t* len);
+int g16_wtns_calc_info(const g16_wtns_calculator* h, uint32_t info[6]);
+int g16_wtns_calc_outputs(const g16_wtns_calculator* h, uint32_t* wires);
+const char* g16_wtns_calc_input(const g16_wtns_calculator* h, uint32_t i, uint32_t* first, uint32_t* count);
+int g16_wtns_calc_timings(const g16_wtns_calculator* h, float ms[3]);
+void g16_wtns_calc_destroy(g16_wtns_calculator* h);
+int g16_stage_inputs(g16_prover* p, uint32_t slot, g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, uint32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

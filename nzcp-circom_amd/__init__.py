@@ -85,7 +85,10 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_ptau_challenge_contribute_files", "g16_ptau_import_response", "g16_ptau_import_response_files",
            "g16_ptau_points_from_be", "g16_ptau_points_compress", "g16_ptau_points_decompress", "g16_fq_sqrt_batch",
            "g16_r1cs_checker_create", "g16_wtns_check", "g16_wtns_check_batch", "g16_wtns_check_files",
-           "g16_r1cs_checker_timings", "g16_r1cs_checker_destroy"]
+           "g16_r1cs_checker_timings", "g16_r1cs_checker_destroy",
+           "g16_nzcp_witness_program", "g16_nzcp_gadget_program", "g16_nzcp_inputs", "g16_wtns_calc_create", "g16_wtns_calc",
+           "g16_wtns_calc_check_text", "g16_wtns_calc_wtns", "g16_wtns_calc_info", "g16_wtns_calc_outputs",
+           "g16_wtns_calc_input", "g16_wtns_calc_timings", "g16_wtns_calc_destroy", "g16_stage_inputs"]
 
 
 def load():
@@ -200,6 +203,23 @@ def load():
     lib.g16_r1cs_checker_timings.argtypes = [vp, C.POINTER(C.c_float)]
     lib.g16_r1cs_checker_destroy.argtypes = [vp]
     lib.g16_r1cs_checker_destroy.restype = None
+    u32p = C.POINTER(C.c_uint32)
+    lib.g16_nzcp_witness_program.argtypes = [u32p, C.POINTER(vp), C.POINTER(sz)]
+    lib.g16_nzcp_gadget_program.argtypes = [C.c_char_p, u32p, C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
+    lib.g16_nzcp_inputs.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p]
+    lib.g16_wtns_calc_create.argtypes = [C.c_char_p, sz, C.c_int, C.POINTER(vp)]
+    lib.g16_wtns_calc.argtypes = [vp, C.c_char_p, sz, sz, C.c_char_p, u32p]
+    lib.g16_wtns_calc_check_text.argtypes = [vp, C.c_uint32]
+    lib.g16_wtns_calc_check_text.restype = C.c_char_p
+    lib.g16_wtns_calc_wtns.argtypes = [vp, C.c_char_p, sz, u32p, C.POINTER(vp), C.POINTER(sz)]
+    lib.g16_wtns_calc_info.argtypes = [vp, u32p]
+    lib.g16_wtns_calc_outputs.argtypes = [vp, u32p]
+    lib.g16_wtns_calc_input.argtypes = [vp, C.c_uint32, u32p, u32p]
+    lib.g16_wtns_calc_input.restype = C.c_char_p
+    lib.g16_wtns_calc_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.g16_wtns_calc_destroy.argtypes = [vp]
+    lib.g16_wtns_calc_destroy.restype = None
+    lib.g16_stage_inputs.argtypes = [vp, C.c_uint32, vp, C.c_char_p, sz, u32p]
     lib.g16_blake2b512.argtypes = [C.c_char_p, sz, C.c_char_p]
     lib.g16_zkey_hash_to_g2.argtypes = [C.c_char_p, C.c_char_p]
     lib.g16_r1cs_setup.argtypes = [C.c_char_p, sz, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
@@ -291,6 +311,14 @@ class Prover:
 
     def stage(self, slot, wtns):
         _check(load().g16_stage_witness(self._h, slot, wtns, len(wtns)))
+
+    def stage_inputs(self, slot, calc, inputs):
+        """The witness of `inputs` computed on this prover's device into `slot` (WitnessCalculator on the same device):
+        -> status (NO_CHECK = staged; else the violated check, and the slot is left unstaged)."""
+        words = calc.words(inputs)
+        st = C.c_uint32()
+        _check(load().g16_stage_inputs(self._h, slot, calc._h, words, len(words) // 32, C.byref(st)))
+        return st.value
 
     def prove_staged(self, slot, r=None, s=None):
         pr, pub = Proof(), self._pub()
@@ -404,6 +432,110 @@ class R1csChecker:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             load().g16_r1cs_checker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+NO_CHECK = 0xffffffff   # the status of a witness that violates no check
+
+
+def nzcp_witness_program(params):
+    """The witness program of NZCPPubIdentity(*params): bytes for WitnessCalculator (takes seconds; keep them)."""
+    ptr, n = C.c_void_p(), C.c_size_t()
+    _check(load().g16_nzcp_witness_program((C.c_uint32 * 7)(*params), C.byref(ptr), C.byref(n)))
+    return _take(ptr, n)
+
+
+def nzcp_gadget_program(name, params):
+    """The witness program of one template of the library (the names and parameters of nzcp_gadget)."""
+    ptr, n = C.c_void_p(), C.c_size_t()
+    prm = (C.c_uint32 * max(1, len(params)))(*params)
+    _check(load().g16_nzcp_gadget_program(name.encode(), prm, len(params), C.byref(ptr), C.byref(n)))
+    return _take(ptr, n)
+
+
+def nzcp_inputs(tbs, max_bytes):
+    """The input words of an NZCP witness program for the ToBeSigned bytes: (8 * max_bytes + 1) * 32 bytes."""
+    out = C.create_string_buffer((8 * max_bytes + 1) * 32)
+    _check(load().g16_nzcp_inputs(bytes(tbs), len(tbs), max_bytes, out))
+    return out.raw
+
+
+class WitnessCalculator:
+    """A resident witness program (g16_wtns_calc): device = a HIP device ordinal, or -1 = host threads.  Inputs are
+    bytes of 32-byte little-endian words, a list of ints, or a dict of the program's named inputs."""
+
+    def __init__(self, prog, device=0):
+        lib = load()
+        if isinstance(prog, (str, os.PathLike)):
+            with open(prog, "rb") as f:
+                prog = f.read()
+        self._h = C.c_void_p()
+        _check(lib.g16_wtns_calc_create(prog, len(prog), device, C.byref(self._h)))
+        info = (C.c_uint32 * 6)()
+        _check(lib.g16_wtns_calc_info(self._h, info))
+        self.n_wires, self.n_public, self.n_inputs, self.n_levels = info[0], info[1], info[2], info[3]
+        outs = (C.c_uint32 * max(1, info[4]))()
+        _check(lib.g16_wtns_calc_outputs(self._h, outs))
+        self.outputs = list(outs[:info[4]])
+        self.inputs = {}
+        for i in range(info[5]):
+            first, count = C.c_uint32(), C.c_uint32()
+            name = lib.g16_wtns_calc_input(self._h, i, C.byref(first), C.byref(count))
+            self.inputs[name.decode()] = (first.value, count.value)
+
+    def words(self, inputs):
+        if isinstance(inputs, (bytes, bytearray)):
+            return bytes(inputs)
+        if isinstance(inputs, dict):
+            vals = [0] * self.n_inputs
+            for name, v in inputs.items():
+                if name not in self.inputs:
+                    raise G16Error(-1, f"wtns calc: the program has no input {name}")
+                first, count = self.inputs[name]
+                v = list(v) if isinstance(v, (list, tuple)) else [v]
+                if len(v) != count:
+                    raise G16Error(-1, f"wtns calc: input {name} takes {count} words, {len(v)} given")
+                vals[first:first + count] = [int(x) for x in v]
+            inputs = vals
+        return b"".join(int(x).to_bytes(32, "little") for x in inputs)
+
+    def calculate_batch(self, inputs_list, want_words=True):
+        """-> [(words or None, status)]: words = the n_wires * 32 bytes of a .wtns body (None when not asked for)."""
+        blob = b"".join(self.words(x) for x in inputs_list)
+        n = len(inputs_list)
+        out = C.create_string_buffer(max(1, n * self.n_wires * 32)) if want_words else None
+        st = (C.c_uint32 * max(1, n))()
+        _check(load().g16_wtns_calc(self._h, blob, len(blob) // 32 // n if n else self.n_inputs, n, out, st))
+        w = self.n_wires * 32
+        return [(out.raw[i * w:(i + 1) * w] if want_words else None, st[i]) for i in range(n)]
+
+    def calculate(self, inputs, want_words=True):
+        """-> (words or None, status); status = NO_CHECK or the lowest violated check (check_text words it)."""
+        return self.calculate_batch([inputs], want_words)[0]
+
+    def wtns(self, inputs):
+        """The .wtns image; a violated check raises G16Error with the check's text."""
+        words = self.words(inputs)
+        st, ptr, n = C.c_uint32(), C.c_void_p(), C.c_size_t()
+        _check(load().g16_wtns_calc_wtns(self._h, words, len(words) // 32, C.byref(st), C.byref(ptr), C.byref(n)))
+        if st.value != NO_CHECK:
+            raise G16Error(-5, "constraint not satisfied: " + (self.check_text(st.value) or "?"))
+        return _take(ptr, n)
+
+    def check_text(self, k):
+        t = load().g16_wtns_calc_check_text(self._h, k)
+        return None if t is None else t.decode()
+
+    def timings(self):
+        ms = (C.c_float * 3)()
+        _check(load().g16_wtns_calc_timings(self._h, ms))
+        return {"upload_ms": ms[0], "kernel_ms": ms[1], "download_ms": ms[2]}
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            load().g16_wtns_calc_destroy(self._h)
             self._h = C.c_void_p()
 
     __del__ = close

@@ -136,7 +136,9 @@ int run_gadget(CBuilder& cb, const std::string& name, const uint32_t* prm, uint3
   auto input = [&]() -> V {   // a private input wire
     const uint64_t v = pos_in < nin ? in[pos_in] : 0;
     pos_in++;
-    return cb.of_wire(cb.new_wire(v));
+    const uint32_t wire = cb.new_wire(v);
+    if (cb.rec) cb.rec->input(wire);
+    return cb.of_wire(wire);
   };
   auto inputs = [&](uint32_t n) { std::vector<V> r; for (uint32_t i = 0; i < n; i++) r.push_back(input()); return r; };
   if (name == "getType") { outs = {cb.get_type(input())}; }
@@ -199,9 +201,11 @@ int run_gadget(CBuilder& cb, const std::string& name, const uint32_t* prm, uint3
     std::vector<Bit> bits((size_t)512 << bs, bit_const(0));
     const uint32_t out_base = cb.new_wire(0);
     for (int i = 1; i < 256; i++) cb.new_wire(0);
-    for (uint32_t j = 0; j + 1 < nin && j < (64u << bs); j++)
+    // (a recorded program takes every bit of the buffer as an input word of its own, whatever this call was given)
+    for (uint32_t j = 0; (cb.rec || j + 1 < nin) && j < (64u << bs); j++)
       for (int i = 0; i < 8; i++) {
-        const uint32_t wire = cb.new_wire((in[1 + j] >> (7 - i)) & 1);
+        const uint32_t wire = cb.new_wire(j + 1 < nin ? (in[1 + j] >> (7 - i)) & 1 : 0);
+        if (cb.rec) cb.rec->input(wire);
         cb.boolean(wire);
         bits[(size_t)j * 8 + (size_t)i] = bit_wire(wire);
       }
@@ -303,4 +307,52 @@ extern "C" int g16_nzcp_circuit_setup(const uint32_t params[7], const uint8_t* t
   const int64_t bad = first_unsatisfied_row(cb);
   if (bad >= 0) { set_error("internal: R1CS row " + std::to_string(bad) + " is not satisfied by the computed witness"); return G16_E_HIP; }
   return emit(cb, "nzcp circuit too large", seed, threads, zkey, zkey_len, wtns, wtns_len, vkey, vkey_len, r1cs, r1cs_len);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Witness programs (witness_program.h): the builders above run once on an all-zero input with a recorder attached;
+// what they record does not depend on the input (which wires exist, and what each is a function of, is decided by
+// the template parameters alone).  The two builder-internal `violate` texts ("a bit-valued expression is not small",
+// "exp is not a small integer") are not checks of the program: with bit-valued toBeSigned words they cannot fire.
+extern "C" int g16_nzcp_witness_program(const uint32_t params[7], uint8_t** prog, size_t* len) {
+  if (!prog || !len) { set_error("NULL argument"); return G16_E_ARG; }
+  if (!params || params[1] == 0 || params[1] > 503 || params[6] < 2 || params[6] > 6) {
+    set_error("nzcp circuit: bad arguments");
+    return G16_E_ARG;
+  }
+  return no_bad_alloc("witness program", [&]() -> int {
+    WpRecorder rec;
+    CBuilder cb;
+    cb.rec = &rec;
+    const uint8_t none = 0;
+    cb.nzcp_pub_identity(params[0] != 0, params[1], params[2], params[3], params[4], params[5], params[6], &none, 0);
+    const Buf z = rec.finish(cb.c.n, cb.c.p);
+    if (!z.p) { set_error("witness program: out of memory"); return G16_E_STATE; }
+    z.give(prog, len);
+    return G16_OK;
+  });
+}
+
+// One template of the library as a program: its private inputs are the program's input words, in run_gadget's order
+// (sha256Var: the length in bits, then the 512 << blockSpace message BITS, MSB first per byte); every output value is
+// settled on a wire of its own, listed in the program's outputs.
+extern "C" int g16_nzcp_gadget_program(const char* name, const uint32_t* params, uint32_t nparams, uint8_t** prog, size_t* len) {
+  if (!name || !prog || !len || (nparams && !params)) { set_error("NULL argument"); return G16_E_ARG; }
+  return no_bad_alloc("witness program", [&]() -> int {
+    WpRecorder rec;
+    CBuilder cb;
+    cb.rec = &rec;
+    std::vector<CBuilder::V> outs;
+    if (const int rc = run_gadget(cb, name, params, nparams, nullptr, 0, outs)) return rc;
+    rec.name_inputs("in", rec.n_inputs);
+    for (const CBuilder::V& o : outs) {
+      const uint32_t wire = cb.new_wire_fr(o.val);
+      rec.quad(wire, {}, {}, o.lin.t);
+      rec.outputs.push_back(wire);
+    }
+    const Buf z = rec.finish((uint32_t)cb.w.size(), 0);
+    if (!z.p) { set_error("witness program: out of memory"); return G16_E_STATE; }
+    z.give(prog, len);
+    return G16_OK;
+  });
 }

@@ -97,6 +97,7 @@ struct CBuilder : ShaBuilder {
   // z = a * b: a fresh wire and one row
   V mul(const V& a, const V& b) {
     const uint32_t z = new_wire_fr(fp_mul(a.val, b.val));
+    if (rec) rec->quad(z, a.lin.t, b.lin.t, {});
     Lin cc;
     cc.t.push_back({z, 1});
     constrain(a.lin, b.lin, cc);
@@ -105,6 +106,7 @@ struct CBuilder : ShaBuilder {
   // a === b  (circom `===`, "hardcore_assert"): one linear row; remembered when the witness violates it
   void assert_eq(const V& a, const V& b, const char* what) {
     if (!fr_eq(a.val, b.val)) violate(what);
+    if (rec) rec->check(vsub(a, b).lin.t, what);
     Lin one, z;
     one.t.push_back({0u, 1});
     constrain(vsub(a, b).lin, one, z);
@@ -113,6 +115,7 @@ struct CBuilder : ShaBuilder {
   V settle(const V& x) {
     if (x.lin.t.size() <= 4) return x;
     const uint32_t z = new_wire_fr(x.val);
+    if (rec) rec->quad(z, {}, {}, x.lin.t);
     V r = of_wire(z);
     Lin one, zero;
     one.t.push_back({0u, 1});
@@ -126,6 +129,7 @@ struct CBuilder : ShaBuilder {
     const bool z = fp_is_zero(x.val);
     const uint32_t inv = new_wire_fr(z ? fp_zero<FrParams>() : fp_inv(x.val));
     const uint32_t out = new_wire(z ? 1 : 0);
+    if (rec) { rec->inv0(inv, x.lin.t); rec->isz(out, x.lin.t); }
     Lin cc;                                   // in * inv = 1 - out
     cc.t.push_back({0u, 1});
     cc.t.push_back({out, -1});
@@ -142,13 +146,16 @@ struct CBuilder : ShaBuilder {
     const bool fits = small_of(x.val, v) && (n >= 63 || v < ((uint64_t)1 << n));
     if (!fits) { violate(what); v = 0; }
     std::vector<Bit> bits((size_t)n);
+    std::vector<uint32_t> targets;
     Lin sum;
     for (int i = 0; i < n; i++) {
       const uint32_t wire = new_wire((v >> i) & 1);
+      targets.push_back(wire);
       boolean(wire);
       bits[(size_t)i] = bit_wire(wire);
       sum.t.push_back({wire, (int64_t)1 << i});
     }
+    if (rec) rec->bits(targets.data(), (uint32_t)n, x.lin.t, what);
     V s;
     s.lin = sum;
     s.val = x.val;
@@ -419,6 +426,7 @@ struct CBuilder : ShaBuilder {
         if (i == 0) bitv = vadd(bitv, eq);                     // the 0x80 marker (lt and eq exclude each other)
         // a boolean wire for the padded bit (the compression gadgets take wires)
         const uint32_t wire = new_wire((uint64_t)val_small(bitv));
+        if (rec) rec->quad(wire, {}, {}, bitv.lin.t);
         Lin one, zero;
         one.t.push_back({0u, 1});
         constrain(vsub(bitv, of_wire(wire)).lin, one, zero);
@@ -437,6 +445,7 @@ struct CBuilder : ShaBuilder {
         const V lv = mul(is_final[(size_t)blk], of_bit(lb[(size_t)i]));
         const V sum = vadd(of_bit(W16[15][i]), lv);            // the padded data is 0 there when the block is final
         const uint32_t wire = new_wire((uint64_t)val_small(sum));
+        if (rec) rec->quad(wire, {}, {}, sum.lin.t);
         boolean(wire);
         Lin one, zero;
         one.t.push_back({0u, 1});
@@ -453,6 +462,7 @@ struct CBuilder : ShaBuilder {
         for (uint32_t b = 0; b < nblk; b++) s = vadd(s, mul(is_final[(size_t)b], of_bit(states[(size_t)b][(size_t)j][i])));
         const uint32_t wire = out_base + 32 * (uint32_t)j + (uint32_t)(31 - i);
         w[wire] = (uint64_t)val_small(s);
+        if (rec) rec->quad(wire, {}, {}, s.lin.t);
         Lin one, zero;
         one.t.push_back({0u, 1});
         constrain(vsub(s, of_wire(wire)).lin, one, zero);
@@ -480,10 +490,16 @@ struct CBuilder : ShaBuilder {
     for (uint32_t k = 0; k < max_bits; k++) {
       const uint32_t byte = k / 8;
       const uint32_t wire = new_wire(byte < tbs_len ? (tbs[byte] >> (7 - (k & 7))) & 1 : 0);
+      if (rec) rec->input(wire);
       boolean(wire);                                          // :470  toBeSigned[i] * (toBeSigned[i] - 1) === 0
       in_bits[(size_t)k] = bit_wire(wire);
     }
     const V len = of_wire(new_wire(tbs_len));
+    if (rec) {
+      rec->name_inputs("toBeSigned", max_bits);
+      rec->input(len.lin.t[0].first);
+      rec->name_inputs("toBeSignedLen", 1);
+    }
     // :477  toBeSignedLen < MaxToBeSignedBytes + 1
     assert_eq(less_than(log2_floor(max_tbs_bytes + 1) + 1, len, konst((int64_t)max_tbs_bytes + 1), "toBeSignedLen"),
               konst(1), "toBeSignedLen exceeds MaxToBeSignedBytes");
@@ -508,6 +524,7 @@ struct CBuilder : ShaBuilder {
       uint64_t e = 0;
       if (!small_of(edu.value.val, e)) violate("exp is not a small integer");
       w[exp_wire] = e;
+      if (rec) rec->quad(exp_wire, {}, {}, edu.value.lin.t);
       Lin one, zero;
       one.t.push_back({0u, 1});
       constrain(vsub(edu.value, of_wire(exp_wire)).lin, one, zero);
@@ -525,6 +542,8 @@ struct CBuilder : ShaBuilder {
       for (int j = 0; j < 8; j++) cbits[(size_t)k * 8 + (size_t)(7 - j)] = b[(size_t)j];
     }
     sha256_var(cbits, vscale(cc.result_len, 8), 1, 1);
+    if (rec)
+      for (uint32_t i = 1; i <= 513; i++) rec->outputs.push_back(i);
     c.n = (uint32_t)w.size();
     c.p = 513;
     c.m = (uint32_t)c.rowA.size() - 1;

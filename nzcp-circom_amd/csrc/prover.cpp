@@ -16,6 +16,7 @@
 #include "../../include/g16_prover.h"
 #include "binfile.h"
 #include "internal.h"
+#include "witness_program.h"
 
 namespace g16 {
 
@@ -1110,6 +1111,44 @@ int g16_prove_staged(g16_prover* p, uint32_t slot, const uint8_t r[32], const ui
   std::lock_guard<std::mutex> lk(p->mu);
   if (int rc = shard_guard(p)) return rc;
   return prove_staged_locked(p, slot, r, s, out, pub);
+}
+
+// The witness computed where the prover reads it: the calculator's program runs on the main stream into the slot, and
+// only the status word and the public signals come back.
+int g16_stage_inputs(g16_prover* p, uint32_t slot, g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, uint32_t* status) {
+  if (!p || !h || !status || (n_inputs && !inputs)) { set_error("NULL argument"); return G16_E_ARG; }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (int rc = shard_guard(p)) return rc;
+  if (!h->dev) { set_error("stage inputs: the calculator runs on the host route (create it on the prover's device)"); return G16_E_STATE; }
+  if (wcalc_device_id(h->dev) != p->device) {
+    set_error("stage inputs: the calculator is on device " + std::to_string(wcalc_device_id(h->dev)) + ", the prover on device " +
+              std::to_string(p->device));
+    return G16_E_STATE;
+  }
+  if (h->p.n_wires != p->nVars || h->p.n_public != p->nPublic) {
+    set_error("stage inputs: the program has " + std::to_string(h->p.n_wires) + " wires and " + std::to_string(h->p.n_public) +
+              " public signals, the key " + std::to_string(p->nVars) + " and " + std::to_string(p->nPublic));
+    return G16_E_STATE;
+  }
+  if (slot >= 65536) { set_error("slot out of range"); return G16_E_ARG; }
+  if (int rc = wcalc_check_inputs(h, inputs, n_inputs, 1)) return rc;
+  G16_HIP(hipSetDevice(p->device));
+  if (p->slot_dev.size() <= slot) { p->slot_dev.resize(slot + 1, nullptr); p->slot_pub.resize(slot + 1); }
+  if (!p->slot_dev[slot]) G16_HIP(hipMalloc(&p->slot_dev[slot], (size_t)p->nVars * sizeof(Fr)));
+  int rc = wcalc_device_run_into(h->dev, inputs, p->slot_dev[slot], p->st, status);
+  if (!rc && *status == 0xffffffffu) {
+    p->slot_pub[slot].resize((size_t)p->nPublic * 32);
+    if (p->nPublic) {
+      const hipError_t e = hipMemcpy(p->slot_pub[slot].data(), p->slot_dev[slot] + 1, (size_t)p->nPublic * 32, hipMemcpyDeviceToHost);
+      if (e != hipSuccess) { set_error(std::string("stage inputs: ") + hipGetErrorString(e)); rc = G16_E_HIP; }
+    }
+    if (!rc) return G16_OK;
+  }
+  // a violated check, or a failure: the slot holds no witness to prove
+  (void)hipStreamSynchronize(p->st);
+  (void)hipFree(p->slot_dev[slot]);
+  p->slot_dev[slot] = nullptr;
+  return rc;
 }
 
 int g16_prove(g16_prover* p, const uint8_t* wtns, size_t wtns_len, const uint8_t r[32], const uint8_t s[32],

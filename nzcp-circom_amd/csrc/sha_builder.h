@@ -4,6 +4,7 @@
 #include <array>
 
 #include "circuit.h"
+#include "witness_program.h"
 
 namespace g16 {
 
@@ -17,6 +18,7 @@ inline bool bit_is_const(const Bit& x) { return x.a == 0; }
 struct ShaBuilder {
   std::vector<uint64_t> w;       // witness: one bit per wire (the NZCP circuit's `exp` output is the one wider value)
   Circuit c;
+  WpRecorder* rec = nullptr;     // when set, every wire's computation is appended to it (witness_program.h); rows and wires are the same either way
   FrM pow2[40];                  // 2^k in Montgomery form, and small-coefficient cache
   ShaBuilder() {
     w.push_back(1);              // wire 0
@@ -56,7 +58,9 @@ struct ShaBuilder {
     if (bit_is_const(y)) return y.b ? bit_not(x) : x;
     const uint32_t z = new_wire(val(x) ^ val(y));
     Lin a, b, cc;                 // (2x) * y = x + y - z
-    add(a, x, 2); add(b, y, 1); add(cc, x, 1); add(cc, y, 1); cc.t.push_back({z, -1});
+    add(a, x, 2); add(b, y, 1); add(cc, x, 1); add(cc, y, 1);
+    if (rec) { Lin m; add(m, x, -2); rec->quad(z, m.t, b.t, cc.t); }   // z = (-2x) y + x + y
+    cc.t.push_back({z, -1});
     constrain(a, b, cc);
     return bit_wire(z);
   }
@@ -65,6 +69,7 @@ struct ShaBuilder {
     const uint32_t o = new_wire(val(e) ? val(f) : val(g));
     Lin a, b, cc;
     add(a, e, 1); add(b, f, 1); add(b, g, -1); cc.t.push_back({o, 1}); add(cc, g, -1);
+    if (rec) { Lin gl; add(gl, g, 1); rec->quad(o, a.t, b.t, gl.t); }
     constrain(a, b, cc);
     return bit_wire(o);
   }
@@ -73,12 +78,14 @@ struct ShaBuilder {
     {
       Lin a, b, cc;
       add(a, x, 1); add(b, y, 1); cc.t.push_back({mid, 1});
+      if (rec) rec->quad(mid, a.t, b.t, {});
       constrain(a, b, cc);
     }
     const int vx = val(x), vy = val(y), vz = val(z);
     const uint32_t o = new_wire((vx & vy) | (vx & vz) | (vy & vz));
     Lin a, b, cc;
     add(a, z, 1); add(b, x, 1); add(b, y, 1); b.t.push_back({mid, -2}); cc.t.push_back({o, 1}); cc.t.push_back({mid, -1});
+    if (rec) rec->quad(o, a.t, b.t, {{mid, 1}});
     constrain(a, b, cc);
     return bit_wire(o);
   }
@@ -103,15 +110,19 @@ struct ShaBuilder {
     for (const Word& o : ops)
       for (int i = 0; i < 32; i++) add(a, o[i], (int64_t)1 << i);
     Word r;
+    uint32_t targets[64];
+    const Lin operands = rec ? a : Lin();
     for (int i = 0; i < 32 + ncarry; i++) {
       const int v = (int)((sum >> i) & 1);
       uint32_t wire;
       if (i < 32 && out_wires) { wire = out_wires[i]; w[wire] = (uint64_t)v; }
       else wire = new_wire(v);
       boolean(wire);
+      targets[i] = wire;
       a.t.push_back({wire, -((int64_t)1 << i)});
       if (i < 32) r[i] = bit_wire(wire);
     }
+    if (rec) rec->bits(targets, (uint32_t)(32 + ncarry), operands.t, nullptr);   // (bit operands: the sum always fits)
     b.t.push_back({0u, 1});
     constrain(a, b, z);
     return r;

@@ -1,0 +1,175 @@
+// Witness calculation on the device (g16_wtns_calc): a witness program (witness_program.h) evaluated level by level.
+//
+// The program -- ops, terms, coefficient table, targets, level index -- stays resident.  ONE workgroup of kWcalcThreads
+// threads computes one witness: its threads stride over the ops of a level (wtns_calc_eval.cuh: the same code the host
+// route runs -- the 8 x 32 Montgomery arithmetic of fp.cuh, with two measured shortcuts for small values: a table of the
+// inverses of small integers and a 64 x 64 product for a small wire times an integer coefficient), then
+// meet at a barrier, because the next level reads what this one wrote.  The loop bounds are the level index alone, which is the same for every thread whatever the data, so
+// every thread meets every barrier.  No workgroup waits for another; nothing spins on memory.
+//
+// Wire values live in global memory (32 bytes per wire: the canonical standard-form words of a .wtns body), written and
+// read by the one workgroup that owns the witness.  A workgroup runs on one CU, whose L1 serves all its waves, so the
+// stores of a level are visible to the loads of the next once every wave has drained them and passed the barrier:
+// __syncthreads() is that (workgroup-scope release, s_barrier, acquire).
+//
+// Status: the lowest violated check of a witness, atomicMin on one word per witness (0xffffffff: none).
+#include "witness_program.h"
+
+namespace g16 {
+
+static constexpr int kWcalcThreads = 256;
+
+__global__ __launch_bounds__(kWcalcThreads) void wtns_calc_kernel(WpView p, const uint32_t* __restrict__ levels, uint32_t n_levels,
+                                                                  const Fr* __restrict__ inputs, uint32_t n_inputs, Fr* w,
+                                                                  uint32_t n_wires, uint32_t* __restrict__ status) {
+  const uint32_t y = blockIdx.x;
+  w += (size_t)y * n_wires;
+  inputs += (size_t)y * n_inputs;
+  if (threadIdx.x == 0) w[0] = wp_small(1);
+  __syncthreads();
+  uint32_t lo = levels[0];
+  for (uint32_t l = 1; l <= n_levels; l++) {   // (uniform: the header's counts only)
+    const uint32_t hi = levels[l];
+    uint32_t worst = kWpNoCheck;
+    for (uint32_t k = lo + threadIdx.x; k < hi; k += kWcalcThreads) {
+      const uint32_t c = wp_eval_op(p, k, inputs, w);
+      worst = c < worst ? c : worst;
+    }
+    if (worst != kWpNoCheck) atomicMin(status + y, worst);
+    lo = hi;
+    __syncthreads();
+  }
+}
+
+struct WcalcDevice {
+  int device = 0;
+  uint32_t n_wires = 0, n_inputs = 0, n_levels = 0, chunk = 1, cap = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  WpOp* ops = nullptr;
+  WpEvalTerm* terms = nullptr;
+  Fr* coefs = nullptr;
+  int64_t* icoefs = nullptr;
+  Fr* inv_small = nullptr;
+  uint32_t *targets = nullptr, *levels = nullptr;
+  Fr *d_w = nullptr, *d_in = nullptr;   // cap * n_wires words; cap * n_inputs words
+  uint32_t *d_status = nullptr, *h_status = nullptr;   // cap words each; h_status pinned
+};
+
+template <class T> static int wcalc_upload(T** dst, const std::vector<T>& src) {
+  G16_HIP(hipMalloc(dst, (src.size() + 1) * sizeof(T)));
+  if (!src.empty()) G16_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return G16_OK;
+}
+
+static void wcalc_free_batch(WcalcDevice* d) {
+  (void)hipFree(d->d_w); (void)hipFree(d->d_in); (void)hipFree(d->d_status);
+  if (d->h_status) (void)hipHostFree(d->h_status);
+  d->d_w = d->d_in = nullptr;
+  d->d_status = d->h_status = nullptr;
+  d->cap = 0;
+}
+
+void wcalc_device_destroy(WcalcDevice* d) {
+  if (!d) return;
+  (void)hipSetDevice(d->device);
+  if (d->st) (void)hipStreamSynchronize(d->st);
+  wcalc_free_batch(d);
+  (void)hipFree(d->ops); (void)hipFree(d->terms); (void)hipFree(d->coefs); (void)hipFree(d->icoefs); (void)hipFree(d->inv_small);(void)hipFree(d->targets); (void)hipFree(d->levels);
+  for (hipEvent_t e : d->ev)
+    if (e) (void)hipEventDestroy(e);
+  if (d->st) (void)hipStreamDestroy(d->st);
+  delete d;
+}
+
+int wcalc_device_id(const WcalcDevice* d) { return d->device; }
+
+// the batch buffers hold `cap` witnesses; they grow to the largest chunk asked for (at most d->chunk)
+static int wcalc_reserve(WcalcDevice* d, uint32_t cnt) {
+  if (cnt <= d->cap) return G16_OK;
+  wcalc_free_batch(d);
+  G16_HIP(hipMalloc(&d->d_w, ((size_t)cnt * d->n_wires + 1) * sizeof(Fr)));
+  G16_HIP(hipMalloc(&d->d_in, ((size_t)cnt * d->n_inputs + 1) * sizeof(Fr)));
+  G16_HIP(hipMalloc(&d->d_status, (size_t)cnt * 4));
+  G16_HIP(hipHostMalloc((void**)&d->h_status, (size_t)cnt * 4));
+  d->cap = cnt;
+  return G16_OK;
+}
+
+static int wcalc_device_fill(WcalcDevice* d, const WitnessProgram& p) {
+  G16_HIP(hipSetDevice(d->device));
+  G16_HIP(hipStreamCreate(&d->st));
+  for (hipEvent_t& e : d->ev) G16_HIP(hipEventCreate(&e));
+  int rc;
+  if ((rc = wcalc_upload(&d->ops, p.ops)) || (rc = wcalc_upload(&d->terms, p.eterms)) || (rc = wcalc_upload(&d->coefs, p.coefs)) || (rc = wcalc_upload(&d->icoefs, p.icoefs)) || (rc = wcalc_upload(&d->inv_small, p.inv_small)) ||
+      (rc = wcalc_upload(&d->targets, p.targets)) || (rc = wcalc_upload(&d->levels, p.levels)))
+    return rc;
+  return wcalc_reserve(d, 1);
+}
+
+int wcalc_device_create(int device, const WitnessProgram& p, uint32_t chunk, WcalcDevice** out) {
+  if (const int rc = require_hip_device(device, "wtns calc: no HIP device (device = -1 is the host route)", "wtns calc: bad device ordinal"))
+    return rc;
+  WcalcDevice* d = new WcalcDevice;
+  d->device = device;
+  d->n_wires = p.n_wires;
+  d->n_inputs = p.n_inputs;
+  d->n_levels = (uint32_t)p.levels.size() - 1;
+  d->chunk = chunk < 1 ? 1 : chunk;
+  if (const int rc = wcalc_device_fill(d, p)) {
+    wcalc_device_destroy(d);
+    return rc;
+  }
+  *out = d;
+  return G16_OK;
+}
+
+// cnt witnesses whose inputs are at d_in, into d_w, on st (enqueue only)
+static int wcalc_launch(WcalcDevice* d, const Fr* d_in, Fr* d_w, uint32_t* d_status, uint32_t cnt, hipStream_t st) {
+  G16_HIP(hipMemsetAsync(d_status, 0xff, (size_t)cnt * 4, st));
+  const WpView v{d->ops, d->terms, d->coefs, d->icoefs, d->targets, d->inv_small};
+  wtns_calc_kernel<<<cnt, kWcalcThreads, 0, st>>>(v, d->levels, d->n_levels, d_in, d->n_inputs, d_w, d->n_wires, d_status);
+  G16_HIP(hipGetLastError());
+  return G16_OK;
+}
+
+int wcalc_device_run(WcalcDevice* d, const uint8_t* inputs, size_t count, uint8_t* out_bodies, uint32_t* status, float ms[3]) {
+  G16_HIP(hipSetDevice(d->device));
+  if (ms) ms[0] = ms[1] = ms[2] = 0.f;
+  for (size_t at = 0; at < count; at += d->chunk) {
+    const uint32_t cnt = (uint32_t)(count - at < d->chunk ? count - at : d->chunk);
+    if (const int rc = wcalc_reserve(d, cnt)) return rc;
+    G16_HIP(hipEventRecord(d->ev[0], d->st));
+    if (d->n_inputs)
+      G16_HIP(hipMemcpyAsync(d->d_in, inputs + at * d->n_inputs * 32, (size_t)cnt * d->n_inputs * 32, hipMemcpyHostToDevice, d->st));
+    G16_HIP(hipEventRecord(d->ev[1], d->st));
+    if (const int rc = wcalc_launch(d, d->d_in, d->d_w, d->d_status, cnt, d->st)) return rc;
+    G16_HIP(hipEventRecord(d->ev[2], d->st));
+    G16_HIP(hipMemcpyAsync(d->h_status, d->d_status, (size_t)cnt * 4, hipMemcpyDeviceToHost, d->st));
+    if (out_bodies)
+      G16_HIP(hipMemcpyAsync(out_bodies + at * d->n_wires * 32, d->d_w, (size_t)cnt * d->n_wires * 32, hipMemcpyDeviceToHost, d->st));
+    G16_HIP(hipEventRecord(d->ev[3], d->st));
+    G16_HIP(hipStreamSynchronize(d->st));
+    for (uint32_t i = 0; i < cnt; i++) status[at + i] = d->h_status[i];
+    if (ms)
+      for (int k = 0; k < 3; k++) {
+        float t = 0.f;
+        G16_HIP(hipEventElapsedTime(&t, d->ev[k], d->ev[k + 1]));
+        ms[k] += t;
+      }
+  }
+  return G16_OK;
+}
+
+int wcalc_device_run_into(WcalcDevice* d, const uint8_t* inputs, Fr* d_out, hipStream_t st, uint32_t* status) {
+  G16_HIP(hipSetDevice(d->device));
+  // (the calculator's own stream is idle between calls: every run ends with a wait)
+  if (d->n_inputs) G16_HIP(hipMemcpyAsync(d->d_in, inputs, (size_t)d->n_inputs * 32, hipMemcpyHostToDevice, st));
+  if (const int rc = wcalc_launch(d, d->d_in, d_out, d->d_status, 1, st)) return rc;
+  G16_HIP(hipMemcpyAsync(d->h_status, d->d_status, 4, hipMemcpyDeviceToHost, st));
+  G16_HIP(hipStreamSynchronize(st));
+  *status = d->h_status[0];
+  return G16_OK;
+}
+
+}  // namespace g16

@@ -37,11 +37,14 @@
  *           ptauImportResponseFiles(oldPath, responsePath, newPath, name | null, device) -> Promise<Buffer(64)>; a failed
  *                                                                              check rejects with its text
  *                                                                              (g16_ptau_import_response_files)
+ *           nzcpProgramFile(params[7] | null, gadget | null, gadgetParams, path); wtnsCalculate(programPath, names, values,
+ *               device) -> {status, text, wtns}   (g16_nzcp_witness_program, g16_wtns_calc_wtns: see above their code)
  *           zkeyVerifyFromInitFiles(initPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_from_init_files)
  *           zkeyVerifyFromInitPtauFiles(initPath, ptauPath, zkeyPath, device) -> Promise<{ok, reason}>   (..._from_init_ptau_files)
  *           zkeyVerifyR1csFiles(r1csPath, ptauPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_r1cs_files)
  */
 #include <node_api.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -1173,6 +1176,115 @@ static napi_value js_wtns_check_files(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* wtns calculate.  Both calls are synchronous: a command-line step each (the program of the full circuit takes seconds).
+ * nzcpProgramFile(params: number[7] | null, gadget: string | null, gadgetParams: number[], path): the witness program
+ * of NZCPPubIdentity(params), or of one template, written to `path`.
+ * wtnsCalculate(programPath, names: string[], values: Buffer[], device) -> {status, text, wtns}: values[i] = the words of
+ * input names[i] (32 bytes each, little-endian); status -1 and the .wtns image, or the violated check, its text and null. */
+static int read_u32_array(napi_env env, napi_value arr, uint32_t* out, uint32_t cap, uint32_t* n) {
+  bool is_arr = false;
+  if (napi_is_array(env, arr, &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, arr, n) != napi_ok || *n > cap) return 0;
+  for (uint32_t i = 0; i < *n; i++) {
+    napi_value v;
+    if (napi_get_element(env, arr, i, &v) != napi_ok || napi_get_value_uint32(env, v, &out[i]) != napi_ok) return 0;
+  }
+  return 1;
+}
+static napi_value js_nzcp_program_file(napi_env env, napi_callback_info info) {
+  size_t argc = 4, n = 0;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  uint32_t params[64], np = 0, gparams[64], ngp = 0;
+  char gadget[64] = "", path[1024];
+  const int whole = argc > 0 && read_u32_array(env, argv[0], params, 64, &np);
+  const int one = argc > 1 && napi_get_value_string_utf8(env, argv[1], gadget, sizeof(gadget), &n) == napi_ok;
+  if (argc < 4 || (whole ? np != 7 : !one) || (one && !read_u32_array(env, argv[2], gparams, 64, &ngp)) ||
+      napi_get_value_string_utf8(env, argv[3], path, sizeof(path), &n) != napi_ok) {
+    napi_throw_type_error(env, NULL, "nzcpProgramFile(params[7] | null, gadget | null, gadgetParams, path)");
+    return NULL;
+  }
+  uint8_t* prog = NULL;
+  size_t len = 0;
+  const int rc = whole ? g16_nzcp_witness_program(params, &prog, &len) : g16_nzcp_gadget_program(gadget, gparams, ngp, &prog, &len);
+  if (rc) { napi_throw_error(env, NULL, g16_last_error()); return NULL; }
+  FILE* f = fopen(path, "wb");
+  const int ok = f && fwrite(prog, 1, len, f) == len;
+  if (f && fclose(f) != 0) { g16_free(prog); napi_throw_error(env, NULL, "nzcp program: cannot write the file"); return NULL; }
+  g16_free(prog);
+  if (!ok) { napi_throw_error(env, NULL, "nzcp program: cannot write the file"); return NULL; }
+  return NULL;
+}
+static napi_value js_wtns_calculate(napi_env env, napi_callback_info info) {
+  size_t argc = 4, n = 0;
+  napi_value argv[4], out = NULL, v;
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  char path[1024], name[256], msg[512];
+  uint32_t count = 0, nvals = 0;
+  int32_t device = -1;
+  if (argc < 3 || napi_get_value_string_utf8(env, argv[0], path, sizeof(path), &n) != napi_ok ||
+      napi_get_array_length(env, argv[1], &count) != napi_ok || napi_get_array_length(env, argv[2], &nvals) != napi_ok || nvals != count) {
+    napi_throw_type_error(env, NULL, "wtnsCalculate(programPath, names, values, device)");
+    return NULL;
+  }
+  if (argc > 3) napi_get_value_int32(env, argv[3], &device);
+  FILE* f = fopen(path, "rb");
+  long flen = -1;
+  uint8_t* prog = NULL;
+  if (f && fseek(f, 0, SEEK_END) == 0 && (flen = ftell(f)) >= 0 && fseek(f, 0, SEEK_SET) == 0 && (prog = (uint8_t*)malloc((size_t)flen + 1)) &&
+      fread(prog, 1, (size_t)flen, f) != (size_t)flen) { free(prog); prog = NULL; }
+  if (f) fclose(f);
+  if (!prog) { snprintf(msg, sizeof(msg), "wtns calculate: cannot read %s", path); napi_throw_error(env, NULL, msg); return NULL; }
+  g16_wtns_calculator* h = NULL;
+  int rc = g16_wtns_calc_create(prog, (size_t)flen, device, &h);
+  free(prog);
+  if (rc) { napi_throw_error(env, NULL, g16_last_error()); return NULL; }
+  uint32_t inf[6];
+  g16_wtns_calc_info(h, inf);
+  uint8_t* words = (uint8_t*)calloc((size_t)inf[2] + 1, 32);
+  uint8_t* seen = (uint8_t*)calloc((size_t)inf[5] + 1, 1);
+  msg[0] = 0;
+  for (uint32_t i = 0; words && seen && i < count && !msg[0]; i++) {
+    napi_value nm, val;
+    void* p = NULL;
+    size_t len = 0;
+    if (napi_get_element(env, argv[1], i, &nm) != napi_ok || napi_get_value_string_utf8(env, nm, name, sizeof(name), &n) != napi_ok ||
+        napi_get_element(env, argv[2], i, &val) != napi_ok || napi_get_buffer_info(env, val, &p, &len) != napi_ok) {
+      snprintf(msg, sizeof(msg), "wtns calculate: bad input %u", i);
+      break;
+    }
+    uint32_t k = 0, first = 0, cnt = 0;
+    const char* have = NULL;
+    for (; k < inf[5]; k++)
+      if ((have = g16_wtns_calc_input(h, k, &first, &cnt)) && strcmp(have, name) == 0) break;
+    if (k == inf[5]) snprintf(msg, sizeof(msg), "wtns calculate: the program has no input %s", name);
+    else if (len != (size_t)cnt * 32) snprintf(msg, sizeof(msg), "wtns calculate: input %s takes %u values, %zu given", name, cnt, len / 32);
+    else { memcpy(words + (size_t)first * 32, p, len); seen[k] = 1; }
+  }
+  for (uint32_t k = 0; words && seen && k < inf[5] && !msg[0]; k++)
+    if (!seen[k]) snprintf(msg, sizeof(msg), "wtns calculate: input %s is missing", g16_wtns_calc_input(h, k, NULL, NULL));
+  if (!words || !seen) snprintf(msg, sizeof(msg), "wtns calculate: out of memory");
+  uint32_t status = 0xffffffffu;
+  uint8_t* wt = NULL;
+  size_t wl = 0;
+  if (!msg[0] && g16_wtns_calc_wtns(h, words, inf[2], &status, &wt, &wl)) snprintf(msg, sizeof(msg), "%s", g16_last_error());
+  if (!msg[0]) {
+    napi_create_object(env, &out);
+    napi_create_int64(env, status == 0xffffffffu ? -1 : (int64_t)status, &v);
+    napi_set_named_property(env, out, "status", v);
+    const char* text = status == 0xffffffffu ? "" : g16_wtns_calc_check_text(h, status);
+    napi_create_string_utf8(env, text ? text : "", NAPI_AUTO_LENGTH, &v);
+    napi_set_named_property(env, out, "text", v);
+    if (wt) { void* copy = NULL; napi_create_buffer_copy(env, wl, wt, &copy, &v); } else napi_get_null(env, &v);
+    napi_set_named_property(env, out, "wtns", v);
+  }
+  g16_free(wt);
+  free(words);
+  free(seen);
+  g16_wtns_calc_destroy(h);
+  if (msg[0]) { napi_throw_error(env, NULL, msg); return NULL; }
+  return out;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"create", NULL, js_create, NULL, NULL, NULL, napi_default, NULL},
@@ -1201,6 +1313,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"ptauChallengeContributeFiles", NULL, js_ptau_challenge_contribute_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauImportResponseFiles", NULL, js_ptau_import_response_files, NULL, NULL, NULL, napi_default, NULL},
       {"wtnsCheckFiles", NULL, js_wtns_check_files, NULL, NULL, NULL, napi_default, NULL},
+      {"nzcpProgramFile", NULL, js_nzcp_program_file, NULL, NULL, NULL, napi_default, NULL},
+      {"wtnsCalculate", NULL, js_wtns_calculate, NULL, NULL, NULL, napi_default, NULL},
   };
   NAPI_OK(napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props));
   return exports;

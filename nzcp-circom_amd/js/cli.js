@@ -28,6 +28,12 @@
 // constraint, how many fail and its three values A.w, B.w, C.w, and exits 1.  [--device n]: a GPU ordinal, -1 = host
 // threads.  `[groth16] prove ... --check <circuit.r1cs>` runs the same check first and stops with the same report and
 // exit status 1 before anything is written.  These texts are modelled on later snarkjs and not compared with it.
+// And of `snarkjs wtns calculate <circuit.wasm> <input.json> <witness.wtns>` (alias `wc`) and `snarkjs groth16 fullprove
+// <input.json> <circuit.wasm> <circuit.zkey> <proof.json> <public.json>` (alias `g16f`), with a WITNESS PROGRAM where
+// snarkjs takes the .wasm: `cli.js nzcp program <example|live> <file>` records one (no circom .wasm is run).  An input
+// that violates a constraint prints "[ERROR] snarkJS: <the constraint's text>" and exits 1 before anything is written.
+// `wtns calculate` runs on host threads unless --device names a GPU; `fullprove` computes the witness likewise and proves
+// on the GPU.
 "use strict";
 const fs = require("fs");
 const { groth16 } = require("./index.js");
@@ -53,6 +59,43 @@ async function main(argv) {
     const v = await wtns.check(pos[0], pos[1], { device });
     if (!v.ok) throw new Error(wtnsCheckReport(v));
     console.log("WITNESS IS CORRECT");
+    return;
+  }
+  if ((a[0] === "wtns" && a[1] === "calculate") || a[0] === "wc") {
+    const rest = a.slice(a[0] === "wc" ? 1 : 2);
+    const pos = [];
+    let device = -1;
+    for (let i = 0; i < rest.length; i++) {
+      if (rest[i] === "--device") device = parseInt(rest[++i], 10);
+      else if (!rest[i].startsWith("--")) pos.push(rest[i]);
+    }
+    if (pos.length < 3) { console.error("usage: cli.js wtns calculate <program> <input.json> <witness.wtns> [--device n]"); process.exit(2); }
+    const { wtns } = require("./index.js");
+    await wtns.calculate(pos[1], pos[0], pos[2], { device });
+    return;
+  }
+  if ((a[0] === "groth16" && a[1] === "fullprove") || a[0] === "g16f") {
+    const rest = a.slice(a[0] === "g16f" ? 1 : 2);
+    const opts = {};
+    const pos = [];
+    for (let i = 0; i < rest.length; i++) {
+      if (rest[i] === "--r") opts.r = rest[++i];
+      else if (rest[i] === "--s") opts.s = rest[++i];
+      else if (rest[i] === "--device") opts.device = parseInt(rest[++i], 10);
+      else pos.push(rest[i]);
+    }
+    if (pos.length < 3) { console.error("usage: cli.js groth16 fullprove <input.json> <program> <circuit.zkey> [proof.json] [public.json] [--r dec --s dec --device n]"); process.exit(2); }
+    const [input, program, zkey, proofFile = "proof.json", publicFile = "public.json"] = pos;
+    const { proof, publicSignals } = await groth16.fullProve(input, program, zkey, opts);
+    fs.writeFileSync(proofFile, JSON.stringify(proof, null, 1), "utf-8");
+    fs.writeFileSync(publicFile, JSON.stringify(publicSignals, null, 1), "utf-8");
+    return;
+  }
+  if (a[0] === "nzcp" && a[1] === "program") {
+    const pos = a.slice(2).filter((x) => !x.startsWith("--"));
+    if (pos.length < 2) { console.error("usage: cli.js nzcp program <example|live> <file>"); process.exit(2); }
+    const { nzcp } = require("./index.js");
+    await nzcp.witnessProgram(pos[0], pos[1]);
     return;
   }
   if ((a[0] === "zkey" && a[1] === "contribute") || a[0] === "zkc") {

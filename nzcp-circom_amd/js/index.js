@@ -11,6 +11,8 @@
 // groth16.verify(vk, publicSignals, proof) is snarkjs's too (GPU pairing check, csrc/verify.hip); createVerifier(vk)
 // keeps the key resident and verifies batches, one verdict per proof.
 // wtns.check(r1cs, wtns) is later snarkjs's witness check (csrc/wtns_check.hip): {ok, constraint, nFailed, a, b, c}.
+// wtns.calculate(input, program, wtnsFile) and groth16.fullProve(input, program, zkey) are snarkjs's, with a witness
+// program recorded by the native builders (nzcp.witnessProgram) where snarkjs takes a circom .wasm.
 // Extensions (not in snarkjs): opts = {r, s, device, devices, windowBits}; groth16.createProver() keeps the
 // proving key resident in HBM across proofs; prover.proveBatch(wtnsList); createProver(zkey, {devices: [0, 1, ...]})
 // shards ONE proof over several GPUs of the node (BASELINE config 4: MSM point ranges + the A/B/C evaluation split
@@ -477,6 +479,36 @@ const wtns = {
     const v = await native().wtnsCheckFiles(String(r1csName), String(wtnsName), device);
     return { ok: v.constraint < 0, constraint: v.constraint, nFailed: v.nFailed, a: dec(v.a, 0), b: dec(v.b, 0), c: dec(v.c, 0) };
   },
+  // snarkjs: wtns.calculate(input, wasmFileName, wtnsFileName) -- here the second argument is a WITNESS PROGRAM recorded
+  // by the native builders (nzcp.witnessProgram), not a circom .wasm, which this library does not run.  input: an object
+  // (or the name of its .json) whose keys are the program's named inputs.  A violated check rejects with its text before
+  // anything is written.  opts.device: a GPU ordinal, or -1 = host threads (the default).
+  async calculate(input, programName, wtnsName, opts = {}) {
+    const image = calculateWitness(input, programName, opts);
+    fs.writeFileSync(String(wtnsName), image);
+  },
+};
+function calculateWitness(input, programName, opts) {
+  if (typeof input === "string") input = JSON.parse(fs.readFileSync(input, "utf-8"));
+  const device = !opts || opts.device === undefined || opts.device === null ? -1 : opts.device | 0;
+  const names = Object.keys(input);
+  const values = names.map((k) => Buffer.concat((Array.isArray(input[k]) ? input[k].flat(Infinity) : [input[k]]).map((x) => scalarToBuffer(x))));
+  const res = native().wtnsCalculate(String(programName), names, values, device);
+  if (res.status >= 0) throw new Error(res.text);
+  return res.wtns;
+}
+// nzcp.witnessProgram(params | "example" | "live", file): the witness program of NZCPPubIdentity(params) written to `file`
+// (seconds at the full size: keep the file); nzcp.gadgetProgram(name, params, file): one template of the library
+const NZCP_PARAMS = { example: [0, 314, 0, 4, 2, 4, 5], live: [1, 355, 0, 4, 2, 4, 6] };
+const nzcp = {
+  async witnessProgram(params, file) {
+    const p = typeof params === "string" ? NZCP_PARAMS[params] : params;
+    if (!Array.isArray(p) || p.length !== 7) throw new Error(`nzcp program: expected "example", "live" or seven template parameters`);
+    native().nzcpProgramFile(p.map(Number), null, [], String(file));
+  },
+  async gadgetProgram(name, params, file) {
+    native().nzcpProgramFile(null, String(name), (params || []).map(Number), String(file));
+  },
 };
 // what the CLI prints for a failed check (modelled on later snarkjs, not compared with it)
 function wtnsCheckReport(v) {
@@ -505,6 +537,12 @@ const groth16 = {
     }
   },
   createProver,
+  // snarkjs: groth16.fullProve(input, wasmFile, zkeyFileName) -> {proof, publicSignals}; the second argument is a witness
+  // program (see wtns.calculate).  The witness never touches a file.  A violated check rejects with its text.
+  async fullProve(input, programName, zkey, opts = {}) {
+    if (opts && typeof opts.debug === "function") opts = { logger: opts };
+    return groth16.prove(zkey, calculateWitness(input, programName, opts), opts);
+  },
 };
 
-module.exports = { groth16, plonk, powersOfTau, wtns, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, verifyFromInit, verifyFromR1cs }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
+module.exports = { groth16, plonk, powersOfTau, wtns, nzcp, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, verifyFromInit, verifyFromR1cs }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
