@@ -693,7 +693,22 @@ void g16_r1cs_checker_destroy(g16_r1cs_checker* k);
  * g16_stage_inputs: the witness evaluated on the prover's stream INTO slot `slot` of the prover, only the public signals
  * copied back; g16_prove_staged then works unchanged.  Refused with a text: a calculator on another device or on the host
  * route, a program whose wire or public counts differ from the key's, a prover between g16_shard_begin and _end.  With a
- * violated check the call succeeds, *status names it and the slot is left unstaged. */
+ * violated check the call succeeds, *status names it and the slot is left unstaged.
+ * g16_fullprove_batch, g16_plonk_fullprove_batch: `count` passes in, proofs and public signals out; the witnesses never
+ * leave the device.  inputs as for g16_wtns_calc (a word >= r fails the whole call with its text before the device is
+ * touched); rs = count * 64 bytes (r | s per proof), blinding = count * 9 * 32 bytes, or NULL: the OS CSPRNG; out = count
+ * proofs; pub (or NULL) = count rows of n_public words, words 1..n_public of each witness; status as for g16_wtns_calc.
+ * A VIOLATED CHECK IS A VERDICT: the call succeeds, proof i and row i of pub are all zero bytes, and the other proofs
+ * are unaffected.  With explicit rs / blinding proof i is byte for byte what g16_wtns_calc_wtns + g16_stage_witness +
+ * g16_prove_staged (g16_plonk_prove) give.  count = 0 succeeds and touches nothing.  Refused with g16_stage_inputs'
+ * texts behind "fullprove:" ("plonk fullprove:"): a calculator on the host route or on another device, wire or public
+ * counts that differ from the key's (PLONK: the key's R1CS wire count, nVars less the addition signals); a sharded
+ * Groth16 handle, or one between g16_shard_begin and _end, as g16_prove_batch refuses it.  The calculator computes chunks
+ * (the 4 GiB rule above, G16_WTNS_CALC_CHUNK) on its own stream into TWO chunk buffers -- chunk k + 1 while the Groth16
+ * proofs of chunk k run through g16_prove_batch's pipeline; PLONK proofs run one after another from one buffer -- so a
+ * batched fullprove holds at most 2 x 4 GiB of witnesses on the device (2 x min(count, chunk) x n_wires x 32 bytes), and
+ * only inputs, status words, public signals and proofs cross the bus.  On an error exit every launch and copy of the call
+ * is drained first; the prover's witness slots are untouched, and both handles stay usable. */
 typedef struct g16_wtns_calculator g16_wtns_calculator;
 int g16_nzcp_witness_program(const uint32_t params[7], uint8_t** prog, size_t* len);
 int g16_nzcp_gadget_program(const char* name, const uint32_t* params, uint32_t nparams, uint8_t** prog, size_t* len);
@@ -708,6 +723,12 @@ const char* g16_wtns_calc_input(const g16_wtns_calculator* h, uint32_t i, uint32
 int g16_wtns_calc_timings(const g16_wtns_calculator* h, float ms[3]);
 void g16_wtns_calc_destroy(g16_wtns_calculator* h);
 int g16_stage_inputs(g16_prover* p, uint32_t slot, g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, uint32_t* status);
+int g16_fullprove_batch(g16_prover* p, g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, size_t count,
+                        const uint8_t* rs /* count * 64 (r | s) or NULL */, g16_proof* out /* count */,
+                        uint8_t* pub /* count * n_public * 32, or NULL */, uint32_t* status /* count */);
+int g16_plonk_fullprove_batch(g16_plonk* p, g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, size_t count,
+                              const uint8_t* blinding /* count * 9 * 32 or NULL */, g16_plonk_proof* out, uint8_t* pub,
+                              uint32_t* status);
 
 #ifdef __cplusplus
 }

@@ -88,7 +88,8 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_r1cs_checker_timings", "g16_r1cs_checker_destroy",
            "g16_nzcp_witness_program", "g16_nzcp_gadget_program", "g16_nzcp_inputs", "g16_wtns_calc_create", "g16_wtns_calc",
            "g16_wtns_calc_check_text", "g16_wtns_calc_wtns", "g16_wtns_calc_info", "g16_wtns_calc_outputs",
-           "g16_wtns_calc_input", "g16_wtns_calc_timings", "g16_wtns_calc_destroy", "g16_stage_inputs"]
+           "g16_wtns_calc_input", "g16_wtns_calc_timings", "g16_wtns_calc_destroy", "g16_stage_inputs",
+           "g16_fullprove_batch", "g16_plonk_fullprove_batch"]
 
 
 def load():
@@ -220,6 +221,8 @@ def load():
     lib.g16_wtns_calc_destroy.argtypes = [vp]
     lib.g16_wtns_calc_destroy.restype = None
     lib.g16_stage_inputs.argtypes = [vp, C.c_uint32, vp, C.c_char_p, sz, u32p]
+    lib.g16_fullprove_batch.argtypes = [vp, vp, C.c_char_p, sz, sz, C.c_char_p, vp, C.c_char_p, u32p]
+    lib.g16_plonk_fullprove_batch.argtypes = [vp, vp, C.c_char_p, sz, sz, C.c_char_p, vp, C.c_char_p, u32p]
     lib.g16_blake2b512.argtypes = [C.c_char_p, sz, C.c_char_p]
     lib.g16_zkey_hash_to_g2.argtypes = [C.c_char_p, C.c_char_p]
     lib.g16_r1cs_setup.argtypes = [C.c_char_p, sz, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz)]
@@ -319,6 +322,23 @@ class Prover:
         st = C.c_uint32()
         _check(load().g16_stage_inputs(self._h, slot, calc._h, words, len(words) // 32, C.byref(st)))
         return st.value
+
+    def fullprove_batch(self, calc, inputs_list, rs=None):
+        """Inputs in, proofs out; the witnesses stay on the device (WitnessCalculator on the same device).  rs: None, or
+        one (r, s) pair of 32-byte LE scalars per pass.  -> [(proof, public_bytes, NO_CHECK)], or (None, None, the
+        violated check) for a pass whose witness violates one."""
+        n, p = len(inputs_list), self.info.n_public * 32
+        blob = b"".join(calc.words(x) for x in inputs_list)
+        prs = (Proof * max(1, n))()
+        pub = C.create_string_buffer(max(1, n * p))
+        st = (C.c_uint32 * max(1, n))()
+        blind = None if rs is None else b"".join(bytes(r) + bytes(s) for r, s in rs)
+        if blind is not None and len(blind) != n * 64:
+            raise G16Error(-1, "fullprove: rs takes one (r, s) pair of 32-byte scalars per pass")
+        _check(load().g16_fullprove_batch(self._h, calc._h, blob, len(blob) // 32 // n if n else calc.n_inputs, n, blind,
+                                          prs, pub, st))
+        return [(proof_to_obj(prs[i]), pub.raw[i * p:(i + 1) * p], st[i]) if st[i] == NO_CHECK else (None, None, st[i])
+                for i in range(n)]
 
     def prove_staged(self, slot, r=None, s=None):
         pr, pub = Proof(), self._pub()
@@ -905,6 +925,33 @@ class PlonkProver:
             blinding = b"".join(int(x).to_bytes(32, "little") for x in blinding)
         pr, pub = self.prove_raw(wtns, blinding)
         return plonk_proof_to_obj(pr), [_dec(pub[i * 32:(i + 1) * 32]) for i in range(self.n_public)]
+
+    def fullprove_batch(self, calc, inputs_list, blindings=None):
+        """Inputs in, proofs out; the witnesses stay on the device (WitnessCalculator on the same device).  blindings:
+        None, or per pass the nine scalars b1..b9 (ints, or 288 bytes).  -> [(proof, public_bytes, NO_CHECK)], or
+        (None, None, the violated check) for a pass whose witness violates one."""
+        n, p = len(inputs_list), self.n_public * 32
+        blob = b"".join(calc.words(x) for x in inputs_list)
+        prs = (PlonkProof * max(1, n))()
+        pub = C.create_string_buffer(max(1, n * p))
+        st = (C.c_uint32 * max(1, n))()
+        blind = None
+        if blindings is not None:
+            blind = b"".join(bytes(b) if isinstance(b, (bytes, bytearray)) else b"".join(int(x).to_bytes(32, "little") for x in b)
+                             for b in blindings)
+            if len(blind) != n * 288:
+                raise G16Error(-1, "plonk fullprove: blindings takes nine 32-byte scalars per pass")
+        _check(load().g16_plonk_fullprove_batch(self._h, calc._h, blob, len(blob) // 32 // n if n else calc.n_inputs, n, blind,
+                                                prs, pub, st))
+        return [(plonk_proof_to_obj(prs[i]), pub.raw[i * p:(i + 1) * p], st[i]) if st[i] == NO_CHECK else (None, None, st[i])
+                for i in range(n)]
+
+    def fullprove(self, calc, inputs, blinding=None):
+        """snarkjs `plonk.fullProve` -> (proof, publicSignals); a violated check raises G16Error with the check's text."""
+        proof, pub, st = self.fullprove_batch(calc, [inputs], None if blinding is None else [blinding])[0]
+        if st != NO_CHECK:
+            raise G16Error(-5, "constraint not satisfied: " + (calc.check_text(st) or "?"))
+        return proof, [_dec(pub[i * 32:(i + 1) * 32]) for i in range(self.n_public)]
 
     def timings(self):
         ms = (C.c_float * 6)()

@@ -35,6 +35,7 @@
 #include "fr29.cuh"
 #include "internal.h"
 #include "transcript.h"
+#include "witness_program.h"
 
 namespace g16 {
 namespace {
@@ -851,6 +852,10 @@ int random_fr(FrM* out) {
   return G16_OK;
 }
 
+int plonk_blinding(const uint8_t* blind, FrM b[10]);
+int plonk_prove_device(g16_plonk* P, const Fr* d_wraw, const FrM b[10], PlonkProofM* pr);
+
+// One proof from a .wtns image: its checks, the upload, then the rounds
 int plonk_prove_impl(g16_plonk* P, const uint8_t* wtns, size_t wlen, const uint8_t* blind, PlonkProofM* pr, uint8_t* pub) {
   BinView f;
   int rc = bin_open(wtns, wlen, "wtns", 2, f);
@@ -878,6 +883,15 @@ int plonk_prove_impl(g16_plonk* P, const uint8_t* wtns, size_t wlen, const uint8
   }
   if (pub && P->nPublic) memcpy(pub, s[2].p + 32, (size_t)P->nPublic * 32);
   FrM b[10];
+  if ((rc = plonk_blinding(blind, b))) return rc;
+  G16_HIP(hipSetDevice(P->device));
+  G16_HIP(hipMemcpyAsync(P->d_wraw, s[2].p, (size_t)P->nBase * 32, hipMemcpyHostToDevice, P->st));
+  return plonk_prove_device(P, P->d_wraw, b, pr);
+}
+
+// the nine blinding scalars b[1..9] as Montgomery words: the caller's (each below r), or fresh ones
+int plonk_blinding(const uint8_t* blind, FrM b[10]) {
+  int rc;
   b[0] = fp_zero<FrParams>();
   for (int i = 1; i <= 9; i++) {
     if (blind) {
@@ -889,6 +903,13 @@ int plonk_prove_impl(g16_plonk* P, const uint8_t* wtns, size_t wlen, const uint8
       return rc;
     }
   }
+  return G16_OK;
+}
+
+// The five rounds.  d_wraw: the nBase canonical standard-form words of the witness on the device, in place for the main
+// stream (an upload enqueued there, or a buffer the stream was made to wait for); they are read once, by the first kernel.
+int plonk_prove_device(g16_plonk* P, const Fr* d_wraw, const FrM b[10], PlonkProofM* pr) {
+  int rc;
   G16_HIP(hipSetDevice(P->device));
   hipStream_t st = P->st;
   const uint32_t N = P->N;
@@ -902,8 +923,7 @@ int plonk_prove_impl(g16_plonk* P, const uint8_t* wtns, size_t wlen, const uint8
   };
   // ---- witness: first element zeroed ("not used in plonk"), additions level by level, A/B/C
   G16_HIP(hipMemsetAsync(P->d_bad, 0, 32, st));
-  G16_HIP(hipMemcpyAsync(P->d_wraw, s[2].p, (size_t)P->nBase * 32, hipMemcpyHostToDevice, st));
-  k_to_mont<<<nblk(P->nBase), 256, 0, st>>>(P->d_wraw, P->d_w, P->nBase, 1u);
+  k_to_mont<<<nblk(P->nBase), 256, 0, st>>>(d_wraw, P->d_w, P->nBase, 1u);
   for (size_t l = 0; l + 1 < P->level_start.size(); l++) {
     const uint32_t lo = P->level_start[l], hi = P->level_start[l + 1];
     if (hi > lo)
@@ -1191,13 +1211,9 @@ extern "C" int g16_plonk_create(const uint8_t* zkey, size_t zkey_len, int device
   return G16_OK;
 }
 
-extern "C" int g16_plonk_prove(g16_plonk* P, const uint8_t* wtns, size_t wtns_len, const uint8_t* blinding,
-                               g16_plonk_proof* out, uint8_t* pub) {
-  if (!P || !wtns || !out) { set_error("NULL argument"); return G16_E_ARG; }
-  std::lock_guard<std::mutex> lk(P->mu);
-  PlonkProofM pr;
-  const int rc = plonk_prove_impl(P, wtns, wtns_len, blinding, &pr, pub);
-  if (rc) return rc;
+namespace {
+
+void plonk_proof_out(const PlonkProofM& pr, g16_plonk_proof* out) {
   g1_std(out->A, pr.A); g1_std(out->B, pr.B); g1_std(out->C, pr.C); g1_std(out->Z, pr.Z);
   g1_std(out->T1, pr.T1); g1_std(out->T2, pr.T2); g1_std(out->T3, pr.T3); g1_std(out->Wxi, pr.Wxi); g1_std(out->Wxiw, pr.Wxiw);
   const FrM* evs[7] = {&pr.ea, &pr.eb, &pr.ec, &pr.es1, &pr.es2, &pr.ezw, &pr.er};
@@ -1205,6 +1221,79 @@ extern "C" int g16_plonk_prove(g16_plonk* P, const uint8_t* wtns, size_t wtns_le
   for (int k = 0; k < 7; k++) {
     const Fr sdt = fp_from_mont(*evs[k]);
     memcpy(dst[k], sdt.v, 32);
+  }
+}
+
+// error paths of the batched fullprove: every stream a proof of this handle enqueues on, synchronised
+void plonk_drain(g16_plonk* P) {
+  const std::string err = get_error();
+  (void)hipSetDevice(P->device);
+  hipStream_t sts[4] = {P->st, P->st2, P->mst[0], P->mst[1]};
+  for (hipStream_t s : sts)
+    if (s) (void)hipStreamSynchronize(s);
+  set_error(err);
+}
+
+}  // namespace
+
+extern "C" int g16_plonk_prove(g16_plonk* P, const uint8_t* wtns, size_t wtns_len, const uint8_t* blinding,
+                               g16_plonk_proof* out, uint8_t* pub) {
+  if (!P || !wtns || !out) { set_error("NULL argument"); return G16_E_ARG; }
+  std::lock_guard<std::mutex> lk(P->mu);
+  PlonkProofM pr;
+  const int rc = plonk_prove_impl(P, wtns, wtns_len, blinding, &pr, pub);
+  if (rc) return rc;
+  plonk_proof_out(pr, out);
+  return G16_OK;
+}
+
+// Inputs in, proofs out: the calculator computes a chunk of witnesses on its own stream (wtns_calc.hip); the proofs of
+// the chunk then run one after another, as g16_plonk_prove does, each reading its raw witness from the chunk buffer after
+// the main stream waited for the chunk's ready event.  Every proof ends with the main stream drained, so the buffer is
+// free again when the last proof of the chunk has returned: one buffer, and no overlap of chunks with proofs.
+extern "C" int g16_plonk_fullprove_batch(g16_plonk* P, g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, size_t count,
+                                         const uint8_t* blinding, g16_plonk_proof* out, uint8_t* pub, uint32_t* status) {
+  if (!P || !h) { set_error("NULL argument"); return G16_E_ARG; }
+  std::lock_guard<std::mutex> lk(P->mu);
+  // (the program knows the R1CS wires; the key's nVars counts the addition signals of the PLONK compilation on top)
+  if (const int rc = wcalc_match_prover(h, "plonk fullprove", P->device, P->nBase, P->nPublic)) return rc;
+  if (!count) return G16_OK;
+  if (!out || !status || (n_inputs && !inputs)) { set_error("NULL argument"); return G16_E_ARG; }
+  if (const int rc = wcalc_check_inputs(h, inputs, n_inputs, count)) return rc;   // (before the device is touched)
+  G16_HIP(hipSetDevice(P->device));
+  WcalcDevice* d = h->dev;
+  const size_t chunk = wcalc_chunk_size(d);
+  const size_t in_bytes = n_inputs * 32, pub_bytes = (size_t)P->nPublic * 32;
+  auto fail = [&](int rc) -> int {   // nothing of this call stays on the device
+    plonk_drain(P);
+    wcalc_chunk_drain(d);
+    return rc;
+  };
+  for (size_t at = 0; at < count; at += chunk) {
+    const uint32_t cnt = (uint32_t)(count - at < chunk ? count - at : chunk);
+    WcalcChunk c;
+    int rc = wcalc_chunk_launch(d, 0, inputs + at * in_bytes, cnt, pub != nullptr, &c);
+    if (rc) return fail(rc);
+    {
+      const hipError_t e = hipEventSynchronize(c.ready);
+      if (e != hipSuccess) { set_error(std::string("plonk fullprove: ") + hipGetErrorString(e)); return fail(G16_E_HIP); }
+    }
+    for (uint32_t i = 0; i < cnt; i++) {
+      status[at + i] = c.status[i];
+      uint8_t* row = pub ? pub + (at + i) * pub_bytes : nullptr;
+      if (c.status[i] != kWpNoCheck) {   // a verdict: no proof
+        memset(&out[at + i], 0, sizeof(g16_plonk_proof));
+        if (row) memset(row, 0, pub_bytes);
+        continue;
+      }
+      if (row && pub_bytes) memcpy(row, c.pub + i * pub_bytes, pub_bytes);
+      FrM b[10];
+      PlonkProofM pr;
+      if ((rc = plonk_blinding(blinding ? blinding + (at + i) * 9 * 32 : nullptr, b))) return fail(rc);
+      if (hipStreamWaitEvent(P->st, c.ready, 0) != hipSuccess) { set_error("plonk fullprove: hipStreamWaitEvent failed"); return fail(G16_E_HIP); }
+      if ((rc = plonk_prove_device(P, c.d_w + (size_t)i * P->nBase, b, &pr))) return fail(rc);
+      plonk_proof_out(pr, &out[at + i]);
+    }
   }
   return G16_OK;
 }

@@ -971,6 +971,100 @@ void shard_drain(g16_prover* P) {
 
 }  // namespace g16
 
+// ====================================================================== the batch pipeline
+// Software pipeline over the contexts (g16_prove_batch, g16_fullprove_batch): while the host waits for, folds and
+// finishes proof n - nctx, proof n is already running on the GPU.  n counts the proofs the pipeline launched -- proof n
+// runs on context n % nctx -- and `i` names the caller's proof: the two differ once a batch leaves witnesses out.
+struct BatchPipe {
+  // What makes the witness of a proof ready for context `c`: it names the words launch_ctx reads (*d_w), enqueues what
+  // must come before them on c's streams -- after setting `busy` -- and marks the middle of its host time (t_mid).
+  using Prepare = std::function<int(ProofCtx& c, bool& busy, const Fr** d_w, double& t_mid)>;
+  g16_prover* const p;
+  const uint8_t* const rs;   // per proof of the caller's: r | s; or nullptr
+  g16_proof* const out;
+  const bool pipelined;      // launch_ctx's throughput forms
+  const bool check_words;    // the words came from the caller: the context's canonicity verdict counts (witness_ok)
+  const size_t nctx;
+  size_t n = 0;
+  size_t idx[g16_prover::kCtx] = {};
+  Blinding bl[g16_prover::kCtx];
+  int bl_rc[g16_prover::kCtx] = {};
+  bool busy[g16_prover::kCtx] = {};   // the context holds an uncollected launch (or an upload from the caller's buffer)
+  const std::chrono::steady_clock::time_point tb0 = std::chrono::steady_clock::now();
+
+  BatchPipe(g16_prover* p_, const uint8_t* rs_, g16_proof* out_, bool pipelined_, bool check_words_)
+      : p(p_), rs(rs_), out(out_), pipelined(pipelined_), check_words(check_words_), nctx((size_t)p_->nctx) {}
+  double now_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count(); }
+
+  int finish_one(size_t k) {
+    ProofCtx& c = p->ctx[k];
+    busy[k] = false;
+    if (bl_rc[k]) {
+      Partial part;
+      (void)collect_ctx(p, c, part);
+      return bl_rc[k];
+    }
+    const int frc = collect_and_assemble(p, c, bl[k], &out[idx[k]]);
+    const int wrc = check_words ? witness_ok(c) : G16_OK;
+    if (!frc && !wrc) mark_completed(p, c);
+    return wrc ? wrc : frc;
+  }
+  // every error exit: the contexts still busy are drained before the first error is returned, so that no work of
+  // this call is left on the device and the caller's buffers are not read after the return
+  int fail(int rc) {
+    for (size_t k = 0; k < nctx; k++)
+      if (busy[k]) { drain_ctx(p, p->ctx[k]); busy[k] = false; }
+    return rc;
+  }
+  int push(size_t i, const Prepare& prepare) {
+    static const bool trace = getenv("G16_TRACE_HOST") != nullptr;
+    const size_t k = n % nctx;
+    ProofCtx& c = p->ctx[k];
+    const double t_a = now_ms();
+    if (n >= nctx) {   // the context is still busy with proof n - nctx
+      int rc = finish_one(k);
+      if (rc) return rc;
+    }
+    const double t_b = now_ms();
+    double t_c = t_b;
+    const Fr* d_w = nullptr;
+    int rc = prepare(c, busy[k], &d_w, t_c);
+    if (!rc) rc = launch_ctx(p, c, d_w, pipelined);
+    if (rc) return rc;
+    idx[k] = i;
+    const double t_d = now_ms();
+    bl_rc[k] = prepare_blinding(&p->kp, rs ? rs + i * 64 : nullptr, rs ? rs + i * 64 + 32 : nullptr, bl[k]);
+    if (trace)
+      fprintf(stderr, "[g16 batch] proof %zu: at %.3f ms  finish(i-%d) %.3f  upload call %.3f  launch %.3f  blinding %.3f\n", i,
+              t_a, (int)nctx, t_b - t_a, t_c - t_b, t_d - t_c, now_ms() - t_d);
+    n++;
+    return G16_OK;
+  }
+  // the proofs still in flight, oldest first
+  int flush() {
+    for (size_t j = n > nctx ? n - nctx : 0; j < n; j++) {
+      int rc = finish_one(j % nctx);
+      if (rc) return rc;
+    }
+    return G16_OK;
+  }
+  // The calculator's stream waits until no proof in flight reads its witness any more: the QAP evaluation (ev[3]) and
+  // both witness lanes, whose repeated-value stage reads the scalars last (the solo B2 group likewise).  Events, no
+  // host wait: the proofs themselves go on.
+  int release_to(WcalcDevice* d) {
+    for (size_t k = 0; k < nctx; k++) {
+      if (!busy[k]) continue;
+      ProofCtx& c = p->ctx[k];
+      hipEvent_t evs[4] = {c.ev[3], c.ws[0] ? msm_event(c.ws[0], 3) : nullptr, c.ws[0] ? msm_event(c.ws[0], 4) : nullptr,
+                           p->b2_solo && c.ws[2] ? msm_event(c.ws[2], 4) : nullptr};
+      for (hipEvent_t e : evs)
+        if (e)
+          if (int rc = wcalc_chunk_release(d, e)) return rc;
+    }
+    return G16_OK;
+  }
+};
+
 // ====================================================================== C ABI
 extern "C" {
 
@@ -1119,17 +1213,7 @@ int g16_stage_inputs(g16_prover* p, uint32_t slot, g16_wtns_calculator* h, const
   if (!p || !h || !status || (n_inputs && !inputs)) { set_error("NULL argument"); return G16_E_ARG; }
   std::lock_guard<std::mutex> lk(p->mu);
   if (int rc = shard_guard(p)) return rc;
-  if (!h->dev) { set_error("stage inputs: the calculator runs on the host route (create it on the prover's device)"); return G16_E_STATE; }
-  if (wcalc_device_id(h->dev) != p->device) {
-    set_error("stage inputs: the calculator is on device " + std::to_string(wcalc_device_id(h->dev)) + ", the prover on device " +
-              std::to_string(p->device));
-    return G16_E_STATE;
-  }
-  if (h->p.n_wires != p->nVars || h->p.n_public != p->nPublic) {
-    set_error("stage inputs: the program has " + std::to_string(h->p.n_wires) + " wires and " + std::to_string(h->p.n_public) +
-              " public signals, the key " + std::to_string(p->nVars) + " and " + std::to_string(p->nPublic));
-    return G16_E_STATE;
-  }
+  if (int rc = wcalc_match_prover(h, "stage inputs", p->device, p->nVars, p->nPublic)) return rc;
   if (slot >= 65536) { set_error("slot out of range"); return G16_E_ARG; }
   if (int rc = wcalc_check_inputs(h, inputs, n_inputs, 1)) return rc;
   G16_HIP(hipSetDevice(p->device));
@@ -1175,70 +1259,98 @@ int g16_prove_batch(g16_prover* p, const uint8_t* const* wtns, const size_t* wtn
   std::lock_guard<std::mutex> lk(p->mu);
   if (int rc = shard_guard(p)) return rc;
   if (p->shard_count != 1) { set_error("sharded handle: use g16_prove_partial/g16_prove_finish"); return G16_E_STATE; }
-  // Software pipeline over the contexts: while the host waits for, folds and finishes proof i-1,
-  // proof i is already running on the GPU.
   const size_t wbytes = (size_t)p->nVars * sizeof(Fr);
-  const size_t nctx = (size_t)p->nctx;
-  Blinding bl[g16_prover::kCtx];
-  int bl_rc[g16_prover::kCtx] = {};
-  bool busy[g16_prover::kCtx] = {};   // the context holds an uncollected launch (or an upload from the caller's buffer)
-  auto finish_one = [&](size_t i) -> int {
-    ProofCtx& c = p->ctx[i % nctx];
-    busy[i % nctx] = false;
-    if (bl_rc[i % nctx]) {
-      Partial part;
-      (void)collect_ctx(p, c, part);
-      return bl_rc[i % nctx];
-    }
-    const int frc = collect_and_assemble(p, c, bl[i % nctx], &out[i]);
-    const int wrc = witness_ok(c);
-    if (!frc && !wrc) mark_completed(p, c);
-    return wrc ? wrc : frc;
-  };
-  // every error exit: the contexts still busy are drained before the first error is returned, so that no work of
-  // this call is left on the device and the caller's buffers are not read after the return
-  auto fail = [&](int rc) -> int {
-    for (size_t k = 0; k < nctx; k++)
-      if (busy[k]) { drain_ctx(p, p->ctx[k]); busy[k] = false; }
-    return rc;
-  };
-  static const bool trace = getenv("G16_TRACE_HOST") != nullptr;
-  const auto tb0 = std::chrono::steady_clock::now();
-  auto now_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count(); };
+  BatchPipe pipe(p, rs, out, count > 1, /*check_words=*/true);
   for (size_t i = 0; i < count; i++) {
-    ProofCtx& c = p->ctx[i % nctx];
-    const double t_a = now_ms();
-    if (i >= nctx) {   // the context is still busy with proof i - kCtx
-      int rc = finish_one(i - nctx);
-      if (rc) return fail(rc);
-    }
-    const double t_b = now_ms();
-    double t_c = t_b;
-    const int rc = [&]() -> int {
+    // the witness source: an upload into the context's own copy, checked there
+    const int rc = pipe.push(i, [&](ProofCtx& c, bool& busy, const Fr** d_w, double& t_mid) -> int {
       const uint8_t* body = nullptr;
       int e = parse_wtns(p, wtns[i], wtns_lens[i], &body);
       if (e) return e;
       G16_HIP(hipSetDevice(p->device));
       if (!c.d_w) G16_HIP(hipMalloc(&c.d_w, wbytes));
-      busy[i % nctx] = true;
+      busy = true;
       G16_HIP(hipMemcpyAsync(c.d_w, body, wbytes, hipMemcpyHostToDevice, c.st));
-      t_c = now_ms();
+      t_mid = pipe.now_ms();
       if ((e = qap_check_witness(c.d_w, p->nVars, c.d_flag, c.h_flag, c.st))) return e;
       if (pub && p->nPublic) memcpy(pub + i * (size_t)p->nPublic * 32, body + 32, (size_t)p->nPublic * 32);
-      return launch_ctx(p, c, c.d_w, count > 1);
-    }();
-    if (rc) return fail(rc);
-    const double t_d = now_ms();
-    bl_rc[i % nctx] = prepare_blinding(&p->kp, rs ? rs + i * 64 : nullptr, rs ? rs + i * 64 + 32 : nullptr,
-                                                    bl[i % nctx]);
-    if (trace)
-      fprintf(stderr, "[g16 batch] proof %zu: at %.3f ms  finish(i-%d) %.3f  upload call %.3f  launch %.3f  blinding %.3f\n", i,
-              t_a, (int)nctx, t_b - t_a, t_c - t_b, t_d - t_c, now_ms() - t_d);
+      *d_w = c.d_w;
+      return G16_OK;
+    });
+    if (rc) return pipe.fail(rc);
   }
-  for (size_t i = count > nctx ? count - nctx : 0; i < count; i++) {
-    int rc = finish_one(i);
-    if (rc) return fail(rc);
+  if (int rc = pipe.flush()) return pipe.fail(rc);
+  return G16_OK;
+}
+
+// Inputs in, proofs out: the witnesses are computed in chunks by the calculator on its own stream and proved from the
+// chunk buffer (wtns_calc.hip), chunk k + 1 while the proofs of chunk k run.  Only the inputs, the status words, the
+// public signals and the proofs cross the bus.  Ordering: a context's streams wait for the chunk's ready event before
+// the proof is launched; the calculator's stream waits, before it writes a buffer again, for the events after which the
+// proofs still in flight no longer read their witness (BatchPipe::release_to).
+int g16_fullprove_batch(g16_prover* p, g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, size_t count,
+                        const uint8_t* rs, g16_proof* out, uint8_t* pub, uint32_t* status) {
+  if (!p || !h) { set_error("NULL argument"); return G16_E_ARG; }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (int rc = shard_guard(p)) return rc;
+  if (p->shard_count != 1) { set_error("sharded handle: use g16_prove_partial/g16_prove_finish"); return G16_E_STATE; }
+  if (int rc = wcalc_match_prover(h, "fullprove", p->device, p->nVars, p->nPublic)) return rc;
+  if (!count) return G16_OK;
+  if (!out || !status || (n_inputs && !inputs)) { set_error("NULL argument"); return G16_E_ARG; }
+  if (int rc = wcalc_check_inputs(h, inputs, n_inputs, count)) return rc;   // (before the device is touched)
+  G16_HIP(hipSetDevice(p->device));
+  WcalcDevice* d = h->dev;
+  const size_t chunk = wcalc_chunk_size(d), nchunks = (count + chunk - 1) / chunk;
+  const size_t in_bytes = n_inputs * 32, pub_bytes = (size_t)p->nPublic * 32;
+  auto cnt_of = [&](size_t k) { return (uint32_t)(count - k * chunk < chunk ? count - k * chunk : chunk); };
+  BatchPipe pipe(p, rs, out, count > 1, /*check_words=*/false);   // (the calculator writes canonical words)
+  // every error exit: the contexts and the calculator's stream drained, so that nothing of this call is left on the
+  // device and the caller's buffers are not read after the return
+  auto fail = [&](int rc) -> int {
+    pipe.fail(rc);
+    wcalc_chunk_drain(d);
+    return rc;
+  };
+  WcalcChunk ck[2];
+  int rc = wcalc_chunk_launch(d, 0, inputs, cnt_of(0), pub != nullptr, &ck[0]);
+  if (rc) return fail(rc);
+  for (size_t k = 0; k < nchunks; k++) {
+    const size_t at = k * chunk;
+    const uint32_t cnt = cnt_of(k);
+    if (k + 1 < nchunks) {
+      // the other buffer held chunk k - 1; no proof of chunk k is launched yet, so what is in flight reads that chunk
+      // (or an earlier one)
+      if ((rc = pipe.release_to(d)) ||
+          (rc = wcalc_chunk_launch(d, (int)((k + 1) & 1), inputs + (at + cnt) * in_bytes, cnt_of(k + 1), pub != nullptr, &ck[(k + 1) & 1])))
+        return fail(rc);
+    }
+    const WcalcChunk& c = ck[k & 1];
+    {
+      const hipError_t e = hipEventSynchronize(c.ready);   // the verdicts, before a proof of the chunk takes a context
+      if (e != hipSuccess) { set_error(std::string("fullprove: ") + hipGetErrorString(e)); return fail(G16_E_HIP); }
+    }
+    for (uint32_t i = 0; i < cnt; i++) {
+      status[at + i] = c.status[i];
+      uint8_t* row = pub ? pub + (at + i) * pub_bytes : nullptr;
+      if (c.status[i] != kWpNoCheck) {   // a verdict: no proof, and no context taken
+        memset(&out[at + i], 0, sizeof(g16_proof));
+        if (row) memset(row, 0, pub_bytes);
+        continue;
+      }
+      if (row && pub_bytes) memcpy(row, c.pub + i * pub_bytes, pub_bytes);
+      rc = pipe.push(at + i, [&](ProofCtx& x, bool& busy, const Fr** d_w, double& t_mid) -> int {
+        busy = true;
+        G16_HIP(hipStreamWaitEvent(x.st, c.ready, 0));
+        if (x.wst != x.st) G16_HIP(hipStreamWaitEvent(x.wst, c.ready, 0));
+        if (x.wst2 != x.st) G16_HIP(hipStreamWaitEvent(x.wst2, c.ready, 0));
+        t_mid = pipe.now_ms();
+        *d_w = c.d_w + (size_t)i * p->nVars;
+        return G16_OK;
+      });
+      if (rc) return fail(rc);
+    }
   }
+  if ((rc = pipe.flush())) return fail(rc);
   return G16_OK;
 }
 

@@ -336,6 +336,22 @@ int wcalc_check_inputs(const g16_wtns_calculator* h, const uint8_t* inputs, size
   return G16_OK;
 }
 
+int wcalc_match_prover(const g16_wtns_calculator* h, const char* who, int device, uint32_t n_wires, uint32_t n_public) {
+  const std::string w(who);
+  if (!h->dev) { set_error(w + ": the calculator runs on the host route (create it on the prover's device)"); return G16_E_STATE; }
+  if (wcalc_device_id(h->dev) != device) {
+    set_error(w + ": the calculator is on device " + std::to_string(wcalc_device_id(h->dev)) + ", the prover on device " +
+              std::to_string(device));
+    return G16_E_STATE;
+  }
+  if (h->p.n_wires != n_wires || h->p.n_public != n_public) {
+    set_error(w + ": the program has " + std::to_string(h->p.n_wires) + " wires and " + std::to_string(h->p.n_public) +
+              " public signals, the key " + std::to_string(n_wires) + " and " + std::to_string(n_public));
+    return G16_E_STATE;
+  }
+  return G16_OK;
+}
+
 extern "C" int g16_wtns_calc_create(const uint8_t* prog, size_t len, int device, g16_wtns_calculator** out) {
   if (!out) { set_error("wtns calc: null argument"); return G16_E_ARG; }
   *out = nullptr;

@@ -105,6 +105,21 @@ int wcalc_device_id(const WcalcDevice* d);
 int wcalc_device_run(WcalcDevice* d, const uint8_t* inputs, size_t count, uint8_t* out_bodies, uint32_t* status, float ms[3]);
 // one witness evaluated on `st` into d_out (n_wires words on d's device); *status once the call returns (it waits)
 int wcalc_device_run_into(WcalcDevice* d, const uint8_t* inputs, Fr* d_out, hipStream_t st, uint32_t* status);
+// Chunks that stay on the device, for a prover there (g16_fullprove_batch, g16_plonk_fullprove_batch).  The calculator
+// keeps two chunk buffers of up to wcalc_chunk_size witnesses each (at most 2 x 4 GiB of device memory, grown on demand).
+struct WcalcChunk {
+  const Fr* d_w = nullptr;            // cnt * n_wires words on the device, valid for a stream that waited for `ready`
+  const uint32_t* status = nullptr;   // cnt words, pinned: valid on the host once `ready` has completed
+  const uint8_t* pub = nullptr;       // cnt * n_public words side by side, pinned (nullptr: not asked for, or none)
+  hipEvent_t ready = nullptr;
+};
+uint32_t wcalc_chunk_size(const WcalcDevice* d);
+// cnt <= wcalc_chunk_size witnesses into buffer `which` (0 or 1) on the calculator's own stream: enqueues only.
+// `inputs` (host, cnt * n_inputs words) is read until `ready`.  The caller releases the buffer first: what still reads
+// its previous chunk is named to wcalc_chunk_release, whose events the calculator's stream waits for.
+int wcalc_chunk_launch(WcalcDevice* d, int which, const uint8_t* inputs, uint32_t cnt, bool want_pub, WcalcChunk* out);
+int wcalc_chunk_release(WcalcDevice* d, hipEvent_t ev);
+void wcalc_chunk_drain(WcalcDevice* d);   // error paths: the calculator's stream, synchronised
 
 }  // namespace g16
 
@@ -117,3 +132,6 @@ struct g16_wtns_calculator {
 };
 // the input words of `count` witnesses: the right number of them, every one below r (the text names the first that is not)
 int wcalc_check_inputs(const g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, size_t count);
+// what a prover on `device` with a key of n_wires wires and n_public public signals refuses, "<who>: ..." (G16_E_STATE): a
+// calculator on the host route or on another device, a program with other counts
+int wcalc_match_prover(const g16_wtns_calculator* h, const char* who, int device, uint32_t n_wires, uint32_t n_public);

@@ -13,6 +13,14 @@
 // __syncthreads() is that (workgroup-scope release, s_barrier, acquire).
 //
 // Status: the lowest violated check of a witness, atomicMin on one word per witness (0xffffffff: none).
+//
+// Chunks for a prover on the same device (g16_fullprove_batch, g16_plonk_fullprove_batch): wcalc_chunk_launch computes
+// up to `chunk` witnesses into one of TWO chunk buffers on the calculator's own stream and records an event once the
+// chunk's status words and its public signals (gathered side by side by one small kernel) are in pinned host memory; the
+// witnesses stay where they are and the prover reads them there.  Two buffers, so that chunk k + 1 is computed while the
+// proofs of chunk k run; each holds what the 4 GiB rule (or G16_WTNS_CALC_CHUNK) allows, so a batched fullprove takes at
+// most 2 x 4 GiB of device memory for witnesses (buffer 0 is the one g16_wtns_calc uses; both grow with the chunks
+// that arrive).
 #include "witness_program.h"
 
 namespace g16 {
@@ -41,19 +49,38 @@ __global__ __launch_bounds__(kWcalcThreads) void wtns_calc_kernel(WpView p, cons
   }
 }
 
+// the public signals of `cnt` witnesses -- words 1 .. n_public of each -- side by side; total = cnt * n_public
+__global__ __launch_bounds__(256) void wtns_gather_pub_kernel(const Fr* __restrict__ w, uint32_t n_wires, uint32_t n_public,
+                                                              uint32_t total, Fr* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= total) return;
+  const uint32_t y = i / n_public, j = i - y * n_public;
+  out[i] = w[(size_t)y * n_wires + 1 + j];
+}
+
+// One set of batch buffers.  Set 0 serves g16_wtns_calc and g16_stage_inputs; the chunks of a batched fullprove
+// alternate between the two.
+struct WcalcBuf {
+  uint32_t cap = 0, cap_pub = 0;        // witnesses the buffers hold; ... the public-signal buffers
+  Fr *d_w = nullptr, *d_in = nullptr;   // cap * n_wires words; cap * n_inputs words
+  uint32_t *d_status = nullptr, *h_status = nullptr;   // cap words each; h_status pinned
+  Fr* d_pub = nullptr;                  // cap_pub * n_public words
+  uint8_t* h_pub = nullptr;             // ... pinned
+  hipEvent_t ready = nullptr;           // the last chunk's status words and public signals are on the host
+};
+
 struct WcalcDevice {
   int device = 0;
-  uint32_t n_wires = 0, n_inputs = 0, n_levels = 0, chunk = 1, cap = 0;
+  uint32_t n_wires = 0, n_inputs = 0, n_public = 0, n_levels = 0, chunk = 1;
   hipStream_t st = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  WcalcBuf buf[2];
   WpOp* ops = nullptr;
   WpEvalTerm* terms = nullptr;
   Fr* coefs = nullptr;
   int64_t* icoefs = nullptr;
   Fr* inv_small = nullptr;
   uint32_t *targets = nullptr, *levels = nullptr;
-  Fr *d_w = nullptr, *d_in = nullptr;   // cap * n_wires words; cap * n_inputs words
-  uint32_t *d_status = nullptr, *h_status = nullptr;   // cap words each; h_status pinned
 };
 
 template <class T> static int wcalc_upload(T** dst, const std::vector<T>& src) {
@@ -62,19 +89,30 @@ template <class T> static int wcalc_upload(T** dst, const std::vector<T>& src) {
   return G16_OK;
 }
 
-static void wcalc_free_batch(WcalcDevice* d) {
-  (void)hipFree(d->d_w); (void)hipFree(d->d_in); (void)hipFree(d->d_status);
-  if (d->h_status) (void)hipHostFree(d->h_status);
-  d->d_w = d->d_in = nullptr;
-  d->d_status = d->h_status = nullptr;
-  d->cap = 0;
+static void wcalc_free_pub(WcalcBuf& b) {
+  (void)hipFree(b.d_pub);
+  if (b.h_pub) (void)hipHostFree(b.h_pub);
+  b.d_pub = nullptr;
+  b.h_pub = nullptr;
+  b.cap_pub = 0;
+}
+static void wcalc_free_batch(WcalcBuf& b) {
+  (void)hipFree(b.d_w); (void)hipFree(b.d_in); (void)hipFree(b.d_status);
+  if (b.h_status) (void)hipHostFree(b.h_status);
+  b.d_w = b.d_in = nullptr;
+  b.d_status = b.h_status = nullptr;
+  b.cap = 0;
 }
 
 void wcalc_device_destroy(WcalcDevice* d) {
   if (!d) return;
   (void)hipSetDevice(d->device);
   if (d->st) (void)hipStreamSynchronize(d->st);
-  wcalc_free_batch(d);
+  for (WcalcBuf& b : d->buf) {
+    wcalc_free_batch(b);
+    wcalc_free_pub(b);
+    if (b.ready) (void)hipEventDestroy(b.ready);
+  }
   (void)hipFree(d->ops); (void)hipFree(d->terms); (void)hipFree(d->coefs); (void)hipFree(d->icoefs); (void)hipFree(d->inv_small);(void)hipFree(d->targets); (void)hipFree(d->levels);
   for (hipEvent_t e : d->ev)
     if (e) (void)hipEventDestroy(e);
@@ -85,14 +123,23 @@ void wcalc_device_destroy(WcalcDevice* d) {
 int wcalc_device_id(const WcalcDevice* d) { return d->device; }
 
 // the batch buffers hold `cap` witnesses; they grow to the largest chunk asked for (at most d->chunk)
-static int wcalc_reserve(WcalcDevice* d, uint32_t cnt) {
-  if (cnt <= d->cap) return G16_OK;
-  wcalc_free_batch(d);
-  G16_HIP(hipMalloc(&d->d_w, ((size_t)cnt * d->n_wires + 1) * sizeof(Fr)));
-  G16_HIP(hipMalloc(&d->d_in, ((size_t)cnt * d->n_inputs + 1) * sizeof(Fr)));
-  G16_HIP(hipMalloc(&d->d_status, (size_t)cnt * 4));
-  G16_HIP(hipHostMalloc((void**)&d->h_status, (size_t)cnt * 4));
-  d->cap = cnt;
+static int wcalc_reserve(WcalcDevice* d, WcalcBuf& b, uint32_t cnt) {
+  if (cnt <= b.cap) return G16_OK;
+  wcalc_free_batch(b);
+  G16_HIP(hipMalloc(&b.d_w, ((size_t)cnt * d->n_wires + 1) * sizeof(Fr)));
+  G16_HIP(hipMalloc(&b.d_in, ((size_t)cnt * d->n_inputs + 1) * sizeof(Fr)));
+  G16_HIP(hipMalloc(&b.d_status, (size_t)cnt * 4));
+  G16_HIP(hipHostMalloc((void**)&b.h_status, (size_t)cnt * 4));
+  b.cap = cnt;
+  return G16_OK;
+}
+// ... and the public signals of a chunk, for the callers that ask for them
+static int wcalc_reserve_pub(WcalcDevice* d, WcalcBuf& b, uint32_t cnt) {
+  if (cnt <= b.cap_pub) return G16_OK;
+  wcalc_free_pub(b);
+  G16_HIP(hipMalloc(&b.d_pub, ((size_t)cnt * d->n_public + 1) * sizeof(Fr)));
+  G16_HIP(hipHostMalloc((void**)&b.h_pub, ((size_t)cnt * d->n_public + 1) * sizeof(Fr)));
+  b.cap_pub = cnt;
   return G16_OK;
 }
 
@@ -104,7 +151,8 @@ static int wcalc_device_fill(WcalcDevice* d, const WitnessProgram& p) {
   if ((rc = wcalc_upload(&d->ops, p.ops)) || (rc = wcalc_upload(&d->terms, p.eterms)) || (rc = wcalc_upload(&d->coefs, p.coefs)) || (rc = wcalc_upload(&d->icoefs, p.icoefs)) || (rc = wcalc_upload(&d->inv_small, p.inv_small)) ||
       (rc = wcalc_upload(&d->targets, p.targets)) || (rc = wcalc_upload(&d->levels, p.levels)))
     return rc;
-  return wcalc_reserve(d, 1);
+  for (WcalcBuf& b : d->buf) G16_HIP(hipEventCreate(&b.ready));
+  return wcalc_reserve(d, d->buf[0], 1);
 }
 
 int wcalc_device_create(int device, const WitnessProgram& p, uint32_t chunk, WcalcDevice** out) {
@@ -114,6 +162,7 @@ int wcalc_device_create(int device, const WitnessProgram& p, uint32_t chunk, Wca
   d->device = device;
   d->n_wires = p.n_wires;
   d->n_inputs = p.n_inputs;
+  d->n_public = p.n_public;
   d->n_levels = (uint32_t)p.levels.size() - 1;
   d->chunk = chunk < 1 ? 1 : chunk;
   if (const int rc = wcalc_device_fill(d, p)) {
@@ -138,19 +187,20 @@ int wcalc_device_run(WcalcDevice* d, const uint8_t* inputs, size_t count, uint8_
   if (ms) ms[0] = ms[1] = ms[2] = 0.f;
   for (size_t at = 0; at < count; at += d->chunk) {
     const uint32_t cnt = (uint32_t)(count - at < d->chunk ? count - at : d->chunk);
-    if (const int rc = wcalc_reserve(d, cnt)) return rc;
+    WcalcBuf& b = d->buf[0];
+    if (const int rc = wcalc_reserve(d, b, cnt)) return rc;
     G16_HIP(hipEventRecord(d->ev[0], d->st));
     if (d->n_inputs)
-      G16_HIP(hipMemcpyAsync(d->d_in, inputs + at * d->n_inputs * 32, (size_t)cnt * d->n_inputs * 32, hipMemcpyHostToDevice, d->st));
+      G16_HIP(hipMemcpyAsync(b.d_in, inputs + at * d->n_inputs * 32, (size_t)cnt * d->n_inputs * 32, hipMemcpyHostToDevice, d->st));
     G16_HIP(hipEventRecord(d->ev[1], d->st));
-    if (const int rc = wcalc_launch(d, d->d_in, d->d_w, d->d_status, cnt, d->st)) return rc;
+    if (const int rc = wcalc_launch(d, b.d_in, b.d_w, b.d_status, cnt, d->st)) return rc;
     G16_HIP(hipEventRecord(d->ev[2], d->st));
-    G16_HIP(hipMemcpyAsync(d->h_status, d->d_status, (size_t)cnt * 4, hipMemcpyDeviceToHost, d->st));
+    G16_HIP(hipMemcpyAsync(b.h_status, b.d_status, (size_t)cnt * 4, hipMemcpyDeviceToHost, d->st));
     if (out_bodies)
-      G16_HIP(hipMemcpyAsync(out_bodies + at * d->n_wires * 32, d->d_w, (size_t)cnt * d->n_wires * 32, hipMemcpyDeviceToHost, d->st));
+      G16_HIP(hipMemcpyAsync(out_bodies + at * d->n_wires * 32, b.d_w, (size_t)cnt * d->n_wires * 32, hipMemcpyDeviceToHost, d->st));
     G16_HIP(hipEventRecord(d->ev[3], d->st));
     G16_HIP(hipStreamSynchronize(d->st));
-    for (uint32_t i = 0; i < cnt; i++) status[at + i] = d->h_status[i];
+    for (uint32_t i = 0; i < cnt; i++) status[at + i] = b.h_status[i];
     if (ms)
       for (int k = 0; k < 3; k++) {
         float t = 0.f;
@@ -164,12 +214,53 @@ int wcalc_device_run(WcalcDevice* d, const uint8_t* inputs, size_t count, uint8_
 int wcalc_device_run_into(WcalcDevice* d, const uint8_t* inputs, Fr* d_out, hipStream_t st, uint32_t* status) {
   G16_HIP(hipSetDevice(d->device));
   // (the calculator's own stream is idle between calls: every run ends with a wait)
-  if (d->n_inputs) G16_HIP(hipMemcpyAsync(d->d_in, inputs, (size_t)d->n_inputs * 32, hipMemcpyHostToDevice, st));
-  if (const int rc = wcalc_launch(d, d->d_in, d_out, d->d_status, 1, st)) return rc;
-  G16_HIP(hipMemcpyAsync(d->h_status, d->d_status, 4, hipMemcpyDeviceToHost, st));
+  WcalcBuf& b = d->buf[0];
+  if (d->n_inputs) G16_HIP(hipMemcpyAsync(b.d_in, inputs, (size_t)d->n_inputs * 32, hipMemcpyHostToDevice, st));
+  if (const int rc = wcalc_launch(d, b.d_in, d_out, b.d_status, 1, st)) return rc;
+  G16_HIP(hipMemcpyAsync(b.h_status, b.d_status, 4, hipMemcpyDeviceToHost, st));
   G16_HIP(hipStreamSynchronize(st));
-  *status = d->h_status[0];
+  *status = b.h_status[0];
   return G16_OK;
+}
+
+uint32_t wcalc_chunk_size(const WcalcDevice* d) { return d->chunk; }
+
+int wcalc_chunk_release(WcalcDevice* d, hipEvent_t ev) {
+  G16_HIP(hipSetDevice(d->device));
+  G16_HIP(hipStreamWaitEvent(d->st, ev, 0));
+  return G16_OK;
+}
+
+int wcalc_chunk_launch(WcalcDevice* d, int which, const uint8_t* inputs, uint32_t cnt, bool want_pub, WcalcChunk* out) {
+  if (cnt < 1 || cnt > d->chunk || (which & ~1)) { set_error("wtns calc: bad chunk"); return G16_E_ARG; }
+  G16_HIP(hipSetDevice(d->device));
+  WcalcBuf& b = d->buf[which];
+  want_pub = want_pub && d->n_public;
+  if (d->n_public >= d->n_wires || (uint64_t)cnt * d->n_public > 0x7fffffffull) { set_error("wtns calc: bad chunk"); return G16_E_ARG; }
+  // (a buffer that grows is freed first: the caller has released it, and hipFree waits for the device)
+  int rc = wcalc_reserve(d, b, cnt);
+  if (!rc && want_pub) rc = wcalc_reserve_pub(d, b, cnt);
+  if (rc) return rc;
+  if (d->n_inputs) G16_HIP(hipMemcpyAsync(b.d_in, inputs, (size_t)cnt * d->n_inputs * 32, hipMemcpyHostToDevice, d->st));
+  if ((rc = wcalc_launch(d, b.d_in, b.d_w, b.d_status, cnt, d->st))) return rc;
+  G16_HIP(hipMemcpyAsync(b.h_status, b.d_status, (size_t)cnt * 4, hipMemcpyDeviceToHost, d->st));
+  if (want_pub) {
+    const uint32_t total = cnt * d->n_public;   // (below cnt * n_wires <= 2^27: the 4 GiB rule)
+    wtns_gather_pub_kernel<<<(total + 255) / 256, 256, 0, d->st>>>(b.d_w, d->n_wires, d->n_public, total, b.d_pub);
+    G16_HIP(hipGetLastError());
+    G16_HIP(hipMemcpyAsync(b.h_pub, b.d_pub, (size_t)total * 32, hipMemcpyDeviceToHost, d->st));
+  }
+  G16_HIP(hipEventRecord(b.ready, d->st));
+  out->d_w = b.d_w;
+  out->status = b.h_status;
+  out->pub = want_pub ? b.h_pub : nullptr;
+  out->ready = b.ready;
+  return G16_OK;
+}
+
+void wcalc_chunk_drain(WcalcDevice* d) {
+  (void)hipSetDevice(d->device);
+  (void)hipStreamSynchronize(d->st);
 }
 
 }  // namespace g16

@@ -39,6 +39,8 @@
  *                                                                              (g16_ptau_import_response_files)
  *           nzcpProgramFile(params[7] | null, gadget | null, gadgetParams, path); wtnsCalculate(programPath, names, values,
  *               device) -> {status, text, wtns}   (g16_nzcp_witness_program, g16_wtns_calc_wtns: see above their code)
+ *           fullProveBatch(plonk: bool, programPath, zkey: Buffer, names: string[][], values: Buffer[][], device,
+ *               blinding: Buffer | null) -> [{status, text, proof, pub}]   (g16_fullprove_batch, g16_plonk_fullprove_batch)
  *           zkeyVerifyFromInitFiles(initPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_from_init_files)
  *           zkeyVerifyFromInitPtauFiles(initPath, ptauPath, zkeyPath, device) -> Promise<{ok, reason}>   (..._from_init_ptau_files)
  *           zkeyVerifyR1csFiles(r1csPath, ptauPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_r1cs_files)
@@ -1214,11 +1216,58 @@ static napi_value js_nzcp_program_file(napi_env env, napi_callback_info info) {
   if (!ok) { napi_throw_error(env, NULL, "nzcp program: cannot write the file"); return NULL; }
   return NULL;
 }
+/* the witness program at `path` -> a calculator on `device`; msg: why not */
+static g16_wtns_calculator* open_calculator(const char* path, int32_t device, char* msg, size_t msg_len) {
+  FILE* f = fopen(path, "rb");
+  long flen = -1;
+  uint8_t* prog = NULL;
+  if (f && fseek(f, 0, SEEK_END) == 0 && (flen = ftell(f)) >= 0 && fseek(f, 0, SEEK_SET) == 0 && (prog = (uint8_t*)malloc((size_t)flen + 1)) &&
+      fread(prog, 1, (size_t)flen, f) != (size_t)flen) { free(prog); prog = NULL; }
+  if (f) fclose(f);
+  if (!prog) { snprintf(msg, msg_len, "wtns calculate: cannot read %s", path); return NULL; }
+  g16_wtns_calculator* h = NULL;
+  const int rc = g16_wtns_calc_create(prog, (size_t)flen, device, &h);
+  free(prog);
+  if (rc) { snprintf(msg, msg_len, "%s", g16_last_error()); return NULL; }
+  return h;
+}
+/* the named inputs of one pass (names[i], values[i] = its words) -> the program's input words (inf[2] of them, zeroed by
+ * the caller); msg: what does not match the program's input table */
+static void input_words(napi_env env, g16_wtns_calculator* h, const uint32_t inf[6], napi_value names, napi_value values, uint8_t* words,
+                        char* msg, size_t msg_len) {
+  char name[256];
+  size_t n = 0;
+  uint32_t count = 0, nvals = 0;
+  uint8_t* seen = (uint8_t*)calloc((size_t)inf[5] + 1, 1);
+  if (!seen) { snprintf(msg, msg_len, "wtns calculate: out of memory"); return; }
+  if (napi_get_array_length(env, names, &count) != napi_ok || napi_get_array_length(env, values, &nvals) != napi_ok || nvals != count)
+    snprintf(msg, msg_len, "wtns calculate: bad input");
+  for (uint32_t i = 0; i < count && !msg[0]; i++) {
+    napi_value nm, val;
+    void* p = NULL;
+    size_t len = 0;
+    if (napi_get_element(env, names, i, &nm) != napi_ok || napi_get_value_string_utf8(env, nm, name, sizeof(name), &n) != napi_ok ||
+        napi_get_element(env, values, i, &val) != napi_ok || napi_get_buffer_info(env, val, &p, &len) != napi_ok) {
+      snprintf(msg, msg_len, "wtns calculate: bad input %u", i);
+      break;
+    }
+    uint32_t k = 0, first = 0, cnt = 0;
+    const char* have = NULL;
+    for (; k < inf[5]; k++)
+      if ((have = g16_wtns_calc_input(h, k, &first, &cnt)) && strcmp(have, name) == 0) break;
+    if (k == inf[5]) snprintf(msg, msg_len, "wtns calculate: the program has no input %s", name);
+    else if (len != (size_t)cnt * 32) snprintf(msg, msg_len, "wtns calculate: input %s takes %u values, %zu given", name, cnt, len / 32);
+    else { memcpy(words + (size_t)first * 32, p, len); seen[k] = 1; }
+  }
+  for (uint32_t k = 0; k < inf[5] && !msg[0]; k++)
+    if (!seen[k]) snprintf(msg, msg_len, "wtns calculate: input %s is missing", g16_wtns_calc_input(h, k, NULL, NULL));
+  free(seen);
+}
 static napi_value js_wtns_calculate(napi_env env, napi_callback_info info) {
   size_t argc = 4, n = 0;
   napi_value argv[4], out = NULL, v;
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  char path[1024], name[256], msg[512];
+  char path[1024], msg[512];
   uint32_t count = 0, nvals = 0;
   int32_t device = -1;
   if (argc < 3 || napi_get_value_string_utf8(env, argv[0], path, sizeof(path), &n) != napi_ok ||
@@ -1227,42 +1276,14 @@ static napi_value js_wtns_calculate(napi_env env, napi_callback_info info) {
     return NULL;
   }
   if (argc > 3) napi_get_value_int32(env, argv[3], &device);
-  FILE* f = fopen(path, "rb");
-  long flen = -1;
-  uint8_t* prog = NULL;
-  if (f && fseek(f, 0, SEEK_END) == 0 && (flen = ftell(f)) >= 0 && fseek(f, 0, SEEK_SET) == 0 && (prog = (uint8_t*)malloc((size_t)flen + 1)) &&
-      fread(prog, 1, (size_t)flen, f) != (size_t)flen) { free(prog); prog = NULL; }
-  if (f) fclose(f);
-  if (!prog) { snprintf(msg, sizeof(msg), "wtns calculate: cannot read %s", path); napi_throw_error(env, NULL, msg); return NULL; }
-  g16_wtns_calculator* h = NULL;
-  int rc = g16_wtns_calc_create(prog, (size_t)flen, device, &h);
-  free(prog);
-  if (rc) { napi_throw_error(env, NULL, g16_last_error()); return NULL; }
+  msg[0] = 0;
+  g16_wtns_calculator* h = open_calculator(path, device, msg, sizeof(msg));
+  if (!h) { napi_throw_error(env, NULL, msg); return NULL; }
   uint32_t inf[6];
   g16_wtns_calc_info(h, inf);
   uint8_t* words = (uint8_t*)calloc((size_t)inf[2] + 1, 32);
-  uint8_t* seen = (uint8_t*)calloc((size_t)inf[5] + 1, 1);
-  msg[0] = 0;
-  for (uint32_t i = 0; words && seen && i < count && !msg[0]; i++) {
-    napi_value nm, val;
-    void* p = NULL;
-    size_t len = 0;
-    if (napi_get_element(env, argv[1], i, &nm) != napi_ok || napi_get_value_string_utf8(env, nm, name, sizeof(name), &n) != napi_ok ||
-        napi_get_element(env, argv[2], i, &val) != napi_ok || napi_get_buffer_info(env, val, &p, &len) != napi_ok) {
-      snprintf(msg, sizeof(msg), "wtns calculate: bad input %u", i);
-      break;
-    }
-    uint32_t k = 0, first = 0, cnt = 0;
-    const char* have = NULL;
-    for (; k < inf[5]; k++)
-      if ((have = g16_wtns_calc_input(h, k, &first, &cnt)) && strcmp(have, name) == 0) break;
-    if (k == inf[5]) snprintf(msg, sizeof(msg), "wtns calculate: the program has no input %s", name);
-    else if (len != (size_t)cnt * 32) snprintf(msg, sizeof(msg), "wtns calculate: input %s takes %u values, %zu given", name, cnt, len / 32);
-    else { memcpy(words + (size_t)first * 32, p, len); seen[k] = 1; }
-  }
-  for (uint32_t k = 0; words && seen && k < inf[5] && !msg[0]; k++)
-    if (!seen[k]) snprintf(msg, sizeof(msg), "wtns calculate: input %s is missing", g16_wtns_calc_input(h, k, NULL, NULL));
-  if (!words || !seen) snprintf(msg, sizeof(msg), "wtns calculate: out of memory");
+  if (words) input_words(env, h, inf, argv[1], argv[2], words, msg, sizeof(msg));
+  else snprintf(msg, sizeof(msg), "wtns calculate: out of memory");
   uint32_t status = 0xffffffffu;
   uint8_t* wt = NULL;
   size_t wl = 0;
@@ -1279,8 +1300,104 @@ static napi_value js_wtns_calculate(napi_env env, napi_callback_info info) {
   }
   g16_free(wt);
   free(words);
-  free(seen);
   g16_wtns_calc_destroy(h);
+  if (msg[0]) { napi_throw_error(env, NULL, msg); return NULL; }
+  return out;
+}
+
+/* fullProveBatch(plonk, programPath, zkey, names[][], values[][], device, blinding): inputs in, proofs out, the witnesses
+ * computed on `device` and proved there from the calculator's chunk buffers (g16_fullprove_batch,
+ * g16_plonk_fullprove_batch).  Pass i's inputs are names[i] / values[i], matched against the program's input table as
+ * wtnsCalculate matches them.  blinding: count * 64 bytes (r | s; PLONK: count * 288, nine scalars) or null.  Synchronous,
+ * like wtnsCalculate.  -> [{status, text, proof, pub}]: status -1 with the proof and public-signal bytes, or the violated
+ * check and its text with nulls. */
+static napi_value js_full_prove_batch(napi_env env, napi_callback_info info) {
+  size_t argc = 7, n = 0;
+  napi_value argv[7], out = NULL, v;
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  char path[1024], msg[512];
+  bool is_plonk = false;
+  uint32_t count = 0, nvals = 0;
+  int32_t device = 0;
+  void *zkey = NULL, *blind = NULL;
+  size_t zlen = 0, blen = 0;
+  if (argc < 6 || napi_get_value_bool(env, argv[0], &is_plonk) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], path, sizeof(path), &n) != napi_ok ||
+      napi_get_array_length(env, argv[3], &count) != napi_ok || napi_get_array_length(env, argv[4], &nvals) != napi_ok || nvals != count ||
+      napi_get_value_int32(env, argv[5], &device) != napi_ok) {
+    napi_throw_type_error(env, NULL, "fullProveBatch(plonk, programPath, zkey, names, values, device, blinding)");
+    return NULL;
+  }
+  bool is_buf = false;   /* (napi_get_buffer_info asserts on a value that is no Buffer in older Node releases) */
+  if (napi_is_buffer(env, argv[2], &is_buf) != napi_ok || !is_buf) {
+    napi_throw_type_error(env, NULL, "fullProveBatch(plonk, programPath, zkey, names, values, device, blinding)");
+    return NULL;
+  }
+  napi_get_buffer_info(env, argv[2], &zkey, &zlen);
+  if (argc > 6 && napi_is_buffer(env, argv[6], &is_buf) == napi_ok && is_buf) napi_get_buffer_info(env, argv[6], &blind, &blen);
+  const size_t proof_bytes = is_plonk ? sizeof(g16_plonk_proof) : sizeof(g16_proof);
+  if (blind && blen != (size_t)count * (is_plonk ? 288 : 64)) {
+    napi_throw_error(env, NULL, "fullprove: the blinding takes 64 bytes per proof (plonk: 288)");
+    return NULL;
+  }
+  msg[0] = 0;
+  g16_wtns_calculator* h = open_calculator(path, device, msg, sizeof(msg));
+  if (!h) { napi_throw_error(env, NULL, msg); return NULL; }
+  uint32_t inf[6];
+  g16_wtns_calc_info(h, inf);
+  const size_t in_bytes = (size_t)inf[2] * 32, pub_bytes = (size_t)inf[1] * 32;
+  uint8_t* words = (uint8_t*)calloc((size_t)count * inf[2] + 1, 32);
+  uint8_t* proofs = (uint8_t*)calloc((size_t)count + 1, proof_bytes);
+  uint8_t* pub = (uint8_t*)calloc((size_t)count * inf[1] + 1, 32);
+  uint32_t* status = (uint32_t*)calloc((size_t)count + 1, 4);
+  if (!words || !proofs || !pub || !status) snprintf(msg, sizeof(msg), "fullprove: out of memory");
+  for (uint32_t i = 0; i < count && !msg[0]; i++) {
+    napi_value nm, val;
+    if (napi_get_element(env, argv[3], i, &nm) != napi_ok || napi_get_element(env, argv[4], i, &val) != napi_ok)
+      snprintf(msg, sizeof(msg), "wtns calculate: bad input");
+    else
+      input_words(env, h, inf, nm, val, words + i * in_bytes, msg, sizeof(msg));
+  }
+  g16_prover* gp = NULL;
+  g16_plonk* pp = NULL;
+  if (!msg[0]) {
+    int rc;
+    if (is_plonk) {
+      rc = g16_plonk_create((const uint8_t*)zkey, zlen, device, &pp);
+      if (!rc) rc = g16_plonk_fullprove_batch(pp, h, words, inf[2], count, (const uint8_t*)blind, (g16_plonk_proof*)proofs, pub, status);
+    } else {
+      g16_opts o;
+      memset(&o, 0, sizeof(o));
+      o.device = device;
+      o.shard_count = 1;
+      rc = g16_create((const uint8_t*)zkey, zlen, &o, &gp);
+      if (!rc) rc = g16_fullprove_batch(gp, h, words, inf[2], count, (const uint8_t*)blind, (g16_proof*)proofs, pub, status);
+    }
+    if (rc) snprintf(msg, sizeof(msg), "%s", g16_last_error());
+  }
+  if (!msg[0]) {
+    napi_create_array_with_length(env, count, &out);
+    for (uint32_t i = 0; i < count; i++) {
+      napi_value obj;
+      void* copy = NULL;
+      const int good = status[i] == 0xffffffffu;
+      napi_create_object(env, &obj);
+      napi_create_int64(env, good ? -1 : (int64_t)status[i], &v);
+      napi_set_named_property(env, obj, "status", v);
+      const char* text = good ? "" : g16_wtns_calc_check_text(h, status[i]);
+      napi_create_string_utf8(env, text ? text : "", NAPI_AUTO_LENGTH, &v);
+      napi_set_named_property(env, obj, "text", v);
+      if (good) napi_create_buffer_copy(env, proof_bytes, proofs + i * proof_bytes, &copy, &v); else napi_get_null(env, &v);
+      napi_set_named_property(env, obj, "proof", v);
+      if (good) napi_create_buffer_copy(env, pub_bytes, pub + i * pub_bytes, &copy, &v); else napi_get_null(env, &v);
+      napi_set_named_property(env, obj, "pub", v);
+      napi_set_element(env, out, i, obj);
+    }
+  }
+  if (gp) g16_destroy(gp);
+  if (pp) g16_plonk_destroy(pp);
+  g16_wtns_calc_destroy(h);
+  free(words); free(proofs); free(pub); free(status);
   if (msg[0]) { napi_throw_error(env, NULL, msg); return NULL; }
   return out;
 }
@@ -1315,6 +1432,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"wtnsCheckFiles", NULL, js_wtns_check_files, NULL, NULL, NULL, napi_default, NULL},
       {"nzcpProgramFile", NULL, js_nzcp_program_file, NULL, NULL, NULL, napi_default, NULL},
       {"wtnsCalculate", NULL, js_wtns_calculate, NULL, NULL, NULL, napi_default, NULL},
+      {"fullProveBatch", NULL, js_full_prove_batch, NULL, NULL, NULL, napi_default, NULL},
   };
   NAPI_OK(napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props));
   return exports;

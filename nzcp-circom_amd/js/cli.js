@@ -34,6 +34,10 @@
 // that violates a constraint prints "[ERROR] snarkJS: <the constraint's text>" and exits 1 before anything is written.
 // `wtns calculate` runs on host threads unless --device names a GPU; `fullprove` computes the witness likewise and proves
 // on the GPU.
+// And of `snarkjs plonk fullprove <input.json> <circuit.wasm> <circuit.zkey> [proof.json] [public.json]` (alias `pkf`), with
+// a witness program likewise: the witness is computed on the GPU and proved from where it lies (g16_plonk_fullprove_batch).
+// A violated constraint prints "[ERROR] snarkJS: <its text>" and exits 1 before anything is written; a usage error exits 2.
+// [--blinding b1,..,b9]: TEST-ONLY, the nine blinding scalars (reproducible bytes).
 "use strict";
 const fs = require("fs");
 const { groth16 } = require("./index.js");
@@ -224,6 +228,24 @@ async function main(argv) {
     if (pos.length < 3) { console.error("usage: cli.js plonk setup <circuit.r1cs> <pot.ptau> <circuit.zkey> [--lagrange]"); process.exit(2); }
     const { plonk } = require("./index.js");
     await plonk.setup(pos[0], pos[1], pos[2], { lagrange: a.includes("--lagrange") });
+    return;
+  }
+  if ((a[0] === "plonk" && a[1] === "fullprove") || a[0] === "pkf") {
+    // snarkjs plonk fullprove <input.json> <circuit.wasm> <circuit.zkey> [proof.json] [public.json]   (alias: pkf)
+    const rest = a.slice(a[0] === "pkf" ? 1 : 2);
+    const opts = {};
+    const pos = [];
+    for (let i = 0; i < rest.length; i++) {
+      if (rest[i] === "--device") opts.device = parseInt(rest[++i], 10);
+      else if (rest[i] === "--blinding") opts.blinding = rest[++i].split(",");
+      else pos.push(rest[i]);
+    }
+    if (pos.length < 3) { console.error("usage: cli.js plonk fullprove <input.json> <program> <circuit.zkey> [proof.json] [public.json] [--device n --blinding b1,..,b9]"); process.exit(2); }
+    const [input, program, zkey, proofFile = "proof.json", publicFile = "public.json"] = pos;
+    const { plonk } = require("./index.js");
+    const { proof, publicSignals } = await plonk.fullProve(input, program, zkey, opts);
+    fs.writeFileSync(proofFile, JSON.stringify(proof, null, 1), "utf-8");
+    fs.writeFileSync(publicFile, JSON.stringify(publicSignals, null, 1), "utf-8");
     return;
   }
   if (a[0] === "plonk" && a[1] === "prove") {   // snarkjs plonk prove <circuit.zkey> <witness.wtns> [proof.json] [public.json]

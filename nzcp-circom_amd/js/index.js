@@ -489,13 +489,36 @@ const wtns = {
   },
 };
 function calculateWitness(input, programName, opts) {
-  if (typeof input === "string") input = JSON.parse(fs.readFileSync(input, "utf-8"));
   const device = !opts || opts.device === undefined || opts.device === null ? -1 : opts.device | 0;
-  const names = Object.keys(input);
-  const values = names.map((k) => Buffer.concat((Array.isArray(input[k]) ? input[k].flat(Infinity) : [input[k]]).map((x) => scalarToBuffer(x))));
+  const { names, values } = inputArrays(input);
   const res = native().wtnsCalculate(String(programName), names, values, device);
   if (res.status >= 0) throw new Error(res.text);
   return res.wtns;
+}
+// One pass's input object (or the name of its .json) -> what the addon matches against the program's input table
+function inputArrays(input) {
+  if (typeof input === "string") input = JSON.parse(fs.readFileSync(input, "utf-8"));
+  const names = Object.keys(input);
+  const values = names.map((k) => Buffer.concat((Array.isArray(input[k]) ? input[k].flat(Infinity) : [input[k]]).map((x) => scalarToBuffer(x))));
+  return { names, values };
+}
+// Batched fullprove (g16_fullprove_batch, g16_plonk_fullprove_batch): the witnesses are computed on the GPU in chunks and
+// proved from the chunk buffers; only inputs, public signals and proofs cross the bus.  `blind`: per pass its fixed
+// blinding bytes, or null.  -> per pass {proof, publicSignals}, or {error: the violated check's text}.
+function fullProveBatchNative(isPlonk, inputs, programName, zkey, opts, blind) {
+  const device = !opts || opts.device === undefined || opts.device === null ? 0 : opts.device | 0;
+  const passes = inputs.map(inputArrays);
+  const res = native().fullProveBatch(isPlonk, String(programName), toBuffer(zkey, "zkey"), passes.map((p) => p.names),
+    passes.map((p) => p.values), device, blind);
+  return res.map((r) => (r.status >= 0 ? { error: r.text }
+    : { proof: isPlonk ? plonkProofObject(r.proof) : proofObject(r.proof), publicSignals: publicSignals(r.pub) }));
+}
+// opts.blinding of a PLONK proof: the nine scalars b1..b9 (TEST-ONLY: reproducible bytes) -> 288 bytes, or null
+function plonkBlinding(b) {
+  if (b === undefined || b === null) return null;
+  if (Buffer.isBuffer(b)) return b;
+  if (!Array.isArray(b) || b.length !== 9) throw new Error("plonk: blinding takes the nine scalars b1..b9");
+  return Buffer.concat(b.map((x) => scalarToBuffer(x)));
 }
 // nzcp.witnessProgram(params | "example" | "live", file): the witness program of NZCPPubIdentity(params) written to `file`
 // (seconds at the full size: keep the file); nzcp.gadgetProgram(name, params, file): one template of the library
@@ -543,6 +566,27 @@ const groth16 = {
     if (opts && typeof opts.debug === "function") opts = { logger: opts };
     return groth16.prove(zkey, calculateWitness(input, programName, opts), opts);
   },
+  // Many passes at once, the witnesses computed on the GPU and proved where they are (no snarkjs counterpart):
+  // resolves to an array of {proof, publicSignals}, or {error: the violated check's text} for a pass whose input violates
+  // a constraint.  opts.r / opts.s are TEST-ONLY, as in proveBatch: one blinding pair for every proof of the batch.
+  async fullProveBatch(inputs, programName, zkey, opts = {}) {
+    const r = scalarToBuffer(opts.r), s = scalarToBuffer(opts.s);
+    const rs = r && s ? Buffer.concat(inputs.map(() => Buffer.concat([r, s]))) : null;
+    return fullProveBatchNative(false, inputs, programName, zkey, opts, rs);
+  },
+};
+// snarkjs: plonk.fullProve(input, wasmFile, zkeyFileName) -> {proof, publicSignals}; the second argument is a witness
+// program (see wtns.calculate), the witness is computed on the GPU and never leaves it.  A violated check rejects with
+// its text.  opts.blinding: the nine scalars b1..b9 (TEST-ONLY).  fullProveBatch: many passes, as groth16.fullProveBatch.
+plonk.fullProve = async function fullProve(input, programName, zkey, opts = {}) {
+  if (opts && typeof opts.debug === "function") opts = { logger: opts };
+  const [res] = fullProveBatchNative(true, [input], programName, zkey, opts, plonkBlinding(opts.blinding));
+  if (res.error !== undefined) throw new Error(res.error);
+  return res;
+};
+plonk.fullProveBatch = async function fullProveBatch(inputs, programName, zkey, opts = {}) {
+  const b = plonkBlinding(opts.blinding);
+  return fullProveBatchNative(true, inputs, programName, zkey, opts, b ? Buffer.concat(inputs.map(() => b)) : null);
 };
 
 module.exports = { groth16, plonk, powersOfTau, wtns, nzcp, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, verifyFromInit, verifyFromR1cs }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
