@@ -567,9 +567,12 @@ int g16_zkey_contribute_files(const char* in_path, const char* out_path, const c
  *   contribution holds the point at infinity", "a contribution's public key is not consistent" (e(g1_s, g2_spx) !=
  *   e(g1_sx, g2_sp)), "a contribution's delta does not continue the chain" (e(cur, g2_spx) != e(deltaAfter, g2_sp)),
  *   "delta1 of the header is not the last contribution's", "delta2 does not match delta1", "sections 8 and 9 are not the
- *   initial key's scaled by 1 / delta" (with fresh random rho_i over both sections together: S = sum rho_i new_i, T =
- *   sum rho_i init_i, e(S, delta2) != e(T, delta2 of init), or the infinity points differ), "the combination of
- *   sections 8 and 9 is the point at infinity".
+ *   initial key's scaled by 1 / delta" (S = sum rho_i new_i, T = sum rho_i init_i over both sections together, e(S,
+ *   delta2) != e(T, delta2 of init); section 8: fresh random rho_i, and its infinity points must be the initial key's;
+ *   section 9: rho_i = (1 / N) sum_k u_k w^((2i+1) k) with fresh random u_0 .. u_(N-2) and u_(N-1) = 0, formed on the
+ *   device as in g16_zkey_h_scalars -- the combinations of quotients of degree <= N - 2, which are what a prover forms
+ *   and what `zkey import bellman` preserves, so an imported key passes; a tampered point still moves the sum), "the
+ *   combination of sections 8 and 9 is the point at infinity".
  * A key with no records beyond init's (init against itself) is accepted.  A malformed file is G16_E_FORMAT, not a
  * verdict.  The two sums are MSMs and the pairings Miller loops + final exponentiations on `device` (G16_E_NOGPU). */
 int g16_zkey_verify_from_init(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_t zkey_len,
@@ -609,6 +612,66 @@ int g16_zkey_verify_r1cs_files(const char* r1cs_path, const char* ptau_path, con
  *   t_out      = u[0..N-2] | 0 | -u[0..N-2] mod r  ((2N - 1) x 32 bytes)
  * so that 2N sum rho_out[i] H_i = sum t_out[j] P_j.  Standard form out. */
 int g16_zkey_h_scalars(int device, const uint8_t* u, uint32_t log_n, uint8_t* rho_out, uint8_t* t_out);
+/* The MPCParams file exchange of phase 2: how somebody who does not hold the .zkey contributes (the twin of the
+ * challenge / response exchange of phase 1).  File format, snarkjs 0.4.12's zkey_export_bellman.js as far as it can be
+ * restated without the package; every G1 is 64 bytes (x | y), every G2 128 bytes (x.c1 | x.c0 | y.c1 | y.c0), big-endian
+ * standard form, infinity = byte 0 = 0x40 and the rest zero; counts are u32 big-endian; n = nVars, p = nPublic, N = the
+ * domain:
+ *   alpha1 | beta1 | beta2 | gamma2 | delta1 | delta2
+ *   u32 p+1 | IC (section 3)    u32 N-1 | H    u32 n-p-1 | L (section 8)
+ *   u32 n | A (section 5)       u32 n | B1 (section 6)    u32 n | B2 (section 7, G2)
+ *   csHash (64) | u32 c | c x ( deltaAfter | delta.g1_s | delta.g1_sx | delta.g2_spx (G2) | transcript (64) )
+ * H is the MONOMIAL basis H_k = [tau^k (tau^N - 1) / delta] G, k < N - 1; section 9 of a key is the odd-coset Lagrange
+ * basis S9[i] = [L^{2N}_{2i+1}(tau) / delta] G.  With w the primitive 2N-th root of unity, T[k] = [-2 w^k] sum_i w^(2ik)
+ * S9[i] = H_k for every k < N (T[N-1] is not infinity); the file holds T[0 .. N-2].  The import puts infinity at k = N - 1,
+ * multiplies point k by -(1/2) w^(-k) and applies the inverse transform with its 1 / N.  So import(export(key)) is the
+ * PROJECTION of section 9 onto the quotients of degree <= N - 2, not the identity: sum e_i S9[i] is unchanged for every
+ * such quotient (every proof of a satisfying witness), the bytes of section 9 generally change, and the projection is
+ * idempotent.  g16_zkey_verify_from_init accepts such keys (its section-9 combination lies on the same subspace).
+ * The transform runs on `device` (csrc/zkey_bellman.hip: L N/2 + N scalar products at N = 2^L; no CPU path: G16_E_NOGPU),
+ * as do the conversions between the file form and the big-endian images (csrc/ptau_points.hip).  Domains up to 2^24.
+ * NOT CLAIMED: an exchange with a snarkjs or bellman contributor.  The files are restated from snarkjs's description
+ * without the package at hand, and csHash of this library's _0000 keys is 64 zero bytes.
+ *
+ * `snarkjs zkey export bellman circuit.zkey circuit.mpcparams` (alias `zkeb`): the MPCParams image of a Groth16 key
+ * (g16_free).  The checks of g16_zkey_contribute on the input, then the device.  A record's type and params are not
+ * carried: the format has no room for them. */
+int g16_zkey_export_bellman(const uint8_t* zkey, size_t zkey_len, int device, uint8_t** out, size_t* out_len);
+int g16_zkey_export_bellman_files(const char* zkey_path, const char* mpcparams_path, int device);
+/* `snarkjs zkey bellman contribute bn128 challenge response -e=..` (alias `zkbc`): the response (g16_free) to an MPCParams
+ * file.  secret = d | s as in g16_zkey_contribute (NULL: OS CSPRNG).  Everything but delta1, delta2, H and L is copied;
+ * delta <- d delta; H and L: from big-endian (every point checked: on its curve), times 1 / d, back to big-endian, on
+ * `device`; one record more, formed exactly as g16_zkey_contribute forms it (the transcript over csHash, every earlier
+ * record as the file holds it -- a record IS its hashPubKey feed --, g1_s and g1_sx), so for the same (d, s)
+ * contribution_hash (optional) and the record equal those of g16_zkey_contribute on the key the file was exported from.
+ * Checked before the device is touched: the length the file's own counts ask for, every flag (a clean 0x40 or none) and
+ * every coordinate below q, delta1 and delta2 on their curves and not infinity -- G16_E_FORMAT "mpcparams: Invalid File
+ * format", as is a point of H or L off its curve. */
+int g16_zkey_bellman_contribute(const uint8_t* challenge, size_t challenge_len, const uint8_t secret[64] /* d | s, or NULL */,
+                                int device, uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]);
+int g16_zkey_bellman_contribute_files(const char* challenge_path, const char* response_path, const uint8_t secret[64],
+                                      int device, uint8_t contribution_hash[64]);
+/* `snarkjs zkey import bellman old.zkey response new.zkey --name=..` (alias `zkib`): the new key (g16_free) with the old
+ * key's sections in the old key's order.  From the old key: sections 1, 3-7 and the header up to delta1; from the file:
+ * delta1, delta2, section 8 (from big-endian), section 9 (the inverse transform, see above); section 10 = the old
+ * records as they are, then the file's new ones (there may be several) with type 0 and params from the name each.
+ * G16_E_FORMAT "mpcparams: Invalid File format": a length that is not what the file's counts ask for, a bad flag, a
+ * coordinate >= q, a point off its curve.  Refused as a VERDICT -- G16_OK with *ok = 0, *out = NULL, nothing written,
+ * g16_last_error() = one fixed text per check, each led by "zkey import bellman: ":
+ *   "a count is not the key's", "alpha, beta, gamma, IC, A, B1 or B2 differ from the key's", "the circuit hash differs
+ *   from the key's", "the response holds no new contribution", "the contributions do not begin with the key's", "delta1
+ *   or delta2 is the point at infinity".
+ * Counts, alpha / beta / gamma, csHash, the records and the infinity flags are checked on the host before the device is
+ * touched; IC, A, B1 and B2 are converted and compared on `device` (G16_E_NOGPU).  The import does not judge the
+ * contribution itself: that is g16_zkey_verify_from_init's job, as in snarkjs. */
+int g16_zkey_import_bellman(const uint8_t* zkey, size_t zkey_len, const uint8_t* response, size_t response_len,
+                            const char* name /* or NULL */, int device, uint8_t** out, size_t* out_len, int* ok);
+int g16_zkey_import_bellman_files(const char* zkey_path, const char* response_path, const char* out_path, const char* name,
+                                  int device, int* ok);
+/* TEST-ONLY layer operator of the exchange: the basis change alone.  points = N = 2^log_n affine LE Montgomery G1 points
+ * (zero bytes = infinity; not checked), out as many; log_n in [0, 24].  inverse = 0: out[k] = [-2 w^k] sum_i w^(2ik)
+ * points[i], ALL N values (T[N-1] included); inverse != 0: out[i] = (1 / N) sum_k w^(-2ik) [-(1/2) w^(-k)] points[k]. */
+int g16_zkey_h_basis(int device, const uint8_t* points, uint32_t log_n, int inverse, uint8_t* out);
 /* Layer operators of the two routes above, host only.  Blake2b-512 (RFC 7693, unkeyed); the transcript's point on G2
  * (ChaCha20 keyed with the first 32 bytes, x drawn as the Montgomery image, cofactor 2q - r; affine LE Montgomery). */
 int g16_blake2b512(const uint8_t* data, size_t len, uint8_t out[64]);

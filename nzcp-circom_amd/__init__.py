@@ -79,6 +79,8 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_zkey_verify_from_init_files", "g16_blake2b512", "g16_zkey_hash_to_g2",
            "g16_zkey_verify_from_init_ptau", "g16_zkey_verify_from_init_ptau_files", "g16_zkey_verify_r1cs",
            "g16_zkey_verify_r1cs_files", "g16_zkey_h_scalars",
+           "g16_zkey_export_bellman", "g16_zkey_export_bellman_files", "g16_zkey_bellman_contribute",
+           "g16_zkey_bellman_contribute_files", "g16_zkey_import_bellman", "g16_zkey_import_bellman_files", "g16_zkey_h_basis",
            "g16_ptau_new", "g16_ptau_new_file", "g16_ptau_contribute", "g16_ptau_contribute_files", "g16_ptau_verify",
            "g16_ptau_verify_file", "g16_ptau_secret_from_text",
            "g16_ptau_export_challenge", "g16_ptau_export_challenge_files", "g16_ptau_challenge_contribute",
@@ -177,6 +179,14 @@ def load():
     lib.g16_zkey_verify_r1cs.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, sz, C.c_int, C.POINTER(C.c_int)]
     lib.g16_zkey_verify_r1cs_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     lib.g16_zkey_h_scalars.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_char_p, C.c_char_p]
+    lib.g16_zkey_export_bellman.argtypes = [C.c_char_p, sz, C.c_int, C.POINTER(vp), C.POINTER(sz)]
+    lib.g16_zkey_export_bellman_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
+    lib.g16_zkey_bellman_contribute.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
+    lib.g16_zkey_bellman_contribute_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
+    lib.g16_zkey_import_bellman.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz),
+                                            C.POINTER(C.c_int)]
+    lib.g16_zkey_import_bellman_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    lib.g16_zkey_h_basis.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p]
     lib.g16_ptau_new.argtypes = [C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
     lib.g16_ptau_new_file.argtypes = [C.c_uint32, C.c_char_p]
     lib.g16_ptau_contribute.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
@@ -1199,6 +1209,48 @@ def zkey_verify_r1cs(r1cs, ptau, zkey, device=0):
     lib = load()
     _check(lib.g16_zkey_verify_r1cs(r1cs, len(r1cs), ptau, len(ptau), zkey, len(zkey), device, C.byref(ok)))
     return bool(ok.value), ("" if ok.value else lib.g16_last_error().decode("utf-8", "replace"))
+
+
+def zkey_export_bellman(zkey, device=0):
+    """`snarkjs zkey export bellman`: Groth16 .zkey bytes -> the MPCParams file's bytes (H in the monomial basis)."""
+    z, zl = C.c_void_p(), C.c_size_t()
+    _check(load().g16_zkey_export_bellman(zkey, len(zkey), device, C.byref(z), C.byref(zl)))
+    return _take(z, zl)
+
+
+def zkey_bellman_contribute(challenge, d=None, s=None, device=0):
+    """`snarkjs zkey bellman contribute`: MPCParams bytes -> (response bytes, 64-byte contribution hash).  d, s as in
+    zkey_contribute: the same pair gives the same record and hash through either route."""
+    if (d is None) != (s is None):
+        raise ValueError("zkey_bellman_contribute: give both d and s, or neither")
+    secret = None if d is None else int(d).to_bytes(32, "little") + int(s).to_bytes(32, "little")
+    z, zl = C.c_void_p(), C.c_size_t()
+    h = C.create_string_buffer(64)
+    _check(load().g16_zkey_bellman_contribute(challenge, len(challenge), secret, device, C.byref(z), C.byref(zl), h))
+    return _take(z, zl), h.raw
+
+
+def zkey_import_bellman(old, response, name=None, device=0):
+    """`snarkjs zkey import bellman`: (old .zkey bytes, response bytes) -> the new .zkey bytes.  A response the import
+    refuses is a verdict, not a malformed file: G16Error with code 0 (G16_OK) and the check's text."""
+    z, zl = C.c_void_p(), C.c_size_t()
+    ok = C.c_int(0)
+    nm = None if name is None else name.encode("utf-8")
+    lib = load()
+    _check(lib.g16_zkey_import_bellman(old, len(old), response, len(response), nm, device, C.byref(z), C.byref(zl), C.byref(ok)))
+    if not ok.value:
+        raise G16Error(0, lib.g16_last_error().decode("utf-8", "replace"))
+    return _take(z, zl)
+
+
+def zkey_h_basis(points, log_n, inverse=False, device=0):
+    """TEST-ONLY layer entry of the MPCParams exchange: 2^log_n file-form G1 points (64 bytes each) -> as many, the basis
+    change of section 9 alone (forward: all N values of T, T[N-1] included)."""
+    if len(points) != 64 << log_n:
+        raise ValueError("zkey_h_basis: 2^log_n points of 64 bytes expected")
+    out = C.create_string_buffer(len(points))
+    _check(load().g16_zkey_h_basis(device, points, log_n, 1 if inverse else 0, out))
+    return out.raw
 
 
 def zkey_h_scalars(u, log_n, device=0):

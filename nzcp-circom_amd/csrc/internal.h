@@ -135,6 +135,21 @@ int zkey_verify_h(int device, const uint8_t* u, int log_n, const uint8_t* sec9, 
 // g16_g1_multiexp with the scalars already on the current device (ops.hip)
 int g1_multiexp_device(const uint8_t* bases, const Fr* d_scalars, size_t n, int window_bits, uint8_t out[64]);
 
+// ---------------------------------------------------------------- the H basis of the MPCParams exchange (zkey_bellman.hip)
+// N = 2^log_n affine Montgomery G1 points in file layout (host) in, N out; w = the primitive 2N-th root of unity:
+//   forward: section 9 of a key (odd-coset Lagrange basis) -> out[k] = [-2 w^k] sum_i w^(2ik) in[i], the monomial basis
+//            [tau^k (tau^N - 1) / delta] G, ALL N values (the file drops out[N-1]);
+//   inverse: out[i] = (1 / N) sum_k w^(-2ik) [-(1/2) w^(-k)] in[k].
+// log_n in [0, 24].  No CPU path (G16_E_NOGPU).
+struct ZkeyBasisStats {
+  float kern_ms = 0.f;          // device time of the kernels
+  uint64_t muls = 0, adds = 0;  // scalar multiplications of a point; point additions (two per butterfly)
+};
+int zkey_h_basis(int device, const uint8_t* in, int log_n, bool inverse, uint8_t* out, ZkeyBasisStats* st);
+// rho[i] = (1 / N) sum_k u[k] w^((2i+1) k) alone, copied to the host (N x 32 bytes, standard form): zkey_verify_h's first
+// scalar vector, for step 5 of zkey verify
+int zkey_h_rho(int device, const uint8_t* u, int log_n, uint8_t* rho_out);
+
 // ---------------------------------------------------------------- powersoftau contribute (ptau_scale.hip)
 // out[i] = [c k^(first + i)] in[i]: n affine Montgomery points of G1 / G2 (host, file layout; infinity = zero bytes in
 // and out), c and k standard form in [1, r), first + n <= 2^31; every lane forms its scalar on the device.  out_be
@@ -153,6 +168,8 @@ int ptau_scale_g2(int device, const uint8_t* in, uint64_t n, const Fr& c_std, co
 // off the curve, no root), else -1; the outputs of a section with a bad point are not to be used.  out_be (optional):
 // the uncompressed image of every decompressed point, from the same pass.  No CPU path (G16_E_NOGPU).
 int ptau_points_from_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, ChunkStats* st);
+// the inverse of from_be: file form -> uncompressed big-endian standard form (every file image has one)
+int ptau_points_to_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st);
 int ptau_points_compress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st);
 int ptau_points_decompress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* out_be, int64_t* first_bad,
                            ChunkStats* st);

@@ -516,32 +516,6 @@ int challenge_contribute_core(const uint8_t* ch, size_t len, const uint8_t* secr
   return G16_OK;
 }
 
-// uncompressed big-endian standard form -> the file image; false for a flag other than a clean 0x40, a coordinate >= q
-// or a point off its curve
-bool image_from_be(const uint8_t* be, size_t psz, uint8_t* lem) {
-  if (be[0] & 0xc0) {
-    if (be[0] != 0x40 || !all_zero(be + 1, psz - 1)) return false;
-    memset(lem, 0, psz);
-    return true;
-  }
-  const int nc = (int)(psz / 32);
-  for (int c = 0; c < nc; c++) {
-    Fq s;
-    for (int i = 0; i < 8; i++) {
-      const uint8_t* w = be + 32 * c + 4 * (7 - i);
-      s.v[i] = (uint32_t)w[0] << 24 | (uint32_t)w[1] << 16 | (uint32_t)w[2] << 8 | w[3];
-    }
-    bool below = false;
-    for (int i = 7; i >= 0; i--)
-      if (s.v[i] != kFqP[i]) { below = s.v[i] < kFqP[i]; break; }
-    if (!below) return false;
-    s = fp_to_mont(s);
-    memcpy(lem + 32 * (nc == 2 ? c : c ^ 1), s.v, 32);
-  }
-  if (all_zero(lem, psz)) return false;   // (infinity is the flagged image alone)
-  return nc == 2 ? mpc_g1_image_ok(lem) : mpc_g2_image_ok(lem);
-}
-
 int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, size_t rlen, const char* name, int device,
                          uint8_t** out, size_t* out_len, uint8_t contribution_hash[64], int* ok) {
   const auto t0 = std::chrono::steady_clock::now();
@@ -570,8 +544,8 @@ int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, s
     const uint8_t* kp = resp + rlen - kKeysBytes;
     bool good = true;
     for (int x = 0; x < 3 && good; x++)
-      good = image_from_be(kp + 128 * x, 64, rec + kPtauKeysAt + 128 * x) && image_from_be(kp + 128 * x + 64, 64, rec + kPtauKeysAt + 128 * x + 64) &&
-             image_from_be(kp + 384 + 128 * x, 128, rec + 832 + 128 * x);
+      good = mpc_image_from_be(kp + 128 * x, 64, rec + kPtauKeysAt + 128 * x) && mpc_image_from_be(kp + 128 * x + 64, 64, rec + kPtauKeysAt + 128 * x + 64) &&
+             mpc_image_from_be(kp + 384 + 128 * x, 128, rec + 832 + 128 * x);
     if (!good) { set_error("ptau import response: a key point is not a valid image"); return G16_E_FORMAT; }
   }
   if (const int rc = require_hip_device("ptau import response", device)) return rc;

@@ -4,6 +4,9 @@
 //                           infinity = zero bytes): the inverse of ptau_be_kernel (ptau_scale.hip), with the checks a
 //                           stranger's file needs -- every coordinate below q, no flag but a clean 0x40, the point on
 //                           its curve;
+//   ptau_to_be_kernel       the file form -> uncompressed big-endian standard form, the inverse of the above (the
+//                           MPCParams files of the phase-2 exchange, zkey_bellman.cpp; grid-stride, unlike
+//                           ptau_scale.hip's ptau_be_kernel, which runs inside that route's own launch);
 //   ptau_compress_kernel    the file form -> x alone, big-endian (G1: 32 bytes; G2: x.c1 | x.c0, 64 bytes), bit 0x80 of
 //                           byte 0 set when y is "negative" (Fq: y > (q - 1) / 2; Fq2: that of c1, or of c0 when c1 = 0),
 //                           infinity = zeros with bit 0x40 of byte 0;
@@ -189,6 +192,23 @@ __global__ __launch_bounds__(kBlock) void ptau_from_be_kernel(const uint32_t* __
 }
 
 template <class FC>
+__global__ __launch_bounds__(kBlock) void ptau_to_be_kernel(const Affine<FC>* __restrict__ in, uint32_t* __restrict__ out, uint32_t n) {
+  constexpr int NC = sizeof(Affine<FC>) / 32;
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const Affine<FC> P = in[i];
+    const Fq* co = reinterpret_cast<const Fq*>(&P);
+    uint32_t* o = out + (size_t)i * NC * 8;
+    if (aff_is_inf(P)) {
+      store_inf(o, NC * 8);
+      continue;
+    }
+#pragma unroll
+    for (int c = 0; c < NC; c++) store_be(o + c * 8, fp_from_mont(co[be_slot<NC>(c)]));
+  }
+}
+
+template <class FC>
 __global__ __launch_bounds__(kBlock) void ptau_compress_kernel(const Affine<FC>* __restrict__ in, uint32_t* __restrict__ out,
                                                                uint32_t n) {
   constexpr int NX = sizeof(Affine<FC>) / 64;   // coordinates of x
@@ -341,6 +361,12 @@ int from_be(int device, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* fi
                          ptau_from_be_kernel<FC><<<grid, block, 0, s>>>((const uint32_t*)i, (Affine<FC>*)o, cnt, base, bad);
                        });
 }
+template <class FC> int to_be(int device, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st) {
+  constexpr size_t PSZ = sizeof(Affine<FC>);
+  return points_device("ptau points to-be", device, in, PSZ, n, out, PSZ, nullptr, 0, nullptr, st,
+                       [](uint32_t grid, uint32_t block, hipStream_t s, const uint8_t* i, uint8_t* o, uint8_t*, uint32_t cnt, uint32_t,
+                          uint32_t*) { ptau_to_be_kernel<FC><<<grid, block, 0, s>>>((const Affine<FC>*)i, (uint32_t*)o, cnt); });
+}
 template <class FC> int compress(int device, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st) {
   constexpr size_t PSZ = sizeof(Affine<FC>);
   return points_device("ptau points compress", device, in, PSZ, n, out, PSZ / 2, nullptr, 0, nullptr, st,
@@ -369,6 +395,9 @@ template <class FC> int sqrt_batch(int device, const uint8_t* in, uint64_t n, ui
 
 int ptau_points_from_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, ChunkStats* st) {
   return g2 ? from_be<Fq2Ops>(device, in, n, out, first_bad, st) : from_be<FqOps>(device, in, n, out, first_bad, st);
+}
+int ptau_points_to_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st) {
+  return g2 ? to_be<Fq2Ops>(device, in, n, out, st) : to_be<FqOps>(device, in, n, out, st);
 }
 int ptau_points_compress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st) {
   return g2 ? compress<Fq2Ops>(device, in, n, out, st) : compress<FqOps>(device, in, n, out, st);

@@ -263,6 +263,32 @@ void g2_uncompressed(const uint8_t lem[128], uint8_t out[128]) {   // x.c1 | x.c
   be32(fp_from_mont(fq_load(lem + 64)), out + 96);
 }
 
+// uncompressed big-endian standard form -> the file image; false for a flag other than a clean 0x40, a coordinate >= q
+// or a point off its curve
+bool mpc_image_from_be(const uint8_t* be, size_t psz, uint8_t* lem) {
+  if (be[0] & 0xc0) {
+    if (be[0] != 0x40 || !all_zero(be + 1, psz - 1)) return false;
+    memset(lem, 0, psz);
+    return true;
+  }
+  const int nc = (int)(psz / 32);
+  for (int c = 0; c < nc; c++) {
+    Fq s;
+    for (int i = 0; i < 8; i++) {
+      const uint8_t* w = be + 32 * c + 4 * (7 - i);
+      s.v[i] = (uint32_t)w[0] << 24 | (uint32_t)w[1] << 16 | (uint32_t)w[2] << 8 | w[3];
+    }
+    bool below = false;
+    for (int i = 7; i >= 0; i--)
+      if (s.v[i] != kFqP[i]) { below = s.v[i] < kFqP[i]; break; }
+    if (!below) return false;
+    s = fp_to_mont(s);
+    memcpy(lem + 32 * (nc == 2 ? c : c ^ 1), s.v, 32);
+  }
+  if (all_zero(lem, psz)) return false;   // (infinity is the flagged image alone)
+  return nc == 2 ? g1_image_ok(lem) : g2_image_ok(lem);
+}
+
 void mpc_hash_pubkey(std::vector<uint8_t>& feed, const MpcRecord& r) {
   const size_t at = feed.size();
   feed.resize(at + 64 + 64 + 64 + 128 + 64);
@@ -331,19 +357,7 @@ int mpc_parse(const BinSection& s10, MpcSection& out) {
   return G16_OK;
 }
 
-// ------------------------------------------------------------------ the key as both routes read it
-namespace {
-
-constexpr size_t kHdrDelta1 = 468, kHdrDelta2 = 532, kHdrEnd = 660;
-
-struct KeyView {
-  BinView f;
-  uint32_t nVars = 0, nPublic = 0, N = 0;
-  MpcSection mpc;
-};
-
-// exact_89: sections 8 and 9 must have the header's sizes (the verifier only needs whole points: a short section is a
-// verdict there, not a malformed file)
+// ------------------------------------------------------------------ the key as the ceremony routes read it
 int open_key(const uint8_t* zkey, size_t len, KeyView& k, bool exact_89) {
   auto bad = []() { set_error("zkey: Invalid File format"); return G16_E_FORMAT; };
   if (const int rc = bin_open(zkey, len, "zkey", 2, k.f)) return rc;
@@ -377,6 +391,49 @@ int open_key(const uint8_t* zkey, size_t len, KeyView& k, bool exact_89) {
   return mpc_parse(k.f.sec[10], k.mpc);
 }
 
+namespace {
+bool scalar_ok(const uint8_t* s, Fr& out) {   // standard form, in [1, r)
+  memcpy(out.v, s, 32);
+  return !fp_is_zero(out) && fr_below_modulus(out.v);
+}
+}  // namespace
+
+int mpc_read_secret(const char* route, const uint8_t* secret, Fr& d, Fr& s) {
+  if (secret) {
+    if (!scalar_ok(secret, d) || !scalar_ok(secret + 32, s)) {
+      set_error(std::string(route) + ": the secret scalars must be in [1, r)");
+      return G16_E_ARG;
+    }
+    return G16_OK;
+  }
+  for (Fr* x : {&d, &s})
+    for (;;) {
+      if (const int rc = os_random((uint8_t*)x->v, 32)) return rc;
+      x->v[7] &= 0x3fffffffu;
+      if (!fp_is_zero(*x) && fr_below_modulus(x->v)) break;
+    }
+  return G16_OK;
+}
+
+void mpc_contribution(std::vector<uint8_t>& feed, const Fr& d, const Fr& s, uint8_t g1_s[64], uint8_t g1_sx[64],
+                      uint8_t g2_spx[128], uint8_t transcript[64]) {
+  G1Affine g1;   // (1, 2)
+  g1.x = fp_one<FqParams>();
+  g1.y = fp_add(g1.x, g1.x);
+  mul_image<FqOps>((const uint8_t*)&g1, s, g1_s);
+  mul_image<FqOps>(g1_s, d, g1_sx);
+  const size_t at = feed.size();
+  feed.resize(at + 128);
+  g1_uncompressed(g1_s, feed.data() + at);
+  g1_uncompressed(g1_sx, feed.data() + at + 64);
+  blake2b512(feed.data(), feed.size(), transcript);
+  G2Affine sp2;
+  hash_to_g2(transcript, sp2);
+  mul_image<Fq2Ops>((const uint8_t*)&sp2, d, g2_spx);
+}
+
+namespace {
+
 // csHash | hashPubKey of records [0, upto) | g1_s | g1_sx (uncompressed)  ->  the transcript of record `upto`
 void transcript_of(const MpcSection& m, size_t upto, const uint8_t* g1_s, const uint8_t* g1_sx, uint8_t out[64]) {
   std::vector<uint8_t> feed(m.cs_hash, m.cs_hash + 64);
@@ -386,11 +443,6 @@ void transcript_of(const MpcSection& m, size_t upto, const uint8_t* g1_s, const 
   g1_uncompressed(g1_s, feed.data() + at);
   g1_uncompressed(g1_sx, feed.data() + at + 64);
   blake2b512(feed.data(), feed.size(), out);
-}
-
-bool scalar_ok(const uint8_t* s, Fr& out) {   // standard form, in [1, r)
-  memcpy(out.v, s, 32);
-  return !fp_is_zero(out) && fr_below_modulus(out.v);
 }
 
 double ms_since(const std::chrono::steady_clock::time_point& t0) {
@@ -403,16 +455,7 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
   KeyView k;
   if (const int rc = open_key(zkey, zkey_len, k, true)) return rc;
   Fr d, s;
-  if (secret) {
-    if (!scalar_ok(secret, d) || !scalar_ok(secret + 32, s)) { set_error("zkey contribute: the secret scalars must be in [1, r)"); return G16_E_ARG; }
-  } else {
-    for (Fr* x : {&d, &s})
-      for (;;) {
-        if (const int rc = os_random((uint8_t*)x->v, 32)) return rc;
-        x->v[7] &= 0x3fffffffu;
-        if (!fp_is_zero(*x) && fr_below_modulus(x->v)) break;
-      }
-  }
+  if (const int rc = mpc_read_secret("zkey contribute", secret, d, s)) return rc;
   if (const int rc = require_hip_device("zkey contribute", device)) return rc;
 
   const std::string params = mpc_name_params(name);
@@ -451,18 +494,9 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
   uint8_t* rec = sp[10] + k.f.sec[10].size;
   const uint8_t* hdr = k.f.sec[2].p;
   {
-    G1Affine g1;   // (1, 2)
-    g1.x = fp_one<FqParams>();
-    g1.y = fp_add(g1.x, g1.x);
-    uint8_t* g1_s = rec + 64;
-    uint8_t* g1_sx = rec + 128;
-    mul_image<FqOps>((const uint8_t*)&g1, s, g1_s);
-    mul_image<FqOps>(g1_s, d, g1_sx);
-    uint8_t* tr = rec + 320;
-    transcript_of(k.mpc, k.mpc.rec.size(), g1_s, g1_sx, tr);
-    G2Affine sp2;
-    hash_to_g2(tr, sp2);
-    mul_image<Fq2Ops>((const uint8_t*)&sp2, d, rec + 192);
+    std::vector<uint8_t> earlier(k.mpc.cs_hash, k.mpc.cs_hash + 64);
+    for (const MpcRecord& r : k.mpc.rec) mpc_hash_pubkey(earlier, r);
+    mpc_contribution(earlier, d, s, rec + 64, rec + 128, rec + 192, rec + 320);
     mul_image<FqOps>(hdr + kHdrDelta1, d, sp[2] + kHdrDelta1);
     mul_image<Fq2Ops>(hdr + kHdrDelta2, d, sp[2] + kHdrDelta2);
     memcpy(rec, sp[2] + kHdrDelta1, 64);   // deltaAfter
@@ -568,7 +602,12 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
   if (!same_ratio(ha + kHdrDelta1, hb + kHdrDelta1, ha + kHdrDelta2, hb + kHdrDelta2, "zkey verify: delta2 does not match delta1"))
     return verdict(inf_text);
 
-  // 5. sections 8 and 9: S = sum rho_i new_i, T = sum rho_i init_i, e(S, delta2) = e(T, delta2 of init)
+  // 5. sections 8 and 9: S = sum rho_i new_i, T = sum rho_i init_i, e(S, delta2) = e(T, delta2 of init).  Section 8
+  // takes fully random rho.  Section 9 takes rho9[i] = (1/N) sum_k u[k] w^((2i+1) k) with u random and u[N-1] = 0, formed
+  // on the device as the ptau leg forms it (zkey_verify_h.hip): the combinations sum e_i S9[i] of quotients of degree <=
+  // N - 2, which are all a prover ever forms and all the MPCParams exchange carries (`zkey import bellman` writes the
+  // projection of section 9 onto them: zkey_bellman.hip).  The infinity patterns are compared for section 8 alone -- the
+  // projection moves section 9's.
   const uint64_t n8 = a.f.sec[8].size / 64, n9 = a.f.sec[9].size / 64, n = n8 + n9;
   double msm_ms = 0;
   uint8_t S[64], T[64];   // standard form
@@ -580,12 +619,17 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
     memcpy(bases_new.data() + n8 * 64, b.f.sec[9].p, n9 * 64);
     for (uint64_t i = 0; i < n; i++) {
       if (!g1_image_ok(bases_new.data() + i * 64)) { set_error("zkey: Invalid File format"); return G16_E_FORMAT; }
-      if (all_zero(bases_new.data() + i * 64, 64) != all_zero(bases_init.data() + i * 64, 64))
+      if (i < n8 && all_zero(bases_new.data() + i * 64, 64) != all_zero(bases_init.data() + i * 64, 64))
         return verdict("zkey verify: sections 8 and 9 are not the initial key's scaled by 1 / delta");
     }
     ChaCha rng;   // fresh scalars: a ChaCha20 stream keyed from the OS CSPRNG
     if (const int rc = os_random((uint8_t*)rng.key, 32)) return rc;
-    for (uint64_t i = 0; i < n; i++) rng.next_below(kFrP, (uint32_t*)(rho.data() + i * 32));
+    for (uint64_t i = 0; i < n8; i++) rng.next_below(kFrP, (uint32_t*)(rho.data() + i * 32));
+    if (L >= 1) {   // (a domain of one point has no quotient: rho9 = 0)
+      std::vector<uint8_t> u(n9 * 32, 0);   // u[N-1] = 0
+      for (uint64_t k = 0; k + 1 < n9; k++) rng.next_below(kFrP, (uint32_t*)(u.data() + k * 32));
+      if (const int rc = zkey_h_rho(device, u.data(), L, rho.data() + n8 * 32)) return rc;
+    }
     const auto t1 = std::chrono::steady_clock::now();
     if (const int rc = g16_g1_multiexp(device, bases_new.data(), rho.data(), n, 0, S)) return rc;
     if (const int rc = g16_g1_multiexp(device, bases_init.data(), rho.data(), n, 0, T)) return rc;
@@ -604,7 +648,7 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
       memcpy(pairs.data() + at + 192 + 64 + 32 * i, w.v, 32);
     }
     reason.push_back("zkey verify: sections 8 and 9 are not the initial key's scaled by 1 / delta");
-  } else if (n) {
+  } else if (n8 || L >= 1) {   // (some scalar was drawn)
     return verdict("zkey verify: the combination of sections 8 and 9 is the point at infinity");
   }
   // 6. the ptau leg: S = sum rho_i new9_i, T = sum t_j tauG1_j with both scalar vectors formed on the device from one

@@ -41,8 +41,30 @@ int mpc_parse(const BinSection& s10, MpcSection& out);
 void mpc_hash_pubkey(std::vector<uint8_t>& feed, const MpcRecord& r);
 void g1_uncompressed(const uint8_t lem[64], uint8_t out[64]);
 void g2_uncompressed(const uint8_t lem[128], uint8_t out[128]);
+// the inverse (psz = 64 / 128): false for a flag other than a clean 0x40, a coordinate >= q or a point off its curve
+bool mpc_image_from_be(const uint8_t* be, size_t psz, uint8_t* lem);
 
 void hash_to_g2(const uint8_t transcript[64], G2Affine& out);
+
+// A Groth16 key as the ceremony routes read it (zkey_mpc.cpp, zkey_bellman_host.cpp).  Section 2: alpha1 at 84, beta1 at 148,
+// beta2 at 212, gamma2 at 340, delta1 at 468, delta2 at 532.
+constexpr size_t kHdrAlpha1 = 84, kHdrDelta1 = 468, kHdrDelta2 = 532, kHdrEnd = 660;
+struct KeyView {
+  BinView f;
+  uint32_t nVars = 0, nPublic = 0, N = 0;
+  MpcSection mpc;
+};
+// exact_89: sections 8 and 9 must have the header's sizes (the verifier only needs whole points: a short section is a
+// verdict there, not a malformed file)
+int open_key(const uint8_t* zkey, size_t len, KeyView& k, bool exact_89);
+// a contribution's secret: d | s, standard form in [1, r) (else G16_E_ARG "<route>: the secret scalars must be in
+// [1, r)"), or NULL for the OS CSPRNG
+int mpc_read_secret(const char* route, const uint8_t* secret, Fr& d, Fr& s);
+// A contribution's own points (file images): g1_s = [s] G, g1_sx = [d] g1_s, transcript = Blake2b-512(feed | g1_s |
+// g1_sx uncompressed) with feed = csHash | hashPubKey of every earlier record (extended here), g2_spx = [d] of the
+// transcript's point on G2.
+void mpc_contribution(std::vector<uint8_t>& feed, const Fr& d, const Fr& s, uint8_t g1_s[64], uint8_t g1_sx[64],
+                      uint8_t g2_spx[128], uint8_t transcript[64]);
 
 // Shared with the .ptau ceremony (ptau_mpc.cpp).  File images are affine little-endian Montgomery, infinity = zeros.
 bool mpc_g1_image_ok(const uint8_t* p);   // coordinates below q and the point on its curve (infinity passes)

@@ -77,6 +77,13 @@ int zkey_verify_h(int device, const uint8_t* u, int log_n, const uint8_t* sec9, 
   return G16_OK;
 }
 
+int zkey_h_rho(int device, const uint8_t* u, int log_n, uint8_t* rho_out) {
+  HJob job;
+  if (const int rc = job.form(device, u, log_n, nullptr)) return rc;
+  G16_HIP(hipMemcpy(rho_out, job.d_rho.p, ((size_t)1 << log_n) * sizeof(Fr), hipMemcpyDeviceToHost));
+  return G16_OK;
+}
+
 }  // namespace g16
 
 using namespace g16;

@@ -811,10 +811,18 @@ typedef struct {
   char a[1024], b[1024], c[1024], name[512];
   uint8_t secret[64], hash[64];
   int has_name, has_secret, verify, device, rc, ok;   /* verify: 1 = a init, b zkey; 2 = a init, c ptau, b zkey; 3 = a r1cs, c ptau, b zkey */
+  int bellman;   /* 1 = export: a zkey, b mpcparams; 2 = contribute: a challenge, b response; 3 = import: a old, c response, b new */
   char err[512];
 } zjob_t;
 static void zjob_execute(napi_env env, void* data) {
   zjob_t* j = (zjob_t*)data;
+  if (j->bellman) {
+    j->rc = j->bellman == 1   ? g16_zkey_export_bellman_files(j->a, j->b, j->device)
+            : j->bellman == 2 ? g16_zkey_bellman_contribute_files(j->a, j->b, j->has_secret ? j->secret : NULL, j->device, j->hash)
+                              : g16_zkey_import_bellman_files(j->a, j->c, j->b, j->has_name ? j->name : NULL, j->device, &j->ok);
+    if (j->rc || (j->bellman == 3 && !j->ok)) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
+    return;
+  }
   j->rc = j->verify == 3 ? g16_zkey_verify_r1cs_files(j->a, j->c, j->b, j->device, &j->ok)
           : j->verify == 2 ? g16_zkey_verify_from_init_ptau_files(j->a, j->c, j->b, j->device, &j->ok)
           : j->verify ? g16_zkey_verify_from_init_files(j->a, j->b, j->device, &j->ok)
@@ -824,11 +832,16 @@ static void zjob_execute(napi_env env, void* data) {
 }
 static void zjob_complete(napi_env env, napi_status status, void* data) {
   zjob_t* j = (zjob_t*)data;
-  if (status != napi_ok || j->rc) {
+  const int refused = j->bellman == 3 && !j->ok;   /* a verdict of the import: its text, nothing written */
+  if (status != napi_ok || j->rc || refused) {
     napi_value msg, err;
-    napi_create_string_utf8(env, j->rc ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
+    napi_create_string_utf8(env, j->rc || refused ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
     napi_create_error(env, NULL, msg, &err);
     napi_reject_deferred(env, j->deferred, err);
+  } else if (j->bellman == 1 || j->bellman == 3) {
+    napi_value undef;
+    napi_get_undefined(env, &undef);
+    napi_resolve_deferred(env, j->deferred, undef);
   } else if (j->verify) {
     napi_value obj, ok, reason;
     napi_create_object(env, &obj);
@@ -883,6 +896,59 @@ static napi_value js_zkey_contribute_files(napi_env env, napi_callback_info info
   int32_t v = 0;
   if (argc > 4 && napi_get_value_int32(env, argv[4], &v) == napi_ok) j->device = v;
   return zjob_start(env, j, "g16_zkey_contribute_files");
+}
+/* zkeyExportBellmanFiles(zkeyPath, mpcparamsPath, device) -> undefined
+ * zkeyBellmanContributeFiles(challengePath, responsePath, secret, device) -> the 64-byte contribution hash
+ * zkeyImportBellmanFiles(oldPath, responsePath, newPath, name, device) -> undefined; a refused response rejects with the verdict's text */
+static napi_value zkey_bellman(napi_env env, napi_callback_info info, int mode, const char* usage, const char* resource) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  zjob_t* j = (zjob_t*)calloc(1, sizeof(zjob_t));
+  size_t n = 0;
+  const size_t npath = mode == 3 ? 3 : 2;
+  char* dst[3] = {j->a, mode == 3 ? j->c : j->b, j->b};
+  bool bad = argc < npath;
+  for (size_t k = 0; !bad && k < npath; k++) bad = napi_get_value_string_utf8(env, argv[k], dst[k], sizeof(j->a), &n) != napi_ok;
+  if (bad) {
+    free(j);
+    napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  j->bellman = mode;
+  size_t next = npath;
+  if (mode == 3 && argc > next && napi_get_value_string_utf8(env, argv[next], j->name, sizeof(j->name), &n) == napi_ok) j->has_name = 1;
+  if (mode == 3) next++;
+  bool is_buf = false;
+  if (mode == 2) {
+    if (argc > next && napi_is_buffer(env, argv[next], &is_buf) == napi_ok && is_buf) {
+      void* p = NULL;
+      size_t len = 0;
+      if (napi_get_buffer_info(env, argv[next], &p, &len) != napi_ok || len != 64) {
+        free(j);
+        napi_throw_type_error(env, NULL, "zkeyBellmanContributeFiles: the secret is a Buffer of 64 bytes (d | s) or null");
+        return NULL;
+      }
+      memcpy(j->secret, p, 64);
+      j->has_secret = 1;
+    }
+    next++;
+  }
+  int32_t v = 0;
+  if (argc > next && napi_get_value_int32(env, argv[next], &v) == napi_ok) j->device = v;
+  return zjob_start(env, j, resource);
+}
+static napi_value js_zkey_export_bellman_files(napi_env env, napi_callback_info info) {
+  return zkey_bellman(env, info, 1, "zkeyExportBellmanFiles(zkeyPath, mpcparamsPath, device): two path strings expected",
+                      "g16_zkey_export_bellman_files");
+}
+static napi_value js_zkey_bellman_contribute_files(napi_env env, napi_callback_info info) {
+  return zkey_bellman(env, info, 2, "zkeyBellmanContributeFiles(challengePath, responsePath, secret, device): two path strings expected",
+                      "g16_zkey_bellman_contribute_files");
+}
+static napi_value js_zkey_import_bellman_files(napi_env env, napi_callback_info info) {
+  return zkey_bellman(env, info, 3, "zkeyImportBellmanFiles(oldPath, responsePath, newPath, name, device): three path strings expected",
+                      "g16_zkey_import_bellman_files");
 }
 static napi_value js_zkey_verify_from_init_files(napi_env env, napi_callback_info info) {
   size_t argc = 3;
@@ -1420,6 +1486,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"groth16SetupFiles", NULL, js_groth16_setup_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauPrepareFiles", NULL, js_ptau_prepare_files, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyContributeFiles", NULL, js_zkey_contribute_files, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyExportBellmanFiles", NULL, js_zkey_export_bellman_files, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyBellmanContributeFiles", NULL, js_zkey_bellman_contribute_files, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyImportBellmanFiles", NULL, js_zkey_import_bellman_files, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerifyFromInitFiles", NULL, js_zkey_verify_from_init_files, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerifyFromInitPtauFiles", NULL, js_zkey_verify_from_init_ptau_files, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerifyR1csFiles", NULL, js_zkey_verify_r1cs_files, NULL, NULL, NULL, napi_default, NULL},

@@ -16,6 +16,12 @@
 // these files, nor this one snarkjs's.
 // And of `snarkjs zkey contribute <old.zkey> <new.zkey> [--name=..] [-e=..]` (alias `zkc`): prints the contribution hash
 // as snarkjs does.  -e: THIS CLI's derivation of the secret from the text (index.js secretFromEntropy), not snarkjs's.
+// And of the phase-2 file exchange: `snarkjs zkey export bellman <circuit.zkey> <circuit.mpcparams>` (alias `zkeb`),
+// `snarkjs zkey bellman contribute bn128 <challenge> <response> [-e=..]` (alias `zkbc`: prints the contribution hash; -e
+// by the rule of `zkey contribute`, so the same text gives the same contribution through either route) and `snarkjs zkey
+// import bellman <old.zkey> <response> <new.zkey> [--name=..]` (alias `zkib`: a refused response prints "[ERROR] snarkJS:
+// <the verdict>" and exits 1, nothing is written).  An exchange with a snarkjs or bellman contributor is not claimed
+// (INTEGRATION.md 5b).
 // And of `snarkjs zkey verify frominit <init.zkey> <pot.ptau> <circuit.zkey>` (alias `zkvi`) and `snarkjs zkey verify
 // <circuit.r1cs> <pot.ptau> <circuit.zkey>` (alias `zkv`: the setup runs in memory, no file is written): prints
 // "[INFO]  snarkJS: ZKey Ok!" and exits 0, or "[ERROR] snarkJS: <reason>" and exits 1.  Both open the ptau and run the
@@ -100,6 +106,33 @@ async function main(argv) {
     if (pos.length < 2) { console.error("usage: cli.js nzcp program <example|live> <file>"); process.exit(2); }
     const { nzcp } = require("./index.js");
     await nzcp.witnessProgram(pos[0], pos[1]);
+    return;
+  }
+  if ((a[0] === "zkey" && a[1] === "export" && a[2] === "bellman") || a[0] === "zkeb") {
+    const pos = a.slice(a[0] === "zkeb" ? 1 : 3).filter((x) => !x.startsWith("-"));
+    if (pos.length < 2) { console.error("usage: cli.js zkey export bellman <circuit.zkey> <circuit.mpcparams>"); process.exit(2); }
+    const { zKey } = require("./index.js");
+    await zKey.exportBellman(pos[0], pos[1]);
+    return;
+  }
+  if ((a[0] === "zkey" && a[1] === "bellman" && a[2] === "contribute") || a[0] === "zkbc") {
+    const rest = a.slice(a[0] === "zkbc" ? 1 : 3);
+    const entropy = rest.map((x) => (x.startsWith("--entropy=") ? x.slice(10) : x.startsWith("-e=") ? x.slice(3) : undefined)).find((x) => x !== undefined);
+    const pos = rest.filter((x) => !x.startsWith("-"));
+    if (pos.length < 3) { console.error("usage: cli.js zkey bellman contribute bn128 <circuit.mpcparams> <circuit_response.mpcparams> [-e=..]"); process.exit(2); }
+    if (!["bn128", "bn254", "altbn128"].includes(pos[0].toLowerCase())) throw new Error(`Curve not supported: ${pos[0]}`);
+    const { zKey, formatHash } = require("./index.js");
+    const hash = await zKey.bellmanContribute(pos[1], pos[2], entropy);
+    console.log(`[INFO]  snarkJS: Contribution Hash: \n${formatHash(hash)}`);
+    return;
+  }
+  if ((a[0] === "zkey" && a[1] === "import" && a[2] === "bellman") || a[0] === "zkib") {
+    const rest = a.slice(a[0] === "zkib" ? 1 : 3);
+    const name = rest.map((x) => (x.startsWith("--name=") ? x.slice(7) : x.startsWith("-n=") ? x.slice(3) : undefined)).find((x) => x !== undefined);
+    const pos = rest.filter((x) => !x.startsWith("-"));
+    if (pos.length < 3) { console.error("usage: cli.js zkey import bellman <circuit_old.zkey> <circuit.mpcparams> <circuit_new.zkey> [--name=..]"); process.exit(2); }
+    const { zKey } = require("./index.js");
+    await zKey.importBellman(pos[0], pos[1], pos[2], name);
     return;
   }
   if ((a[0] === "zkey" && a[1] === "contribute") || a[0] === "zkc") {

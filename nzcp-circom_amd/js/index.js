@@ -377,6 +377,29 @@ async function contribute(oldZkeyName, newZkeyName, name, entropy, opts = {}) {
   const secret = entropy === undefined || entropy === null || entropy === "" ? null : secretFromEntropy(entropy);
   return native().zkeyContributeFiles(String(oldZkeyName), String(newZkeyName), name ? String(name) : null, secret, opts.device | 0);
 }
+// The MPCParams file exchange (g16_prover.h: g16_zkey_export_bellman and the two entries after it).
+// snarkjs: zKey.exportBellman(zkeyName, mpcparamsName[, logger]).
+async function exportBellman(zkeyName, mpcparamsName, opts = {}) {
+  if (typeof opts !== "object" || opts === null || typeof opts.debug === "function") opts = {};
+  return native().zkeyExportBellmanFiles(String(zkeyName), String(mpcparamsName), opts.device | 0);
+}
+// snarkjs: zKey.bellmanContribute(curve, challengeName, responseName, entropy[, logger]) -> the 64-byte contribution
+// hash.  The curve is bn128 and may be left out.  entropy: the rule of contribute() above, so the same text gives the
+// same contribution through either route.
+async function bellmanContribute(...args) {
+  if (args.length >= 3 && typeof args[0] === "string" && typeof args[2] === "string" && ["bn128", "bn254", "altbn128"].includes(args[0].toLowerCase())) args = args.slice(1);
+  const [challengeName, responseName, entropy] = args;
+  let opts = args[3] || {};
+  if (typeof opts !== "object" || typeof opts.debug === "function") opts = {};
+  const secret = entropy === undefined || entropy === null || entropy === "" ? null : secretFromEntropy(entropy);
+  return native().zkeyBellmanContributeFiles(String(challengeName), String(responseName), secret, opts.device | 0);
+}
+// snarkjs: zKey.importBellman(zkeyNameOld, mpcparamsName, zkeyNameNew, name[, logger]).  A response the import refuses
+// rejects with the verdict's text and writes nothing.
+async function importBellman(oldZkeyName, responseName, newZkeyName, name, opts = {}) {
+  if (typeof opts !== "object" || opts === null || typeof opts.debug === "function") opts = {};
+  return native().zkeyImportBellmanFiles(String(oldZkeyName), String(responseName), String(newZkeyName), name ? String(name) : null, opts.device | 0);
+}
 // snarkjs: zKey.verifyFromInit(initFileName, pTauFileName, zkeyFileName[, logger]) -> boolean.  The ptau (prepared or
 // not) is opened and the ptau leg runs: section 9 of the key is the H basis of that file's section 2 scaled by 1 / delta.
 // opts.ptau === false: without the leg, the ptau argument is then not opened.  opts.reason = true returns {ok, reason}
@@ -589,4 +612,4 @@ plonk.fullProveBatch = async function fullProveBatch(inputs, programName, zkey, 
   return fullProveBatchNative(true, inputs, programName, zkey, opts, b ? Buffer.concat(inputs.map(() => b)) : null);
 };
 
-module.exports = { groth16, plonk, powersOfTau, wtns, nzcp, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, verifyFromInit, verifyFromR1cs }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
+module.exports = { groth16, plonk, powersOfTau, wtns, nzcp, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, exportBellman, bellmanContribute, importBellman, verifyFromInit, verifyFromR1cs }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
