@@ -430,8 +430,8 @@ int g16_ptau_new_file(uint32_t power, const char* path);
  * nextChallenge = challengeHash(new state, responseHash).
  * DEPARTURES from snarkjs: it hashes a response file of COMPRESSED points and stores a hasher snapshot in partialHash;
  * here the new points enter through nextChallenge only and partialHash is 216 zero bytes that nothing reads.  The layout
- * and the powers are snarkjs's; its `powersoftau verify` is NOT claimed to accept this transcript.  NOT implemented:
- * `powersoftau beacon`.  The challenge / response file exchange is g16_ptau_export_challenge and its neighbours below.
+ * and the powers are snarkjs's; its `powersoftau verify` is NOT claimed to accept this transcript.  `powersoftau beacon`
+ * is g16_ptau_beacon, the challenge / response file exchange g16_ptau_export_challenge and its neighbours, all below.
  * The G2 derivation is NOT cross-checked against snarkjs.
  * Checked before the device is touched: the container, curve and power texts of g16_ptau_prepare ("ptau: Invalid File
  * format...", a power above 24: G16_E_ARG naming the limit); sections 2-6 present with exactly the sizes the power
@@ -443,6 +443,32 @@ int g16_ptau_contribute(const uint8_t* ptau, size_t ptau_len, const char* name /
 /* the same from / to files: the input is mapped read-only and the output written in chunks */
 int g16_ptau_contribute_files(const char* in_path, const char* out_path, const char* name, const uint8_t secret[192],
                               int device, uint8_t contribution_hash[64]);
+/* The secret scalars of a BEACON contribution: what closes a ceremony, a last contribution whose secret anyone can
+ * recompute from a public random value and a delay function, so that the last contributor's secret is no longer what
+ * the ceremony rests on.  beacon = the beacon hash, 1 to 255 bytes; num_iterations_exp = e, 10 <= e <= 63 (snarkjs's
+ * range).  seed = SHA-256 applied 2^e times (the first application hashes the raw beacon bytes, every later one 32
+ * bytes).  The scalars are draws of the ChaCha20 word stream of g16_zkey_hash_to_g2, keyed with the seed as eight
+ * big-endian 32-bit words from counter 0: four 64-bit words each (low word first), masked to 254 bits, redrawn until
+ * below r, a zero draw mapped to 1.  count = 6: tau, alpha, beta, s_tau, s_alpha, s_beta in the order of secret[192];
+ * count = 2: d, s -- the first two of the same stream.  out <- count standard-form little-endian scalars of 32 bytes.
+ * Like the `-e` rule (g16_ptau_secret_from_text) this derivation is THIS LIBRARY'S, not snarkjs's: ffjavascript's
+ * fromRng is not available to restate, so a beacon record made by snarkjs does not pass the verifiers' beacon check
+ * here, and one made here not snarkjs's.  Host only, one thread: the 2^e applications depend on each other, and the call
+ * takes that long (e = 63 does not end).  G16_E_ARG, before any hashing: "beacon: the beacon hash must be 1 to 255
+ * bytes", "beacon: numIterationsExp must be between 10 and 63", "beacon: count must be 2 or 6". */
+int g16_beacon_scalars(const uint8_t* beacon, size_t beacon_len, uint32_t num_iterations_exp, int count, uint8_t* out);
+/* `snarkjs powersoftau beacon old.ptau new.ptau <beaconHash(hex)> <numIterationsExp> --name=..`: g16_ptau_contribute with
+ * secret = g16_beacon_scalars(beacon, e, 6), byte for byte and with the same contribution hash, except that the new
+ * record has type = 1 and its params state the beacon, ids ascending as snarkjs's readers demand: the name's params if
+ * any (byte 1, len, bytes), then byte 2, byte e, then byte 3, byte beacon_len, the beacon bytes.  type and params enter
+ * no hash.  Every check, error and output rule of g16_ptau_contribute applies (texts led by "ptau beacon: "; no CPU path:
+ * G16_E_NOGPU; sections 12-15 dropped; any power 0-24); after the file's checks come the argument errors of
+ * g16_beacon_scalars, then the chain on the calling thread, and only then is the device touched. */
+int g16_ptau_beacon(const uint8_t* ptau, size_t ptau_len, const char* name /* or NULL */, const uint8_t* beacon,
+                    size_t beacon_len, uint32_t num_iterations_exp, int device, uint8_t** out, size_t* out_len,
+                    uint8_t contribution_hash[64]);
+int g16_ptau_beacon_files(const char* in_path, const char* out_path, const char* name, const uint8_t* beacon, size_t beacon_len,
+                          uint32_t num_iterations_exp, int device, uint8_t contribution_hash[64]);
 /* `snarkjs powersoftau verify pot.ptau`: is the file the generator file plus a chain of honest contributions (of THIS
  * library's transcript, see above)?  G16_OK with *ok = 1 / 0; for 0 g16_last_error() holds the reason, one fixed text
  * per check, each led by "ptau verify: ", in this order:
@@ -453,7 +479,14 @@ int g16_ptau_contribute_files(const char* in_path, const char* out_path, const c
  *      tauG2 does not match its tauG1" (e(tauG1, G2) != e(G1, tauG2)), "... betaG2 does not match its betaG1".  g2_sp is
  *      recomputed from the record's challenge: the generator file's for the first record, the nextChallenge of the
  *      record before for every other.  nextChallenge itself can be recomputed only where the state it hashes is at hand,
- *      that is for the last record (check 4); the first record's challenge is that of the generator file of this power;
+ *      that is for the last record (check 4); the first record's challenge is that of the generator file of this power.
+ *      A record of type 1 (a beacon) must also BE its beacon's: its params are walked by snarkjs's rule (ids 1, 2, 3
+ *      ascending, nothing else, nothing cut short); without both id 2 (e, in 10 .. 63) and id 3 (the beacon hash, not
+ *      empty) "a beacon contribution does not state its beacon"; else g16_beacon_scalars is recomputed and every key
+ *      must have g1_s = [s_x]G1 and g1_sx = [x]g1_s, else "a beacon contribution's key is not the beacon's" (g2_spx is
+ *      tied to these by the consistency pairing).  Reported after the pairing checks of the records and instead of
+ *      checks 3 to 5.  This costs 2^e hashes per beacon record on one host thread: a record that states a large e makes
+ *      verification that slow.  A record of any other type is not touched by this;
  *   3. "the file's points are not the last contribution's" (point 1 of sections 2 and 3 -- power >= 1 --, point 0 of
  *      sections 4, 5, 6), or, without records, "a file without contributions is not the generator file";
  *   4. "the last contribution's challenge hash does not match the file" (skipped without records);
@@ -488,7 +521,7 @@ int g16_ptau_verify_file(const char* path, int device, int* ok);
  * name) is g16_ptau_contribute(old, name, secret) byte for byte, with the same hash.
  * DEPARTURES from snarkjs: the hash printed and returned by challenge contribute and import response is THIS library's
  * responseHash = Blake2b-512(challenge | the nine key points), i.e. over the response's first 64 and last 768 bytes, not
- * snarkjs's Blake2b-512 of the whole response file; partialHash stays zero; `powersoftau beacon` is not implemented.
+ * snarkjs's Blake2b-512 of the whole response file; partialHash stays zero.  An imported record has type 0.
  *
  * `snarkjs powersoftau export challenge pot.ptau challenge` (alias `ptec`): the challenge file (g16_free) and --
  * optionally -- its Blake2b-512.  Host only (never G16_E_NOGPU); any power 0-24; the checks of g16_ptau_contribute on the
@@ -532,7 +565,8 @@ int g16_ptau_import_response(const uint8_t* ptau, size_t ptau_len, const uint8_t
 int g16_ptau_import_response_files(const char* ptau_path, const char* response_path, const char* out_path, const char* name,
                                    int device, uint8_t contribution_hash[64], int* ok);
 /* The CLI's rule for `-e=<text>` (NOT snarkjs's): h_j = Blake2b-512(text | byte j), j = 0, 1, 2; the first 32 bytes of
- * h_j (little-endian, reduced mod r, zero mapped to 1) are key j (tau, alpha, beta), the last 32 bytes s_j. */
+ * h_j (little-endian, reduced mod r, zero mapped to 1) are key j (tau, alpha, beta), the last 32 bytes s_j.  The scalars
+ * of a beacon (g16_beacon_scalars) are this library's rule in the same way, and not snarkjs's either. */
 int g16_ptau_secret_from_text(const char* text, uint8_t secret[192]);
 
 /* `snarkjs zkey contribute old.zkey new.zkey --name=.. -e=..`: one phase-2 contribution to a Groth16 .zkey (g16_free).
@@ -548,8 +582,9 @@ int g16_ptau_secret_from_text(const char* text, uint8_t secret[192]);
  * standard form (G1: x | y; G2: x.c1 | x.c0 | y.c1 | y.c0; infinity: zeros with bit 0x40 of byte 0), then the transcript.
  * Every input is checked before the device is touched: "zkey file is not groth16", "zkey: Invalid File format" (the
  * container, the header, section sizes, a section 10 shorter than its records say or with trailing bytes, a point
- * coordinate >= q or a point off its curve).  A beacon record (type 1) in the input is carried and hashed like any other.
- * NOT implemented: `zkey beacon`; the csHash of `zkey new` (this library's _0000 keys hold 64 zero bytes there, the
+ * coordinate >= q or a point off its curve).  A beacon record (type 1) in the input is carried and hashed like any other,
+ * its params untouched.  `zkey beacon` is g16_zkey_beacon below.
+ * NOT implemented: the csHash of `zkey new` (this library's _0000 keys hold 64 zero bytes there, the
  * chain is hashed from whatever section 10 holds), so `snarkjs zkey verify` rejects these keys: the file layout and the
  * proofs are snarkjs's, its ceremony verifier is not claimed.  The G2 derivation is NOT cross-checked against snarkjs. */
 int g16_zkey_contribute(const uint8_t* zkey, size_t zkey_len, const char* name /* or NULL */,
@@ -558,6 +593,17 @@ int g16_zkey_contribute(const uint8_t* zkey, size_t zkey_len, const char* name /
 /* the same from / to files: the input is mapped read-only and the key is written in chunks */
 int g16_zkey_contribute_files(const char* in_path, const char* out_path, const char* name,
                               const uint8_t secret[64], int device, uint8_t contribution_hash[64]);
+/* `snarkjs zkey beacon old.zkey new.zkey <beaconHash(hex)> <numIterationsExp> --name=..`: g16_zkey_contribute with secret =
+ * g16_beacon_scalars(beacon, e, 2) = d | s, byte for byte and with the same contribution hash, except that the new
+ * record has type = 1 and params = the name's if any | byte 2, byte e | byte 3, byte beacon_len, the beacon bytes (as in
+ * g16_ptau_beacon; type and params enter no hash).  Every check, error and output rule of g16_zkey_contribute applies
+ * (no CPU path: G16_E_NOGPU); after the key's checks come the argument errors of g16_beacon_scalars, then the chain on
+ * the calling thread, and only then is the device touched.  The derivation is this library's, not snarkjs's. */
+int g16_zkey_beacon(const uint8_t* zkey, size_t zkey_len, const char* name /* or NULL */, const uint8_t* beacon,
+                    size_t beacon_len, uint32_t num_iterations_exp, int device, uint8_t** out, size_t* out_len,
+                    uint8_t contribution_hash[64]);
+int g16_zkey_beacon_files(const char* in_path, const char* out_path, const char* name, const uint8_t* beacon, size_t beacon_len,
+                          uint32_t num_iterations_exp, int device, uint8_t contribution_hash[64]);
 /* `snarkjs zkey verify frominit init.zkey pot.ptau circuit.zkey` without the ptau leg (section 9 is not checked against
  * a ceremony file; g16_zkey_verify_from_init_ptau below is the route with it): is `zkey` the key `init` plus a chain of honest contributions?  G16_OK with *ok = 1 / 0; for 0
  * g16_last_error() holds the reason, one fixed text per check, each led by "zkey verify: ":
@@ -573,6 +619,10 @@ int g16_zkey_contribute_files(const char* in_path, const char* out_path, const c
  *   device as in g16_zkey_h_scalars -- the combinations of quotients of degree <= N - 2, which are what a prover forms
  *   and what `zkey import bellman` preserves, so an imported key passes; a tampered point still moves the sum), "the
  *   combination of sections 8 and 9 is the point at infinity".
+ * Every further record of type 1 (a beacon) must also BE its beacon's, as in check 2 of g16_ptau_verify: "a beacon
+ * contribution does not state its beacon" (params without ids 2 and 3 by snarkjs's sorted-id rule, or e outside 10 ..
+ * 63), "a beacon contribution's key is not the beacon's" (g1_s != [s]G1 or g1_sx != [d]g1_s for d, s =
+ * g16_beacon_scalars); reported after every pairing check; 2^e hashes per beacon record on one host thread.
  * A key with no records beyond init's (init against itself) is accepted.  A malformed file is G16_E_FORMAT, not a
  * verdict.  The two sums are MSMs and the pairings Miller loops + final exponentiations on `device` (G16_E_NOGPU). */
 int g16_zkey_verify_from_init(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_t zkey_len,

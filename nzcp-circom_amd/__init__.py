@@ -91,7 +91,8 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_nzcp_witness_program", "g16_nzcp_gadget_program", "g16_nzcp_inputs", "g16_wtns_calc_create", "g16_wtns_calc",
            "g16_wtns_calc_check_text", "g16_wtns_calc_wtns", "g16_wtns_calc_info", "g16_wtns_calc_outputs",
            "g16_wtns_calc_input", "g16_wtns_calc_timings", "g16_wtns_calc_destroy", "g16_stage_inputs",
-           "g16_fullprove_batch", "g16_plonk_fullprove_batch"]
+           "g16_fullprove_batch", "g16_plonk_fullprove_batch",
+           "g16_beacon_scalars", "g16_ptau_beacon", "g16_ptau_beacon_files", "g16_zkey_beacon", "g16_zkey_beacon_files"]
 
 
 def load():
@@ -191,6 +192,11 @@ def load():
     lib.g16_ptau_new_file.argtypes = [C.c_uint32, C.c_char_p]
     lib.g16_ptau_contribute.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
     lib.g16_ptau_contribute_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
+    lib.g16_beacon_scalars.argtypes = [C.c_char_p, sz, C.c_uint32, C.c_int, C.c_char_p]
+    for fn in (lib.g16_ptau_beacon, lib.g16_zkey_beacon):
+        fn.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_char_p, sz, C.c_uint32, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
+    for fn in (lib.g16_ptau_beacon_files, lib.g16_zkey_beacon_files):
+        fn.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz, C.c_uint32, C.c_int, C.c_char_p]
     lib.g16_ptau_verify.argtypes = [C.c_char_p, sz, C.c_int, C.POINTER(C.c_int)]
     lib.g16_ptau_verify_file.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     lib.g16_ptau_secret_from_text.argtypes = [C.c_char_p, C.c_char_p]
@@ -1068,6 +1074,39 @@ def ptau_contribute(ptau, name=None, secret=None, device=0):
     nm = None if name is None else name.encode("utf-8")
     _check(load().g16_ptau_contribute(ptau, len(ptau), nm, blob, device, C.byref(z), C.byref(zl), h))
     return _take(z, zl), h.raw
+
+
+def beacon_scalars(beacon, exp, count):
+    """The secret scalars of a beacon contribution (ints in [1, r)): count 6 = (tau, alpha, beta, s_tau, s_alpha,
+    s_beta), count 2 = (d, s), the first two of the same stream.  beacon: 1 to 255 bytes; exp: 10 to 63, and the call
+    hashes 2^exp times on this thread.  This library's derivation, not snarkjs's (host only)."""
+    if not 0 <= exp < 1 << 32:
+        raise ValueError("beacon_scalars: exp does not fit 32 bits")
+    out = C.create_string_buffer(192)
+    _check(load().g16_beacon_scalars(bytes(beacon), len(beacon), exp, count, out))
+    return tuple(int.from_bytes(out.raw[32 * i:32 * i + 32], "little") for i in range(count))
+
+
+def _beacon(fn, data, beacon, exp, name, device):
+    if not 0 <= exp < 1 << 32:
+        raise ValueError("beacon: exp does not fit 32 bits")
+    z, zl = C.c_void_p(), C.c_size_t()
+    h = C.create_string_buffer(64)
+    nm = None if name is None else name.encode("utf-8")
+    _check(fn(data, len(data), nm, bytes(beacon), len(beacon), exp, device, C.byref(z), C.byref(zl), h))
+    return _take(z, zl), h.raw
+
+
+def ptau_beacon(ptau, beacon, exp, name=None, device=0):
+    """`snarkjs powersoftau beacon`: .ptau bytes -> (the .ptau bytes with the beacon contribution, 64-byte contribution
+    hash): ptau_contribute with secret = beacon_scalars(beacon, exp, 6), and a record of type 1 that states the beacon."""
+    return _beacon(load().g16_ptau_beacon, ptau, beacon, exp, name, device)
+
+
+def zkey_beacon(zkey, beacon, exp, name=None, device=0):
+    """`snarkjs zkey beacon`: Groth16 .zkey bytes -> (the .zkey bytes with the beacon contribution, 64-byte contribution
+    hash): zkey_contribute with (d, s) = beacon_scalars(beacon, exp, 2), and a record of type 1 that states the beacon."""
+    return _beacon(load().g16_zkey_beacon, zkey, beacon, exp, name, device)
 
 
 def ptau_verify(ptau, device=0):

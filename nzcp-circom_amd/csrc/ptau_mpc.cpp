@@ -15,8 +15,11 @@
 // nextChallenge; for key x (tau = 0, alpha = 1, beta = 2) g1_s = [s_x]G1, g1_sx = [x]g1_s, g2_sp =
 // hash_to_g2(Blake2b-512(challenge | byte x | g1_s | g1_sx)), g2_spx = [x]g2_sp; responseHash = Blake2b-512(challenge |
 // the nine key points in record order); nextChallenge = challengeHash(new state, responseHash); partialHash is 216 zero
-// bytes that nothing reads.  snarkjs's `powersoftau verify` is NOT claimed to accept this transcript.  NOT here:
-// `powersoftau beacon`.
+// bytes that nothing reads.  snarkjs's `powersoftau verify` is NOT claimed to accept this transcript.
+//   beacon:     a contribution whose six secret scalars anyone recomputes from a public beacon hash and an iteration
+//               exponent (beacon.h, mpc_beacon_scalars): a record of type 1 that states both; verify recomputes them for
+//               every such record.  The derivation is this library's, as the `-e` rule is: a snarkjs-made beacon record
+//               fails that check here.
 // The challenge / response file exchange ([EXT] powersoftau_export_challenge.js, powersoftau_challenge_contribute.js,
 // powersoftau_import.js, restated without ffjavascript, which is not available here): the transcript above already IS
 // that of the files --
@@ -36,6 +39,7 @@
 #include <chrono>
 #include <thread>
 
+#include "beacon.h"
 #include "internal.h"
 #include "mapped_file.h"
 #include "ptau.h"
@@ -315,7 +319,7 @@ void file_challenge(const Ceremony& c, std::vector<uint8_t>& feed, uint8_t chall
 // feed: the state after the contribution -- tauG1 / tauG2 are point 1 of sections 2 / 3, which a power-0 file does not
 // hold (the caller has set them) --, response <- responseHash, and the seal: nextChallenge, type and params
 void seal_record(const Ceremony& c, uint8_t* const sp[16], const uint8_t challenge[64], std::vector<uint8_t>& feed,
-                 const std::string& params, uint8_t* rec, uint8_t response[64]) {
+                 uint32_t type, const std::string& params, uint8_t* rec, uint8_t response[64]) {
   if (c.pv.power >= 1) {
     memcpy(rec, sp[2] + 64, 64);
     memcpy(rec + 64, sp[3] + 128, 128);
@@ -326,27 +330,37 @@ void seal_record(const Ceremony& c, uint8_t* const sp[16], const uint8_t challen
   response_hash(challenge, PtauRecord{rec, kPtauRecordFixed + params.size()}, response);
   memcpy(feed.data(), response, 64);
   blake2b512(feed.data(), feed.size(), rec + kPtauNextChallengeAt);
-  const uint32_t type = 0, plen = (uint32_t)params.size();
+  const uint32_t plen = (uint32_t)params.size();
   memcpy(rec + kPtauNextChallengeAt + 64, &type, 4);
   memcpy(rec + kPtauNextChallengeAt + 68, &plen, 4);
   if (plen) memcpy(rec + kPtauRecordFixed, params.data(), plen);
 }
 
-int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uint8_t* secret, int device, uint8_t** out,
-                    size_t* out_len, uint8_t contribution_hash[64]) {
+// bc: `powersoftau beacon` -- the secret is the beacon's (the chain runs here, on this thread, before the device is
+// touched), the record is of type 1 and states the beacon after the name; everything else is the contribution's
+int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uint8_t* secret, const BeaconArg* bc, int device,
+                    uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]) {
   const auto t0 = std::chrono::steady_clock::now();
+  const char* route = bc ? "ptau beacon" : "ptau contribute";
   Ceremony c;
-  if (const int rc = open_ceremony(ptau, len, "ptau contribute", c)) return rc;
+  if (const int rc = open_ceremony(ptau, len, route, c)) return rc;
   Fr key[3], sk[3];
-  if (const int rc = read_secret("ptau contribute", secret, key, sk)) return rc;
-  if (const int rc = require_hip_device("ptau contribute", device)) return rc;
+  if (bc) {
+    Fr x[6];
+    if (const int rc = mpc_beacon_scalars(bc->hash, bc->len, bc->exp, 6, x)) return rc;
+    for (int i = 0; i < 3; i++) { key[i] = x[i]; sk[i] = x[3 + i]; }
+  } else if (const int rc = read_secret(route, secret, key, sk)) {
+    return rc;
+  }
+  if (const int rc = require_hip_device(route, device)) return rc;
 
-  const std::string params = mpc_name_params(name);
+  std::string params = mpc_name_params(name);
+  if (bc) params += beacon_params(bc->hash, bc->len, bc->exp);
   const size_t rec_len = kPtauRecordFixed + params.size();
   Buf z;
   uint8_t* sp[16] = {};
   uint8_t* rec = layout_with_record(c, rec_len, z, sp);
-  if (!rec) { set_error("ptau contribute: out of memory"); return G16_E_STATE; }
+  if (!rec) { set_error(std::string(route) + ": out of memory"); return G16_E_STATE; }
   struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
   memset(rec, 0, rec_len);   // (partialHash stays zero)
 
@@ -382,7 +396,7 @@ int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uin
     mpc_mul_g2(c.rec.empty() ? gens().g2 : c.rec.back().tau_g2(), key[0], rec + 64);
   }
   uint8_t response[64];
-  seal_record(c, sp, challenge, feed, params, rec, response);
+  seal_record(c, sp, challenge, feed, bc ? 1 : 0, params, rec, response);
   if (contribution_hash) memcpy(contribution_hash, response, 64);
   hash_ms += ms_since(th1);
 
@@ -395,9 +409,9 @@ int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uin
       xf += s.xfer_ms;
     }
     fprintf(stderr,
-            "[g16] ptau contribute: points G1 %llu G2 %llu; kernels G1 %.3f ms G2 %.3f ms, transfers %.3f ms; host hashing %.3f ms "
+            "[g16] %s: points G1 %llu G2 %llu; kernels G1 %.3f ms G2 %.3f ms, transfers %.3f ms; host hashing %.3f ms "
             "(big-endian images of the new points made on the device%s); call %.3f ms\n",
-            (unsigned long long)g1, (unsigned long long)g2, k1, k2, xf, hash_ms,
+            route, (unsigned long long)g1, (unsigned long long)g2, k1, k2, xf, hash_ms,
             c.rec.empty() ? ", of the input on the host" : "", ms_since(t0));
   }
   guard.p = nullptr;
@@ -573,7 +587,7 @@ int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, s
 
   // the record, as contribute builds it
   uint8_t response[64];
-  seal_record(c, sp, challenge, feed, params, rec, response);
+  seal_record(c, sp, challenge, feed, 0, params, rec, response);
 
   // step 2 of verify for this one record, against the record before it or the generators: ONE pairing call
   {
@@ -638,22 +652,36 @@ int verify_core(const uint8_t* ptau, size_t len, int device, int* ok) {
   static const RecordTexts texts = G16_RECORD_TEXTS("ptau verify");
   const uint8_t* cur[3] = {G.g1, G.g1, G.g1};   // tauG1, alphaG1, betaG1 before the record
   uint8_t challenge[64];
+  const char* beacon_fail = nullptr;
   std::vector<G2Affine> g2_sp(3 * c.rec.size());
   for (size_t i = 0; i < c.rec.size(); i++) {
     if (i == 0) generator_challenge(c, challenge);
     else memcpy(challenge, c.rec[i - 1].next_challenge(), 64);
     if (const char* inf = record_checks(texts, c.rec[i], cur, challenge, &g2_sp[3 * i], pairs, reason)) return verdict(inf);
+    const PtauRecord& r = c.rec[i];
+    if (rd32(r.p + kPtauNextChallengeAt + 64) == 1 && !beacon_fail) {   // a beacon: the keys are what anyone recomputes
+      BeaconStated st;
+      Fr x[6];
+      if (!beacon_params_walk(r.p + kPtauRecordFixed, r.len - kPtauRecordFixed, st)) {
+        beacon_fail = "ptau verify: a beacon contribution does not state its beacon";
+      } else {
+        bool ok = mpc_beacon_scalars(st.hash, st.hash_len, st.exp, 6, x) == G16_OK;
+        for (int k = 0; k < 3 && ok; k++) ok = mpc_beacon_key_ok(r.g1_s(k), r.g1_sx(k), x[k], x[3 + k]);
+        if (!ok) beacon_fail = "ptau verify: a beacon contribution's key is not the beacon's";
+      }
+    }
   }
 
-  // 3, 4 (host): a failure here is reported after the walk's pairings, and spares the sums of check 5
-  const char* host_fail = nullptr;
+  // 3, 4 (host): a failure here, a beacon's included, is reported after the walk's pairings, and spares the sums of
+  // check 5
+  const char* host_fail = beacon_fail;
   if (c.rec.empty()) {
     bool gen = true;
     for (int id = 2; id <= 6 && gen; id++)
       for (uint64_t i = 0; i < c.cnt[id] && gen; i++)
         gen = Ceremony::psz(id) == 64 ? memcmp(sec[id] + i * 64, G.g1, 64) == 0 : memcmp(sec[id] + i * 128, G.g2, 128) == 0;
     if (!gen) host_fail = "ptau verify: a file without contributions is not the generator file";
-  } else {
+  } else if (!host_fail) {
     const PtauRecord& r = c.rec.back();
     bool same = memcmp(r.alpha_g1(), sec[4], 64) == 0 && memcmp(r.beta_g1(), sec[5], 64) == 0 && memcmp(r.beta_g2(), sec[6], 128) == 0;
     if (c.pv.power >= 1) same = same && memcmp(r.tau_g1(), sec[2] + 64, 64) == 0 && memcmp(r.tau_g2(), sec[3] + 128, 128) == 0;
@@ -780,7 +808,7 @@ extern "C" int g16_ptau_contribute(const uint8_t* ptau, size_t ptau_len, const c
                                    uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]) {
   if (!ptau || !out || !out_len) { set_error("NULL argument"); return G16_E_ARG; }
   return no_bad_alloc("ptau contribute",
-                      [&]() { return contribute_core(ptau, ptau_len, name, secret, device, out, out_len, contribution_hash); });
+                      [&]() { return contribute_core(ptau, ptau_len, name, secret, nullptr, device, out, out_len, contribution_hash); });
 }
 
 extern "C" int g16_ptau_contribute_files(const char* in_path, const char* out_path, const char* name, const uint8_t secret[192],
@@ -788,6 +816,22 @@ extern "C" int g16_ptau_contribute_files(const char* in_path, const char* out_pa
   if (!in_path || !out_path) { set_error("NULL argument"); return G16_E_ARG; }
   return files_form(&in_path, 1, out_path, [&](const MappedFile* m, uint8_t** z, size_t* zl) {
     return g16_ptau_contribute((const uint8_t*)m[0].p, m[0].len, name, secret, device, z, zl, contribution_hash);
+  });
+}
+
+extern "C" int g16_ptau_beacon(const uint8_t* ptau, size_t ptau_len, const char* name, const uint8_t* beacon, size_t beacon_len,
+                               uint32_t num_iterations_exp, int device, uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]) {
+  if (!ptau || !out || !out_len) { set_error("NULL argument"); return G16_E_ARG; }
+  const BeaconArg bc{beacon, beacon_len, num_iterations_exp};
+  return no_bad_alloc("ptau beacon",
+                      [&]() { return contribute_core(ptau, ptau_len, name, nullptr, &bc, device, out, out_len, contribution_hash); });
+}
+
+extern "C" int g16_ptau_beacon_files(const char* in_path, const char* out_path, const char* name, const uint8_t* beacon,
+                                     size_t beacon_len, uint32_t num_iterations_exp, int device, uint8_t contribution_hash[64]) {
+  if (!in_path || !out_path) { set_error("NULL argument"); return G16_E_ARG; }
+  return files_form(&in_path, 1, out_path, [&](const MappedFile* m, uint8_t** z, size_t* zl) {
+    return g16_ptau_beacon((const uint8_t*)m[0].p, m[0].len, name, beacon, beacon_len, num_iterations_exp, device, z, zl, contribution_hash);
   });
 }
 

@@ -8,8 +8,12 @@
 //               sectionHasSameRatioH): section 9 is the H basis of THAT ceremony's section 2 scaled by 1 / delta
 //               (zkey_verify_h.hip).  The leg reads section 2 only; whether the file is a sound ceremony is
 //               `powersoftau verify`'s question.
-// NOT here, on purpose: `zkey beacon`; the real csHash of `zkey new` (section 10 of this library's _0000 keys holds 64
-// zero bytes, and the chain is hashed from whatever section 10 holds).
+//   beacon:     a contribution whose d and s anyone recomputes from a public beacon hash and an iteration exponent
+//               (beacon.h, mpc_beacon_scalars): a record of type 1 that states both; verify recomputes them for every
+//               such record.  The derivation is this library's, as the `-e` rule is: a snarkjs-made beacon record
+//               fails that check here.
+// NOT here, on purpose: the real csHash of `zkey new` (section 10 of this library's _0000 keys holds 64 zero bytes, and
+// the chain is hashed from whatever section 10 holds).
 // Because csHash is not snarkjs's, `snarkjs zkey verify` rejects these keys: the file LAYOUT and the proofs are
 // compatible, snarkjs's ceremony verifier is not claimed.
 #include "zkey_mpc.h"
@@ -19,6 +23,7 @@
 
 #include <chrono>
 
+#include "beacon.h"
 #include "internal.h"
 #include "mapped_file.h"
 #include "ptau.h"
@@ -415,6 +420,32 @@ int mpc_read_secret(const char* route, const uint8_t* secret, Fr& d, Fr& s) {
   return G16_OK;
 }
 
+// The ChaCha20 word stream keyed with the seed as hash_to_g2 keys it, from counter 0; every scalar one next_below(r), a
+// zero draw mapped to 1.  count 2 = the first two of count 6: it is one stream.
+int mpc_beacon_scalars(const uint8_t* beacon, size_t beacon_len, uint32_t exp, int count, Fr* out) {
+  if (count != 2 && count != 6) { set_error("beacon: count must be 2 or 6"); return G16_E_ARG; }
+  if (!beacon || beacon_len < 1 || beacon_len > kBeaconHashMax) { set_error("beacon: the beacon hash must be 1 to 255 bytes"); return G16_E_ARG; }
+  if (exp < kBeaconExpMin || exp > kBeaconExpMax) { set_error("beacon: numIterationsExp must be between 10 and 63"); return G16_E_ARG; }
+  ChaCha rng;
+  beacon_chain(beacon, beacon_len, exp, rng.key);
+  for (int i = 0; i < count; i++) {
+    rng.next_below(kFrP, out[i].v);
+    if (fp_is_zero(out[i])) out[i].v[0] = 1;
+  }
+  return G16_OK;
+}
+
+bool mpc_beacon_key_ok(const uint8_t* g1_s, const uint8_t* g1_sx, const Fr& x, const Fr& s) {
+  G1Affine g1;   // (1, 2)
+  g1.x = fp_one<FqParams>();
+  g1.y = fp_add(g1.x, g1.x);
+  uint8_t want[64];
+  mul_image<FqOps>((const uint8_t*)&g1, s, want);
+  if (memcmp(want, g1_s, 64) != 0) return false;
+  mul_image<FqOps>(want, x, want);
+  return memcmp(want, g1_sx, 64) == 0;
+}
+
 void mpc_contribution(std::vector<uint8_t>& feed, const Fr& d, const Fr& s, uint8_t g1_s[64], uint8_t g1_sx[64],
                       uint8_t g2_spx[128], uint8_t transcript[64]) {
   G1Affine g1;   // (1, 2)
@@ -449,16 +480,26 @@ double ms_since(const std::chrono::steady_clock::time_point& t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, const uint8_t* secret, int device, uint8_t** out,
-                    size_t* out_len, uint8_t contribution_hash[64]) {
+// bc: `zkey beacon` -- the secret is the beacon's (the chain runs here, on this thread, before the device is touched),
+// the record is of type 1 and states the beacon after the name; everything else is the contribution's
+int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, const uint8_t* secret, const BeaconArg* bc, int device,
+                    uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]) {
   const auto t0 = std::chrono::steady_clock::now();
+  const char* route = bc ? "zkey beacon" : "zkey contribute";
   KeyView k;
   if (const int rc = open_key(zkey, zkey_len, k, true)) return rc;
   Fr d, s;
-  if (const int rc = mpc_read_secret("zkey contribute", secret, d, s)) return rc;
-  if (const int rc = require_hip_device("zkey contribute", device)) return rc;
+  if (bc) {
+    Fr ds[2];
+    if (const int rc = mpc_beacon_scalars(bc->hash, bc->len, bc->exp, 2, ds)) return rc;
+    d = ds[0]; s = ds[1];
+  } else if (const int rc = mpc_read_secret(route, secret, d, s)) {
+    return rc;
+  }
+  if (const int rc = require_hip_device(route, device)) return rc;
 
-  const std::string params = mpc_name_params(name);
+  std::string params = mpc_name_params(name);
+  if (bc) params += beacon_params(bc->hash, bc->len, bc->exp);
   const uint32_t plen = (uint32_t)params.size();
   const size_t rec_len = kMpcRecordFixed + plen;
 
@@ -477,7 +518,7 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
   for (const Entry& e : table) total += 12 + e.size;
   total += rec_len;
   Buf z;
-  if (!z.reserve(total)) { set_error("zkey contribute: out of memory"); return G16_E_STATE; }
+  if (!z.reserve(total)) { set_error(std::string(route) + ": out of memory"); return G16_E_STATE; }
   z.put(zkey, 12);
   uint8_t* sp[16] = {};
   for (const Entry& e : table) {
@@ -500,7 +541,7 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
     mul_image<FqOps>(hdr + kHdrDelta1, d, sp[2] + kHdrDelta1);
     mul_image<Fq2Ops>(hdr + kHdrDelta2, d, sp[2] + kHdrDelta2);
     memcpy(rec, sp[2] + kHdrDelta1, 64);   // deltaAfter
-    const uint32_t type = 0;
+    const uint32_t type = bc ? 1 : 0;
     memcpy(rec + 384, &type, 4);
     memcpy(rec + 388, &plen, 4);
     if (plen) memcpy(rec + 392, params.data(), plen);
@@ -518,8 +559,8 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
   if (!rc) rc = zkey_scale_g1(device, k.f.sec[9].p, k.f.sec[9].size / 64, dinv, sp[9], &st[1]);
   if (rc) { free(z.p); return rc; }
   if (getenv("G16_TRACE_HOST"))
-    fprintf(stderr, "[g16] zkey contribute: points %llu; kernels %.3f ms, transfers %.3f ms, MSM 0.000 ms, pairings 0.000 ms; call %.3f ms\n",
-            (unsigned long long)(st[0].points + st[1].points), st[0].kern_ms + st[1].kern_ms, st[0].xfer_ms + st[1].xfer_ms, ms_since(t0));
+    fprintf(stderr, "[g16] %s: points %llu; kernels %.3f ms, transfers %.3f ms, MSM 0.000 ms, pairings 0.000 ms; call %.3f ms\n",
+            route, (unsigned long long)(st[0].points + st[1].points), st[0].kern_ms + st[1].kern_ms, st[0].xfer_ms + st[1].xfer_ms, ms_since(t0));
   z.give(out, out_len);
   return G16_OK;
 }
@@ -585,6 +626,7 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
   };
   const char* inf_text = "zkey verify: a contribution holds the point at infinity";
   const uint8_t* cur = ha + kHdrDelta1;
+  const char* beacon_fail = nullptr;   // reported after the pairing checks: a beacon record passes its own checks first
   std::vector<G2Affine> g2_sp(b.mpc.rec.size());
   for (size_t i = a.mpc.rec.size(); i < b.mpc.rec.size(); i++) {
     const MpcRecord& r = b.mpc.rec[i];
@@ -596,6 +638,14 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
     if (!same_ratio(r.g1_s(), r.g1_sx(), sp2, r.g2_spx(), "zkey verify: a contribution's public key is not consistent")) return verdict(inf_text);
     if (!same_ratio(cur, r.delta_after(), sp2, r.g2_spx(), "zkey verify: a contribution's delta does not continue the chain")) return verdict(inf_text);
     cur = r.delta_after();
+    if (rd32(r.p + 384) == 1 && !beacon_fail) {   // a beacon: the key is what anyone recomputes from the stated beacon
+      BeaconStated st;
+      Fr ds[2];
+      if (!beacon_params_walk(r.p + kMpcRecordFixed, r.len - kMpcRecordFixed, st))
+        beacon_fail = "zkey verify: a beacon contribution does not state its beacon";
+      else if (mpc_beacon_scalars(st.hash, st.hash_len, st.exp, 2, ds) || !mpc_beacon_key_ok(r.g1_s(), r.g1_sx(), ds[0], ds[1]))
+        beacon_fail = "zkey verify: a beacon contribution's key is not the beacon's";
+    }
   }
   // 4. the header's delta
   if (memcmp(cur, hb + kHdrDelta1, 64) != 0) return verdict("zkey verify: delta1 of the header is not the last contribution's");
@@ -696,6 +746,7 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
   }
   for (size_t c = 0; c < reason.size(); c++)
     if (memcmp(gt.data() + 2 * c * 384, gt.data() + (2 * c + 1) * 384, 384) != 0) return verdict(reason[c]);
+  if (beacon_fail) return verdict(beacon_fail);
   set_error("");
   *ok = 1;
   return G16_OK;
@@ -724,7 +775,7 @@ extern "C" int g16_zkey_contribute(const uint8_t* zkey, size_t zkey_len, const c
                                    uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]) {
   if (!zkey || !out || !out_len) { set_error("NULL argument"); return G16_E_ARG; }
   return no_bad_alloc("zkey contribute",
-                      [&]() { return contribute_core(zkey, zkey_len, name, secret, device, out, out_len, contribution_hash); });
+                      [&]() { return contribute_core(zkey, zkey_len, name, secret, nullptr, device, out, out_len, contribution_hash); });
 }
 
 extern "C" int g16_zkey_contribute_files(const char* in_path, const char* out_path, const char* name, const uint8_t secret[64],
@@ -733,6 +784,30 @@ extern "C" int g16_zkey_contribute_files(const char* in_path, const char* out_pa
   return files_form(&in_path, 1, out_path, [&](const MappedFile* m, uint8_t** z, size_t* zl) {
     return g16_zkey_contribute((const uint8_t*)m[0].p, m[0].len, name, secret, device, z, zl, contribution_hash);
   });
+}
+
+extern "C" int g16_zkey_beacon(const uint8_t* zkey, size_t zkey_len, const char* name, const uint8_t* beacon, size_t beacon_len,
+                               uint32_t num_iterations_exp, int device, uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]) {
+  if (!zkey || !out || !out_len) { set_error("NULL argument"); return G16_E_ARG; }
+  const BeaconArg bc{beacon, beacon_len, num_iterations_exp};
+  return no_bad_alloc("zkey beacon",
+                      [&]() { return contribute_core(zkey, zkey_len, name, nullptr, &bc, device, out, out_len, contribution_hash); });
+}
+
+extern "C" int g16_zkey_beacon_files(const char* in_path, const char* out_path, const char* name, const uint8_t* beacon,
+                                     size_t beacon_len, uint32_t num_iterations_exp, int device, uint8_t contribution_hash[64]) {
+  if (!in_path || !out_path) { set_error("NULL argument"); return G16_E_ARG; }
+  return files_form(&in_path, 1, out_path, [&](const MappedFile* m, uint8_t** z, size_t* zl) {
+    return g16_zkey_beacon((const uint8_t*)m[0].p, m[0].len, name, beacon, beacon_len, num_iterations_exp, device, z, zl, contribution_hash);
+  });
+}
+
+extern "C" int g16_beacon_scalars(const uint8_t* beacon, size_t beacon_len, uint32_t num_iterations_exp, int count, uint8_t* out) {
+  if (!out) { set_error("NULL argument"); return G16_E_ARG; }
+  Fr x[6];
+  if (const int rc = mpc_beacon_scalars(beacon, beacon_len, num_iterations_exp, count, x)) return rc;
+  memcpy(out, x, (size_t)count * 32);
+  return G16_OK;
 }
 
 extern "C" int g16_zkey_verify_from_init(const uint8_t* init, size_t init_len, const uint8_t* zkey, size_t zkey_len, int device,

@@ -66,6 +66,15 @@ int mpc_read_secret(const char* route, const uint8_t* secret, Fr& d, Fr& s);
 void mpc_contribution(std::vector<uint8_t>& feed, const Fr& d, const Fr& s, uint8_t g1_s[64], uint8_t g1_sx[64],
                       uint8_t g2_spx[128], uint8_t transcript[64]);
 
+// A beacon contribution's public parameters, and its secret scalars (standard form, in [1, r)): count 2 (d, s) or 6
+// (tau, alpha, beta, s_tau, s_alpha, s_beta) draws of ONE stream seeded by the delay function (beacon.h), which runs on
+// the calling thread.  G16_E_ARG "beacon: the beacon hash must be 1 to 255 bytes" / "beacon: numIterationsExp must be
+// between 10 and 63" / "beacon: count must be 2 or 6" before any hashing.
+struct BeaconArg { const uint8_t* hash; size_t len; uint32_t exp; };
+int mpc_beacon_scalars(const uint8_t* beacon, size_t beacon_len, uint32_t exp, int count, Fr* out);
+// a beacon record's key under the verifiers: g1_s = [s] G1 and g1_sx = [x] g1_s (file images)
+bool mpc_beacon_key_ok(const uint8_t* g1_s, const uint8_t* g1_sx, const Fr& x, const Fr& s);
+
 // Shared with the .ptau ceremony (ptau_mpc.cpp).  File images are affine little-endian Montgomery, infinity = zeros.
 bool mpc_g1_image_ok(const uint8_t* p);   // coordinates below q and the point on its curve (infinity passes)
 bool mpc_g2_image_ok(const uint8_t* p);

@@ -44,6 +44,9 @@
  *           zkeyVerifyFromInitFiles(initPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_from_init_files)
  *           zkeyVerifyFromInitPtauFiles(initPath, ptauPath, zkeyPath, device) -> Promise<{ok, reason}>   (..._from_init_ptau_files)
  *           zkeyVerifyR1csFiles(r1csPath, ptauPath, zkeyPath, device) -> Promise<{ok, reason}>   (g16_zkey_verify_r1cs_files)
+ *           ptauBeaconFiles(inPath, outPath, name | null, beaconHash: Buffer, numIterationsExp, device) -> Promise<Buffer(64)>
+ *           zkeyBeaconFiles(inPath, outPath, name | null, beaconHash: Buffer, numIterationsExp, device) -> Promise<Buffer(64)>
+ *                                                            (g16_ptau_beacon_files, g16_zkey_beacon_files: the hash)
  */
 #include <node_api.h>
 #include <stdio.h>
@@ -1182,6 +1185,75 @@ static napi_value js_ptau_import_response_files(napi_env env, napi_callback_info
   return tjob_start(env, j, "g16_ptau_import_response_files");
 }
 
+/* powersoftau beacon / zkey beacon from / to files.  The delay function runs in the worker, off the event loop. */
+typedef struct {
+  napi_async_work work;
+  napi_deferred deferred;
+  char a[1024], b[1024], name[512];
+  uint8_t beacon[256], hash[64];   /* (a hash of more than 255 bytes is cut to 256: the library refuses it by its length) */
+  size_t beacon_len;
+  uint32_t exp;
+  int zkey, has_name, device, rc;
+  char err[512];
+} bjob_t;
+static void bjob_execute(napi_env env, void* data) {
+  bjob_t* j = (bjob_t*)data;
+  j->rc = (j->zkey ? g16_zkey_beacon_files : g16_ptau_beacon_files)(j->a, j->b, j->has_name ? j->name : NULL, j->beacon, j->beacon_len,
+                                                                     j->exp, j->device, j->hash);
+  if (j->rc) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
+}
+static void bjob_complete(napi_env env, napi_status status, void* data) {
+  bjob_t* j = (bjob_t*)data;
+  if (status != napi_ok || j->rc) {
+    napi_value msg, err;
+    napi_create_string_utf8(env, status == napi_ok ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_reject_deferred(env, j->deferred, err);
+  } else {
+    napi_value buf;
+    void* copy = NULL;
+    napi_create_buffer_copy(env, 64, j->hash, &copy, &buf);
+    napi_resolve_deferred(env, j->deferred, buf);
+  }
+  napi_delete_async_work(env, j->work);
+  free(j);
+}
+static napi_value beacon_files(napi_env env, napi_callback_info info, int zkey, const char* usage, const char* resource) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bjob_t* j = (bjob_t*)calloc(1, sizeof(bjob_t));
+  size_t n = 0, len = 0;
+  void* p = NULL;
+  bool is_buf = false;
+  if (argc < 5 || napi_get_value_string_utf8(env, argv[0], j->a, sizeof(j->a), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], j->b, sizeof(j->b), &n) != napi_ok ||
+      napi_is_buffer(env, argv[3], &is_buf) != napi_ok || !is_buf || napi_get_buffer_info(env, argv[3], &p, &len) != napi_ok ||
+      napi_get_value_uint32(env, argv[4], &j->exp) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  if (napi_get_value_string_utf8(env, argv[2], j->name, sizeof(j->name), &n) == napi_ok) j->has_name = 1;
+  j->beacon_len = len < sizeof(j->beacon) ? len : sizeof(j->beacon);
+  if (j->beacon_len) memcpy(j->beacon, p, j->beacon_len);
+  int32_t v = 0;
+  if (argc > 5 && napi_get_value_int32(env, argv[5], &v) == napi_ok) j->device = v;
+  j->zkey = zkey;
+  napi_value promise, resname;
+  NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
+  NAPI_OK(napi_create_string_utf8(env, resource, NAPI_AUTO_LENGTH, &resname));
+  NAPI_OK(napi_create_async_work(env, NULL, resname, bjob_execute, bjob_complete, j, &j->work));
+  NAPI_OK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+static napi_value js_ptau_beacon_files(napi_env env, napi_callback_info info) {
+  return beacon_files(env, info, 0, "ptauBeaconFiles(inPath, outPath, name, beaconHash: Buffer, numIterationsExp, device)", "g16_ptau_beacon_files");
+}
+static napi_value js_zkey_beacon_files(napi_env env, napi_callback_info info) {
+  return beacon_files(env, info, 1, "zkeyBeaconFiles(inPath, outPath, name, beaconHash: Buffer, numIterationsExp, device)", "g16_zkey_beacon_files");
+}
+
 /* wtns check from files: the verdict of g16_wtns_check_files (an unsatisfied witness resolves, a malformed file rejects) */
 typedef struct {
   napi_async_work work;
@@ -1494,6 +1566,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"zkeyVerifyR1csFiles", NULL, js_zkey_verify_r1cs_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauNewFile", NULL, js_ptau_new_file, NULL, NULL, NULL, napi_default, NULL},
       {"ptauContributeFiles", NULL, js_ptau_contribute_files, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauBeaconFiles", NULL, js_ptau_beacon_files, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyBeaconFiles", NULL, js_zkey_beacon_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauVerifyFile", NULL, js_ptau_verify_file, NULL, NULL, NULL, napi_default, NULL},
       {"ptauExportChallengeFiles", NULL, js_ptau_export_challenge_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauChallengeContributeFiles", NULL, js_ptau_challenge_contribute_files, NULL, NULL, NULL, napi_default, NULL},

@@ -16,6 +16,13 @@
 // these files, nor this one snarkjs's.
 // And of `snarkjs zkey contribute <old.zkey> <new.zkey> [--name=..] [-e=..]` (alias `zkc`): prints the contribution hash
 // as snarkjs does.  -e: THIS CLI's derivation of the secret from the text (index.js secretFromEntropy), not snarkjs's.
+// And of the two commands that close a ceremony: `snarkjs powersoftau beacon <old.ptau> <new.ptau> <beaconHash(hex)>
+// <numIterationsExp> [--name=..]` (alias `ptb`) and `snarkjs zkey beacon <old.zkey> <new.zkey> <beaconHash(hex)>
+// <numIterationsExp> [--name=..]` (alias `zkb`): a last contribution whose secret anyone recomputes from the beacon hash
+// (1 to 255 bytes) by 2^numIterationsExp SHA-256 applications (10 to 63); both print the contribution hash.  A hex string
+// of odd length or with other characters, or a missing argument, prints the usage and exits 2; a value out of range
+// prints "[ERROR] snarkJS: <text>" and exits 1, nothing is written.  The derivation of the secret from the beacon is THIS
+// LIBRARY'S, as the -e rule is: a beacon made by snarkjs fails `verify` here, and one made here fails snarkjs's.
 // And of the phase-2 file exchange: `snarkjs zkey export bellman <circuit.zkey> <circuit.mpcparams>` (alias `zkeb`),
 // `snarkjs zkey bellman contribute bn128 <challenge> <response> [-e=..]` (alias `zkbc`: prints the contribution hash; -e
 // by the rule of `zkey contribute`, so the same text gives the same contribution through either route) and `snarkjs zkey
@@ -106,6 +113,22 @@ async function main(argv) {
     if (pos.length < 2) { console.error("usage: cli.js nzcp program <example|live> <file>"); process.exit(2); }
     const { nzcp } = require("./index.js");
     await nzcp.witnessProgram(pos[0], pos[1]);
+    return;
+  }
+  const ptb = (a[0] === "powersoftau" && a[1] === "beacon") || a[0] === "ptb";
+  if (ptb || (a[0] === "zkey" && a[1] === "beacon") || a[0] === "zkb") {
+    const rest = a.slice(a[0] === "ptb" || a[0] === "zkb" ? 1 : 2);
+    const name = rest.map((x) => (x.startsWith("--name=") ? x.slice(7) : x.startsWith("-n=") ? x.slice(3) : undefined)).find((x) => x !== undefined);
+    const pos = rest.filter((x) => !x.startsWith("-"));
+    const hex = pos.length >= 3 && /^0x/i.test(pos[2]) ? pos[2].slice(2) : pos[2];
+    if (pos.length < 4 || hex.length % 2 !== 0 || !/^[0-9a-fA-F]*$/.test(hex) || !/^\d{1,9}$/.test(pos[3])) {
+      console.error(ptb ? "usage: cli.js powersoftau beacon <old_powersoftau.ptau> <new_powersoftau.ptau> <beaconHash(hex)> <numIterationsExp> [--name=..]"
+        : "usage: cli.js zkey beacon <circuit_old.zkey> <circuit_new.zkey> <beaconHash(hex)> <numIterationsExp> [--name=..]");
+      process.exit(2);
+    }
+    const { powersOfTau, zKey, formatHash } = require("./index.js");
+    const hash = await (ptb ? powersOfTau : zKey).beacon(pos[0], pos[1], name, hex, parseInt(pos[3], 10));
+    console.log(`[INFO]  snarkJS: Contribution Hash: \n${formatHash(hash)}`);
     return;
   }
   if ((a[0] === "zkey" && a[1] === "export" && a[2] === "bellman") || a[0] === "zkeb") {

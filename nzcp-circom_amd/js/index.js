@@ -310,6 +310,15 @@ const powersOfTau = {
     const secret = entropy === undefined || entropy === null || entropy === "" ? null : ptauSecretFromEntropy(entropy);
     return native().ptauContributeFiles(String(oldPtauName), String(newPtauName), name ? String(name) : null, secret, opts.device | 0);
   },
+  // snarkjs: powersOfTau.beacon(oldPtauFilename, newPTauFilename, name, beaconHashStr, numIterationsExp[, logger]) ->
+  // the 64-byte contribution hash / CLI `powersoftau beacon` (alias `ptb`).  beaconHashStr: hex (or a Buffer), 1 to 255
+  // bytes; numIterationsExp: 10 to 63.  The secret scalars come from the beacon by THIS LIBRARY'S rule (g16_beacon_scalars),
+  // not snarkjs's: `verify` here recomputes them, snarkjs's would not find them.
+  async beacon(oldPtauName, newPtauName, name, beaconHash, numIterationsExp, opts = {}) {
+    if (typeof opts !== "object" || opts === null || typeof opts.debug === "function") opts = {};
+    return native().ptauBeaconFiles(String(oldPtauName), String(newPtauName), name ? String(name) : null, beaconBytes(beaconHash),
+      beaconExp(numIterationsExp), opts.device | 0);
+  },
   // snarkjs: powersOfTau.verify(tauFilename[, logger]) -> boolean / CLI `powersoftau verify` (alias `ptv`).
   // opts.reason = true returns {ok, reason} instead.
   async verify(ptauName, opts = {}) {
@@ -342,8 +351,22 @@ const powersOfTau = {
     return native().ptauImportResponseFiles(String(oldPtauName), String(responseName), String(newPtauName), name ? String(name) : null, opts.device | 0);
   },
 };
+// a beacon hash as snarkjs takes it (misc.js hex2ByteArray: hex digits, "0x" allowed), checked; a Buffer passes as it is
+function beaconBytes(h) {
+  if (Buffer.isBuffer(h) || h instanceof Uint8Array) return Buffer.from(h);
+  let s = String(h);
+  if (/^0x/i.test(s)) s = s.slice(2);
+  if (s.length % 2 !== 0 || !/^[0-9a-fA-F]*$/.test(s)) throw new Error("beacon: the beacon hash must be a hex string of whole bytes");
+  return Buffer.from(s, "hex");
+}
+function beaconExp(e) {
+  const n = Number(e);
+  if (!Number.isInteger(n) || n < 0 || n > 0xffffffff) throw new Error("beacon: numIterationsExp must be between 10 and 63");
+  return n;
+}
 // tau | alpha | beta | s_tau | s_alpha | s_beta from a text: h_j = Blake2b-512(text | byte j), j = 0, 1, 2; the first
-// 32 bytes of h_j (little-endian, reduced mod r, 0 becomes 1) are key j, the last 32 bytes s_j (g16_ptau_secret_from_text)
+// 32 bytes of h_j (little-endian, reduced mod r, 0 becomes 1) are key j, the last 32 bytes s_j (g16_ptau_secret_from_text).
+// This library's rule, not snarkjs's -- as is the rule that turns a beacon hash into scalars (g16_beacon_scalars).
 function ptauSecretFromEntropy(entropy) {
   const out = Buffer.alloc(192);
   for (let j = 0; j < 3; j++) {
@@ -361,7 +384,8 @@ function ptauSecretFromEntropy(entropy) {
 // snarkjs: zKey.contribute(oldZkeyName, newZKeyName, name, entropy[, logger]) -> the 64-byte contribution hash.
 // entropy: a string (or Buffer), hashed with Blake2b-512 into the two secret scalars d | s -- each 32-byte half, read
 // little-endian, reduced mod r (0 becomes 1): THIS LIBRARY'S derivation, not snarkjs's (which seeds a ChaCha stream),
-// so the same text gives the same key here and another one there.  Absent: the OS CSPRNG.
+// so the same text gives the same key here and another one there.  Absent: the OS CSPRNG.  (A beacon's d | s come from
+// g16_beacon_scalars, this library's rule likewise: see beacon() below.)
 function secretFromEntropy(entropy) {
   const h = require("crypto").createHash("blake2b512").update(entropy).digest();
   const out = Buffer.alloc(64);
@@ -376,6 +400,13 @@ async function contribute(oldZkeyName, newZkeyName, name, entropy, opts = {}) {
   if (opts && typeof opts.debug === "function") opts = {};
   const secret = entropy === undefined || entropy === null || entropy === "" ? null : secretFromEntropy(entropy);
   return native().zkeyContributeFiles(String(oldZkeyName), String(newZkeyName), name ? String(name) : null, secret, opts.device | 0);
+}
+// snarkjs: zKey.beacon(zkeyNameOld, zkeyNameNew, name, beaconHashStr, numIterationsExp[, logger]) -> the 64-byte
+// contribution hash / CLI `zkey beacon` (alias `zkb`).  Arguments and the rule as in powersOfTau.beacon.
+async function beacon(oldZkeyName, newZkeyName, name, beaconHash, numIterationsExp, opts = {}) {
+  if (typeof opts !== "object" || opts === null || typeof opts.debug === "function") opts = {};
+  return native().zkeyBeaconFiles(String(oldZkeyName), String(newZkeyName), name ? String(name) : null, beaconBytes(beaconHash),
+    beaconExp(numIterationsExp), opts.device | 0);
 }
 // The MPCParams file exchange (g16_prover.h: g16_zkey_export_bellman and the two entries after it).
 // snarkjs: zKey.exportBellman(zkeyName, mpcparamsName[, logger]).
@@ -612,4 +643,4 @@ plonk.fullProveBatch = async function fullProveBatch(inputs, programName, zkey, 
   return fullProveBatchNative(true, inputs, programName, zkey, opts, b ? Buffer.concat(inputs.map(() => b)) : null);
 };
 
-module.exports = { groth16, plonk, powersOfTau, wtns, nzcp, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, exportBellman, bellmanContribute, importBellman, verifyFromInit, verifyFromR1cs }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
+module.exports = { groth16, plonk, powersOfTau, wtns, nzcp, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, beacon, exportBellman, bellmanContribute, importBellman, verifyFromInit, verifyFromR1cs }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
