@@ -360,8 +360,9 @@ int g16_plonk_setup_files(const char* r1cs_path, const char* ptau_path, const ch
  * taken from each section's length) give every point section, as sums of the R1CS coefficients times the ceremony's
  * points on `device` (there is no CPU path: G16_E_NOGPU).  Only blocks L (13-15) and L + 1 (12) are uploaded, 2^L the
  * smallest domain with 2^L >= m + p + 1.  The key is a fresh _0000 key: gamma = delta = 1 and section 10 (the
- * contribution hash, csHash) is 64 zero bytes and no contributions.  Correct, but NOT safe to deploy until a phase-2
- * contribution changes delta (`zkey contribute`: g16_zkey_contribute below).
+ * circuit hash, csHash) is 64 zero bytes and no contributions -- the LEGACY form, kept because keys of this entry are
+ * compared byte for byte; g16_zkey_new below writes the same key with the real csHash.  Correct, but NOT safe to deploy
+ * until a phase-2 contribution changes delta (`zkey contribute`: g16_zkey_contribute below).
  * Every input is checked before the device is touched: the r1cs as g16_r1cs_setup reads it; "Powers of tau is not
  * prepared." (no section 12); "ptau: Invalid File format" (a section that is not whole blocks or has more than the
  * power allows); "circuit too big for this power of tau ceremony. M > 2**P" when block L or L + 1 is missing. */
@@ -369,6 +370,37 @@ int g16_groth16_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* 
                            uint8_t** zkey, size_t* zkey_len);
 /* the same from / to files: the inputs are mapped read-only and the key is written in chunks (ceremony files are GBs) */
 int g16_groth16_setup_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device);
+/* `snarkjs zkey new c.r1cs pot.ptau c_0000.zkey` WITH the circuit hash: the key of g16_groth16_setup_ptau, byte for byte
+ * in sections 1-9 and in section order, and section 10 = csHash (64) | u32 0.  snarkjs 0.4.12 zkey_new.js, as far as it
+ * can be restated without the package:
+ *   csHash = Blake2b-512( alpha1 | beta1 | beta2 | gamma2 | delta1 | delta2
+ *                         | u32be p+1 | IC | u32be N-1 | H | u32be n-p-1 | L | u32be n | A | u32be n | B1 | u32be n | B2 )
+ * every point uncompressed big-endian standard form: the MPCParams image of the fresh key (g16_zkey_export_bellman
+ * below) up to its csHash field.  H is taken from section 2 of the ceremony file, not from section 9 of the key:
+ * H_k = P_(k+N) - P_k, k < N - 1, P_j = point j of section 2 (snarkjs hashHPoints), a batched affine subtraction on
+ * `device` (csrc/zkey_cshash.hip); the other runs go through the conversions of the export; every chunk is hashed on the
+ * calling thread as it comes down.  g16_zkey_export_bellman derives the same H from section 9 by its basis change, so
+ * Blake2b-512 of an exported initial key's image up to csHash IS this hash: two device routes with no code in common.
+ * cs_hash (optional) receives the 64 bytes.  With this hash a ceremony's transcripts are bound to the circuit and to the
+ * phase-1 file: every contribution, beacon, export and import chains from and compares whatever section 10 holds.
+ * NOT CLAIMED: that the value is the one snarkjs computes for the same inputs (the package is not at hand).
+ * Checked before the device is touched: everything g16_groth16_setup_ptau checks, with its texts and first (the ptau
+ * must be prepared; "circuit too big for this power of tau ceremony..."); a domain above 2^24: G16_E_ARG; section 2 of
+ * the ptau present with at least 2N - 1 points, each with coordinates below q and on the curve, else "ptau: Invalid
+ * File format".  No CPU path: G16_E_NOGPU. */
+int g16_zkey_new(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len, int device, uint8_t** zkey,
+                 size_t* zkey_len, uint8_t cs_hash[64] /* or NULL */);
+int g16_zkey_new_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device,
+                       uint8_t cs_hash[64] /* or NULL */);
+/* The hash g16_zkey_new stores, for an INITIAL key that is already there: out <- csHash of `zkey` over `ptau` (prepared
+ * or not: only section 2 is read).  Defined for initial keys only: delta1 / delta2 other than the generators, or a
+ * section 10 with records, is G16_E_ARG "zkey cs hash: not an initial key".  The 64 bytes section 10 already holds are
+ * not read: this is how the owner of a legacy zero-hash key checks or upgrades it.  Checked before the device is
+ * touched: the key as g16_zkey_contribute reads it; the ptau's container, header and curve with the texts of
+ * g16_zkey_verify_from_init_ptau; a power below log2 N: G16_E_ARG "zkey new: the ptau is too small for this key"; section
+ * 2 as above.  No CPU path: G16_E_NOGPU. */
+int g16_zkey_cs_hash(const uint8_t* zkey, size_t zkey_len, const uint8_t* ptau, size_t ptau_len, int device, uint8_t out[64]);
+int g16_zkey_cs_hash_files(const char* zkey_path, const char* ptau_path, int device, uint8_t out[64]);
 /* `snarkjs powersoftau prepare phase2 in.ptau out.ptau` (alias `pt2`): the .ptau v1 image (g16_free) that holds
  * sections 1-7 of the input, byte for byte and in that order, then the sections 12-15 the setups above read, computed
  * on `device` (there is no CPU path: G16_E_NOGPU).  Section 12 comes from section 2, 13 / 14 / 15 from 3 / 4 / 5: block
@@ -584,9 +616,10 @@ int g16_ptau_secret_from_text(const char* text, uint8_t secret[192]);
  * container, the header, section sizes, a section 10 shorter than its records say or with trailing bytes, a point
  * coordinate >= q or a point off its curve).  A beacon record (type 1) in the input is carried and hashed like any other,
  * its params untouched.  `zkey beacon` is g16_zkey_beacon below.
- * NOT implemented: the csHash of `zkey new` (this library's _0000 keys hold 64 zero bytes there, the
- * chain is hashed from whatever section 10 holds), so `snarkjs zkey verify` rejects these keys: the file layout and the
- * proofs are snarkjs's, its ceremony verifier is not claimed.  The G2 derivation is NOT cross-checked against snarkjs. */
+ * The chain is hashed from whatever csHash section 10 holds: the circuit hash of g16_zkey_new above, or the 64 zero
+ * bytes of g16_groth16_setup_ptau's legacy keys (then nothing in the transcripts binds them to the circuit).  That the
+ * csHash built here equals snarkjs's own value is NOT claimed, so neither is `snarkjs zkey verify` of these keys: the
+ * file layout and the proofs are snarkjs's.  The G2 derivation is NOT cross-checked against snarkjs. */
 int g16_zkey_contribute(const uint8_t* zkey, size_t zkey_len, const char* name /* or NULL */,
                         const uint8_t secret[64] /* d | s, or NULL = OS CSPRNG */, int device,
                         uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]);
@@ -651,7 +684,12 @@ int g16_zkey_verify_from_init_ptau(const uint8_t* init, size_t init_len, const u
 int g16_zkey_verify_from_init_ptau_files(const char* init_path, const char* ptau_path, const char* zkey_path, int device,
                                          int* ok);
 /* `snarkjs zkey verify circuit.r1cs pot.ptau circuit.zkey`: g16_groth16_setup_ptau(r1cs, ptau) in memory (its errors and
- * texts; the ptau must be prepared; no temporary file), then g16_zkey_verify_from_init_ptau against that key. */
+ * texts; the ptau must be prepared; no temporary file), then g16_zkey_verify_from_init_ptau against that key.  Which
+ * csHash the in-memory initial key gets follows the key under test: 64 zero bytes there -- the legacy initial key, as
+ * before; anything else -- the real csHash of g16_zkey_new (one g16_zkey_cs_hash more on `device`).  Every input that
+ * was accepted or rejected before gets the same verdict and text; only keys that carry the true hash change, from
+ * rejected ("the circuit hash differs from the initial key's") to accepted.  g16_zkey_verify_from_init(_ptau) compare
+ * the two section 10s as they are. */
 int g16_zkey_verify_r1cs(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len, const uint8_t* zkey,
                          size_t zkey_len, int device, int* ok);
 int g16_zkey_verify_r1cs_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device, int* ok);
@@ -681,7 +719,8 @@ int g16_zkey_h_scalars(int device, const uint8_t* u, uint32_t log_n, uint8_t* rh
  * The transform runs on `device` (csrc/zkey_bellman.hip: L N/2 + N scalar products at N = 2^L; no CPU path: G16_E_NOGPU),
  * as do the conversions between the file form and the big-endian images (csrc/ptau_points.hip).  Domains up to 2^24.
  * NOT CLAIMED: an exchange with a snarkjs or bellman contributor.  The files are restated from snarkjs's description
- * without the package at hand, and csHash of this library's _0000 keys is 64 zero bytes.
+ * without the package at hand; csHash is carried as section 10 holds it (g16_zkey_new's circuit hash, or the 64 zero
+ * bytes of a legacy _0000 key), and its agreement with snarkjs's own value is not claimed either.
  *
  * `snarkjs zkey export bellman circuit.zkey circuit.mpcparams` (alias `zkeb`): the MPCParams image of a Groth16 key
  * (g16_free).  The checks of g16_zkey_contribute on the input, then the device.  A record's type and params are not
@@ -726,6 +765,15 @@ int g16_zkey_h_basis(int device, const uint8_t* points, uint32_t log_n, int inve
  * (ChaCha20 keyed with the first 32 bytes, x drawn as the Montgomery image, cofactor 2q - r; affine LE Montgomery). */
 int g16_blake2b512(const uint8_t* data, size_t len, uint8_t out[64]);
 int g16_zkey_hash_to_g2(const uint8_t transcript[64], uint8_t out[128] /* affine LE Montgomery */);
+/* TEST-ONLY layer entries of g16_zkey_new's circuit hash.
+ * The difference kernel alone: points = 2N - 1 affine LE Montgomery G1 points, N = 2^log_n (zero bytes = infinity; not
+ * checked); out = (N - 1) x 64 bytes, out[k] = the uncompressed big-endian image of points[k + N] - points[k] (infinity =
+ * 0x40 and zeros).  log_n in [0, 24]; log_n = 0 writes nothing and returns G16_OK.  G16_CSHASH_CHUNK / G16_CSHASH_LANES
+ * set the chunk (points) and the grid (threads) of the run.
+ * The streaming hasher (host only): Blake2b-512 of data fed in the parts the ascending offsets cuts[0 .. n_cuts) split
+ * it into (equal offsets, 0 and len give empty parts); G16_E_ARG for offsets that descend or pass len. */
+int g16_zkey_h_monomial(int device, const uint8_t* points, uint32_t log_n, uint8_t* out);
+int g16_blake2b512_parts(const uint8_t* data, size_t len, const size_t* cuts, size_t n_cuts, uint8_t out[64]);
 
 /* PLONK batch verifier on the device: [EXT] snarkjs 0.4.12 plonk_verify.js `plonk.verify(vk, publicSignals, proof)` for
  * many proofs against one key, one verdict per proof (transcript and scalar arithmetic on host threads, the twenty

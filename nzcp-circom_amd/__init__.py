@@ -92,7 +92,9 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_wtns_calc_check_text", "g16_wtns_calc_wtns", "g16_wtns_calc_info", "g16_wtns_calc_outputs",
            "g16_wtns_calc_input", "g16_wtns_calc_timings", "g16_wtns_calc_destroy", "g16_stage_inputs",
            "g16_fullprove_batch", "g16_plonk_fullprove_batch",
-           "g16_beacon_scalars", "g16_ptau_beacon", "g16_ptau_beacon_files", "g16_zkey_beacon", "g16_zkey_beacon_files"]
+           "g16_beacon_scalars", "g16_ptau_beacon", "g16_ptau_beacon_files", "g16_zkey_beacon", "g16_zkey_beacon_files",
+           "g16_zkey_new", "g16_zkey_new_files", "g16_zkey_cs_hash", "g16_zkey_cs_hash_files", "g16_zkey_h_monomial",
+           "g16_blake2b512_parts"]
 
 
 def load():
@@ -188,6 +190,12 @@ def load():
                                             C.POINTER(C.c_int)]
     lib.g16_zkey_import_bellman_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     lib.g16_zkey_h_basis.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p]
+    lib.g16_zkey_new.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
+    lib.g16_zkey_new_files.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
+    lib.g16_zkey_cs_hash.argtypes = [C.c_char_p, sz, C.c_char_p, sz, C.c_int, C.c_char_p]
+    lib.g16_zkey_cs_hash_files.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
+    lib.g16_zkey_h_monomial.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_char_p]
+    lib.g16_blake2b512_parts.argtypes = [C.c_char_p, sz, C.POINTER(sz), sz, C.c_char_p]
     lib.g16_ptau_new.argtypes = [C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
     lib.g16_ptau_new_file.argtypes = [C.c_uint32, C.c_char_p]
     lib.g16_ptau_contribute.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(sz), C.c_char_p]
@@ -1307,6 +1315,43 @@ def blake2b512(data):
     out = C.create_string_buffer(64)
     _check(load().g16_blake2b512(data, len(data), out))
     return out.raw
+
+
+def blake2b512_parts(data, cuts):
+    """TEST-ONLY layer entry: Blake2b-512 by the library's streaming hasher, `data` fed in the parts the ascending
+    offsets `cuts` split it into (host only)."""
+    out = C.create_string_buffer(64)
+    arr = (C.c_size_t * max(1, len(cuts)))(*cuts)
+    _check(load().g16_blake2b512_parts(data, len(data), arr, len(cuts), out))
+    return out.raw
+
+
+def zkey_new(r1cs, ptau, device=0):
+    """`snarkjs zkey new` with the circuit hash: .r1cs and prepared .ptau bytes -> (Groth16 .zkey bytes, 64-byte csHash).
+    The key is groth16_setup_ptau's except for the first 64 bytes of section 10, which hold the hash."""
+    z, zl = C.c_void_p(), C.c_size_t()
+    h = C.create_string_buffer(64)
+    _check(load().g16_zkey_new(r1cs, len(r1cs), ptau, len(ptau), device, C.byref(z), C.byref(zl), h))
+    return _take(z, zl), h.raw
+
+
+def zkey_cs_hash(zkey, ptau, device=0):
+    """The circuit hash zkey_new stores for this INITIAL key over this ceremony file (prepared or not): 64 bytes.  What
+    section 10 already holds is not read, so a legacy zero-hash key can be checked or upgraded."""
+    h = C.create_string_buffer(64)
+    _check(load().g16_zkey_cs_hash(zkey, len(zkey), ptau, len(ptau), device, h))
+    return h.raw
+
+
+def zkey_h_monomial(points, log_n, device=0):
+    """TEST-ONLY layer entry of the circuit hash: 2^(log_n + 1) - 1 file-form G1 points P -> the big-endian images of
+    P[k + N] - P[k], k < N - 1, N = 2^log_n (64 bytes each)."""
+    if len(points) != 64 * ((2 << log_n) - 1):
+        raise ValueError("zkey_h_monomial: 2^(log_n + 1) - 1 points of 64 bytes expected")
+    n = (1 << log_n) - 1
+    out = C.create_string_buffer(max(1, 64 * n))
+    _check(load().g16_zkey_h_monomial(device, points, log_n, out))
+    return out.raw[:64 * n]
 
 
 def zkey_hash_to_g2(transcript):

@@ -10,8 +10,15 @@
 // returns and before anything is freed.  What a stage needs beyond the buffers (tables, digits, a result word) stays
 // with its caller: a DeviceBuf each, declared AHEAD of the pipeline (device_job.h: the pipeline owns the streams),
 // written and read over stream() before and after run().
+// Two options, both off unless asked for (zkey_cshash.hip asks for both, ptau_points.hip's to-be stage for the sink):
+//   second(off)  every item has a partner `off` items further on in the host buffer: the upload side takes TWO copies
+//                per chunk, items [lo, lo + cnt) to the head of in[b] and [lo + off, lo + off + cnt) to its second half,
+//                which starts chunk * in_sz bytes in, whatever cnt is;
+//   a sink       run(.., sink): sink(lo, cnt) is called on the calling thread, chunk by chunk in order, once the copies
+//                down of that chunk have landed in the host buffer -- while the next chunk computes and copies.
 #pragma once
 #include <algorithm>
+#include <functional>
 
 #include "internal.h"
 
@@ -53,6 +60,7 @@ class ChunkPipeline : public DeviceJob {   // fail(): also for the caller's own 
     for (hipStream_t s : {xst_, cst_}) if (s) (void)hipStreamDestroy(s);
   }
   hipStream_t stream() const { return cst_; }   // the compute stream
+  void second(uint64_t off_items) { in2_off_ = off_items; }   // before open()
   // streams, events and buffers: n > 0 items of in_sz bytes, out_sz bytes out each and -- when out2_sz -- as many into out2
   bool open(uint64_t n, uint32_t chunk, size_t in_sz, size_t out_sz, size_t out2_sz) {
     n_ = n; chunk_ = chunk; in_sz_ = in_sz; out_sz_ = out_sz; out2_sz_ = out2_sz;
@@ -64,15 +72,21 @@ class ChunkPipeline : public DeviceJob {   // fail(): also for the caller's own 
     te_.assign(6 * nchunks_, nullptr);
     for (auto& e : te_) if (fail(hipEventCreate(&e))) return false;
     for (int b = 0; b < (nchunks_ > 1 ? 2 : 1); b++) {
-      if (fail(hipMalloc(&in_[b], (size_t)chunk * in_sz)) || fail(hipMalloc(&out_[b], (size_t)chunk * out_sz))) return false;
+      if (fail(hipMalloc(&in_[b], (size_t)chunk * in_sz * (in2_off_ ? 2 : 1))) || fail(hipMalloc(&out_[b], (size_t)chunk * out_sz))) return false;
       if (out2_sz && fail(hipMalloc(&out2_[b], (size_t)chunk * out2_sz))) return false;
     }
     return true;
   }
   // every chunk through launch(stream, d_in, d_out, d_out2, cnt, lo) (lo = the chunk's first item), in -> out, out2
-  template <class Launch> int run(const uint8_t* in, uint8_t* out, uint8_t* out2, ChunkStats* st, Launch launch) {
+  using Sink = std::function<void(uint64_t lo, uint32_t cnt)>;
+  template <class Launch>
+  int run(const uint8_t* in, uint8_t* out, uint8_t* out2, ChunkStats* st, Launch launch, const Sink* sink = nullptr) {
     bool ok = upload(in, 0);
-    for (uint64_t c = 0; ok && c < nchunks_; c++) ok = (c + 1 == nchunks_ || upload(in, c + 1)) && chunk(c, out, out2, launch);
+    for (uint64_t c = 0; ok && c < nchunks_; c++) {
+      ok = (c + 1 == nchunks_ || upload(in, c + 1)) && chunk(c, out, out2, launch);
+      if (ok && sink && c >= 1) ok = landed(c - 1, *sink);
+    }
+    if (ok && sink) ok = landed(nchunks_ - 1, *sink);
     if (ok) ok = !fail(hipStreamSynchronize(xst_)) && !fail(hipStreamSynchronize(cst_));
     if (!ok) { drain(); return rc; }
     for (uint64_t c = 0; st && c < nchunks_; c++) {
@@ -91,6 +105,8 @@ class ChunkPipeline : public DeviceJob {   // fail(): also for the caller's own 
     const uint64_t lo = c * chunk_, cnt = std::min<uint64_t>(chunk_, n_ - lo);
     return !(c >= 2 && fail(hipStreamWaitEvent(xst_, ev_k_[b], 0))) && !fail(hipEventRecord(te_[6 * c + 2], xst_)) &&
            !fail(hipMemcpyAsync(in_[b], in + lo * in_sz_, cnt * in_sz_, hipMemcpyHostToDevice, xst_)) &&
+           !(in2_off_ && fail(hipMemcpyAsync(in_[b] + (size_t)chunk_ * in_sz_, in + (lo + in2_off_) * in_sz_, cnt * in_sz_,
+                                             hipMemcpyHostToDevice, xst_))) &&
            !fail(hipEventRecord(te_[6 * c + 3], xst_)) && !fail(hipEventRecord(ev_up_[b], xst_));
   }
   template <class Launch> bool chunk(uint64_t c, uint8_t* out, uint8_t* out2, Launch& launch) {
@@ -107,7 +123,15 @@ class ChunkPipeline : public DeviceJob {   // fail(): also for the caller's own 
     return !fail(hipEventRecord(te_[6 * c + 5], xst_)) && !fail(hipEventRecord(ev_down_[b], xst_));
   }
 
-  uint64_t n_ = 0, nchunks_ = 0;
+  // chunk c's copies down have landed (ev_down[c & 1] is recorded again only by chunk c + 2, which is not enqueued yet)
+  bool landed(uint64_t c, const Sink& sink) {
+    if (fail(hipEventSynchronize(ev_down_[c & 1]))) return false;
+    const uint64_t lo = c * chunk_;
+    sink(lo, (uint32_t)std::min<uint64_t>(chunk_, n_ - lo));
+    return true;
+  }
+
+  uint64_t n_ = 0, nchunks_ = 0, in2_off_ = 0;
   uint32_t chunk_ = 0;
   size_t in_sz_ = 0, out_sz_ = 0, out2_sz_ = 0;
   hipStream_t cst_ = nullptr, xst_ = nullptr;   // compute, copies

@@ -115,6 +115,7 @@ struct ChunkStats {
   float xfer_ms = 0.f;   // device time of the copies in and out
   uint64_t points = 0;
 };
+using ChunkSink = std::function<void(const uint8_t* p, size_t bytes)>;   // a chunk of a route's output, on the host
 
 // ---------------------------------------------------------------- zkey contribute (zkey_scale.hip)
 // out[i] = [k] in[i]: n affine Montgomery G1 points (host, file layout; infinity = zero bytes in and out) times ONE
@@ -150,6 +151,13 @@ int zkey_h_basis(int device, const uint8_t* in, int log_n, bool inverse, uint8_t
 // scalar vector, for step 5 of zkey verify
 int zkey_h_rho(int device, const uint8_t* u, int log_n, uint8_t* rho_out);
 
+// ---------------------------------------------------------------- the monomial H points of zkey new (zkey_cshash.hip)
+// points = 2N - 1 affine Montgomery G1 points in file layout (host), N = 2^log_n, P_j = [tau^j] G of a ceremony's
+// section 2: out[k] = the uncompressed big-endian standard-form image of P_(k+N) - P_k, k < N - 1 (infinity = 0x40 and
+// zeros), in chunks (G16_CSHASH_CHUNK / G16_CSHASH_LANES); sink as in ptau_points_to_be.  log_n in [0, 24]; log_n = 0
+// writes nothing.  No CPU path (G16_E_NOGPU).
+int zkey_h_monomial(int device, const uint8_t* points, int log_n, uint8_t* out, ChunkStats* st, const ChunkSink* sink = nullptr);
+
 // ---------------------------------------------------------------- powersoftau contribute (ptau_scale.hip)
 // out[i] = [c k^(first + i)] in[i]: n affine Montgomery points of G1 / G2 (host, file layout; infinity = zero bytes in
 // and out), c and k standard form in [1, r), first + n <= 2^31; every lane forms its scalar on the device.  out_be
@@ -168,8 +176,11 @@ int ptau_scale_g2(int device, const uint8_t* in, uint64_t n, const Fr& c_std, co
 // off the curve, no root), else -1; the outputs of a section with a bad point are not to be used.  out_be (optional):
 // the uncompressed image of every decompressed point, from the same pass.  No CPU path (G16_E_NOGPU).
 int ptau_points_from_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, ChunkStats* st);
-// the inverse of from_be: file form -> uncompressed big-endian standard form (every file image has one)
-int ptau_points_to_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st);
+// the inverse of from_be: file form -> uncompressed big-endian standard form (every file image has one).  sink
+// (optional): called on the calling thread with every chunk of `out`, in order, as soon as its copy down has landed --
+// while the next chunk is computed and copied (the circuit hash is taken this way: zkey_cshash.hip)
+int ptau_points_to_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st,
+                      const ChunkSink* sink = nullptr);
 int ptau_points_compress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st);
 int ptau_points_decompress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* out_be, int64_t* first_bad,
                            ChunkStats* st);

@@ -1,6 +1,8 @@
 // The .ptau reader of the routes that take a ceremony file (PLONK setup, Groth16 setup, prepare phase2, and the ptau leg
 // of zkey verify, which opens with ptau_open and reads section 2 alone).
 #pragma once
+#include <functional>
+
 #include "binfile.h"
 
 namespace g16 {
@@ -20,5 +22,11 @@ int ptau_bad(const char* why);   // sets "ptau: <why>" -> G16_E_FORMAT
 int ptau_open(const uint8_t* ptau, size_t ptau_len, PtauView& v, bool tau_sections);
 // ptau_open and the prepared-section block layout (sections 12-15, v.blocks)
 int ptau_open_prepared(const uint8_t* ptau, size_t ptau_len, PtauView& v);
+
+// g16_groth16_setup_ptau (setup_groth16.cpp) with a caller's check of the opened ptau for the key's domain 2^log_n, run
+// after the setup's own checks and before the device is asked for (`zkey new` with the circuit hash reads section 2 too)
+using SetupPtauCheck = std::function<int(const PtauView& pv, int log_n)>;
+int groth16_setup_ptau_checked(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len, int device,
+                               uint8_t** zkey, size_t* zkey_len, const SetupPtauCheck* before_device);
 
 }  // namespace g16

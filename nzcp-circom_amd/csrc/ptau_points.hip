@@ -325,7 +325,8 @@ __global__ __launch_bounds__(kBlock) void fq_sqrt_kernel(const typename FC::T* _
 // (out_sz bytes each) and -- when out2 -- out2 (out2_sz each); *first_bad = the device word after the last chunk, or -1
 template <class Launch>
 int points_device(const char* what, int device, const uint8_t* in, size_t in_sz, uint64_t n, uint8_t* out, size_t out_sz,
-                  uint8_t* out2, size_t out2_sz, int64_t* first_bad, ChunkStats* st, Launch launch) {
+                  uint8_t* out2, size_t out2_sz, int64_t* first_bad, ChunkStats* st, Launch launch,
+                  const ChunkSink* sink = nullptr) {
   if (first_bad) *first_bad = -1;
   if (st) *st = ChunkStats{};
   if (n >= ((uint64_t)1 << 31)) { set_error(std::string(what) + ": more than 2^31 items"); return G16_E_ARG; }
@@ -340,9 +341,10 @@ int points_device(const char* what, int device, const uint8_t* in, size_t in_sz,
   if (!pipe.open(n, plan.chunk, in_sz, out_sz, out2 ? out2_sz : 0) || pipe.fail(bad.alloc(1)) ||
       pipe.fail(hipMemcpyAsync(bad.p, &h_bad, sizeof(uint32_t), hipMemcpyHostToDevice, pipe.stream())))
     return pipe.rc;
+  const ChunkPipeline::Sink landed = [&](uint64_t lo, uint32_t cnt) { (*sink)(out + lo * out_sz, (size_t)cnt * out_sz); };
   const int rc = pipe.run(in, out, out2, st, [&](hipStream_t s, const uint8_t* i, uint8_t* o, uint8_t* o2, uint32_t cnt, uint64_t lo) {
     launch(plan.grid(cnt), plan.block, s, i, o, o2, cnt, (uint32_t)lo, bad.p);
-  });
+  }, sink ? &landed : nullptr);
   if (rc) return rc;
   if (pipe.fail(hipMemcpy(&h_bad, bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost))) {
     if (st) *st = ChunkStats{};
@@ -361,11 +363,12 @@ int from_be(int device, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* fi
                          ptau_from_be_kernel<FC><<<grid, block, 0, s>>>((const uint32_t*)i, (Affine<FC>*)o, cnt, base, bad);
                        });
 }
-template <class FC> int to_be(int device, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st) {
+template <class FC> int to_be(int device, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st, const ChunkSink* sink) {
   constexpr size_t PSZ = sizeof(Affine<FC>);
   return points_device("ptau points to-be", device, in, PSZ, n, out, PSZ, nullptr, 0, nullptr, st,
                        [](uint32_t grid, uint32_t block, hipStream_t s, const uint8_t* i, uint8_t* o, uint8_t*, uint32_t cnt, uint32_t,
-                          uint32_t*) { ptau_to_be_kernel<FC><<<grid, block, 0, s>>>((const Affine<FC>*)i, (uint32_t*)o, cnt); });
+                          uint32_t*) { ptau_to_be_kernel<FC><<<grid, block, 0, s>>>((const Affine<FC>*)i, (uint32_t*)o, cnt); },
+                       sink);
 }
 template <class FC> int compress(int device, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st) {
   constexpr size_t PSZ = sizeof(Affine<FC>);
@@ -396,8 +399,8 @@ template <class FC> int sqrt_batch(int device, const uint8_t* in, uint64_t n, ui
 int ptau_points_from_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, int64_t* first_bad, ChunkStats* st) {
   return g2 ? from_be<Fq2Ops>(device, in, n, out, first_bad, st) : from_be<FqOps>(device, in, n, out, first_bad, st);
 }
-int ptau_points_to_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st) {
-  return g2 ? to_be<Fq2Ops>(device, in, n, out, st) : to_be<FqOps>(device, in, n, out, st);
+int ptau_points_to_be(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st, const ChunkSink* sink) {
+  return g2 ? to_be<Fq2Ops>(device, in, n, out, st, sink) : to_be<FqOps>(device, in, n, out, st, sink);
 }
 int ptau_points_compress(int device, bool g2, const uint8_t* in, uint64_t n, uint8_t* out, ChunkStats* st) {
   return g2 ? compress<Fq2Ops>(device, in, n, out, st) : compress<FqOps>(device, in, n, out, st);

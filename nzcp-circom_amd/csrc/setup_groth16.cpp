@@ -201,9 +201,10 @@ extern "C" int g16_r1cs_setup_trapdoor(const uint8_t* r1cs, size_t r1cs_len, con
 // gamma = delta = 1 (a fresh _0000 key), section 10 as setup_core writes it.  The sums run on the device
 // (setup_ptau.hip); the key for a ptau of a known (tau, alpha, beta) is byte for byte setup_core's with
 // (tau, alpha, beta, 1, 1).
-extern "C" int g16_groth16_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len,
-                                      int device, uint8_t** zkey, size_t* zkey_len) {
-  if (!r1cs || !ptau || !zkey || !zkey_len) { set_error("NULL argument"); return G16_E_ARG; }
+// before_device (optional; zkey_cshash_host.cpp): a caller's own checks of the ptau for this domain, run after every
+// check of the setup and before the device is asked for
+int g16::groth16_setup_ptau_checked(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len, int device,
+                                    uint8_t** zkey, size_t* zkey_len, const SetupPtauCheck* before_device) {
   return no_bad_alloc("groth16 setup", [&]() -> int {
     // every input is checked before the device is touched
     Circuit c;
@@ -220,6 +221,7 @@ extern "C" int g16_groth16_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, cons
                 std::to_string(pv.power));
       return G16_E_FORMAT;
     }
+    if (before_device && (rc = (*before_device)(pv, L))) return rc;
     if ((rc = require_hip_device("groth16 setup", device))) return rc;
     const size_t N = (size_t)1 << L;
     const size_t blkL = N - 1, blkL1 = 2 * N - 1;   // first point of block L / L + 1
@@ -315,6 +317,12 @@ extern "C" int g16_groth16_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, cons
     im.z.give(zkey, zkey_len);
     return G16_OK;
   });
+}
+
+extern "C" int g16_groth16_setup_ptau(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len,
+                                      int device, uint8_t** zkey, size_t* zkey_len) {
+  if (!r1cs || !ptau || !zkey || !zkey_len) { set_error("NULL argument"); return G16_E_ARG; }
+  return groth16_setup_ptau_checked(r1cs, r1cs_len, ptau, ptau_len, device, zkey, zkey_len, nullptr);
 }
 
 extern "C" int g16_groth16_setup_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device) {

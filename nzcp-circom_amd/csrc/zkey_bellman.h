@@ -27,4 +27,9 @@ struct MpView {
 // clean 0x40 or none, every coordinate below q.  G16_E_FORMAT "mpcparams: Invalid File format".
 int mp_open(const uint8_t* p, size_t len, MpView& m);
 
+// The image's head from a key (the export's own; the circuit hash of `zkey new` is taken over it, zkey_cshash_host.cpp):
+// the six header points of section 2, and the six counts p + 1, N - 1, n - p - 1, n, n, n.
+void mp_header_image(const uint8_t* sec2, uint8_t out[kMpHeader]);
+void mp_key_counts(uint32_t nVars, uint32_t nPublic, uint32_t N, uint32_t cnt[kMpRuns]);
+
 }  // namespace g16

@@ -15,7 +15,8 @@
 //               contribution is honest is `zkey verify`'s question, as in snarkjs.
 // Checks that need no point arithmetic run before the device is asked for; there is no CPU path for the rest.
 // NOT claimed: an exchange with a snarkjs or bellman contributor (the files are restated without the package at hand,
-// and csHash of this library's _0000 keys is 64 zero bytes).
+// and csHash -- carried as section 10 holds it: g16_zkey_new's circuit hash, zkey_cshash_host.cpp, or the 64 zero bytes
+// of a legacy _0000 key -- is not claimed to equal snarkjs's value).
 #include "zkey_bellman.h"
 
 #include <chrono>
@@ -320,6 +321,13 @@ int import_core(const uint8_t* old, size_t old_len, const uint8_t* resp, size_t 
 }
 
 }  // namespace
+
+void mp_header_image(const uint8_t* sec2, uint8_t out[kMpHeader]) { header_image(sec2, out); }
+void mp_key_counts(uint32_t nVars, uint32_t nPublic, uint32_t N, uint32_t cnt[kMpRuns]) {
+  KeyView k;
+  k.nVars = nVars; k.nPublic = nPublic; k.N = N;
+  key_counts(k, cnt);
+}
 
 int mp_open(const uint8_t* p, size_t len, MpView& m) {
   m = MpView{};

@@ -12,21 +12,25 @@
 //               (beacon.h, mpc_beacon_scalars): a record of type 1 that states both; verify recomputes them for every
 //               such record.  The derivation is this library's, as the `-e` rule is: a snarkjs-made beacon record
 //               fails that check here.
-// NOT here, on purpose: the real csHash of `zkey new` (section 10 of this library's _0000 keys holds 64 zero bytes, and
-// the chain is hashed from whatever section 10 holds).
-// Because csHash is not snarkjs's, `snarkjs zkey verify` rejects these keys: the file LAYOUT and the proofs are
-// compatible, snarkjs's ceremony verifier is not claimed.
+// The csHash of `zkey new` is built in zkey_cshash_host.cpp (g16_zkey_new; the legacy keys of g16_groth16_setup_ptau
+// keep 64 zero bytes); here the chain is hashed from, and compared with, whatever section 10 holds.  The r1cs form of
+// verify sets its in-memory initial key up with the real csHash when the key under test carries one.  Blake2b-512 has a
+// streaming form (Blake2b512) for that hash, whose feed arrives chunk by chunk from the device.
+// That the csHash equals snarkjs's own value is NOT claimed (restated without the package), so neither is `snarkjs zkey
+// verify` of these keys: the file LAYOUT and the proofs are compatible.
 #include "zkey_mpc.h"
 
 #include <fcntl.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 
 #include "beacon.h"
 #include "internal.h"
 #include "mapped_file.h"
 #include "ptau.h"
+#include "zkey_cshash.h"
 
 namespace g16 {
 
@@ -70,19 +74,41 @@ void b2_compress(uint64_t h[8], const uint8_t block[128], uint64_t t, bool last)
 }
 }  // namespace
 
-void blake2b512(const uint8_t* data, size_t len, uint8_t out[64]) {
-  uint64_t h[8];
-  for (int i = 0; i < 8; i++) h[i] = kB2Iv[i];
-  h[0] ^= 0x01010000ull ^ 64;   // digest length 64, no key, fanout = depth = 1
-  size_t off = 0;
-  while (len - off > 128) {
-    b2_compress(h, data + off, (uint64_t)off + 128, false);
-    off += 128;
+// The streaming form.  A full block is compressed only once a byte beyond it has arrived: the block that turns out to
+// be the last must carry the final flag, also when the total length is a non-zero multiple of 128.
+Blake2b512::Blake2b512() {
+  for (int i = 0; i < 8; i++) h_[i] = kB2Iv[i];
+  h_[0] ^= 0x01010000ull ^ 64;   // digest length 64, no key, fanout = depth = 1
+}
+void Blake2b512::update(const uint8_t* data, size_t len) {
+  if (!len) return;
+  if (have_) {   // top up the held-back bytes first
+    const size_t take = std::min(len, (size_t)128 - have_);
+    memcpy(buf_ + have_, data, take);
+    have_ += take; data += take; len -= take;
+    if (!len) return;   // (a full buffer stays: it may be the last block)
+    t_ += 128;
+    b2_compress(h_, buf_, t_, false);
+    have_ = 0;
   }
-  uint8_t block[128] = {0};
-  if (len - off) memcpy(block, data + off, len - off);
-  b2_compress(h, block, (uint64_t)len, true);
-  memcpy(out, h, 64);   // little-endian words
+  while (len > 128) {   // whole blocks where they lie, all but a last full one
+    t_ += 128;
+    b2_compress(h_, data, t_, false);
+    data += 128; len -= 128;
+  }
+  memcpy(buf_, data, len);
+  have_ = len;
+}
+void Blake2b512::final(uint8_t out[64]) {
+  memset(buf_ + have_, 0, 128 - have_);
+  b2_compress(h_, buf_, t_ + have_, true);
+  memcpy(out, h_, 64);   // little-endian words
+}
+
+void blake2b512(const uint8_t* data, size_t len, uint8_t out[64]) {
+  Blake2b512 b;
+  b.update(data, len);
+  b.final(out);
 }
 
 // ------------------------------------------------------------------ field and curve helpers
@@ -763,6 +789,24 @@ extern "C" int g16_blake2b512(const uint8_t* data, size_t len, uint8_t out[64]) 
   return G16_OK;
 }
 
+extern "C" int g16_blake2b512_parts(const uint8_t* data, size_t len, const size_t* cuts, size_t n_cuts, uint8_t out[64]) {
+  if ((!data && len) || (!cuts && n_cuts) || !out) { set_error("NULL argument"); return G16_E_ARG; }
+  size_t at = 0;
+  for (size_t i = 0; i < n_cuts; i++) {
+    if (cuts[i] < at || cuts[i] > len) { set_error("blake2b512 parts: the cuts must ascend and lie within the data"); return G16_E_ARG; }
+    at = cuts[i];
+  }
+  Blake2b512 b;
+  at = 0;
+  for (size_t i = 0; i < n_cuts; i++) {
+    b.update(data + at, cuts[i] - at);
+    at = cuts[i];
+  }
+  b.update(data + at, len - at);
+  b.final(out);
+  return G16_OK;
+}
+
 extern "C" int g16_zkey_hash_to_g2(const uint8_t transcript[64], uint8_t out[128]) {
   if (!transcript || !out) { set_error("NULL argument"); return G16_E_ARG; }
   G2Affine p;
@@ -850,9 +894,29 @@ extern "C" int g16_zkey_verify_r1cs(const uint8_t* r1cs, size_t r1cs_len, const 
   uint8_t* init = nullptr;
   size_t init_len = 0;
   if (const int rc = g16_groth16_setup_ptau(r1cs, r1cs_len, ptau, ptau_len, device, &init, &init_len)) return rc;
-  const int rc = g16_zkey_verify_from_init_ptau(init, init_len, ptau, ptau_len, zkey, zkey_len, device, ok);
-  free(init);
-  return rc;
+  struct Free { uint8_t* p; ~Free() { free(p); } } guard{init};
+  // A key that carries a circuit hash (anything but the legacy 64 zero bytes) is held against the initial key WITH its
+  // real csHash.  Only where that can matter: the key parses and has the initial key's domain -- every other input
+  // gets its error or verdict from the route below before section 10 is compared, exactly as without this step; and
+  // with the same domain the hash's checks of the ptau are the ones the route below makes at the same point.
+  const int rc = no_bad_alloc("zkey verify", [&]() -> int {
+    KeyView a, b;
+    if (open_key(zkey, zkey_len, b, false) != G16_OK || all_zero(b.mpc.cs_hash, 64)) return G16_OK;
+    if (const int rc2 = open_key(init, init_len, a, true)) return rc2;
+    if (a.N != b.N || a.N > ((uint32_t)1 << 24)) return G16_OK;
+    PtauView pv;
+    if (const int rc2 = ptau_open(ptau, ptau_len, pv, /*tau_sections=*/false)) return rc2;
+    int L = 0;
+    while (((uint32_t)1 << L) < a.N) L++;
+    if ((int)pv.power < L) return G16_OK;   // (the route below has the verdict)
+    if (const int rc2 = cshash_check_ptau(pv, L)) return rc2;
+    uint8_t h[64];
+    if (const int rc2 = zkey_cs_hash_core(a, pv, device, h)) return rc2;
+    memcpy(init + (a.mpc.cs_hash - init), h, 64);
+    return G16_OK;
+  });
+  if (rc) return rc;
+  return g16_zkey_verify_from_init_ptau(init, init_len, ptau, ptau_len, zkey, zkey_len, device, ok);
 }
 
 extern "C" int g16_zkey_verify_r1cs_files(const char* r1cs_path, const char* ptau_path, const char* zkey_path, int device,

@@ -13,6 +13,18 @@
 namespace g16 {
 
 void blake2b512(const uint8_t* data, size_t len, uint8_t out[64]);   // RFC 7693, unkeyed
+// the same over a feed that arrives in parts of any length (empty ones included); final() once
+class Blake2b512 {
+ public:
+  Blake2b512();
+  void update(const uint8_t* data, size_t len);
+  void final(uint8_t out[64]);
+
+ private:
+  uint64_t h_[8], t_ = 0;   // t_: bytes compressed so far
+  uint8_t buf_[128];
+  size_t have_ = 0;         // bytes held back in buf_, 0 .. 128
+};
 
 // One contribution record of section 10, as it lies in the file (p[0, len)):
 //   deltaAfter G1 (64) | delta.g1_s (64) | delta.g1_sx (64) | delta.g2_spx (128) | transcript (64) | u32 type |

@@ -21,6 +21,8 @@
  *           plonkDestroy(phandle)
  *           plonkSetupFiles(r1csPath, ptauPath, zkeyPath, device, withLagrange) -> Promise<undefined>   (g16_plonk_setup_files)
  *           groth16SetupFiles(r1csPath, ptauPath, zkeyPath, device) -> Promise<undefined>   (g16_groth16_setup_files)
+ *           zkeyNewFiles(r1csPath, ptauPath, zkeyPath, device) -> Promise<Buffer(64): csHash>   (g16_zkey_new_files)
+ *           zkeyCsHashFiles(zkeyPath, ptauPath, device) -> Promise<Buffer(64): csHash>   (g16_zkey_cs_hash_files)
  *           ptauPrepareFiles(inPath, outPath, device) -> Promise<undefined>   (g16_ptau_prepare_files)
  *           zkeyContributeFiles(inPath, outPath, name | null, secret Buffer(64) | null, device) -> Promise<Buffer(64)>
  *                                                                              (g16_zkey_contribute_files: the hash)
@@ -709,11 +711,15 @@ typedef struct {
   int device, lagrange, rc;
   int groth16;   /* 1: g16_groth16_setup_files (groth16SetupFiles) */
   int prepare;   /* 1: g16_ptau_prepare_files (ptauPrepareFiles): ptau = input, zkey = output */
+  int cshash;    /* 1: g16_zkey_new_files (zkeyNewFiles); 2: g16_zkey_cs_hash_files (zkeyCsHashFiles): zkey = input.  Resolve with hash */
+  uint8_t hash[64];
   char err[512];
 } sjob_t;
 static void sjob_execute(napi_env env, void* data) {
   sjob_t* j = (sjob_t*)data;
-  j->rc = j->prepare   ? g16_ptau_prepare_files(j->ptau, j->zkey, j->device)
+  j->rc = j->cshash == 1 ? g16_zkey_new_files(j->r1cs, j->ptau, j->zkey, j->device, j->hash)
+          : j->cshash  ? g16_zkey_cs_hash_files(j->zkey, j->ptau, j->device, j->hash)
+          : j->prepare ? g16_ptau_prepare_files(j->ptau, j->zkey, j->device)
           : j->groth16 ? g16_groth16_setup_files(j->r1cs, j->ptau, j->zkey, j->device)
                        : g16_plonk_setup_files(j->r1cs, j->ptau, j->zkey, j->device, j->lagrange);
   if (j->rc) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
@@ -725,6 +731,16 @@ static void sjob_complete(napi_env env, napi_status status, void* data) {
     napi_create_string_utf8(env, j->rc ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
     napi_create_error(env, NULL, msg, &err);
     napi_reject_deferred(env, j->deferred, err);
+  } else if (j->cshash) {
+    napi_value buf;
+    void* q = NULL;
+    if (napi_create_buffer_copy(env, 64, j->hash, &q, &buf) == napi_ok) napi_resolve_deferred(env, j->deferred, buf);
+    else {
+      napi_value msg, err;
+      napi_create_string_utf8(env, "g16 addon: cannot create the hash buffer", NAPI_AUTO_LENGTH, &msg);
+      napi_create_error(env, NULL, msg, &err);
+      napi_reject_deferred(env, j->deferred, err);
+    }
   } else {
     napi_value undef;
     napi_get_undefined(env, &undef);
@@ -778,6 +794,53 @@ static napi_value js_groth16_setup_files(napi_env env, napi_callback_info info) 
   if (argc > 3 && napi_get_value_int32(env, argv[3], &v) == napi_ok) j->device = v;
   NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
   NAPI_OK(napi_create_string_utf8(env, "g16_groth16_setup_files", NAPI_AUTO_LENGTH, &resname));
+  NAPI_OK(napi_create_async_work(env, NULL, resname, sjob_execute, sjob_complete, j, &j->work));
+  NAPI_OK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+
+/* zkey new with the circuit hash, and the hash of an initial key alone: the same async job, resolved with the 64 bytes */
+static napi_value js_zkey_new_files(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4], promise, resname;
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 3) { napi_throw_type_error(env, NULL, "zkeyNewFiles(r1csPath, ptauPath, zkeyPath, device)"); return NULL; }
+  sjob_t* j = (sjob_t*)calloc(1, sizeof(sjob_t));
+  size_t n = 0;
+  if (napi_get_value_string_utf8(env, argv[0], j->r1cs, sizeof(j->r1cs), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], j->ptau, sizeof(j->ptau), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[2], j->zkey, sizeof(j->zkey), &n) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, "zkeyNewFiles: three path strings expected");
+    return NULL;
+  }
+  j->cshash = 1;
+  int32_t v = 0;
+  if (argc > 3 && napi_get_value_int32(env, argv[3], &v) == napi_ok) j->device = v;
+  NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
+  NAPI_OK(napi_create_string_utf8(env, "g16_zkey_new_files", NAPI_AUTO_LENGTH, &resname));
+  NAPI_OK(napi_create_async_work(env, NULL, resname, sjob_execute, sjob_complete, j, &j->work));
+  NAPI_OK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+static napi_value js_zkey_cs_hash_files(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3], promise, resname;
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 2) { napi_throw_type_error(env, NULL, "zkeyCsHashFiles(zkeyPath, ptauPath, device)"); return NULL; }
+  sjob_t* j = (sjob_t*)calloc(1, sizeof(sjob_t));
+  size_t n = 0;
+  if (napi_get_value_string_utf8(env, argv[0], j->zkey, sizeof(j->zkey), &n) != napi_ok ||
+      napi_get_value_string_utf8(env, argv[1], j->ptau, sizeof(j->ptau), &n) != napi_ok) {
+    free(j);
+    napi_throw_type_error(env, NULL, "zkeyCsHashFiles: two path strings expected");
+    return NULL;
+  }
+  j->cshash = 2;
+  int32_t v = 0;
+  if (argc > 2 && napi_get_value_int32(env, argv[2], &v) == napi_ok) j->device = v;
+  NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
+  NAPI_OK(napi_create_string_utf8(env, "g16_zkey_cs_hash_files", NAPI_AUTO_LENGTH, &resname));
   NAPI_OK(napi_create_async_work(env, NULL, resname, sjob_execute, sjob_complete, j, &j->work));
   NAPI_OK(napi_queue_async_work(env, j->work));
   return promise;
@@ -1556,6 +1619,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"plonkDestroy", NULL, js_plonk_destroy, NULL, NULL, NULL, napi_default, NULL},
       {"plonkSetupFiles", NULL, js_plonk_setup_files, NULL, NULL, NULL, napi_default, NULL},
       {"groth16SetupFiles", NULL, js_groth16_setup_files, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyNewFiles", NULL, js_zkey_new_files, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyCsHashFiles", NULL, js_zkey_cs_hash_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauPrepareFiles", NULL, js_ptau_prepare_files, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyContributeFiles", NULL, js_zkey_contribute_files, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyExportBellmanFiles", NULL, js_zkey_export_bellman_files, NULL, NULL, NULL, napi_default, NULL},

@@ -3,6 +3,9 @@
 // (snarkjs cli.js groth16Prove [EXT]; the reference's Makefile scripts the sibling PLONK lines,
 // /root/reference/Makefile:30-33).  Writes JSON.stringify(x, null, 1) like snarkjs.
 // And of `snarkjs groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>` (alias `zkey new`; prepared ptau only).
+// [--cshash]: the key carries the circuit hash of snarkjs's zkey_new.js at the head of section 10 (printed as snarkjs
+// prints it) instead of the legacy 64 zero bytes, which stay the default; every later contribution, beacon, export and
+// `zkey verify` chains from and compares what the key holds.  That the value equals snarkjs's own is not claimed.
 // And of `snarkjs powersoftau prepare phase2 <powersoftau.ptau> <new_powersoftau.ptau>` (alias `pt2`).
 // And of `snarkjs powersoftau new bn128 <power> <pot_0000.ptau>` (alias `ptn`), `snarkjs powersoftau contribute <old.ptau>
 // <new.ptau> [--name=..] [-e=..]` (alias `ptc`: prints the contribution hash as snarkjs does; -e: THIS CLI's derivation of
@@ -33,7 +36,10 @@
 // <circuit.r1cs> <pot.ptau> <circuit.zkey>` (alias `zkv`: the setup runs in memory, no file is written): prints
 // "[INFO]  snarkJS: ZKey Ok!" and exits 0, or "[ERROR] snarkJS: <reason>" and exits 1.  Both open the ptau and run the
 // ptau leg: section 9 of the key against the ceremony file's section 2.  [--skip-ptau]: without the leg (`zkv` then runs
-// the setup into a temporary file beside the zkey).  csHash is not snarkjs's (see INTEGRATION.md 5b).
+// the setup into a temporary file beside the zkey: a legacy zero-hash initial key, so a key made with --cshash is
+// rejected on that path).  `zkv` with the leg gives the in-memory initial key the circuit hash when the key under test
+// carries one.  csHash is built as snarkjs's zkey_new.js describes it; equality with snarkjs's value is not claimed
+// (see INTEGRATION.md 5b).
 // And of `snarkjs groth16 verify <verification_key.json> <public.json> <proof.json>` (groth16Verify [EXT]): prints
 // "[INFO]  snarkJS: OK!" and exits 0, or "[ERROR] snarkJS: Invalid proof" and exits 1.
 // And of `snarkjs wtns check <circuit.r1cs> <witness.wtns>` (alias `wchk`) of LATER snarkjs releases -- the pinned 0.4.12
@@ -203,9 +209,10 @@ async function main(argv) {
   if ((a[0] === "groth16" && a[1] === "setup") || (a[0] === "zkey" && a[1] === "new")) {
     // snarkjs groth16 setup <circuit.r1cs> <powersoftau.ptau> <circuit_0000.zkey>   (alias: zkey new)
     const pos = a.slice(2).filter((x) => !x.startsWith("--"));
-    if (pos.length < 3) { console.error("usage: cli.js groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>"); process.exit(2); }
-    const { newZKey } = require("./index.js");
-    await newZKey(pos[0], pos[1], pos[2]);
+    if (pos.length < 3) { console.error("usage: cli.js groth16 setup <circuit.r1cs> <pot.ptau> <circuit_0000.zkey> [--cshash]"); process.exit(2); }
+    const { newZKey, formatHash } = require("./index.js");
+    const hash = await newZKey(pos[0], pos[1], pos[2], { csHash: a.includes("--cshash") });
+    if (hash) console.log(`[INFO]  snarkJS: Circuit Hash: \n${formatHash(hash)}`);
     return;
   }
   if ((a[0] === "powersoftau" && a[1] === "new") || a[0] === "ptn") {

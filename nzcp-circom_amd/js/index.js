@@ -277,9 +277,18 @@ const plonk = {
 // snarkjs: zKey.newZKey(r1csName, ptauName, zkeyName[, logger]) / CLI `groth16 setup` = `zkey new` -- file names (a
 // ceremony file exceeds a Buffer).  The ptau must be prepared (`powersoftau prepare phase2`).  The key is a fresh
 // _0000 key (gamma = delta = 1, no contribution): not safe to deploy before a phase-2 contribution.
+// opts.csHash: the key carries the circuit hash of snarkjs's zkey_new.js (g16_zkey_new; resolves with its 64 bytes)
+// instead of the legacy 64 zero bytes, which stay the default.  Equality with snarkjs's own value is not claimed.
 async function newZKey(r1csName, ptauName, zkeyName, opts = {}) {
-  if (opts && typeof opts.debug === "function") opts = {};
+  if (!opts || typeof opts.debug === "function") opts = {};
+  if (opts.csHash) return native().zkeyNewFiles(String(r1csName), String(ptauName), String(zkeyName), opts.device | 0);
   await native().groth16SetupFiles(String(r1csName), String(ptauName), String(zkeyName), opts.device | 0);
+  return undefined;
+}
+// The circuit hash `newZKey(.., { csHash: true })` stores for this INITIAL key over this ceremony file (g16_zkey_cs_hash):
+// what section 10 already holds is not read, so the owner of a legacy zero-hash key can check or upgrade it.
+async function csHash(zkeyName, ptauName, opts = {}) {
+  return native().zkeyCsHashFiles(String(zkeyName), String(ptauName), (opts && opts.device) | 0);
 }
 
 // ------------------------------------------------------------------ powersoftau prepare phase2
@@ -643,4 +652,4 @@ plonk.fullProveBatch = async function fullProveBatch(inputs, programName, zkey, 
   return fullProveBatchNative(true, inputs, programName, zkey, opts, b ? Buffer.concat(inputs.map(() => b)) : null);
 };
 
-module.exports = { groth16, plonk, powersOfTau, wtns, nzcp, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, contribute, beacon, exportBellman, bellmanContribute, importBellman, verifyFromInit, verifyFromR1cs }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
+module.exports = { groth16, plonk, powersOfTau, wtns, nzcp, wtnsCheckReport, zKey: { exportVerificationKey, newZKey, csHash, contribute, beacon, exportBellman, bellmanContribute, importBellman, verifyFromInit, verifyFromR1cs }, formatHash, exportVerificationKey, newZKey, PlonkProver, plonkProofObject, createProver, Prover, createVerifier, Verifier, proofObject, publicSignals, proofBytes, vkeyBytes };
