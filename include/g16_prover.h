@@ -891,6 +891,42 @@ int g16_plonk_fullprove_batch(g16_plonk* p, g16_wtns_calculator* h, const uint8_
                               const uint8_t* blinding /* count * 9 * 32 or NULL */, g16_plonk_proof* out, uint8_t* pub,
                               uint32_t* status);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * NZCP pass verification: ES256 (ECDSA over NIST P-256 with SHA-256, COSE alg -7) for batches of signatures against a
+ * few resident issuer keys.  The circuit does not check the pass signature; it publishes toBeSignedSha256 so that the
+ * relying party can.  One handle = the 4-bit window tables of G and of every key (61 KB per point), resident on one
+ * GPU, or in host memory with device -1: the same code on at most 16 host threads, no GPU needed.
+ *
+ * keys: n_keys x 64 bytes, x | y big-endian (the JWK / COSE form), 1 <= n_keys <= 16.  G16_E_FORMAT, the text names the
+ *       key index: a coordinate >= p, a point off the curve, (0, 0).  n_keys out of range: G16_E_ARG.
+ * hashes: count x 32 (SHA-256 digests, big-endian; reduced modulo n here); sigs: count x 64 (r | s big-endian);
+ * key_idx: count x u32 or NULL (= key 0); an entry >= n_keys is G16_E_ARG, the text names the item.
+ * ok[i] = 1 iff signature i verifies under its key.  An invalid signature -- r or s outside [1, n), a sum at
+ * infinity, a different x -- is a verdict (0), never an error.  One batch at a time per handle (serialised). */
+typedef struct g16_es256_verifier g16_es256_verifier;
+int g16_es256_verifier_create(const uint8_t* keys, uint32_t n_keys, int device, g16_es256_verifier** out);
+int g16_es256_verify_batch(g16_es256_verifier* v, const uint8_t* hashes, const uint8_t* sigs, const uint32_t* key_idx,
+                           size_t count, uint8_t* ok);
+/* time of the last batch, ms: [0] scalars (s^-1, u1, u2), [1] point sum + compare (device time; wall time on the host route) */
+int g16_es256_verifier_timings(const g16_es256_verifier* v, float ms[2]);
+void g16_es256_verifier_destroy(g16_es256_verifier* v);
+/* Layer-test operator of csrc/p256.cuh, n items, device -1 = host threads.  Every value is 32 bytes big-endian,
+ * standard form, below its modulus (else G16_E_ARG naming the item).  op 0 / 1 / 2: base field a + b, a - b, a b;
+ * 3 / 4 / 5: the same in the scalar field; 6 / 7: inverse in the scalar / base field (b unused, inverse of 0 = 0);
+ * 8: affine a + affine b (x | y, 64 bytes each; (0, 0) = infinity in and out; points are not checked) by the mixed
+ * addition, 9: the same sum by the full addition on rescaled operands; 10: a = X | Z, b = r (below n) -> one byte:
+ * Z != 0 and x(X : Z) mod n == r, compared projectively. */
+int g16_p256_op(int device, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n);
+/* The relying party's combined verdict for proofs of NZCPPubIdentity (public.json: 256 credSubjSha256 bits, 256
+ * toBeSignedSha256 bits MSB-first, exp -- n_public of the verifier must be 513, else G16_E_ARG).  The digest each
+ * signature is checked against is packed from public signals 256..511 of that proof: the caller never supplies it.
+ * sigs / key_idx as above; both handles on the same device (else G16_E_ARG; the proof verifier has no host route).
+ * verdict[i]: 0 ok, 1 proof rejected, 2 signals 0..511 are not all 0 / 1, 3 signature rejected, 4 expired (exp <= now;
+ * now = 0 skips the test) -- the first that applies, in this order.  The proofs take g16_verify_batch's path; the
+ * signatures run on the ES256 handle's own stream meanwhile. */
+int g16_nzcp_pass_proof_verify_batch(g16_verifier* v, g16_es256_verifier* e, const g16_proof* proofs, const uint8_t* pubs,
+                                     const uint8_t* sigs, const uint32_t* key_idx, uint64_t now, size_t count, uint8_t* verdict);
+
 #ifdef __cplusplus
 }
 #endif

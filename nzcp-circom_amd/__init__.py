@@ -94,7 +94,9 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_fullprove_batch", "g16_plonk_fullprove_batch",
            "g16_beacon_scalars", "g16_ptau_beacon", "g16_ptau_beacon_files", "g16_zkey_beacon", "g16_zkey_beacon_files",
            "g16_zkey_new", "g16_zkey_new_files", "g16_zkey_cs_hash", "g16_zkey_cs_hash_files", "g16_zkey_h_monomial",
-           "g16_blake2b512_parts"]
+           "g16_blake2b512_parts",
+           "g16_es256_verifier_create", "g16_es256_verify_batch", "g16_es256_verifier_timings", "g16_es256_verifier_destroy",
+           "g16_p256_op", "g16_nzcp_pass_proof_verify_batch"]
 
 
 def load():
@@ -257,6 +259,13 @@ def load():
     lib.g16_finish_host.argtypes = [C.c_char_p, sz, C.c_char_p, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(Proof)]
     lib.g16_shard_range.argtypes = [C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.g16_shard_range.restype = None
+    lib.g16_es256_verifier_create.argtypes = [C.c_char_p, C.c_uint32, C.c_int, C.POINTER(vp)]
+    lib.g16_es256_verify_batch.argtypes = [vp, C.c_char_p, C.c_char_p, u32p, sz, C.c_char_p]
+    lib.g16_es256_verifier_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.g16_es256_verifier_destroy.argtypes = [vp]
+    lib.g16_es256_verifier_destroy.restype = None
+    lib.g16_p256_op.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, sz]
+    lib.g16_nzcp_pass_proof_verify_batch.argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, u32p, C.c_uint64, sz, C.c_char_p]
     lib.g16_free.argtypes = [vp]
     lib.g16_free.restype = None
     _lib = lib
@@ -918,6 +927,86 @@ class Verifier:
             self._h = C.c_void_p()
 
     __del__ = close
+
+
+# ------------------------------------------------------------------ NZCP pass verification (ES256 on NIST P-256)
+P256_OPS = {"fp_add": 0, "fp_sub": 1, "fp_mul": 2, "fn_add": 3, "fn_sub": 4, "fn_mul": 5, "fn_inv": 6, "fp_inv": 7,
+            "madd": 8, "add": 9, "xcmp": 10}
+
+
+def p256_op(op, a, b=None, device=0):
+    """Layer operator of csrc/p256.cuh (g16_p256_op): `op` a name of P256_OPS; a, b packed big-endian items (32 bytes a
+    field value, 64 a point x | y or X | Z); device -1 = host threads.  Returns the packed results."""
+    code = P256_OPS[op] if isinstance(op, str) else int(op)
+    sa = 64 if code in (8, 9, 10) else 32
+    so = 1 if code == 10 else sa
+    n = len(a) // sa
+    out = C.create_string_buffer(max(1, n * so))
+    _check(load().g16_p256_op(device, code, bytes(a), None if b is None else bytes(b), out, n))
+    return out.raw[:n * so]
+
+
+def _key_idx(key_idx, count):
+    if key_idx is None:
+        return None
+    if len(key_idx) != count:
+        raise G16Error(-1, "key_idx: one entry per item")
+    return (C.c_uint32 * max(1, count))(*key_idx)
+
+
+class Es256Verifier:
+    """Resident ES256 issuer keys (x | y, 64 big-endian bytes each, at most 16) on one GPU, or on host threads with
+    device=-1: batches of (SHA-256 digest, r | s) -> one verdict each."""
+
+    def __init__(self, keys, device=0):
+        keys = [bytes(k) for k in ([keys] if isinstance(keys, (bytes, bytearray)) else keys)]
+        if any(len(k) != 64 for k in keys):
+            raise G16Error(-1, "es256 verifier: a key is 64 bytes, x | y")
+        self.n_keys = len(keys)
+        self._h = C.c_void_p()
+        _check(load().g16_es256_verifier_create(b"".join(keys) or b"\0", self.n_keys, device, C.byref(self._h)))
+
+    def verify_batch(self, hashes, sigs, key_idx=None):
+        """hashes: count 32-byte digests (a list, or packed); sigs: count 64-byte r | s -> list of bool."""
+        hashes = hashes if isinstance(hashes, (bytes, bytearray)) else b"".join(hashes)
+        sigs = sigs if isinstance(sigs, (bytes, bytearray)) else b"".join(sigs)
+        count = len(sigs) // 64
+        if len(sigs) != 64 * count or len(hashes) != 32 * count:
+            raise G16Error(-1, "es256 verify: 32 bytes per digest and 64 per signature, as many of each")
+        ok = C.create_string_buffer(max(1, count))
+        _check(load().g16_es256_verify_batch(self._h, bytes(hashes), bytes(sigs), _key_idx(key_idx, count), count, ok))
+        return [b != 0 for b in ok.raw[:count]]
+
+    def timings(self):
+        ms = (C.c_float * 2)()
+        _check(load().g16_es256_verifier_timings(self._h, ms))
+        return list(ms)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            load().g16_es256_verifier_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+NZCP_VERDICTS = ("ok", "proof rejected", "public signals 0..511 are not all bits", "signature rejected", "expired")
+
+
+def nzcp_pass_proof_verify(verifier, es, proofs, pubs, sigs, key_idx=None, now=0):
+    """The relying party's combined check (g16_nzcp_pass_proof_verify_batch): verifier a Verifier of a 513-signal key,
+    es an Es256Verifier on the same device; proofs: proof.json objects or packed g16_proof bytes; pubs: per proof the 513
+    public signals (or packed 32-byte LE words); sigs: the 64 bytes r | s of each pass -> verdict codes (NZCP_VERDICTS)."""
+    pr = proofs if isinstance(proofs, (bytes, bytearray)) else b"".join(proof_from_obj(p) for p in proofs)
+    pb = pubs if isinstance(pubs, (bytes, bytearray)) else b"".join(b"".join(_le32(x) for x in ps) for ps in pubs)
+    sg = sigs if isinstance(sigs, (bytes, bytearray)) else b"".join(sigs)
+    count = len(sg) // 64
+    if len(sg) != 64 * count or len(pr) != 256 * count or len(pb) != 32 * verifier.n_public * count:
+        raise G16Error(-1, "nzcp pass proof: as many proofs, public-signal rows and 64-byte signatures")
+    out = C.create_string_buffer(max(1, count))
+    _check(load().g16_nzcp_pass_proof_verify_batch(verifier._h, es._h, bytes(pr), bytes(pb), bytes(sg), _key_idx(key_idx, count),
+                                                   int(now), count, out))
+    return list(out.raw[:count])
 
 
 _PLONK_G1 = ("A", "B", "C", "Z", "T1", "T2", "T3")

@@ -70,6 +70,9 @@ int shard_end_collect(g16_prover* p, uint8_t partial[G16_PARTIAL_BYTES]);
 // after a failure between begin and end: wait for what begin launched
 void shard_drain(g16_prover* p);
 
+// ---------------------------------------------------------------- of a Groth16 verifier handle (verify.hip)
+void verifier_info(const g16_verifier* v, int* device, uint32_t* n_public);   // for the combined pass verdict (es256_host.cpp)
+
 // ---------------------------------------------------------------- trapdoor setup on the device (setup_gpu.hip)
 // out[i] = [k_i] G as affine Montgomery bytes; tbl = host table [nwin][2^wb - 1] of d * 2^(wb j) * G, k in Montgomery form
 int setup_fixed_mul_g1(int device, const G1Affine* tbl, int wb, int nwin, const Fr* ks_mont, size_t n, uint8_t* out);

@@ -379,6 +379,11 @@ extern "C" int g16_verifier_timings(const g16_verifier* V, float ms[3]) {
 
 extern "C" void g16_verifier_destroy(g16_verifier* V) { delete V; }
 
+void g16::verifier_info(const g16_verifier* V, int* device, uint32_t* n_public) {
+  *device = V->device;
+  *n_public = V->n_public;
+}
+
 // Layer-test operator (tests/test_gpu_verify.py): count pairs (P in G1, Q in G2) as 6 standard-form 32-byte words
 // each -> the 12 standard-form words of the pairing value the verifier kernels compute.
 extern "C" int g16_pairing_op(int device, const uint8_t* in, uint32_t count, uint8_t* out) {

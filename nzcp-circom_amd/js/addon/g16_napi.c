@@ -49,6 +49,11 @@
  *           ptauBeaconFiles(inPath, outPath, name | null, beaconHash: Buffer, numIterationsExp, device) -> Promise<Buffer(64)>
  *           zkeyBeaconFiles(inPath, outPath, name | null, beaconHash: Buffer, numIterationsExp, device) -> Promise<Buffer(64)>
  *                                                            (g16_ptau_beacon_files, g16_zkey_beacon_files: the hash)
+ *           es256VerifyBatch(keys: Buffer(nKeys*64), hashes: Buffer(count*32), sigs: Buffer(count*64),
+ *               keyIdx: Buffer(count*4, u32 LE) | null, device) -> Promise<Buffer(count)>   (g16_es256_verify_batch: ONE batch
+ *               under a verifier created for the call; device -1 = host threads)
+ *           nzcpPassProofVerify(vkey: Buffer, nPublic, keys, proofs: Buffer(count*256), pubs: Buffer(count*nPublic*32), sigs,
+ *               keyIdx | null, now, device) -> Promise<Buffer(count): verdict codes>   (g16_nzcp_pass_proof_verify_batch)
  */
 #include <node_api.h>
 #include <stdio.h>
@@ -1603,6 +1608,122 @@ static napi_value js_full_prove_batch(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* ES256 pass signatures, and the combined verdict with the Groth16 proofs: one batch per call, the handles live for the
+ * call (the tables of a few keys are built in well under a millisecond on the device).  The inputs are copied: the work
+ * runs off the main thread. */
+typedef struct {
+  napi_async_work work;
+  napi_deferred deferred;
+  uint8_t* in[6];   /* keys, hashes | proofs, sigs, keyIdx, vkey, pubs */
+  size_t len[6];
+  uint32_t n_public;
+  uint64_t now;
+  size_t count;
+  uint8_t* out;
+  int combined, device, rc;
+  char err[512];
+} ejob_t;
+static void ejob_free(ejob_t* j) {
+  for (int k = 0; k < 6; k++) free(j->in[k]);
+  free(j->out);
+  free(j);
+}
+static void ejob_execute(napi_env env, void* data) {
+  ejob_t* j = (ejob_t*)data;
+  g16_es256_verifier* e = NULL;
+  g16_verifier* v = NULL;
+  const uint32_t* idx = j->len[3] ? (const uint32_t*)j->in[3] : NULL;
+  j->rc = g16_es256_verifier_create(j->in[0], (uint32_t)(j->len[0] / 64), j->device, &e);
+  if (!j->rc && j->combined) j->rc = g16_verifier_create(j->in[4], j->len[4], j->n_public, 0, j->device, &v);
+  if (!j->rc)
+    j->rc = j->combined ? g16_nzcp_pass_proof_verify_batch(v, e, (const g16_proof*)j->in[1], j->in[5], j->in[2], idx, j->now, j->count, j->out)
+                        : g16_es256_verify_batch(e, j->in[1], j->in[2], idx, j->count, j->out);
+  if (j->rc) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
+  if (v) g16_verifier_destroy(v);
+  if (e) g16_es256_verifier_destroy(e);
+}
+static void ejob_complete(napi_env env, napi_status status, void* data) {
+  ejob_t* j = (ejob_t*)data;
+  if (status != napi_ok || j->rc) {
+    napi_value msg, err;
+    napi_create_string_utf8(env, status == napi_ok ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_reject_deferred(env, j->deferred, err);
+  } else {
+    napi_value buf;
+    void* copy = NULL;
+    napi_create_buffer_copy(env, j->count, j->out, &copy, &buf);
+    napi_resolve_deferred(env, j->deferred, buf);
+  }
+  napi_delete_async_work(env, j->work);
+  ejob_free(j);
+}
+/* argv[slot[k]] -> in[k]: a Buffer (copied), or null / undefined where `optional` */
+static int ejob_take(napi_env env, ejob_t* j, int k, napi_value v, int optional) {
+  bool is_buf = false;
+  void* p = NULL;
+  size_t len = 0;
+  if (napi_is_buffer(env, v, &is_buf) != napi_ok || !is_buf) return optional;
+  if (napi_get_buffer_info(env, v, &p, &len) != napi_ok) return 0;
+  j->in[k] = (uint8_t*)malloc(len ? len : 1);
+  if (!j->in[k]) return 0;
+  if (len) memcpy(j->in[k], p, len);
+  j->len[k] = len;
+  return 1;
+}
+static napi_value ejob_start(napi_env env, ejob_t* j, const char* usage, const char* resource) {
+  j->count = j->len[2] / 64;
+  const int sized = j->len[0] % 64 == 0 && j->len[2] == j->count * 64 && (!j->len[3] || j->len[3] == j->count * 4) &&
+                    (j->combined ? j->len[1] == j->count * 256 && j->len[5] == j->count * (size_t)j->n_public * 32
+                                 : j->len[1] == j->count * 32);
+  j->out = (uint8_t*)calloc(j->count ? j->count : 1, 1);
+  if (!sized || !j->out) {
+    ejob_free(j);
+    napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  napi_value promise, resname;
+  NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
+  NAPI_OK(napi_create_string_utf8(env, resource, NAPI_AUTO_LENGTH, &resname));
+  NAPI_OK(napi_create_async_work(env, NULL, resname, ejob_execute, ejob_complete, j, &j->work));
+  NAPI_OK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+static napi_value js_es256_verify_batch(napi_env env, napi_callback_info info) {
+  static const char* usage = "es256VerifyBatch(keys: Buffer(n*64), hashes: Buffer(count*32), sigs: Buffer(count*64), keyIdx: Buffer(count*4) | null, device)";
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  ejob_t* j = (ejob_t*)calloc(1, sizeof(ejob_t));
+  if (!j || argc < 5 || !ejob_take(env, j, 0, argv[0], 0) || !ejob_take(env, j, 1, argv[1], 0) || !ejob_take(env, j, 2, argv[2], 0) ||
+      !ejob_take(env, j, 3, argv[3], 1) || napi_get_value_int32(env, argv[4], &j->device) != napi_ok) {
+    if (j) ejob_free(j);
+    napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  return ejob_start(env, j, usage, "g16_es256_verify_batch");
+}
+static napi_value js_nzcp_pass_proof_verify(napi_env env, napi_callback_info info) {
+  static const char* usage = "nzcpPassProofVerify(vkey: Buffer, nPublic, keys: Buffer(n*64), proofs: Buffer(count*256), pubs: Buffer(count*nPublic*32), sigs: Buffer(count*64), keyIdx: Buffer(count*4) | null, now, device)";
+  size_t argc = 9;
+  napi_value argv[9];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  ejob_t* j = (ejob_t*)calloc(1, sizeof(ejob_t));
+  double now = 0;
+  if (!j || argc < 9 || !ejob_take(env, j, 4, argv[0], 0) || napi_get_value_uint32(env, argv[1], &j->n_public) != napi_ok ||
+      !ejob_take(env, j, 0, argv[2], 0) || !ejob_take(env, j, 1, argv[3], 0) || !ejob_take(env, j, 5, argv[4], 0) ||
+      !ejob_take(env, j, 2, argv[5], 0) || !ejob_take(env, j, 3, argv[6], 1) || napi_get_value_double(env, argv[7], &now) != napi_ok ||
+      now < 0 || napi_get_value_int32(env, argv[8], &j->device) != napi_ok) {
+    if (j) ejob_free(j);
+    napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  j->combined = 1;
+  j->now = (uint64_t)now;
+  return ejob_start(env, j, usage, "g16_nzcp_pass_proof_verify_batch");
+}
+
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"create", NULL, js_create, NULL, NULL, NULL, napi_default, NULL},
@@ -1638,6 +1759,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"ptauChallengeContributeFiles", NULL, js_ptau_challenge_contribute_files, NULL, NULL, NULL, napi_default, NULL},
       {"ptauImportResponseFiles", NULL, js_ptau_import_response_files, NULL, NULL, NULL, napi_default, NULL},
       {"wtnsCheckFiles", NULL, js_wtns_check_files, NULL, NULL, NULL, napi_default, NULL},
+      {"es256VerifyBatch", NULL, js_es256_verify_batch, NULL, NULL, NULL, napi_default, NULL},
+      {"nzcpPassProofVerify", NULL, js_nzcp_pass_proof_verify, NULL, NULL, NULL, napi_default, NULL},
       {"nzcpProgramFile", NULL, js_nzcp_program_file, NULL, NULL, NULL, napi_default, NULL},
       {"wtnsCalculate", NULL, js_wtns_calculate, NULL, NULL, NULL, napi_default, NULL},
       {"fullProveBatch", NULL, js_full_prove_batch, NULL, NULL, NULL, napi_default, NULL},

@@ -114,6 +114,42 @@ async function main(argv) {
     fs.writeFileSync(publicFile, JSON.stringify(publicSignals, null, 1), "utf-8");
     return;
   }
+  if (a[0] === "nzcp" && a[1] === "verify") {
+    // nzcp verify <file of URIs | URI> --keys keys.json [--now t] [--device n]: one line per pass, exit 0 iff all are valid
+    // nzcp verify proof <verification_key.json> <public.json> <proof.json> <pass URI> --keys keys.json [--now t] [--device n]
+    const rest = a.slice(2);
+    const opts = {};
+    const pos = [];
+    let keysFile;
+    for (let i = 0; i < rest.length; i++) {
+      if (rest[i] === "--keys") keysFile = rest[++i];
+      else if (rest[i] === "--now") opts.now = parseInt(rest[++i], 10);
+      else if (rest[i] === "--device") opts.device = parseInt(rest[++i], 10);
+      else pos.push(rest[i]);
+    }
+    const proofMode = pos[0] === "proof";
+    if (!keysFile || pos.length < (proofMode ? 5 : 1)) {
+      console.error("usage: cli.js nzcp verify <file of URIs | URI> --keys keys.json [--now t] [--device n]\n" +
+                    "       cli.js nzcp verify proof <verification_key.json> <public.json> <proof.json> <pass URI> --keys keys.json [--now t] [--device n]");
+      process.exit(2);
+    }
+    const { nzcp } = require("./index.js");
+    const doc = JSON.parse(fs.readFileSync(keysFile, "utf-8"));
+    opts.keys = doc.keys || doc;
+    const readJson = (f) => JSON.parse(fs.readFileSync(f, "utf-8"));
+    if (proofMode) {
+      const p = require("./nzcpInput.js").passSignatureInput(pos[4]);
+      const [res] = await nzcp.verifyPassProof(readJson(pos[1]), [{ proof: readJson(pos[3]), publicSignals: readJson(pos[2]), signature: p.signature, iss: p.iss, kid: p.kid }], opts);
+      if (!res.ok) throw new Error(res.reason);
+      console.log("[INFO]  snarkJS: OK!");
+      return;
+    }
+    const uris = /^NZCP:/.test(pos[0]) ? [pos[0]] : fs.readFileSync(pos[0], "utf-8").split("\n").map((x) => x.trim()).filter((x) => x);
+    const res = await nzcp.verifyPass(uris, opts);
+    res.forEach((r, i) => console.log(r.ok ? `pass ${i}: OK ${r.claims.givenName} ${r.claims.familyName} ${r.claims.dob}` : `pass ${i}: INVALID ${r.reason}`));
+    if (!res.every((r) => r.ok)) process.exit(1);
+    return;
+  }
   if (a[0] === "nzcp" && a[1] === "program") {
     const pos = a.slice(2).filter((x) => !x.startsWith("--"));
     if (pos.length < 2) { console.error("usage: cli.js nzcp program <example|live> <file>"); process.exit(2); }

@@ -583,6 +583,90 @@ function plonkBlinding(b) {
   if (!Array.isArray(b) || b.length !== 9) throw new Error("plonk: blinding takes the nine scalars b1..b9");
   return Buffer.concat(b.map((x) => scalarToBuffer(x)));
 }
+// ---- pass verification (the twin of @vaxxnz/nzcp's offline verification; fetching the issuer's DID document stays with
+// the caller): keys = { "<iss>#<kid>": {x, y} } with base64url P-256 coordinates as in a DID document's publicKeyJwk
+const nzcpInput = require("./nzcpInput.js");
+const PASS_REASONS = {
+  malformed: "the pass URI is malformed",
+  alg: "the pass is not signed with ES256 (alg -7)",
+  key: "no issuer key for this iss and kid",
+  signature: "the signature does not verify",
+  notYet: "the pass is not yet valid (nbf)",
+  expired: "the pass has expired (exp)",
+  proof: "the proof does not verify",
+  bits: "public signals 0..511 are not all bits",
+};
+const PASS_PROOF_VERDICTS = [null, PASS_REASONS.proof, PASS_REASONS.bits, PASS_REASONS.signature, PASS_REASONS.expired];
+function issuerKeys(keys) {
+  const names = Object.keys(keys || {});
+  if (!names.length) throw new Error("verifyPass: no issuer keys given");
+  const coord = (v, name) => {
+    const b = Buffer.from(String(v).replace(/-/g, "+").replace(/_/g, "/"), "base64");
+    if (b.length !== 32) throw new Error(`verifyPass: key ${name}: a coordinate is not 32 bytes`);
+    return b;
+  };
+  return { names, bytes: Buffer.concat(names.map((n) => Buffer.concat([coord(keys[n].x, n), coord(keys[n].y, n)]))) };
+}
+function keyIndexBuffer(idx) {
+  const b = Buffer.alloc(idx.length * 4);
+  idx.forEach((k, i) => b.writeUInt32LE(k, i * 4));
+  return b;
+}
+function passNow(opts) { return opts.now === undefined ? Math.floor(Date.now() / 1000) : Number(opts.now); }
+
+// nzcp.verifyPass(uri | uris, {keys, now, device = -1}) -> {ok, reason, claims} (an array for an array): the URI is parsed,
+// the key looked up and nbf / exp checked here; the signatures of all passes go through ONE g16_es256_verify_batch
+async function verifyPass(uriOrUris, opts = {}) {
+  const many = Array.isArray(uriOrUris);
+  const uris = many ? uriOrUris : [uriOrUris];
+  const { names, bytes } = issuerKeys(opts.keys);
+  const now = passNow(opts);
+  const res = uris.map(() => null);
+  const batch = [];
+  uris.forEach((uri, i) => {
+    let p;
+    try { p = nzcpInput.passSignatureInput(String(uri)); } catch (e) { res[i] = { ok: false, reason: PASS_REASONS.malformed }; return; }
+    const key = names.indexOf(`${p.iss}#${p.kid}`);
+    if (p.alg !== -7) res[i] = { ok: false, reason: PASS_REASONS.alg };
+    else if (key < 0) res[i] = { ok: false, reason: PASS_REASONS.key };
+    else batch.push({ i, p, key });
+  });
+  if (batch.length) {
+    const ok = await native().es256VerifyBatch(bytes, Buffer.concat(batch.map((b) => b.p.digest)), Buffer.concat(batch.map((b) => b.p.signature)),
+      keyIndexBuffer(batch.map((b) => b.key)), opts.device === undefined ? -1 : opts.device | 0);
+    batch.forEach(({ i, p }, k) => {
+      const reason = !ok[k] ? PASS_REASONS.signature : now < p.nbf ? PASS_REASONS.notYet : now >= p.exp ? PASS_REASONS.expired : null;
+      res[i] = reason ? { ok: false, reason } : { ok: true, reason: null, claims: p.claims };
+    });
+  }
+  return many ? res : res[0];
+}
+
+// nzcp.verifyPassProof(vKey, [{proof, publicSignals, signature, iss, kid}], {keys, now, device = 0}) -> [{ok, reason}]: the
+// Groth16 proofs and the pass signatures (64 bytes r | s each, forwarded by the prover) in one
+// g16_nzcp_pass_proof_verify_batch; the digest a signature is checked against comes from the proof's public signals
+async function verifyPassProof(vk, items, opts = {}) {
+  const { names, bytes } = issuerKeys(opts.keys);
+  const nPublic = Number(vk.nPublic);
+  const res = items.map(() => null);
+  const batch = [];
+  items.forEach((it, i) => {
+    const key = names.indexOf(`${it.iss}#${it.kid}`);
+    const sig = Buffer.isBuffer(it.signature) ? it.signature : Buffer.from(it.signature || []);
+    if (key < 0) res[i] = { ok: false, reason: PASS_REASONS.key };
+    else if (sig.length !== 64) res[i] = { ok: false, reason: PASS_REASONS.signature };
+    else if (!Array.isArray(it.publicSignals) || it.publicSignals.length !== nPublic) res[i] = { ok: false, reason: PASS_REASONS.proof };
+    else batch.push({ i, it, key, sig });
+  });
+  if (batch.length) {
+    const verdicts = await native().nzcpPassProofVerify(vkeyBytes(vk), nPublic, bytes, Buffer.concat(batch.map((b) => proofBytes(b.it.proof))),
+      Buffer.concat(batch.map((b) => Buffer.concat(b.it.publicSignals.map(le32)))), Buffer.concat(batch.map((b) => b.sig)),
+      keyIndexBuffer(batch.map((b) => b.key)), passNow(opts), opts.device | 0);
+    batch.forEach(({ i }, k) => { res[i] = verdicts[k] === 0 ? { ok: true, reason: null } : { ok: false, reason: PASS_PROOF_VERDICTS[verdicts[k]] }; });
+  }
+  return res;
+}
+
 // nzcp.witnessProgram(params | "example" | "live", file): the witness program of NZCPPubIdentity(params) written to `file`
 // (seconds at the full size: keep the file); nzcp.gadgetProgram(name, params, file): one template of the library
 const NZCP_PARAMS = { example: [0, 314, 0, 4, 2, 4, 5], live: [1, 355, 0, 4, 2, 4, 6] };
@@ -595,6 +679,9 @@ const nzcp = {
   async gadgetProgram(name, params, file) {
     native().nzcpProgramFile(null, String(name), (params || []).map(Number), String(file));
   },
+  verifyPass,
+  verifyPassProof,
+  PASS_REASONS,
 };
 // what the CLI prints for a failed check (modelled on later snarkjs, not compared with it)
 function wtnsCheckReport(v) {

@@ -119,6 +119,20 @@ function expectedPublicSignals(uri) {
   return bitsMsbFirst(h1).concat(bitsMsbFirst(h2)).map(String).concat([String(c.exp)]);
 }
 
+// What a verifier of the pass needs (nzcp.verifyPass / verifyPassProof): the protected header's alg and kid, the CWT's
+// iss / nbf / exp, SHA-256(ToBeSigned) and the signature r | s.  Throws on a URI that is not a well-formed pass.
+function passSignatureInput(uri) {
+  const { protectedHdr, signature } = parsePassURI(uri);
+  const hdr = new Cbor(protectedHdr).item();
+  if (!(hdr instanceof Map)) throw new Error("protected header is not a map");
+  const kid = hdr.get(4);
+  const c = claims(uri);
+  if (typeof c.iss !== "string" || !Number.isInteger(c.exp) || !Number.isInteger(c.nbf)) throw new Error("iss / nbf / exp missing");
+  if (signature.length !== 64) throw new Error("the signature is not 64 bytes");
+  return { alg: hdr.get(1), kid: Buffer.isBuffer(kid) ? kid.toString("utf-8") : String(kid), iss: c.iss, nbf: c.nbf, exp: c.exp,
+           claims: c, digest: crypto.createHash("sha256").update(toBeSigned(uri)).digest(), signature };
+}
+
 // convenience for `groth16.prove` users: does a public.json match the pass it claims to be about?
 function publicSignalsMatchPass(publicSignals, uri) {
   const want = expectedPublicSignals(uri);
@@ -209,5 +223,5 @@ function fixedLayout(uri) {
            credSubjAt: subjKey + 18, segs: [given, family, dob] };
 }
 
-module.exports = { base32Decode, base32Encode, parsePassURI, toBeSigned, circuitInput, claims, expectedPublicSignals,
+module.exports = { passSignatureInput, base32Decode, base32Encode, parsePassURI, toBeSigned, circuitInput, claims, expectedPublicSignals,
                    publicSignalsMatchPass, syntheticPass, fixedLayout };
