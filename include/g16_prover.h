@@ -927,6 +927,70 @@ int g16_p256_op(int device, int op, const uint8_t* a, const uint8_t* b, uint8_t*
 int g16_nzcp_pass_proof_verify_batch(g16_verifier* v, g16_es256_verifier* e, const g16_proof* proofs, const uint8_t* pubs,
                                      const uint8_t* sigs, const uint32_t* key_idx, uint64_t now, size_t count, uint8_t* verdict);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * NZCP pass verification from URIs: the whole of a relying party's offline check in one call for many passes -- text,
+ * base32, the COSE_Sign1 / CWT walk, SHA-256(ToBeSigned), the issuer-key lookup, the ES256 signature, nbf / exp.  On a
+ * device the front end is one kernel that writes digests, signatures and key indices into the scratch of the ES256
+ * handle this handle owns; with device -1 the same code runs on at most 16 host threads.  One fixed-size record per pass.
+ *
+ * Passes are attacker-supplied bytes: whatever is wrong with one is a verdict in its record, never an error code.  A
+ * pass is WELL-FORMED when all of 1 to 6 hold; anything else is G16_PASS_MALFORMED.
+ * 1. Text.  Leading and trailing ' ' / \t / \r / \n are trimmed; then the literal "NZCP:/1/", at least one character of
+ *    A-Z2-7, and an optional run of trailing '='.  Other version digits, '=' elsewhere, any other character fail.
+ * 2. Base32, RFC 4648 alphabet: 5 bits a character, a byte whenever 8 bits are held, leftover bits dropped unchecked.
+ * 3. CBOR.  The first item of the decoded bytes is tag 18 around an array of exactly 4; items 0, 2 and 3 are byte
+ *    strings, item 1 is any well-formed item and is skipped; bytes after the first item are ignored.  A well-formed
+ *    item: major types 0..6, additional info < 24 or 24..27 (non-minimal encodings accepted; 28..31 -- indefinite
+ *    lengths among them -- and major type 7 refused), every length inside its buffer, and at most G16_PASS_CBOR_DEPTH
+ *    arrays, non-empty maps and tags open at once inside any one skipped item, itself included.  Every item of every
+ *    structure walked is validated, not only the entries that are read.
+ * 4. Protected header: its first item is a map; key 1 is alg, key 4 is kid, a later duplicate overrides an earlier one.
+ *    alg other than the integer -7, or absent, is G16_PASS_ALG.  kid is compared bytewise, as a byte or text string;
+ *    of another type or absent it matches no key.
+ * 5. Payload: its first item is a map; key 1 iss is a text string; keys 4 exp and 5 nbf are integers that fit int64;
+ *    text key "vc" is a map whose text key "credentialSubject" is a map (the last duplicate decides, everywhere).  If
+ *    its givenName, familyName and dob are all text strings, cred_subj_sha256 = SHA-256(given "," family "," dob) over
+ *    their raw bytes and G16_PASS_HAS_SUBJECT is set; otherwise the digest is zero and the flag clear.
+ * 6. The signature is exactly 64 bytes.  ToBeSigned = 84 6A "Signature1" bstr(protected) 40 bstr(payload), the heads
+ *    of bstr in their shortest form; tbs_sha256 is its SHA-256, the digest the signature is checked against.
+ * Verdict: the first that applies of 1 malformed, 2 alg, 3 no key with this iss and kid, 4 the signature does not
+ * verify, 5 now < nbf, 6 now >= exp; else 0.  G16_PASS_TOO_LONG (7) is decided before all of them, on the item's length
+ * alone (offsets[i + 1] - offsets[i] > G16_PASS_URI_MAX, the untrimmed text): such text is never read.
+ * Stricter than js/nzcpInput.js on purpose: the nesting cap, the int64 range of nbf / exp, verdict 7 (the JS reader has
+ * no such limits), and a kid that is neither a byte nor a text string matches nothing (the JS reader prints it).
+ * A well-formed pass has every field of its record filled whatever its verdict (key_idx = 0 when no key matched);
+ * a malformed or too long one has all but the verdict zero.
+ *
+ * keys as for g16_es256_verifier_create, with the same checks and texts; iss[j] / kid[j]: the NUL-terminated name of
+ * key j, each 1 to G16_PASS_NAME_MAX bytes (else G16_E_ARG); the first key whose iss and kid both match is taken.
+ * text + offsets: pass i is text[offsets[i], offsets[i + 1]); offsets ascend (else G16_E_ARG).  count = 0 is accepted.
+ * One batch at a time per handle (serialised). */
+#define G16_PASS_URI_MAX 2048
+#define G16_PASS_CBOR_DEPTH 16
+#define G16_PASS_NAME_MAX 128
+#define G16_PASS_HAS_SUBJECT 1u
+enum { G16_PASS_OK = 0, G16_PASS_MALFORMED = 1, G16_PASS_ALG = 2, G16_PASS_KEY = 3, G16_PASS_SIGNATURE = 4,
+       G16_PASS_NOT_YET = 5, G16_PASS_EXPIRED = 6, G16_PASS_TOO_LONG = 7 };
+typedef struct {
+  uint32_t verdict, key_idx, tbs_len, flags;
+  int64_t nbf, exp;
+  uint8_t tbs_sha256[32], cred_subj_sha256[32];
+} g16_pass_result;
+typedef struct g16_pass_verifier g16_pass_verifier;
+int g16_pass_verifier_create(const uint8_t* keys /* n x (x|y), big-endian */, const char* const* iss, const char* const* kid,
+                             uint32_t n_keys /* <= 16 */, int device, g16_pass_verifier** out);
+int g16_pass_verify_batch(g16_pass_verifier* v, const uint8_t* text, const uint64_t* offsets /* count + 1 */, size_t count,
+                          int64_t now, g16_pass_result* out);
+/* time of the last batch, ms: [0] the front end, [1] scalars, [2] point sum + compare (device time; wall time on the host route) */
+int g16_pass_verifier_timings(const g16_pass_verifier* v, float ms[3]);
+void g16_pass_verifier_destroy(g16_pass_verifier* v);
+/* Layer-test operator of csrc/nzcp_pass.cuh and csrc/sha256.cuh over the items text[offsets[i], offsets[i + 1]), device
+ * -1 = host threads.  op 0: base32-decode each item (A-Z2-7 then trailing '=', at most G16_PASS_URI_MAX characters):
+ * out is count x (4 + 1280) bytes, a u32 length (0xffffffff: not base32, or too long) then the bytes.  op 1: SHA-256 of
+ * each item's bytes, out count x 32.  op 2: the front end alone on pass URIs with an empty key table, out count x
+ * g16_pass_result: verdict 1, 2, 7, or 3 for every well-formed ES256 pass; no signature work is done. */
+int g16_pass_op(int device, int op, const uint8_t* text, const uint64_t* offsets, size_t count, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

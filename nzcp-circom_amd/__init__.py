@@ -61,6 +61,11 @@ class Timings(C.Structure):
                 ("msm_accum_kernel_ms", C.c_float * 5)]
 
 
+class PassResult(C.Structure):
+    _fields_ = [("verdict", C.c_uint32), ("key_idx", C.c_uint32), ("tbs_len", C.c_uint32), ("flags", C.c_uint32),
+                ("nbf", C.c_int64), ("exp", C.c_int64), ("tbs_sha256", C.c_uint8 * 32), ("cred_subj_sha256", C.c_uint8 * 32)]
+
+
 EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g16_prove_staged",
            "g16_prove_partial", "g16_prove_finish", "g16_get_info", "g16_get_timings", "g16_destroy",
            "g16_last_error", "g16_fr_fft", "g16_fr_ifft", "g16_fr_batch_mul", "g16_field_op",
@@ -96,7 +101,9 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_zkey_new", "g16_zkey_new_files", "g16_zkey_cs_hash", "g16_zkey_cs_hash_files", "g16_zkey_h_monomial",
            "g16_blake2b512_parts",
            "g16_es256_verifier_create", "g16_es256_verify_batch", "g16_es256_verifier_timings", "g16_es256_verifier_destroy",
-           "g16_p256_op", "g16_nzcp_pass_proof_verify_batch"]
+           "g16_p256_op", "g16_nzcp_pass_proof_verify_batch",
+           "g16_pass_verifier_create", "g16_pass_verify_batch", "g16_pass_verifier_timings", "g16_pass_verifier_destroy",
+           "g16_pass_op"]
 
 
 def load():
@@ -266,6 +273,13 @@ def load():
     lib.g16_es256_verifier_destroy.restype = None
     lib.g16_p256_op.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, sz]
     lib.g16_nzcp_pass_proof_verify_batch.argtypes = [vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, u32p, C.c_uint64, sz, C.c_char_p]
+    u64p, strs = C.POINTER(C.c_uint64), C.POINTER(C.c_char_p)
+    lib.g16_pass_verifier_create.argtypes = [C.c_char_p, strs, strs, C.c_uint32, C.c_int, C.POINTER(vp)]
+    lib.g16_pass_verify_batch.argtypes = [vp, C.c_char_p, u64p, sz, C.c_int64, C.POINTER(PassResult)]
+    lib.g16_pass_verifier_timings.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.g16_pass_verifier_destroy.argtypes = [vp]
+    lib.g16_pass_verifier_destroy.restype = None
+    lib.g16_pass_op.argtypes = [C.c_int, C.c_int, C.c_char_p, u64p, sz, C.c_char_p]
     lib.g16_free.argtypes = [vp]
     lib.g16_free.restype = None
     _lib = lib
@@ -1007,6 +1021,91 @@ def nzcp_pass_proof_verify(verifier, es, proofs, pubs, sigs, key_idx=None, now=0
     _check(load().g16_nzcp_pass_proof_verify_batch(verifier._h, es._h, bytes(pr), bytes(pb), bytes(sg), _key_idx(key_idx, count),
                                                    int(now), count, out))
     return list(out.raw[:count])
+
+
+# ------------------------------------------------------------------ NZCP pass verification from URIs
+PASS_VERDICTS = ("ok", "malformed", "alg", "key", "signature", "not yet valid", "expired", "too long")
+PASS_HAS_SUBJECT = 1
+PASS_URI_MAX = 2048
+PASS_OPS = {"base32": 0, "sha256": 1, "front": 2}
+_PASS_B32_STRIDE = 4 + PASS_URI_MAX * 5 // 8
+
+
+def _pass_items(items):
+    """texts (str or bytes) -> (packed bytes, the count + 1 offsets)"""
+    items = [u.encode("utf-8") if isinstance(u, str) else bytes(u) for u in items]
+    offsets = (C.c_uint64 * (len(items) + 1))()
+    for i, u in enumerate(items):
+        offsets[i + 1] = offsets[i] + len(u)
+    return b"".join(items), offsets
+
+
+def _pass_record(r):
+    return {"verdict": r.verdict, "key_idx": r.key_idx, "tbs_len": r.tbs_len, "flags": r.flags, "nbf": r.nbf, "exp": r.exp,
+            "tbs_sha256": bytes(r.tbs_sha256), "cred_subj_sha256": bytes(r.cred_subj_sha256)}
+
+
+def pass_op(op, items, device=0):
+    """Layer operator of csrc/nzcp_pass.cuh and csrc/sha256.cuh (g16_pass_op) over a list of items (str or bytes); device
+    -1 = host threads.  "base32": the decoded bytes of each item, None where it is not base32; "sha256": the 32-byte
+    digests; "front": the front end's records (dicts; no key table, no signature work)."""
+    code = PASS_OPS[op] if isinstance(op, str) else int(op)
+    text, offsets = _pass_items(items)
+    n = len(items)
+    stride = {0: _PASS_B32_STRIDE, 1: 32, 2: C.sizeof(PassResult)}.get(code, 1)
+    out = (PassResult * max(1, n))() if code == 2 else C.create_string_buffer(max(1, n * stride))
+    _check(load().g16_pass_op(device, code, text, offsets, n, C.cast(out, C.c_char_p)))
+    if code == 2:
+        return [_pass_record(r) for r in out[:n]]
+    rows = [out.raw[i * stride:(i + 1) * stride] for i in range(n)]
+    if code == 1:
+        return rows
+    lens = [int.from_bytes(r[:4], "little") for r in rows]
+    return [None if k == 0xFFFFFFFF else r[4:4 + k] for r, k in zip(rows, lens)]
+
+
+class PassVerifier:
+    """A relying party's offline check of NZ COVID Passes from their URIs (g16_pass_*): keys is the {"<iss>#<kid>": {x, y}}
+    object of a DID document's keys (base64url P-256 coordinates, at most 16); on one GPU, or on host threads with
+    device=-1.  verify_batch(uris, now) -> one record (dict) per pass: verdict (an index of PASS_VERDICTS), key_idx,
+    tbs_len, flags, nbf, exp, tbs_sha256, cred_subj_sha256."""
+
+    def __init__(self, keys, device=0):
+        import base64
+        names = list(keys)
+
+        def coord(v):
+            b = base64.urlsafe_b64decode(v + "=" * (-len(v) % 4))
+            if len(b) != 32:
+                raise G16Error(-1, "pass verifier: a key coordinate is not 32 bytes")
+            return b
+        packed = b"".join(coord(keys[n]["x"]) + coord(keys[n]["y"]) for n in names)
+        parts = [n.rpartition("#") for n in names]
+        arr = C.c_char_p * max(1, len(names))
+        iss = arr(*[p[0].encode("utf-8") for p in parts])
+        kid = arr(*[p[2].encode("utf-8") for p in parts])
+        self.names = names
+        self._h = C.c_void_p()
+        _check(load().g16_pass_verifier_create(packed or b"\0", iss, kid, len(names), device, C.byref(self._h)))
+
+    def verify_batch(self, uris, now):
+        text, offsets = _pass_items(uris)
+        out = (PassResult * max(1, len(uris)))()
+        _check(load().g16_pass_verify_batch(self._h, text, offsets, len(uris), int(now), out))
+        return [_pass_record(r) for r in out[:len(uris)]]
+
+    def timings(self):
+        """ms of the last batch: the front end, the scalars, the point sums + compare"""
+        ms = (C.c_float * 3)()
+        _check(load().g16_pass_verifier_timings(self._h, ms))
+        return list(ms)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            load().g16_pass_verifier_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
 
 
 _PLONK_G1 = ("A", "B", "C", "Z", "T1", "T2", "T3")

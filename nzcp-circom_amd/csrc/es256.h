@@ -96,5 +96,20 @@ int es256_device_launch(Es256Device* d, const uint8_t* hashes, const uint8_t* si
 // wait for it: ok[count], ms = device time of the two phases
 int es256_device_finish(Es256Device* d, uint8_t* ok, float ms[2]);
 int es256_device_op(int device, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n);
+// For a front end that fills the inputs on the device (pass_verify.hip): the handle's scratch for `count` signatures
+// (grown on demand) and its stream (a hipStream_t); then the two kernels over what lies there.  es256_device_finish
+// ends such a batch as it ends any other.
+struct Es256Scratch {
+  uint8_t* hashes;     // count x 32
+  uint8_t* sigs;       // count x 64
+  uint32_t* key_idx;   // count
+  void* stream;
+};
+int es256_device_scratch(Es256Device* d, size_t count, Es256Scratch* out);
+int es256_device_launch_resident(Es256Device* d, size_t count);
 
 }  // namespace g16
+
+// of an ES256 verifier handle (es256_host.cpp): its device side, NULL on the host route
+struct g16_es256_verifier;
+g16::Es256Device* es256_verifier_device(g16_es256_verifier* v);

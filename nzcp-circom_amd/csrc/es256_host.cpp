@@ -22,6 +22,8 @@ struct g16_es256_verifier {
   ~g16_es256_verifier() { if (dev) es256_device_destroy(dev); }
 };
 
+Es256Device* es256_verifier_device(g16_es256_verifier* v) { return v->dev; }
+
 namespace {
 
 int host_threads(size_t n) {

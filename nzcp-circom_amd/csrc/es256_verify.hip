@@ -175,6 +175,32 @@ int es256_device_launch(Es256Device* D, const uint8_t* hashes, const uint8_t* si
   return G16_OK;
 }
 
+int es256_device_scratch(Es256Device* D, size_t count, Es256Scratch* out) {
+  G16_HIP(hipSetDevice(D->device));
+  if (const int rc = ensure_scratch(D, count)) return rc;
+  *out = Es256Scratch{D->d_hashes, D->d_sigs, D->d_key, (void*)D->st};
+  return G16_OK;
+}
+
+// the two kernels of es256_device_launch over digests, signatures and key indices that a kernel on the handle's stream
+// has written into the scratch (count <= the capacity es256_device_scratch was asked for)
+int es256_device_launch_resident(Es256Device* D, size_t count) {
+  G16_HIP(hipSetDevice(D->device));
+  if (count > D->cap) { set_error("es256 verify: the resident batch is larger than the scratch"); return G16_E_STATE; }
+  const uint32_t n = (uint32_t)count;
+  hipStream_t st = D->st;
+  G16_HIP(hipEventRecord(D->ev[0], st));
+  es256_scalars_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, st>>>(D->d_hashes, D->d_sigs, n, D->d_u, D->d_live);
+  G16_HIP(hipEventRecord(D->ev[1], st));
+  const uint64_t lanes = (uint64_t)n * kEs256Lanes;
+  es256_sum_kernel<<<(uint32_t)((lanes + kBlock - 1) / kBlock), kBlock, 0, st>>>(D->d_tbl, D->d_u, D->d_live, D->d_sigs, D->d_key, n,
+                                                                                 D->d_ok);
+  G16_HIP(hipEventRecord(D->ev[2], st));
+  G16_HIP(hipGetLastError());
+  D->in_flight = count;
+  return G16_OK;
+}
+
 int es256_device_finish(Es256Device* D, uint8_t* ok, float ms[2]) {
   G16_HIP(hipSetDevice(D->device));
   const size_t count = D->in_flight;

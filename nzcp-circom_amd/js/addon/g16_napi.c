@@ -54,6 +54,9 @@
  *               under a verifier created for the call; device -1 = host threads)
  *           nzcpPassProofVerify(vkey: Buffer, nPublic, keys, proofs: Buffer(count*256), pubs: Buffer(count*nPublic*32), sigs,
  *               keyIdx | null, now, device) -> Promise<Buffer(count): verdict codes>   (g16_nzcp_pass_proof_verify_batch)
+ *           passVerifyBatch(keys: Buffer(nKeys*64), names: Buffer("iss\0kid\0" per key), text: Buffer, offsets:
+ *               Buffer((count+1)*8, u64 LE), now, device) -> Promise<Buffer(count*96): g16_pass_result records>
+ *               (g16_pass_verify_batch: ONE batch under a verifier created for the call; device -1 = host threads)
  */
 #include <node_api.h>
 #include <stdio.h>
@@ -1723,6 +1726,86 @@ static napi_value js_nzcp_pass_proof_verify(napi_env env, napi_callback_info inf
   return ejob_start(env, j, usage, "g16_nzcp_pass_proof_verify_batch");
 }
 
+/* Passes from their URIs: one g16_pass_verify_batch per call, the handle lives for the call.  in[0] keys, in[1] the key
+ * names ("iss\0kid\0" per key), in[2] the URI text, in[3] the count + 1 offsets (u64 LE); out: count g16_pass_result. */
+static void passjob_execute(napi_env env, void* data) {
+  ejob_t* j = (ejob_t*)data;
+  const uint32_t n_keys = (uint32_t)(j->len[0] / 64);
+  const char* iss[16];
+  const char* kid[16];
+  const char* p = (const char*)j->in[1];
+  const char* end = p + j->len[1];
+  uint32_t k = 0;
+  for (; k < n_keys && k < 16 && p < end; k++) {
+    iss[k] = p;
+    p += strlen(p) + 1;
+    if (p >= end) break;
+    kid[k] = p;
+    p += strlen(p) + 1;
+  }
+  g16_pass_verifier* v = NULL;
+  if (k != n_keys || n_keys > 16) {
+    j->rc = -1;
+    strcpy(j->err, "passVerifyBatch: one iss and one kid per key, at most 16 keys");
+    return;
+  }
+  j->rc = g16_pass_verifier_create(j->in[0], iss, kid, n_keys, j->device, &v);
+  if (!j->rc) j->rc = g16_pass_verify_batch(v, j->in[2], (const uint64_t*)j->in[3], j->count, (int64_t)j->now, (g16_pass_result*)j->out);
+  if (j->rc) { strncpy(j->err, g16_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
+  if (v) g16_pass_verifier_destroy(v);
+}
+static void passjob_complete(napi_env env, napi_status status, void* data) {
+  ejob_t* j = (ejob_t*)data;
+  if (status != napi_ok || j->rc) {
+    napi_value msg, err;
+    napi_create_string_utf8(env, status == napi_ok ? j->err : "g16 addon: async work cancelled", NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_reject_deferred(env, j->deferred, err);
+  } else {
+    napi_value buf;
+    void* copy = NULL;
+    napi_create_buffer_copy(env, j->count * sizeof(g16_pass_result), j->out, &copy, &buf);
+    napi_resolve_deferred(env, j->deferred, buf);
+  }
+  napi_delete_async_work(env, j->work);
+  ejob_free(j);
+}
+static napi_value js_pass_verify_batch(napi_env env, napi_callback_info info) {
+  static const char* usage = "passVerifyBatch(keys: Buffer(n*64), names: Buffer('iss\\0kid\\0' per key), text: Buffer, offsets: Buffer((count+1)*8, u64 LE), now, device)";
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  ejob_t* j = (ejob_t*)calloc(1, sizeof(ejob_t));
+  double now = 0;
+  int ok = j && argc >= 6 && ejob_take(env, j, 0, argv[0], 0) && ejob_take(env, j, 1, argv[1], 0) && ejob_take(env, j, 2, argv[2], 0) &&
+           ejob_take(env, j, 3, argv[3], 0) && napi_get_value_double(env, argv[4], &now) == napi_ok &&
+           napi_get_value_int32(env, argv[5], &j->device) == napi_ok;
+  /* the names end with a NUL, the offsets are whole words that ascend and stay inside the text */
+  if (ok) ok = j->len[0] % 64 == 0 && j->len[1] > 0 && j->in[1][j->len[1] - 1] == 0 && j->len[3] >= 8 && j->len[3] % 8 == 0;
+  if (ok) {
+    j->count = j->len[3] / 8 - 1;
+    uint64_t prev = 0, cur = 0;
+    for (size_t i = 0; i <= j->count && ok; i++, prev = cur) {
+      memcpy(&cur, j->in[3] + i * 8, 8);
+      ok = cur >= prev && cur <= j->len[2];
+    }
+    j->out = (uint8_t*)calloc(j->count ? j->count : 1, sizeof(g16_pass_result));
+    ok = ok && j->out;
+  }
+  if (!ok) {
+    if (j) ejob_free(j);
+    napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  j->now = (uint64_t)(int64_t)now;
+  napi_value promise, resname;
+  NAPI_OK(napi_create_promise(env, &j->deferred, &promise));
+  NAPI_OK(napi_create_string_utf8(env, "g16_pass_verify_batch", NAPI_AUTO_LENGTH, &resname));
+  NAPI_OK(napi_create_async_work(env, NULL, resname, passjob_execute, passjob_complete, j, &j->work));
+  NAPI_OK(napi_queue_async_work(env, j->work));
+  return promise;
+}
+
 
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
@@ -1761,6 +1844,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"wtnsCheckFiles", NULL, js_wtns_check_files, NULL, NULL, NULL, napi_default, NULL},
       {"es256VerifyBatch", NULL, js_es256_verify_batch, NULL, NULL, NULL, napi_default, NULL},
       {"nzcpPassProofVerify", NULL, js_nzcp_pass_proof_verify, NULL, NULL, NULL, napi_default, NULL},
+      {"passVerifyBatch", NULL, js_pass_verify_batch, NULL, NULL, NULL, napi_default, NULL},
       {"nzcpProgramFile", NULL, js_nzcp_program_file, NULL, NULL, NULL, napi_default, NULL},
       {"wtnsCalculate", NULL, js_wtns_calculate, NULL, NULL, NULL, napi_default, NULL},
       {"fullProveBatch", NULL, js_full_prove_batch, NULL, NULL, NULL, napi_default, NULL},

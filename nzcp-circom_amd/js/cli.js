@@ -116,20 +116,23 @@ async function main(argv) {
   }
   if (a[0] === "nzcp" && a[1] === "verify") {
     // nzcp verify <file of URIs | URI> --keys keys.json [--now t] [--device n]: one line per pass, exit 0 iff all are valid
+    // nzcp verify <file of URIs | URI> --batch --keys keys.json [--now t] [--device n]: the same verdicts from ONE native call
+    //   that parses and hashes the passes too (device 0 unless --device; -1 = host threads); prints exp and credSubjSha256
     // nzcp verify proof <verification_key.json> <public.json> <proof.json> <pass URI> --keys keys.json [--now t] [--device n]
     const rest = a.slice(2);
     const opts = {};
     const pos = [];
-    let keysFile;
+    let keysFile, batch = false;
     for (let i = 0; i < rest.length; i++) {
       if (rest[i] === "--keys") keysFile = rest[++i];
+      else if (rest[i] === "--batch") batch = true;
       else if (rest[i] === "--now") opts.now = parseInt(rest[++i], 10);
       else if (rest[i] === "--device") opts.device = parseInt(rest[++i], 10);
       else pos.push(rest[i]);
     }
     const proofMode = pos[0] === "proof";
     if (!keysFile || pos.length < (proofMode ? 5 : 1)) {
-      console.error("usage: cli.js nzcp verify <file of URIs | URI> --keys keys.json [--now t] [--device n]\n" +
+      console.error("usage: cli.js nzcp verify <file of URIs | URI> [--batch] --keys keys.json [--now t] [--device n]\n" +
                     "       cli.js nzcp verify proof <verification_key.json> <public.json> <proof.json> <pass URI> --keys keys.json [--now t] [--device n]");
       process.exit(2);
     }
@@ -145,6 +148,12 @@ async function main(argv) {
       return;
     }
     const uris = /^NZCP:/.test(pos[0]) ? [pos[0]] : fs.readFileSync(pos[0], "utf-8").split("\n").map((x) => x.trim()).filter((x) => x);
+    if (batch) {   // every pass parsed, hashed and checked in one native call
+      const res = await nzcp.verifyPassBatch(uris, opts);
+      res.forEach((r, i) => console.log(r.ok ? `pass ${i}: OK exp ${r.exp} ${r.credSubjSha256 || "-"}` : `pass ${i}: INVALID ${r.reason}`));
+      if (!res.every((r) => r.ok)) process.exit(1);
+      return;
+    }
     const res = await nzcp.verifyPass(uris, opts);
     res.forEach((r, i) => console.log(r.ok ? `pass ${i}: OK ${r.claims.givenName} ${r.claims.familyName} ${r.claims.dob}` : `pass ${i}: INVALID ${r.reason}`));
     if (!res.every((r) => r.ok)) process.exit(1);

@@ -595,6 +595,7 @@ const PASS_REASONS = {
   expired: "the pass has expired (exp)",
   proof: "the proof does not verify",
   bits: "public signals 0..511 are not all bits",
+  tooLong: "the pass URI is longer than 2048 bytes",
 };
 const PASS_PROOF_VERDICTS = [null, PASS_REASONS.proof, PASS_REASONS.bits, PASS_REASONS.signature, PASS_REASONS.expired];
 function issuerKeys(keys) {
@@ -642,6 +643,37 @@ async function verifyPass(uriOrUris, opts = {}) {
   return many ? res : res[0];
 }
 
+// nzcp.verifyPassBatch(uris, {keys, now, device = 0}) -> [{ok, reason, nbf, exp, toBeSignedSha256, credSubjSha256}]: the whole
+// check of every pass -- text, base32, the COSE_Sign1 / CWT walk, the digests, the key lookup, the signature, nbf / exp -- in
+// ONE g16_pass_verify_batch (include/g16_prover.h has the contract; device -1 = host threads).  The digests are hex
+// strings, null where the pass is malformed or too long; credSubjSha256 is null too when the pass has no name or dob.
+const PASS_BATCH_REASONS = [null, PASS_REASONS.malformed, PASS_REASONS.alg, PASS_REASONS.key, PASS_REASONS.signature,
+  PASS_REASONS.notYet, PASS_REASONS.expired, PASS_REASONS.tooLong];
+async function verifyPassBatch(uris, opts = {}) {
+  const { names, bytes } = issuerKeys(opts.keys);
+  const split = names.map((n) => { const at = n.lastIndexOf("#"); return [n.slice(0, Math.max(at, 0)), n.slice(at + 1)]; });
+  const nameBytes = Buffer.concat(split.map(([iss, kid]) => Buffer.concat([Buffer.from(iss, "utf-8"), Buffer.from([0]), Buffer.from(kid, "utf-8"), Buffer.from([0])])));
+  const texts = uris.map((u) => Buffer.from(String(u), "utf-8"));
+  const offsets = Buffer.alloc((texts.length + 1) * 8);
+  let at = 0;
+  texts.forEach((t, i) => { at += t.length; offsets.writeBigUInt64LE(BigInt(at), (i + 1) * 8); });
+  const out = await native().passVerifyBatch(bytes, nameBytes, Buffer.concat(texts), offsets, passNow(opts), opts.device === undefined ? 0 : opts.device | 0);
+  return texts.map((_, i) => {
+    const r = out.subarray(i * 96, (i + 1) * 96);
+    const verdict = r.readUInt32LE(0), parsed = verdict !== 1 && verdict !== 7;
+    return { ok: verdict === 0, reason: PASS_BATCH_REASONS[verdict], nbf: parsed ? Number(r.readBigInt64LE(16)) : null,
+             exp: parsed ? Number(r.readBigInt64LE(24)) : null, toBeSignedSha256: parsed ? r.subarray(32, 64).toString("hex") : null,
+             credSubjSha256: parsed && (r.readUInt32LE(12) & 1) ? r.subarray(64, 96).toString("hex") : null };
+  });
+}
+// nzcp.passPublicSignals(result): the 513 public signals of NZCPPubIdentity for a pass, from one entry of verifyPassBatch:
+// what nzcpInput.expectedPublicSignals(uri) returns
+function passPublicSignals(result) {
+  if (!result || !result.toBeSignedSha256 || !result.credSubjSha256) throw new Error("passPublicSignals: the pass has no digests (malformed, or without givenName / familyName / dob)");
+  const bits = (hex) => Array.from(Buffer.from(hex, "hex")).flatMap((b) => [7, 6, 5, 4, 3, 2, 1, 0].map((k) => String((b >> k) & 1)));
+  return bits(result.credSubjSha256).concat(bits(result.toBeSignedSha256), [String(result.exp)]);
+}
+
 // nzcp.verifyPassProof(vKey, [{proof, publicSignals, signature, iss, kid}], {keys, now, device = 0}) -> [{ok, reason}]: the
 // Groth16 proofs and the pass signatures (64 bytes r | s each, forwarded by the prover) in one
 // g16_nzcp_pass_proof_verify_batch; the digest a signature is checked against comes from the proof's public signals
@@ -680,6 +712,8 @@ const nzcp = {
     native().nzcpProgramFile(null, String(name), (params || []).map(Number), String(file));
   },
   verifyPass,
+  verifyPassBatch,
+  passPublicSignals,
   verifyPassProof,
   PASS_REASONS,
 };
