@@ -1,11 +1,17 @@
-// What a one-shot device route owns (host code only): device buffers, its stream, its timing events, its status.
-// THE RULE, for every route: whatever work on the stream reads or writes -- a DeviceBuf, a NttTablesOwned, a MsmJob --
-// is declared AHEAD of the DeviceStream.  Destructors run in reverse order, the stream's waits for its work and then
-// destroys it, so the stream has drained before anything is freed, on every path out of the route.
+// What device code's host side owns: device and pinned buffers, its stream, its timing events, its status.
+// THE RULE, for every one-shot route: whatever work on the stream reads or writes -- a DeviceBuf, a NttTablesOwned, a
+// MsmJob -- is declared AHEAD of the DeviceStream.  Destructors run in reverse order, the stream's waits for its work and
+// then destroys it, so the stream has drained before anything is freed, on every path out of the route.
+// ... and for every long-lived handle (a verifier, a witness checker or calculator): the members that work on its stream
+// touches -- DeviceBuf, PinnedBuf, PhaseEvents -- come BEFORE its DeviceStream member, and the handle's destructor body
+// does hipSetDevice(device) and nothing else: the members release themselves, the stream first.  A batch entry holds a
+// StreamDrain from its first enqueue to its own successful wait, so that no failing call returns while the stream still
+// reads or writes the caller's memory, or a temporary of the entry's.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/g16_prover.h"
 
@@ -52,7 +58,32 @@ template <class T> struct DeviceBuf {
   DeviceBuf& operator=(const DeviceBuf&) = delete;
   ~DeviceBuf() { reset(); }
   void reset() { if (p) (void)hipFree(p); p = nullptr; }
-  hipError_t alloc(size_t count) { reset(); return hipMalloc(&p, (count ? count : 1) * sizeof(T)); }   // (never empty)
+  hipError_t alloc(size_t count) {   // (never empty; frees what it held first; null when it fails)
+    reset();
+    const hipError_t e = hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
+    if (e != hipSuccess) p = nullptr;
+    return e;
+  }
+};
+// src on the device, in an allocation one element larger than src (so an empty array still has an address)
+template <class T> hipError_t upload(DeviceBuf<T>& dst, const std::vector<T>& src) {
+  const hipError_t e = dst.alloc(src.size() + 1);
+  return e != hipSuccess || src.empty() ? e : hipMemcpy(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+template <class T> struct PinnedBuf {   // page-locked host memory, as DeviceBuf
+  T* p = nullptr;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf() { reset(); }
+  void reset() { if (p) (void)hipHostFree(p); p = nullptr; }
+  hipError_t alloc(size_t count) {
+    reset();
+    const hipError_t e = hipHostMalloc((void**)&p, (count ? count : 1) * sizeof(T), hipHostMallocDefault);
+    if (e != hipSuccess) p = nullptr;
+    return e;
+  }
 };
 
 struct DeviceStream {
@@ -61,8 +92,58 @@ struct DeviceStream {
   DeviceStream(const DeviceStream&) = delete;
   DeviceStream& operator=(const DeviceStream&) = delete;
   ~DeviceStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
-  hipError_t create() { return hipStreamCreate(&s); }
+  hipError_t create() {
+    const hipError_t e = hipStreamCreate(&s);
+    if (e != hipSuccess) s = nullptr;
+    return e;
+  }
   operator hipStream_t() const { return s; }
+};
+
+// waits for a stream when its scope ends, unless the scope reached its own successful wait and said so
+struct StreamDrain {
+  hipStream_t s;
+  bool armed = true;
+  explicit StreamDrain(hipStream_t st) : s(st) {}
+  StreamDrain(const StreamDrain&) = delete;
+  StreamDrain& operator=(const StreamDrain&) = delete;
+  ~StreamDrain() { if (armed) (void)hipStreamSynchronize(s); }
+  void dismiss() { armed = false; }
+};
+
+struct DeviceEvent {   // one event: a hand-over to another stream or to the host
+  hipEvent_t e = nullptr;
+  DeviceEvent() = default;
+  DeviceEvent(const DeviceEvent&) = delete;
+  DeviceEvent& operator=(const DeviceEvent&) = delete;
+  ~DeviceEvent() { if (e) (void)hipEventDestroy(e); }
+  hipError_t create() {
+    const hipError_t r = hipEventCreate(&e);
+    if (r != hipSuccess) e = nullptr;
+    return r;
+  }
+  hipError_t record(hipStream_t st) { return hipEventRecord(e, st); }
+};
+
+template <int N> struct PhaseEvents {   // the N + 1 events around the N phases of a batch
+  static_assert(N >= 1, "PhaseEvents times phases; a single event is a DeviceEvent");
+  hipEvent_t e[N + 1] = {};
+  PhaseEvents() = default;
+  PhaseEvents(const PhaseEvents&) = delete;
+  PhaseEvents& operator=(const PhaseEvents&) = delete;
+  ~PhaseEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  hipError_t create() {
+    for (hipEvent_t& x : e) {
+      const hipError_t r = hipEventCreate(&x);
+      if (r != hipSuccess) { x = nullptr; return r; }
+    }
+    return hipSuccess;
+  }
+  hipError_t record(int k, hipStream_t st) { return hipEventRecord(e[k], st); }
+  float ms(int k) const {   // phase k, once the stream has passed event k + 1; 0 when it cannot be read
+    float v = 0.f;
+    return hipEventElapsedTime(&v, e[k], e[k + 1]) == hipSuccess ? v : 0.f;
+  }
 };
 
 struct DeviceTimer {   // two events around a stretch of a stream's work

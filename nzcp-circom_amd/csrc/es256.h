@@ -107,6 +107,8 @@ struct Es256Scratch {
 };
 int es256_device_scratch(Es256Device* d, size_t count, Es256Scratch* out);
 int es256_device_launch_resident(Es256Device* d, size_t count);
+// ... and when such a batch fails before its finish: wait for the handle's stream, nothing stays in flight
+void es256_device_abandon(Es256Device* d);
 
 }  // namespace g16
 

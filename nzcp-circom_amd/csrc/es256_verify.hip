@@ -15,6 +15,8 @@
 // are reachable and handled in p256_madd / p256_add; lanes that take them diverge from their wavefront for one addition.
 #include <hip/hip_runtime.h>
 
+#include <memory>
+
 #include "es256.h"
 #include "internal.h"
 
@@ -88,53 +90,39 @@ __global__ __launch_bounds__(64) void es256_op_kernel(int op, const uint8_t* __r
 struct Es256Device {
   int device = 0;
   uint32_t n_keys = 0;
-  P256Affine* d_tbl = nullptr;
+  DeviceBuf<P256Affine> d_tbl;
   // per-batch scratch, grown on demand
   size_t cap = 0;
-  uint8_t* d_hashes = nullptr;
-  uint8_t* d_sigs = nullptr;
-  uint32_t* d_key = nullptr;
-  uint32_t* d_u = nullptr;
-  uint8_t* d_live = nullptr;
-  uint8_t* d_ok = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[3] = {};
+  DeviceBuf<uint8_t> d_hashes, d_sigs;
+  DeviceBuf<uint32_t> d_key, d_u;
+  DeviceBuf<uint8_t> d_live, d_ok;
+  PhaseEvents<2> ev;
+  DeviceStream st;   // (device_job.h: after everything its work touches)
   size_t in_flight = 0;
-  ~Es256Device() {
-    (void)hipSetDevice(device);
-    if (st) (void)hipStreamSynchronize(st);
-    void* bufs[] = {d_tbl, d_hashes, d_sigs, d_key, d_u, d_live, d_ok};
-    for (void* p : bufs) if (p) (void)hipFree(p);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    if (st) (void)hipStreamDestroy(st);
-  }
+  ~Es256Device() { (void)hipSetDevice(device); }
 };
-
-static int device_create_impl(Es256Device* D, int device, const P256Affine* points, uint32_t n_points) {
-  D->device = device;
-  D->n_keys = n_points - 1;
-  G16_HIP(hipSetDevice(device));
-  G16_HIP(hipStreamCreate(&D->st));
-  for (auto& e : D->ev) G16_HIP(hipEventCreate(&e));
-  DeviceBuf<P256Affine> d_points;
-  G16_HIP(d_points.alloc(n_points));
-  G16_HIP(hipMalloc(&D->d_tbl, (size_t)n_points * kP256TblPoint * sizeof(P256Affine)));
-  G16_HIP(hipMemcpyAsync(d_points.p, points, (size_t)n_points * sizeof(P256Affine), hipMemcpyHostToDevice, D->st));
-  const uint32_t nt = n_points * kP256Win;
-  es256_table_kernel<<<(nt + kBlock - 1) / kBlock, kBlock, 0, D->st>>>(d_points.p, n_points, D->d_tbl);
-  G16_HIP(hipGetLastError());
-  G16_HIP(hipStreamSynchronize(D->st));
-  return G16_OK;
-}
 
 int es256_device_create(int device, const P256Affine* points, uint32_t n_points, Es256Device** out) {
   if (const int rc = require_hip_device(device, "es256 verifier: no HIP device (device -1 selects the host route)",
                                         "es256 verifier: bad device ordinal"))
     return rc;
-  Es256Device* D = new Es256Device();
-  const int rc = device_create_impl(D, device, points, n_points);
-  if (rc) { delete D; return rc; }
-  *out = D;
+  std::unique_ptr<Es256Device> D(new Es256Device());
+  D->device = device;
+  D->n_keys = n_points - 1;
+  G16_HIP(hipSetDevice(device));
+  G16_HIP(D->st.create());
+  G16_HIP(D->ev.create());
+  DeviceBuf<P256Affine> d_points;
+  G16_HIP(d_points.alloc(n_points));
+  G16_HIP(D->d_tbl.alloc((size_t)n_points * kP256TblPoint));
+  StreamDrain drain(D->st);   // (points is the caller's, d_points a temporary)
+  G16_HIP(hipMemcpyAsync(d_points.p, points, (size_t)n_points * sizeof(P256Affine), hipMemcpyHostToDevice, D->st));
+  const uint32_t nt = n_points * kP256Win;
+  es256_table_kernel<<<(nt + kBlock - 1) / kBlock, kBlock, 0, D->st>>>(d_points.p, n_points, D->d_tbl.p);
+  G16_HIP(hipGetLastError());
+  G16_HIP(hipStreamSynchronize(D->st));
+  drain.dismiss();
+  *out = D.release();
   return G16_OK;
 }
 
@@ -142,72 +130,79 @@ void es256_device_destroy(Es256Device* D) { delete D; }
 
 static int ensure_scratch(Es256Device* D, size_t count) {
   if (count <= D->cap) return G16_OK;
-  void** bufs[] = {(void**)&D->d_hashes, (void**)&D->d_sigs, (void**)&D->d_key, (void**)&D->d_u, (void**)&D->d_live, (void**)&D->d_ok};
-  for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
   D->cap = 0;
-  G16_HIP(hipMalloc(&D->d_hashes, count * 32));
-  G16_HIP(hipMalloc(&D->d_sigs, count * 64));
-  G16_HIP(hipMalloc(&D->d_key, count * 4));
-  G16_HIP(hipMalloc(&D->d_u, count * 64));
-  G16_HIP(hipMalloc(&D->d_live, count));
-  G16_HIP(hipMalloc(&D->d_ok, count));
+  G16_HIP(D->d_hashes.alloc(count * 32));
+  G16_HIP(D->d_sigs.alloc(count * 64));
+  G16_HIP(D->d_key.alloc(count));
+  G16_HIP(D->d_u.alloc(count * 16));
+  G16_HIP(D->d_live.alloc(count));
+  G16_HIP(D->d_ok.alloc(count));
   D->cap = count;
+  return G16_OK;
+}
+
+// a batch that cannot be finished: wait for what it enqueued and forget it
+void es256_device_abandon(Es256Device* D) {
+  (void)hipSetDevice(D->device);
+  (void)hipStreamSynchronize(D->st);
+  D->in_flight = 0;
+}
+
+// the two kernels over the digests, signatures and key indices in the scratch (key: NULL = key 0 for every signature)
+static int launch_scratch(Es256Device* D, const uint32_t* key, size_t count) {
+  const uint32_t n = (uint32_t)count;
+  hipStream_t st = D->st;
+  G16_HIP(D->ev.record(0, st));
+  es256_scalars_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, st>>>(D->d_hashes.p, D->d_sigs.p, n, D->d_u.p, D->d_live.p);
+  G16_HIP(D->ev.record(1, st));
+  const uint64_t lanes = (uint64_t)n * kEs256Lanes;
+  es256_sum_kernel<<<(uint32_t)((lanes + kBlock - 1) / kBlock), kBlock, 0, st>>>(D->d_tbl.p, D->d_u.p, D->d_live.p, D->d_sigs.p, key, n,
+                                                                                 D->d_ok.p);
+  G16_HIP(D->ev.record(2, st));
+  G16_HIP(hipGetLastError());
+  D->in_flight = count;
   return G16_OK;
 }
 
 int es256_device_launch(Es256Device* D, const uint8_t* hashes, const uint8_t* sigs, const uint32_t* key_idx, size_t count) {
   G16_HIP(hipSetDevice(D->device));
   if (const int rc = ensure_scratch(D, count)) return rc;
-  const uint32_t n = (uint32_t)count;
   hipStream_t st = D->st;
-  G16_HIP(hipMemcpyAsync(D->d_hashes, hashes, count * 32, hipMemcpyHostToDevice, st));
-  G16_HIP(hipMemcpyAsync(D->d_sigs, sigs, count * 64, hipMemcpyHostToDevice, st));
-  if (key_idx) G16_HIP(hipMemcpyAsync(D->d_key, key_idx, count * 4, hipMemcpyHostToDevice, st));
-  G16_HIP(hipEventRecord(D->ev[0], st));
-  es256_scalars_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, st>>>(D->d_hashes, D->d_sigs, n, D->d_u, D->d_live);
-  G16_HIP(hipEventRecord(D->ev[1], st));
-  const uint64_t lanes = (uint64_t)n * kEs256Lanes;
-  es256_sum_kernel<<<(uint32_t)((lanes + kBlock - 1) / kBlock), kBlock, 0, st>>>(D->d_tbl, D->d_u, D->d_live, D->d_sigs,
-                                                                                 key_idx ? D->d_key : nullptr, n, D->d_ok);
-  G16_HIP(hipEventRecord(D->ev[2], st));
-  G16_HIP(hipGetLastError());
-  D->in_flight = count;
+  D->in_flight = 0;
+  StreamDrain drain(st);   // (the host buffers are promised to a finish, which a failing launch does not get)
+  G16_HIP(hipMemcpyAsync(D->d_hashes.p, hashes, count * 32, hipMemcpyHostToDevice, st));
+  G16_HIP(hipMemcpyAsync(D->d_sigs.p, sigs, count * 64, hipMemcpyHostToDevice, st));
+  if (key_idx) G16_HIP(hipMemcpyAsync(D->d_key.p, key_idx, count * 4, hipMemcpyHostToDevice, st));
+  if (const int rc = launch_scratch(D, key_idx ? D->d_key.p : nullptr, count)) return rc;
+  drain.dismiss();
   return G16_OK;
 }
 
 int es256_device_scratch(Es256Device* D, size_t count, Es256Scratch* out) {
   G16_HIP(hipSetDevice(D->device));
   if (const int rc = ensure_scratch(D, count)) return rc;
-  *out = Es256Scratch{D->d_hashes, D->d_sigs, D->d_key, (void*)D->st};
+  *out = Es256Scratch{D->d_hashes.p, D->d_sigs.p, D->d_key.p, (void*)D->st.s};
   return G16_OK;
 }
 
 // the two kernels of es256_device_launch over digests, signatures and key indices that a kernel on the handle's stream
-// has written into the scratch (count <= the capacity es256_device_scratch was asked for)
+// has written into the scratch (count <= the capacity es256_device_scratch was asked for); the caller abandons the
+// batch if this fails
 int es256_device_launch_resident(Es256Device* D, size_t count) {
   G16_HIP(hipSetDevice(D->device));
   if (count > D->cap) { set_error("es256 verify: the resident batch is larger than the scratch"); return G16_E_STATE; }
-  const uint32_t n = (uint32_t)count;
-  hipStream_t st = D->st;
-  G16_HIP(hipEventRecord(D->ev[0], st));
-  es256_scalars_kernel<<<(n + kBlock - 1) / kBlock, kBlock, 0, st>>>(D->d_hashes, D->d_sigs, n, D->d_u, D->d_live);
-  G16_HIP(hipEventRecord(D->ev[1], st));
-  const uint64_t lanes = (uint64_t)n * kEs256Lanes;
-  es256_sum_kernel<<<(uint32_t)((lanes + kBlock - 1) / kBlock), kBlock, 0, st>>>(D->d_tbl, D->d_u, D->d_live, D->d_sigs, D->d_key, n,
-                                                                                 D->d_ok);
-  G16_HIP(hipEventRecord(D->ev[2], st));
-  G16_HIP(hipGetLastError());
-  D->in_flight = count;
-  return G16_OK;
+  return launch_scratch(D, D->d_key.p, count);
 }
 
 int es256_device_finish(Es256Device* D, uint8_t* ok, float ms[2]) {
   G16_HIP(hipSetDevice(D->device));
   const size_t count = D->in_flight;
   D->in_flight = 0;
-  G16_HIP(hipMemcpyAsync(ok, D->d_ok, count, hipMemcpyDeviceToHost, D->st));
+  StreamDrain drain(D->st);   // (ok is the caller's)
+  G16_HIP(hipMemcpyAsync(ok, D->d_ok.p, count, hipMemcpyDeviceToHost, D->st));
   G16_HIP(hipStreamSynchronize(D->st));
-  for (int k = 0; k < 2; k++) (void)hipEventElapsedTime(&ms[k], D->ev[k], D->ev[k + 1]);
+  drain.dismiss();
+  for (int k = 0; k < 2; k++) ms[k] = D->ev.ms(k);
   return G16_OK;
 }
 

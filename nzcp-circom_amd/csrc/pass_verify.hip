@@ -16,6 +16,8 @@
 // A pass whose verdict is decided gets a zero signature: the range check of es256_scalars_kernel retires its lanes.
 #include <hip/hip_runtime.h>
 
+#include <memory>
+
 #include "internal.h"
 #include "pass_verify.h"
 
@@ -92,42 +94,33 @@ __global__ __launch_bounds__(64) void pass_op_kernel(int op, const uint8_t* __re
 
 }  // namespace
 
+// (device_job.h) No stream of its own: a batch runs on the ES256 handle's, and pass_device_batch leaves on no path
+// before that stream has passed the batch, so nothing is at work on these members between calls
 struct PassDevice {
   int device = 0;
   uint32_t n_keys = 0;
-  PassKeyName* d_keys = nullptr;
+  DeviceBuf<PassKeyName> d_keys;
   // per-batch scratch, grown on demand
   size_t cap = 0, text_cap = 0;
-  uint64_t* d_offsets = nullptr;
-  g16_pass_result* d_records = nullptr;
-  uint8_t* d_text = nullptr;
-  hipEvent_t ev[2] = {};
-  ~PassDevice() {
-    (void)hipSetDevice(device);
-    void* bufs[] = {d_keys, d_offsets, d_records, d_text};
-    for (void* p : bufs) if (p) (void)hipFree(p);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-  }
+  DeviceBuf<uint64_t> d_offsets;
+  DeviceBuf<g16_pass_result> d_records;
+  DeviceBuf<uint8_t> d_text;
+  PhaseEvents<1> ev;
+  ~PassDevice() { (void)hipSetDevice(device); }
 };
-
-static int device_create_impl(PassDevice* D, int device, const PassKeyName* names, uint32_t n_keys) {
-  D->device = device;
-  D->n_keys = n_keys;
-  G16_HIP(hipSetDevice(device));
-  for (auto& e : D->ev) G16_HIP(hipEventCreate(&e));
-  G16_HIP(hipMalloc(&D->d_keys, (size_t)n_keys * sizeof(PassKeyName)));
-  G16_HIP(hipMemcpy(D->d_keys, names, (size_t)n_keys * sizeof(PassKeyName), hipMemcpyHostToDevice));
-  return G16_OK;
-}
 
 int pass_device_create(int device, const PassKeyName* names, uint32_t n_keys, PassDevice** out) {
   if (const int rc = require_hip_device(device, "pass verifier: no HIP device (device -1 selects the host route)",
                                         "pass verifier: bad device ordinal"))
     return rc;
-  PassDevice* D = new PassDevice();
-  const int rc = device_create_impl(D, device, names, n_keys);
-  if (rc) { delete D; return rc; }
-  *out = D;
+  std::unique_ptr<PassDevice> D(new PassDevice());
+  D->device = device;
+  D->n_keys = n_keys;
+  G16_HIP(hipSetDevice(device));
+  G16_HIP(D->ev.create());
+  G16_HIP(D->d_keys.alloc(n_keys));
+  G16_HIP(hipMemcpy(D->d_keys.p, names, (size_t)n_keys * sizeof(PassKeyName), hipMemcpyHostToDevice));
+  *out = D.release();
   return G16_OK;
 }
 
@@ -135,19 +128,34 @@ void pass_device_destroy(PassDevice* D) { delete D; }
 
 static int ensure_scratch(PassDevice* D, size_t count, size_t text_bytes) {
   if (count > D->cap) {
-    if (D->d_offsets) { (void)hipFree(D->d_offsets); D->d_offsets = nullptr; }
-    if (D->d_records) { (void)hipFree(D->d_records); D->d_records = nullptr; }
     D->cap = 0;
-    G16_HIP(hipMalloc(&D->d_offsets, (count + 1) * sizeof(uint64_t)));
-    G16_HIP(hipMalloc(&D->d_records, count * sizeof(g16_pass_result)));
+    G16_HIP(D->d_offsets.alloc(count + 1));
+    G16_HIP(D->d_records.alloc(count));
     D->cap = count;
   }
   if (text_bytes > D->text_cap) {
-    if (D->d_text) { (void)hipFree(D->d_text); D->d_text = nullptr; }
     D->text_cap = 0;
-    G16_HIP(hipMalloc(&D->d_text, text_bytes));
+    G16_HIP(D->d_text.alloc(text_bytes));
     D->text_cap = text_bytes;
   }
+  return G16_OK;
+}
+
+// the front end, then the signature kernels, on the ES256 handle's stream (enqueue only)
+static int pass_enqueue(PassDevice* D, Es256Device* es, const Es256Scratch& sc, const uint8_t* text, const uint64_t* offsets,
+                        size_t count, g16_pass_result* records) {
+  hipStream_t st = (hipStream_t)sc.stream;
+  const uint32_t n = (uint32_t)count;
+  const size_t text_bytes = (size_t)(offsets[count] - offsets[0]);
+  G16_HIP(hipMemcpyAsync(D->d_offsets.p, offsets, (count + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  if (text_bytes) G16_HIP(hipMemcpyAsync(D->d_text.p, text + offsets[0], text_bytes, hipMemcpyHostToDevice, st));
+  G16_HIP(D->ev.record(0, st));
+  pass_front_kernel<<<(n + kPassPerBlock - 1) / kPassPerBlock, kBlock, 0, st>>>(D->d_text.p, D->d_offsets.p, n, D->d_keys.p, D->n_keys,
+                                                                                D->d_records.p, sc.hashes, sc.sigs, sc.key_idx);
+  G16_HIP(D->ev.record(1, st));
+  G16_HIP(hipGetLastError());
+  if (const int rc = es256_device_launch_resident(es, count)) return rc;
+  G16_HIP(hipMemcpyAsync(records, D->d_records.p, count * sizeof(g16_pass_result), hipMemcpyDeviceToHost, st));
   return G16_OK;
 }
 
@@ -158,19 +166,12 @@ int pass_device_batch(PassDevice* D, Es256Device* es, const uint8_t* text, const
   if (const int rc = ensure_scratch(D, count, text_bytes ? text_bytes : 1)) return rc;
   Es256Scratch sc;
   if (const int rc = es256_device_scratch(es, count, &sc)) return rc;
-  hipStream_t st = (hipStream_t)sc.stream;
-  const uint32_t n = (uint32_t)count;
-  G16_HIP(hipMemcpyAsync(D->d_offsets, offsets, (count + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  if (text_bytes) G16_HIP(hipMemcpyAsync(D->d_text, text + offsets[0], text_bytes, hipMemcpyHostToDevice, st));
-  G16_HIP(hipEventRecord(D->ev[0], st));
-  pass_front_kernel<<<(n + kPassPerBlock - 1) / kPassPerBlock, kBlock, 0, st>>>(D->d_text, D->d_offsets, n, D->d_keys, D->n_keys,
-                                                                                D->d_records, sc.hashes, sc.sigs, sc.key_idx);
-  G16_HIP(hipEventRecord(D->ev[1], st));
-  G16_HIP(hipGetLastError());
-  if (const int rc = es256_device_launch_resident(es, count)) return rc;
-  G16_HIP(hipMemcpyAsync(records, D->d_records, count * sizeof(g16_pass_result), hipMemcpyDeviceToHost, st));
-  if (const int rc = es256_device_finish(es, ok, ms + 1)) return rc;   // (waits for the stream)
-  (void)hipEventElapsedTime(&ms[0], D->ev[0], D->ev[1]);
+  if (const int rc = pass_enqueue(D, es, sc, text, offsets, count, records)) {
+    es256_device_abandon(es);   // (text, offsets and records are the caller's; the scratch is the ES256 handle's)
+    return rc;
+  }
+  if (const int rc = es256_device_finish(es, ok, ms + 1)) return rc;   // (waits for the stream, also when it fails)
+  ms[0] = D->ev.ms(0);
   return G16_OK;
 }
 

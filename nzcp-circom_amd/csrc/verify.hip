@@ -23,6 +23,7 @@
 // throughput comes from the batch size (BASELINE config 3's 1 024 proofs fill 48 + 16 wavefronts).
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -221,30 +222,21 @@ struct g16_verifier {
   uint32_t n_public = 0;
   PairingConsts pc;
   Fq12 ml_alphabeta;
-  G1Affine* d_ic = nullptr;
-  G1Affine* d_tbl = nullptr;
-  EllCoeffs* d_co_gamma = nullptr;
-  EllCoeffs* d_co_delta = nullptr;
+  DeviceBuf<G1Affine> d_ic, d_tbl;
+  DeviceBuf<EllCoeffs> d_co_gamma, d_co_delta;
   // per-batch scratch, grown on demand
   size_t cap = 0;
-  g16_proof* d_raw = nullptr;
-  ProofM* d_proofs = nullptr;
-  uint32_t* d_flags = nullptr;
-  uint32_t* d_pub = nullptr;
-  G1Affine* d_vkx = nullptr;
-  Fq12* d_ml = nullptr;
-  uint8_t* d_ok = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[4] = {};
+  DeviceBuf<g16_proof> d_raw;
+  DeviceBuf<ProofM> d_proofs;
+  DeviceBuf<uint32_t> d_flags, d_pub;
+  DeviceBuf<G1Affine> d_vkx;
+  DeviceBuf<Fq12> d_ml;
+  DeviceBuf<uint8_t> d_ok;
+  PhaseEvents<3> ev;
+  DeviceStream st;                // (device_job.h: after everything its work touches)
   float last_ms[3] = {0, 0, 0};   // vk_x, Miller loops, final exponentiation of the last batch
   std::mutex mu;
-  ~g16_verifier() {
-    (void)hipSetDevice(device);
-    void* bufs[] = {d_ic, d_tbl, d_co_gamma, d_co_delta, d_raw, d_proofs, d_flags, d_pub, d_vkx, d_ml, d_ok};
-    for (void* p : bufs) if (p) (void)hipFree(p);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    if (st) (void)hipStreamDestroy(st);
-  }
+  ~g16_verifier() { (void)hipSetDevice(device); }
 };
 
 static bool fq_canonical(const uint8_t* p) {
@@ -264,9 +256,7 @@ static int verifier_create_impl(const uint8_t* vkey, size_t vkey_len, uint32_t n
               std::to_string(n_public) + "]), got " + std::to_string(vkey_len));
     return G16_E_FORMAT;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device: the verifier has no CPU path"); return G16_E_NOGPU; }
-  if (device < 0 || device >= ndev) { set_error("bad device ordinal"); return G16_E_ARG; }
+  if (const int rc = require_hip_device(device, "no HIP device: the verifier has no CPU path", "bad device ordinal")) return rc;
   V->device = device;
   V->n_public = n_public;
   // every coordinate as a Montgomery Fq
@@ -298,20 +288,22 @@ static int verifier_create_impl(const uint8_t* vkey, size_t vkey_len, uint32_t n
   g2_precompute(delta, V->pc, cd.data());
   V->ml_alphabeta = miller_loop(alpha, beta, V->pc);
   G16_HIP(hipSetDevice(device));
-  G16_HIP(hipStreamCreate(&V->st));
-  for (auto& e : V->ev) G16_HIP(hipEventCreate(&e));
+  G16_HIP(V->st.create());
+  G16_HIP(V->ev.create());
   const size_t tbl_n = (size_t)(n_public + 1) * kIcWin * kIcRow;
-  G16_HIP(hipMalloc(&V->d_ic, ic.size() * sizeof(G1Affine)));
-  G16_HIP(hipMalloc(&V->d_tbl, tbl_n * sizeof(G1Affine)));
-  G16_HIP(hipMalloc(&V->d_co_gamma, kEllSteps * sizeof(EllCoeffs)));
-  G16_HIP(hipMalloc(&V->d_co_delta, kEllSteps * sizeof(EllCoeffs)));
-  G16_HIP(hipMemcpyAsync(V->d_ic, ic.data(), ic.size() * sizeof(G1Affine), hipMemcpyHostToDevice, V->st));
-  G16_HIP(hipMemcpyAsync(V->d_co_gamma, cg.data(), kEllSteps * sizeof(EllCoeffs), hipMemcpyHostToDevice, V->st));
-  G16_HIP(hipMemcpyAsync(V->d_co_delta, cd.data(), kEllSteps * sizeof(EllCoeffs), hipMemcpyHostToDevice, V->st));
+  G16_HIP(V->d_ic.alloc(ic.size()));
+  G16_HIP(V->d_tbl.alloc(tbl_n));
+  G16_HIP(V->d_co_gamma.alloc(kEllSteps));
+  G16_HIP(V->d_co_delta.alloc(kEllSteps));
+  StreamDrain drain(V->st);   // (ic, cg and cd are host temporaries)
+  G16_HIP(hipMemcpyAsync(V->d_ic.p, ic.data(), ic.size() * sizeof(G1Affine), hipMemcpyHostToDevice, V->st));
+  G16_HIP(hipMemcpyAsync(V->d_co_gamma.p, cg.data(), kEllSteps * sizeof(EllCoeffs), hipMemcpyHostToDevice, V->st));
+  G16_HIP(hipMemcpyAsync(V->d_co_delta.p, cd.data(), kEllSteps * sizeof(EllCoeffs), hipMemcpyHostToDevice, V->st));
   const uint32_t nt = (n_public + 1) * kIcWin;
-  verify_ic_table_kernel<<<(nt + 63) / 64, 64, 0, V->st>>>(V->d_ic, n_public + 1, V->d_tbl);
+  verify_ic_table_kernel<<<(nt + 63) / 64, 64, 0, V->st>>>(V->d_ic.p, n_public + 1, V->d_tbl.p);
   G16_HIP(hipGetLastError());
   G16_HIP(hipStreamSynchronize(V->st));
+  drain.dismiss();
   return G16_OK;
 }
 
@@ -319,26 +311,22 @@ extern "C" int g16_verifier_create(const uint8_t* vkey, size_t vkey_len, uint32_
                                    g16_verifier** out) {
   if (!vkey || !out) { set_error("NULL argument"); return G16_E_ARG; }
   if (n_public > (1u << 20)) { set_error("verification key: too many public signals"); return G16_E_ARG; }
-  g16_verifier* V = new g16_verifier();
-  const int rc = verifier_create_impl(vkey, vkey_len, n_public, montgomery, device, V);
-  if (rc) { delete V; return rc; }
-  *out = V;
+  std::unique_ptr<g16_verifier> V(new g16_verifier());
+  if (const int rc = verifier_create_impl(vkey, vkey_len, n_public, montgomery, device, V.get())) return rc;
+  *out = V.release();
   return G16_OK;
 }
 
 static int ensure_scratch(g16_verifier* V, size_t count) {
   if (count <= V->cap) return G16_OK;
-  void** bufs[] = {(void**)&V->d_raw, (void**)&V->d_proofs, (void**)&V->d_flags, (void**)&V->d_pub, (void**)&V->d_vkx,
-                   (void**)&V->d_ml, (void**)&V->d_ok};
-  for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
   V->cap = 0;
-  G16_HIP(hipMalloc(&V->d_raw, count * sizeof(g16_proof)));
-  G16_HIP(hipMalloc(&V->d_proofs, count * sizeof(ProofM)));
-  G16_HIP(hipMalloc(&V->d_flags, count * 4));
-  G16_HIP(hipMalloc(&V->d_pub, count * (size_t)(V->n_public ? V->n_public : 1) * 32));
-  G16_HIP(hipMalloc(&V->d_vkx, count * sizeof(G1Affine)));
-  G16_HIP(hipMalloc(&V->d_ml, count * 3 * sizeof(Fq12)));
-  G16_HIP(hipMalloc(&V->d_ok, count));
+  G16_HIP(V->d_raw.alloc(count));
+  G16_HIP(V->d_proofs.alloc(count));
+  G16_HIP(V->d_flags.alloc(count));
+  G16_HIP(V->d_pub.alloc(count * (size_t)(V->n_public ? V->n_public : 1) * 8));   // (32-byte words)
+  G16_HIP(V->d_vkx.alloc(count));
+  G16_HIP(V->d_ml.alloc(count * 3));
+  G16_HIP(V->d_ok.alloc(count));
   V->cap = count;
   return G16_OK;
 }
@@ -353,21 +341,23 @@ extern "C" int g16_verify_batch(g16_verifier* V, const g16_proof* proofs, const 
   if (rc) return rc;
   const uint32_t n = (uint32_t)count;
   hipStream_t st = V->st;
-  G16_HIP(hipMemcpyAsync(V->d_raw, proofs, count * sizeof(g16_proof), hipMemcpyHostToDevice, st));
-  if (V->n_public) G16_HIP(hipMemcpyAsync(V->d_pub, pubs, count * (size_t)V->n_public * 32, hipMemcpyHostToDevice, st));
-  G16_HIP(hipEventRecord(V->ev[0], st));
-  verify_load_kernel<<<(n + 63) / 64, 64, 0, st>>>(V->d_raw, n, V->pc, V->d_proofs, V->d_flags);
-  verify_vkx_kernel<<<n, 256, 0, st>>>(V->d_ic, V->d_tbl, V->d_pub, V->n_public, V->d_vkx);
-  G16_HIP(hipEventRecord(V->ev[1], st));
-  verify_miller_kernel<<<dim3((n + 63) / 64, 3), 64, 0, st>>>(V->d_proofs, V->d_flags, V->d_vkx, V->d_co_gamma,
-                                                              V->d_co_delta, n, V->pc, V->d_ml);
-  G16_HIP(hipEventRecord(V->ev[2], st));
-  verify_final_kernel<<<(n + 63) / 64, 64, 0, st>>>(V->d_ml, V->d_flags, n, V->pc, V->ml_alphabeta, V->d_ok);
-  G16_HIP(hipEventRecord(V->ev[3], st));
+  StreamDrain drain(st);   // (proofs, pubs and ok are the caller's)
+  G16_HIP(hipMemcpyAsync(V->d_raw.p, proofs, count * sizeof(g16_proof), hipMemcpyHostToDevice, st));
+  if (V->n_public) G16_HIP(hipMemcpyAsync(V->d_pub.p, pubs, count * (size_t)V->n_public * 32, hipMemcpyHostToDevice, st));
+  G16_HIP(V->ev.record(0, st));
+  verify_load_kernel<<<(n + 63) / 64, 64, 0, st>>>(V->d_raw.p, n, V->pc, V->d_proofs.p, V->d_flags.p);
+  verify_vkx_kernel<<<n, 256, 0, st>>>(V->d_ic.p, V->d_tbl.p, V->d_pub.p, V->n_public, V->d_vkx.p);
+  G16_HIP(V->ev.record(1, st));
+  verify_miller_kernel<<<dim3((n + 63) / 64, 3), 64, 0, st>>>(V->d_proofs.p, V->d_flags.p, V->d_vkx.p, V->d_co_gamma.p,
+                                                              V->d_co_delta.p, n, V->pc, V->d_ml.p);
+  G16_HIP(V->ev.record(2, st));
+  verify_final_kernel<<<(n + 63) / 64, 64, 0, st>>>(V->d_ml.p, V->d_flags.p, n, V->pc, V->ml_alphabeta, V->d_ok.p);
+  G16_HIP(V->ev.record(3, st));
   G16_HIP(hipGetLastError());
-  G16_HIP(hipMemcpyAsync(ok, V->d_ok, count, hipMemcpyDeviceToHost, st));
+  G16_HIP(hipMemcpyAsync(ok, V->d_ok.p, count, hipMemcpyDeviceToHost, st));
   G16_HIP(hipStreamSynchronize(st));
-  for (int k = 0; k < 3; k++) (void)hipEventElapsedTime(&V->last_ms[k], V->ev[k], V->ev[k + 1]);
+  drain.dismiss();
+  for (int k = 0; k < 3; k++) V->last_ms[k] = V->ev.ms(k);
   return G16_OK;
 }
 

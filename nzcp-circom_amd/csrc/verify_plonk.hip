@@ -18,6 +18,7 @@
 //   pv_miller_kernel a lane per (proof, pairing); pv_final_kernel a lane per proof: product, final exponentiation, == 1
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -124,21 +125,16 @@ struct g16_plonk_verifier {
   Fr k1, k2, w1;                 // Montgomery
   G1Affine cm[8];                // Qm Ql Qr Qo Qc S1 S2 S3, Montgomery affine
   PairingConsts pc;
-  EllCoeffs *d_co_x2 = nullptr, *d_co_g2 = nullptr;
+  DeviceBuf<EllCoeffs> d_co_x2, d_co_g2;
   size_t cap = 0;
-  G1Affine *d_bases = nullptr, *d_pts = nullptr;
-  Fr* d_scal = nullptr;
-  G1XYZZ* d_terms = nullptr;
-  Fq12* d_ml = nullptr;
-  uint8_t *d_rej = nullptr, *d_ok = nullptr;
-  hipStream_t st = nullptr;
+  DeviceBuf<G1Affine> d_bases, d_pts;
+  DeviceBuf<Fr> d_scal;
+  DeviceBuf<G1XYZZ> d_terms;
+  DeviceBuf<Fq12> d_ml;
+  DeviceBuf<uint8_t> d_rej, d_ok;
+  DeviceStream st;   // (device_job.h: after everything its work touches)
   std::mutex mu;
-  ~g16_plonk_verifier() {
-    (void)hipSetDevice(device);
-    void* v[] = {d_co_x2, d_co_g2, d_bases, d_pts, d_scal, d_terms, d_ml, d_rej, d_ok};
-    for (void* p : v) if (p) (void)hipFree(p);
-    if (st) (void)hipStreamDestroy(st);
-  }
+  ~g16_plonk_verifier() { (void)hipSetDevice(device); }
 };
 
 static bool fq_word_ok(const uint8_t* p) {
@@ -161,52 +157,49 @@ extern "C" int g16_plonk_verifier_create(const uint8_t* vkey, size_t vkey_len, i
   if (!vkey || !out) { set_error("NULL argument"); return G16_E_ARG; }
   const size_t need = 8 + 64 + 8 * 64 + 128;
   if (vkey_len != need) { set_error("plonk verification key: expected " + std::to_string(need) + " bytes"); return G16_E_FORMAT; }
-  g16_plonk_verifier* V = new g16_plonk_verifier();
-  auto fail = [&](int rc) { delete V; return rc; };
+  std::unique_ptr<g16_plonk_verifier> V(new g16_plonk_verifier());
   memcpy(&V->power, vkey, 4);
   memcpy(&V->n_public, vkey + 4, 4);
-  if (V->power < 2 || V->power > 28) { set_error("plonk verification key: power out of range"); return fail(G16_E_FORMAT); }
+  if (V->power < 2 || V->power > 28) { set_error("plonk verification key: power out of range"); return G16_E_FORMAT; }
   static const uint32_t kR[8] = G16_FR_P;
   for (int k = 0; k < 2; k++) {
     Fr x;
     memcpy(x.v, vkey + 8 + 32 * k, 32);
-    if (!lt_words(x.v, kR)) { set_error("plonk verification key: k1 / k2 not below r"); return fail(G16_E_FORMAT); }
+    if (!lt_words(x.v, kR)) { set_error("plonk verification key: k1 / k2 not below r"); return G16_E_FORMAT; }
     (k ? V->k2 : V->k1) = fp_to_mont(x);
   }
   for (int k = 0; k < 8; k++)
-    if (!read_g1_std(vkey + 72 + 64 * k, &V->cm[k])) { set_error("plonk verification key: a commitment is not a curve point"); return fail(G16_E_FORMAT); }
+    if (!read_g1_std(vkey + 72 + 64 * k, &V->cm[k])) { set_error("plonk verification key: a commitment is not a curve point"); return G16_E_FORMAT; }
   pairing_consts_init(V->pc);
   G2Affine x2;
   {
     const uint8_t* p = vkey + 72 + 512;
     Fq c[4];
     for (int k = 0; k < 4; k++) {
-      if (!fq_word_ok(p + 32 * k)) { set_error("plonk verification key: X_2 coordinate not below q"); return fail(G16_E_FORMAT); }
+      if (!fq_word_ok(p + 32 * k)) { set_error("plonk verification key: X_2 coordinate not below q"); return G16_E_FORMAT; }
       Fq x;
       memcpy(x.v, p + 32 * k, 32);
       c[k] = fp_to_mont(x);
     }
     x2 = G2Affine{Fq2{c[0], c[1]}, Fq2{c[2], c[3]}};
-    if (aff_is_inf(x2) || !g2_on_curve(x2, V->pc)) { set_error("plonk verification key: X_2 is not a point of the twist"); return fail(G16_E_FORMAT); }
+    if (aff_is_inf(x2) || !g2_on_curve(x2, V->pc)) { set_error("plonk verification key: X_2 is not a point of the twist"); return G16_E_FORMAT; }
   }
   V->w1 = root_of_unity(V->power);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device: the PLONK verifier has no CPU path"); return fail(G16_E_NOGPU); }
-  if (device < 0 || device >= ndev) { set_error("bad device ordinal"); return fail(G16_E_ARG); }
+  if (const int rc = require_hip_device(device, "no HIP device: the PLONK verifier has no CPU path", "bad device ordinal")) return rc;
   V->device = device;
   G2Affine g2;
   g2.x.a = Fq{G16_G2X0}; g2.x.b = Fq{G16_G2X1}; g2.y.a = Fq{G16_G2Y0}; g2.y.b = Fq{G16_G2Y1};
   std::vector<EllCoeffs> cx(kEllSteps), cg(kEllSteps);
   g2_precompute(x2, V->pc, cx.data());
   g2_precompute(g2, V->pc, cg.data());
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&V->st) != hipSuccess ||
-      hipMalloc(&V->d_co_x2, kEllSteps * sizeof(EllCoeffs)) != hipSuccess || hipMalloc(&V->d_co_g2, kEllSteps * sizeof(EllCoeffs)) != hipSuccess ||
-      hipMemcpy(V->d_co_x2, cx.data(), kEllSteps * sizeof(EllCoeffs), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(V->d_co_g2, cg.data(), kEllSteps * sizeof(EllCoeffs), hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipSetDevice(device) != hipSuccess || V->st.create() != hipSuccess ||
+      V->d_co_x2.alloc(kEllSteps) != hipSuccess || V->d_co_g2.alloc(kEllSteps) != hipSuccess ||
+      hipMemcpy(V->d_co_x2.p, cx.data(), kEllSteps * sizeof(EllCoeffs), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(V->d_co_g2.p, cg.data(), kEllSteps * sizeof(EllCoeffs), hipMemcpyHostToDevice) != hipSuccess) {
     set_error("plonk verifier: HIP initialisation failed");
-    return fail(G16_E_HIP);
+    return G16_E_HIP;
   }
-  *out = V;
+  *out = V.release();
   return G16_OK;
 }
 
@@ -378,31 +371,30 @@ extern "C" int g16_plonk_verify_batch(g16_plonk_verifier* V, const g16_plonk_pro
   }
   G16_HIP(hipSetDevice(V->device));
   if (count > V->cap) {
-    void** bufs[] = {(void**)&V->d_bases, (void**)&V->d_pts, (void**)&V->d_scal, (void**)&V->d_terms, (void**)&V->d_ml, (void**)&V->d_rej,
-                     (void**)&V->d_ok};
-    for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
     V->cap = 0;
-    G16_HIP(hipMalloc(&V->d_bases, count * kTerms * sizeof(G1Affine)));
-    G16_HIP(hipMalloc(&V->d_scal, count * kTerms * sizeof(Fr)));
-    G16_HIP(hipMalloc(&V->d_terms, count * kTerms * sizeof(G1XYZZ)));
-    G16_HIP(hipMalloc(&V->d_pts, count * 2 * sizeof(G1Affine)));
-    G16_HIP(hipMalloc(&V->d_ml, count * 2 * sizeof(Fq12)));
-    G16_HIP(hipMalloc(&V->d_rej, count));
-    G16_HIP(hipMalloc(&V->d_ok, count));
+    G16_HIP(V->d_bases.alloc(count * kTerms));
+    G16_HIP(V->d_scal.alloc(count * kTerms));
+    G16_HIP(V->d_terms.alloc(count * kTerms));
+    G16_HIP(V->d_pts.alloc(count * 2));
+    G16_HIP(V->d_ml.alloc(count * 2));
+    G16_HIP(V->d_rej.alloc(count));
+    G16_HIP(V->d_ok.alloc(count));
     V->cap = count;
   }
   hipStream_t st = V->st;
   const uint32_t n = (uint32_t)count, nt20 = n * kTerms;
-  G16_HIP(hipMemcpyAsync(V->d_bases, bases.data(), bases.size() * sizeof(G1Affine), hipMemcpyHostToDevice, st));
-  G16_HIP(hipMemcpyAsync(V->d_scal, scal.data(), scal.size() * sizeof(Fr), hipMemcpyHostToDevice, st));
-  G16_HIP(hipMemcpyAsync(V->d_rej, rej.data(), count, hipMemcpyHostToDevice, st));
-  pv_terms_kernel<<<(nt20 + 63) / 64, 64, 0, st>>>(V->d_bases, V->d_scal, nt20, V->d_terms);
-  pv_sum_kernel<<<(n + 63) / 64, 64, 0, st>>>(V->d_terms, n, V->d_pts);
-  pv_miller_kernel<<<dim3((n + 63) / 64, 2), 64, 0, st>>>(V->d_pts, V->d_rej, V->d_co_x2, V->d_co_g2, n, V->d_ml);
-  pv_final_kernel<<<(n + 63) / 64, 64, 0, st>>>(V->d_ml, V->d_rej, n, V->pc, V->d_ok);
+  StreamDrain drain(st);   // (bases / scal / rej are host temporaries, ok is the caller's)
+  G16_HIP(hipMemcpyAsync(V->d_bases.p, bases.data(), bases.size() * sizeof(G1Affine), hipMemcpyHostToDevice, st));
+  G16_HIP(hipMemcpyAsync(V->d_scal.p, scal.data(), scal.size() * sizeof(Fr), hipMemcpyHostToDevice, st));
+  G16_HIP(hipMemcpyAsync(V->d_rej.p, rej.data(), count, hipMemcpyHostToDevice, st));
+  pv_terms_kernel<<<(nt20 + 63) / 64, 64, 0, st>>>(V->d_bases.p, V->d_scal.p, nt20, V->d_terms.p);
+  pv_sum_kernel<<<(n + 63) / 64, 64, 0, st>>>(V->d_terms.p, n, V->d_pts.p);
+  pv_miller_kernel<<<dim3((n + 63) / 64, 2), 64, 0, st>>>(V->d_pts.p, V->d_rej.p, V->d_co_x2.p, V->d_co_g2.p, n, V->d_ml.p);
+  pv_final_kernel<<<(n + 63) / 64, 64, 0, st>>>(V->d_ml.p, V->d_rej.p, n, V->pc, V->d_ok.p);
   G16_HIP(hipGetLastError());
-  G16_HIP(hipMemcpyAsync(ok, V->d_ok, count, hipMemcpyDeviceToHost, st));
-  G16_HIP(hipStreamSynchronize(st));   // (bases / scal / rej are host temporaries)
+  G16_HIP(hipMemcpyAsync(ok, V->d_ok.p, count, hipMemcpyDeviceToHost, st));
+  G16_HIP(hipStreamSynchronize(st));
+  drain.dismiss();
   return G16_OK;
 }
 

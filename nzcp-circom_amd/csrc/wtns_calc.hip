@@ -21,6 +21,8 @@
 // proofs of chunk k run; each holds what the 4 GiB rule (or G16_WTNS_CALC_CHUNK) allows, so a batched fullprove takes at
 // most 2 x 4 GiB of device memory for witnesses (buffer 0 is the one g16_wtns_calc uses; both grow with the chunks
 // that arrive).
+#include <memory>
+
 #include "witness_program.h"
 
 namespace g16 {
@@ -61,123 +63,90 @@ __global__ __launch_bounds__(256) void wtns_gather_pub_kernel(const Fr* __restri
 // One set of batch buffers.  Set 0 serves g16_wtns_calc and g16_stage_inputs; the chunks of a batched fullprove
 // alternate between the two.
 struct WcalcBuf {
-  uint32_t cap = 0, cap_pub = 0;        // witnesses the buffers hold; ... the public-signal buffers
-  Fr *d_w = nullptr, *d_in = nullptr;   // cap * n_wires words; cap * n_inputs words
-  uint32_t *d_status = nullptr, *h_status = nullptr;   // cap words each; h_status pinned
-  Fr* d_pub = nullptr;                  // cap_pub * n_public words
-  uint8_t* h_pub = nullptr;             // ... pinned
-  hipEvent_t ready = nullptr;           // the last chunk's status words and public signals are on the host
+  uint32_t cap = 0, cap_pub = 0;   // witnesses the buffers hold; ... the public-signal buffers
+  DeviceBuf<Fr> d_w, d_in;         // cap * n_wires words; cap * n_inputs words
+  DeviceBuf<uint32_t> d_status;    // cap words
+  PinnedBuf<uint32_t> h_status;    // ... pinned
+  DeviceBuf<Fr> d_pub;             // cap_pub * n_public words
+  PinnedBuf<uint8_t> h_pub;        // ... pinned
+  DeviceEvent ready;               // the last chunk's status words and public signals are on the host
 };
 
 struct WcalcDevice {
   int device = 0;
   uint32_t n_wires = 0, n_inputs = 0, n_public = 0, n_levels = 0, chunk = 1;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   WcalcBuf buf[2];
-  WpOp* ops = nullptr;
-  WpEvalTerm* terms = nullptr;
-  Fr* coefs = nullptr;
-  int64_t* icoefs = nullptr;
-  Fr* inv_small = nullptr;
-  uint32_t *targets = nullptr, *levels = nullptr;
+  DeviceBuf<WpOp> ops;
+  DeviceBuf<WpEvalTerm> terms;
+  DeviceBuf<Fr> coefs;
+  DeviceBuf<int64_t> icoefs;
+  DeviceBuf<Fr> inv_small;
+  DeviceBuf<uint32_t> targets, levels;
+  PhaseEvents<3> ev;
+  DeviceStream st;   // (device_job.h: after everything its work touches)
+  ~WcalcDevice() { (void)hipSetDevice(device); }
 };
 
-template <class T> static int wcalc_upload(T** dst, const std::vector<T>& src) {
-  G16_HIP(hipMalloc(dst, (src.size() + 1) * sizeof(T)));
-  if (!src.empty()) G16_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return G16_OK;
-}
-
-static void wcalc_free_pub(WcalcBuf& b) {
-  (void)hipFree(b.d_pub);
-  if (b.h_pub) (void)hipHostFree(b.h_pub);
-  b.d_pub = nullptr;
-  b.h_pub = nullptr;
-  b.cap_pub = 0;
-}
-static void wcalc_free_batch(WcalcBuf& b) {
-  (void)hipFree(b.d_w); (void)hipFree(b.d_in); (void)hipFree(b.d_status);
-  if (b.h_status) (void)hipHostFree(b.h_status);
-  b.d_w = b.d_in = nullptr;
-  b.d_status = b.h_status = nullptr;
-  b.cap = 0;
-}
-
-void wcalc_device_destroy(WcalcDevice* d) {
-  if (!d) return;
-  (void)hipSetDevice(d->device);
-  if (d->st) (void)hipStreamSynchronize(d->st);
-  for (WcalcBuf& b : d->buf) {
-    wcalc_free_batch(b);
-    wcalc_free_pub(b);
-    if (b.ready) (void)hipEventDestroy(b.ready);
-  }
-  (void)hipFree(d->ops); (void)hipFree(d->terms); (void)hipFree(d->coefs); (void)hipFree(d->icoefs); (void)hipFree(d->inv_small);(void)hipFree(d->targets); (void)hipFree(d->levels);
-  for (hipEvent_t e : d->ev)
-    if (e) (void)hipEventDestroy(e);
-  if (d->st) (void)hipStreamDestroy(d->st);
-  delete d;
-}
+void wcalc_device_destroy(WcalcDevice* d) { delete d; }
 
 int wcalc_device_id(const WcalcDevice* d) { return d->device; }
 
 // the batch buffers hold `cap` witnesses; they grow to the largest chunk asked for (at most d->chunk)
 static int wcalc_reserve(WcalcDevice* d, WcalcBuf& b, uint32_t cnt) {
   if (cnt <= b.cap) return G16_OK;
-  wcalc_free_batch(b);
-  G16_HIP(hipMalloc(&b.d_w, ((size_t)cnt * d->n_wires + 1) * sizeof(Fr)));
-  G16_HIP(hipMalloc(&b.d_in, ((size_t)cnt * d->n_inputs + 1) * sizeof(Fr)));
-  G16_HIP(hipMalloc(&b.d_status, (size_t)cnt * 4));
-  G16_HIP(hipHostMalloc((void**)&b.h_status, (size_t)cnt * 4));
+  b.cap = 0;
+  G16_HIP(b.d_w.alloc((size_t)cnt * d->n_wires + 1));
+  G16_HIP(b.d_in.alloc((size_t)cnt * d->n_inputs + 1));
+  G16_HIP(b.d_status.alloc(cnt));
+  G16_HIP(b.h_status.alloc(cnt));
   b.cap = cnt;
   return G16_OK;
 }
 // ... and the public signals of a chunk, for the callers that ask for them
 static int wcalc_reserve_pub(WcalcDevice* d, WcalcBuf& b, uint32_t cnt) {
   if (cnt <= b.cap_pub) return G16_OK;
-  wcalc_free_pub(b);
-  G16_HIP(hipMalloc(&b.d_pub, ((size_t)cnt * d->n_public + 1) * sizeof(Fr)));
-  G16_HIP(hipHostMalloc((void**)&b.h_pub, ((size_t)cnt * d->n_public + 1) * sizeof(Fr)));
+  b.cap_pub = 0;
+  G16_HIP(b.d_pub.alloc((size_t)cnt * d->n_public + 1));
+  G16_HIP(b.h_pub.alloc(((size_t)cnt * d->n_public + 1) * sizeof(Fr)));
   b.cap_pub = cnt;
   return G16_OK;
 }
 
 static int wcalc_device_fill(WcalcDevice* d, const WitnessProgram& p) {
   G16_HIP(hipSetDevice(d->device));
-  G16_HIP(hipStreamCreate(&d->st));
-  for (hipEvent_t& e : d->ev) G16_HIP(hipEventCreate(&e));
-  int rc;
-  if ((rc = wcalc_upload(&d->ops, p.ops)) || (rc = wcalc_upload(&d->terms, p.eterms)) || (rc = wcalc_upload(&d->coefs, p.coefs)) || (rc = wcalc_upload(&d->icoefs, p.icoefs)) || (rc = wcalc_upload(&d->inv_small, p.inv_small)) ||
-      (rc = wcalc_upload(&d->targets, p.targets)) || (rc = wcalc_upload(&d->levels, p.levels)))
-    return rc;
-  for (WcalcBuf& b : d->buf) G16_HIP(hipEventCreate(&b.ready));
+  G16_HIP(d->st.create());
+  G16_HIP(d->ev.create());
+  G16_HIP(upload(d->ops, p.ops));
+  G16_HIP(upload(d->terms, p.eterms));
+  G16_HIP(upload(d->coefs, p.coefs));
+  G16_HIP(upload(d->icoefs, p.icoefs));
+  G16_HIP(upload(d->inv_small, p.inv_small));
+  G16_HIP(upload(d->targets, p.targets));
+  G16_HIP(upload(d->levels, p.levels));
+  for (WcalcBuf& b : d->buf) G16_HIP(b.ready.create());
   return wcalc_reserve(d, d->buf[0], 1);
 }
 
 int wcalc_device_create(int device, const WitnessProgram& p, uint32_t chunk, WcalcDevice** out) {
   if (const int rc = require_hip_device(device, "wtns calc: no HIP device (device = -1 is the host route)", "wtns calc: bad device ordinal"))
     return rc;
-  WcalcDevice* d = new WcalcDevice;
+  std::unique_ptr<WcalcDevice> d(new WcalcDevice);
   d->device = device;
   d->n_wires = p.n_wires;
   d->n_inputs = p.n_inputs;
   d->n_public = p.n_public;
   d->n_levels = (uint32_t)p.levels.size() - 1;
   d->chunk = chunk < 1 ? 1 : chunk;
-  if (const int rc = wcalc_device_fill(d, p)) {
-    wcalc_device_destroy(d);
-    return rc;
-  }
-  *out = d;
+  if (const int rc = wcalc_device_fill(d.get(), p)) return rc;
+  *out = d.release();
   return G16_OK;
 }
 
 // cnt witnesses whose inputs are at d_in, into d_w, on st (enqueue only)
 static int wcalc_launch(WcalcDevice* d, const Fr* d_in, Fr* d_w, uint32_t* d_status, uint32_t cnt, hipStream_t st) {
   G16_HIP(hipMemsetAsync(d_status, 0xff, (size_t)cnt * 4, st));
-  const WpView v{d->ops, d->terms, d->coefs, d->icoefs, d->targets, d->inv_small};
-  wtns_calc_kernel<<<cnt, kWcalcThreads, 0, st>>>(v, d->levels, d->n_levels, d_in, d->n_inputs, d_w, d->n_wires, d_status);
+  const WpView v{d->ops.p, d->terms.p, d->coefs.p, d->icoefs.p, d->targets.p, d->inv_small.p};
+  wtns_calc_kernel<<<cnt, kWcalcThreads, 0, st>>>(v, d->levels.p, d->n_levels, d_in, d->n_inputs, d_w, d->n_wires, d_status);
   G16_HIP(hipGetLastError());
   return G16_OK;
 }
@@ -185,29 +154,28 @@ static int wcalc_launch(WcalcDevice* d, const Fr* d_in, Fr* d_w, uint32_t* d_sta
 int wcalc_device_run(WcalcDevice* d, const uint8_t* inputs, size_t count, uint8_t* out_bodies, uint32_t* status, float ms[3]) {
   G16_HIP(hipSetDevice(d->device));
   if (ms) ms[0] = ms[1] = ms[2] = 0.f;
+  hipStream_t st = d->st;
+  StreamDrain drain(st);   // (inputs and out_bodies are the caller's)
   for (size_t at = 0; at < count; at += d->chunk) {
     const uint32_t cnt = (uint32_t)(count - at < d->chunk ? count - at : d->chunk);
     WcalcBuf& b = d->buf[0];
     if (const int rc = wcalc_reserve(d, b, cnt)) return rc;
-    G16_HIP(hipEventRecord(d->ev[0], d->st));
+    G16_HIP(d->ev.record(0, st));
     if (d->n_inputs)
-      G16_HIP(hipMemcpyAsync(b.d_in, inputs + at * d->n_inputs * 32, (size_t)cnt * d->n_inputs * 32, hipMemcpyHostToDevice, d->st));
-    G16_HIP(hipEventRecord(d->ev[1], d->st));
-    if (const int rc = wcalc_launch(d, b.d_in, b.d_w, b.d_status, cnt, d->st)) return rc;
-    G16_HIP(hipEventRecord(d->ev[2], d->st));
-    G16_HIP(hipMemcpyAsync(b.h_status, b.d_status, (size_t)cnt * 4, hipMemcpyDeviceToHost, d->st));
+      G16_HIP(hipMemcpyAsync(b.d_in.p, inputs + at * d->n_inputs * 32, (size_t)cnt * d->n_inputs * 32, hipMemcpyHostToDevice, st));
+    G16_HIP(d->ev.record(1, st));
+    if (const int rc = wcalc_launch(d, b.d_in.p, b.d_w.p, b.d_status.p, cnt, st)) return rc;
+    G16_HIP(d->ev.record(2, st));
+    G16_HIP(hipMemcpyAsync(b.h_status.p, b.d_status.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, st));
     if (out_bodies)
-      G16_HIP(hipMemcpyAsync(out_bodies + at * d->n_wires * 32, b.d_w, (size_t)cnt * d->n_wires * 32, hipMemcpyDeviceToHost, d->st));
-    G16_HIP(hipEventRecord(d->ev[3], d->st));
-    G16_HIP(hipStreamSynchronize(d->st));
-    for (uint32_t i = 0; i < cnt; i++) status[at + i] = b.h_status[i];
+      G16_HIP(hipMemcpyAsync(out_bodies + at * d->n_wires * 32, b.d_w.p, (size_t)cnt * d->n_wires * 32, hipMemcpyDeviceToHost, st));
+    G16_HIP(d->ev.record(3, st));
+    G16_HIP(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < cnt; i++) status[at + i] = b.h_status.p[i];
     if (ms)
-      for (int k = 0; k < 3; k++) {
-        float t = 0.f;
-        G16_HIP(hipEventElapsedTime(&t, d->ev[k], d->ev[k + 1]));
-        ms[k] += t;
-      }
+      for (int k = 0; k < 3; k++) ms[k] += d->ev.ms(k);
   }
+  drain.dismiss();
   return G16_OK;
 }
 
@@ -215,11 +183,13 @@ int wcalc_device_run_into(WcalcDevice* d, const uint8_t* inputs, Fr* d_out, hipS
   G16_HIP(hipSetDevice(d->device));
   // (the calculator's own stream is idle between calls: every run ends with a wait)
   WcalcBuf& b = d->buf[0];
-  if (d->n_inputs) G16_HIP(hipMemcpyAsync(b.d_in, inputs, (size_t)d->n_inputs * 32, hipMemcpyHostToDevice, st));
-  if (const int rc = wcalc_launch(d, b.d_in, d_out, b.d_status, 1, st)) return rc;
-  G16_HIP(hipMemcpyAsync(b.h_status, b.d_status, 4, hipMemcpyDeviceToHost, st));
+  StreamDrain drain(st);   // (inputs and d_out are the caller's)
+  if (d->n_inputs) G16_HIP(hipMemcpyAsync(b.d_in.p, inputs, (size_t)d->n_inputs * 32, hipMemcpyHostToDevice, st));
+  if (const int rc = wcalc_launch(d, b.d_in.p, d_out, b.d_status.p, 1, st)) return rc;
+  G16_HIP(hipMemcpyAsync(b.h_status.p, b.d_status.p, 4, hipMemcpyDeviceToHost, st));
   G16_HIP(hipStreamSynchronize(st));
-  *status = b.h_status[0];
+  drain.dismiss();
+  *status = b.h_status.p[0];
   return G16_OK;
 }
 
@@ -241,20 +211,22 @@ int wcalc_chunk_launch(WcalcDevice* d, int which, const uint8_t* inputs, uint32_
   int rc = wcalc_reserve(d, b, cnt);
   if (!rc && want_pub) rc = wcalc_reserve_pub(d, b, cnt);
   if (rc) return rc;
-  if (d->n_inputs) G16_HIP(hipMemcpyAsync(b.d_in, inputs, (size_t)cnt * d->n_inputs * 32, hipMemcpyHostToDevice, d->st));
-  if ((rc = wcalc_launch(d, b.d_in, b.d_w, b.d_status, cnt, d->st))) return rc;
-  G16_HIP(hipMemcpyAsync(b.h_status, b.d_status, (size_t)cnt * 4, hipMemcpyDeviceToHost, d->st));
+  StreamDrain drain(d->st);   // (inputs is promised to `ready`, which a failing launch does not record)
+  if (d->n_inputs) G16_HIP(hipMemcpyAsync(b.d_in.p, inputs, (size_t)cnt * d->n_inputs * 32, hipMemcpyHostToDevice, d->st));
+  if ((rc = wcalc_launch(d, b.d_in.p, b.d_w.p, b.d_status.p, cnt, d->st))) return rc;
+  G16_HIP(hipMemcpyAsync(b.h_status.p, b.d_status.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, d->st));
   if (want_pub) {
     const uint32_t total = cnt * d->n_public;   // (below cnt * n_wires <= 2^27: the 4 GiB rule)
-    wtns_gather_pub_kernel<<<(total + 255) / 256, 256, 0, d->st>>>(b.d_w, d->n_wires, d->n_public, total, b.d_pub);
+    wtns_gather_pub_kernel<<<(total + 255) / 256, 256, 0, d->st>>>(b.d_w.p, d->n_wires, d->n_public, total, b.d_pub.p);
     G16_HIP(hipGetLastError());
-    G16_HIP(hipMemcpyAsync(b.h_pub, b.d_pub, (size_t)total * 32, hipMemcpyDeviceToHost, d->st));
+    G16_HIP(hipMemcpyAsync(b.h_pub.p, b.d_pub.p, (size_t)total * 32, hipMemcpyDeviceToHost, d->st));
   }
-  G16_HIP(hipEventRecord(b.ready, d->st));
-  out->d_w = b.d_w;
-  out->status = b.h_status;
-  out->pub = want_pub ? b.h_pub : nullptr;
-  out->ready = b.ready;
+  G16_HIP(b.ready.record(d->st));
+  drain.dismiss();
+  out->d_w = b.d_w.p;
+  out->status = b.h_status.p;
+  out->pub = want_pub ? b.h_pub.p : nullptr;
+  out->ready = b.ready.e;
   return G16_OK;
 }
 

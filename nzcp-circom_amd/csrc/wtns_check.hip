@@ -12,6 +12,8 @@
 // weak-reduced before the shuffle tree and after its steps 8 and 1, so at most 8 partials below ~2r meet between
 // reductions.  The product takes a, b < 16r and gives a*b / 2^261 + r < 1.6r; c is weak-reduced to 1.0001r before it
 // is subtracted with the constant 2r, so the difference is below 3.6r, inside what fr29_to_plain accepts (< 16r).
+#include <memory>
+
 #include "qap_rows.cuh"
 #include "wtns_check.h"
 
@@ -89,70 +91,52 @@ __global__ __launch_bounds__(256) void wtns_check_mont_kernel(const Fr* __restri
 struct WcDevice {
   int device = 0;
   uint32_t m = 0, n_w = 0, chunk = 1;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  uint32_t *rp[3] = {}, *mid[3] = {}, *vptr[3] = {}, *col[3] = {}, *rows = nullptr;
-  F29* val[3] = {};
+  DeviceBuf<uint32_t> rp[3], mid[3], vptr[3], col[3], rows;
+  DeviceBuf<F29> val[3];
   uint32_t n_mid = 0, n_long = 0;
-  Fr* d_w = nullptr;       // chunk * n_w plain words
-  F29* d_wm = nullptr;     // ... and their Montgomery images
-  uint32_t *d_first = nullptr, *d_nfail = nullptr, *h_out = nullptr;   // chunk words each; h_out: 2 * chunk, pinned
+  DeviceBuf<Fr> d_w;       // chunk * n_w plain words
+  DeviceBuf<F29> d_wm;     // ... and their Montgomery images
+  DeviceBuf<uint32_t> d_first, d_nfail;   // chunk words each
+  PinnedBuf<uint32_t> h_out;              // 2 * chunk
+  PhaseEvents<2> ev;
+  DeviceStream st;   // (device_job.h: after everything its work touches)
+  ~WcDevice() { (void)hipSetDevice(device); }
 };
 
-template <class T> static int wc_upload(T** dst, const std::vector<T>& src) {
-  G16_HIP(hipMalloc(dst, (src.size() + 1) * sizeof(T)));
-  if (!src.empty()) G16_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return G16_OK;
-}
-
-void wc_device_destroy(WcDevice* d) {
-  if (!d) return;
-  (void)hipSetDevice(d->device);
-  for (int k = 0; k < 3; k++) {
-    (void)hipFree(d->rp[k]); (void)hipFree(d->mid[k]); (void)hipFree(d->vptr[k]); (void)hipFree(d->col[k]); (void)hipFree(d->val[k]);
-  }
-  (void)hipFree(d->rows); (void)hipFree(d->d_w); (void)hipFree(d->d_wm); (void)hipFree(d->d_first); (void)hipFree(d->d_nfail);
-  if (d->h_out) (void)hipHostFree(d->h_out);
-  for (int k = 0; k < 3; k++)
-    if (d->ev[k]) (void)hipEventDestroy(d->ev[k]);
-  if (d->st) (void)hipStreamDestroy(d->st);
-  delete d;
-}
+void wc_device_destroy(WcDevice* d) { delete d; }
 
 static int wc_device_fill(WcDevice* d, const WcCsr& q) {
   G16_HIP(hipSetDevice(d->device));
-  G16_HIP(hipStreamCreate(&d->st));
-  for (int k = 0; k < 3; k++) G16_HIP(hipEventCreate(&d->ev[k]));
+  G16_HIP(d->st.create());
+  G16_HIP(d->ev.create());
   for (int k = 0; k < 3; k++) {
-    int rc;
-    if ((rc = wc_upload(&d->rp[k], q.rp[k])) || (rc = wc_upload(&d->mid[k], q.mid[k])) || (rc = wc_upload(&d->vptr[k], q.vptr[k])) ||
-        (rc = wc_upload(&d->col[k], q.col[k])) || (rc = wc_upload(&d->val[k], q.val[k])))
-      return rc;
+    G16_HIP(upload(d->rp[k], q.rp[k]));
+    G16_HIP(upload(d->mid[k], q.mid[k]));
+    G16_HIP(upload(d->vptr[k], q.vptr[k]));
+    G16_HIP(upload(d->col[k], q.col[k]));
+    G16_HIP(upload(d->val[k], q.val[k]));
   }
-  if (const int rc = wc_upload(&d->rows, q.long_rows)) return rc;
+  G16_HIP(upload(d->rows, q.long_rows));
   const size_t words = (size_t)d->chunk * d->n_w;
-  G16_HIP(hipMalloc(&d->d_w, (words + 1) * sizeof(Fr)));
-  G16_HIP(hipMalloc(&d->d_wm, (words + 1) * sizeof(F29)));
-  G16_HIP(hipMalloc(&d->d_first, (size_t)d->chunk * 4));
-  G16_HIP(hipMalloc(&d->d_nfail, (size_t)d->chunk * 4));
-  G16_HIP(hipHostMalloc((void**)&d->h_out, (size_t)d->chunk * 8));
+  G16_HIP(d->d_w.alloc(words + 1));
+  G16_HIP(d->d_wm.alloc(words + 1));
+  G16_HIP(d->d_first.alloc(d->chunk));
+  G16_HIP(d->d_nfail.alloc(d->chunk));
+  G16_HIP(d->h_out.alloc((size_t)d->chunk * 2));
   return G16_OK;
 }
 
 int wc_device_create(int device, const WcCsr& q, uint32_t chunk, WcDevice** out) {
   if (const int rc = require_hip_device("wtns check", device)) return rc;
-  WcDevice* d = new WcDevice;
+  std::unique_ptr<WcDevice> d(new WcDevice);
   d->device = device;
   d->m = q.m;
   d->n_w = q.n_w;
   d->chunk = chunk < 1 ? 1 : (chunk > 65535 ? 65535 : chunk);   // (a chunk is the y dimension of one grid)
   d->n_mid = q.n_mid;
   d->n_long = q.n_long;
-  if (const int rc = wc_device_fill(d, q)) {
-    wc_device_destroy(d);
-    return rc;
-  }
-  *out = d;
+  if (const int rc = wc_device_fill(d.get(), q)) return rc;
+  *out = d.release();
   return G16_OK;
 }
 
@@ -160,44 +144,43 @@ int wc_device_check(WcDevice* d, const uint8_t* const* bodies, size_t count, uin
   G16_HIP(hipSetDevice(d->device));
   if (ms) ms[0] = ms[1] = 0.f;
   WcRows lr;
-  lr.rows = d->rows;
+  lr.rows = d->rows.p;
   lr.n_mid = d->n_mid;
   lr.n_long = d->n_long;
   lr.nb_long = (d->n_long - d->n_mid + 3) / 4;
   lr.nb_mid = (d->n_mid + 31) / 32;
-  const QapMat A{d->rp[0], d->mid[0], d->vptr[0], d->col[0], d->val[0]}, B{d->rp[1], d->mid[1], d->vptr[1], d->col[1], d->val[1]},
-      Cm{d->rp[2], d->mid[2], d->vptr[2], d->col[2], d->val[2]};
+  const QapMat A{d->rp[0].p, d->mid[0].p, d->vptr[0].p, d->col[0].p, d->val[0].p},
+      B{d->rp[1].p, d->mid[1].p, d->vptr[1].p, d->col[1].p, d->val[1].p},
+      Cm{d->rp[2].p, d->mid[2].p, d->vptr[2].p, d->col[2].p, d->val[2].p};
+  hipStream_t st = d->st;
+  StreamDrain drain(st);   // (the bodies are the caller's)
   for (size_t at = 0; at < count; at += d->chunk) {
     const uint32_t cnt = (uint32_t)(count - at < d->chunk ? count - at : d->chunk);
-    G16_HIP(hipEventRecord(d->ev[0], d->st));
+    G16_HIP(d->ev.record(0, st));
     for (uint32_t i = 0; i < cnt; i++)
-      if (d->n_w) G16_HIP(hipMemcpyAsync(d->d_w + (size_t)i * d->n_w, bodies[at + i], (size_t)d->n_w * 32, hipMemcpyHostToDevice, d->st));
-    G16_HIP(hipEventRecord(d->ev[1], d->st));
-    G16_HIP(hipMemsetAsync(d->d_first, 0xff, (size_t)cnt * 4, d->st));   // the verdict of the call before is gone
-    G16_HIP(hipMemsetAsync(d->d_nfail, 0, (size_t)cnt * 4, d->st));
+      if (d->n_w) G16_HIP(hipMemcpyAsync(d->d_w.p + (size_t)i * d->n_w, bodies[at + i], (size_t)d->n_w * 32, hipMemcpyHostToDevice, st));
+    G16_HIP(d->ev.record(1, st));
+    G16_HIP(hipMemsetAsync(d->d_first.p, 0xff, (size_t)cnt * 4, st));   // the verdict of the call before is gone
+    G16_HIP(hipMemsetAsync(d->d_nfail.p, 0, (size_t)cnt * 4, st));
     if (d->m) {
       const size_t words = (size_t)cnt * d->n_w;
-      wtns_check_mont_kernel<<<(unsigned)((words + 255) / 256), 256, 0, d->st>>>(d->d_w, d->d_wm, words);
+      wtns_check_mont_kernel<<<(unsigned)((words + 255) / 256), 256, 0, st>>>(d->d_w.p, d->d_wm.p, words);
       const dim3 grid(lr.nb_long + lr.nb_mid + (d->m + 255) / 256, cnt);
-      wtns_check_kernel<<<grid, 256, 0, d->st>>>(lr, A, B, Cm, d->d_w, d->d_wm, d->n_w, d->m, d->d_first, d->d_nfail);
+      wtns_check_kernel<<<grid, 256, 0, st>>>(lr, A, B, Cm, d->d_w.p, d->d_wm.p, d->n_w, d->m, d->d_first.p, d->d_nfail.p);
       G16_HIP(hipGetLastError());
     }
-    G16_HIP(hipEventRecord(d->ev[2], d->st));
-    G16_HIP(hipMemcpyAsync(d->h_out, d->d_first, (size_t)cnt * 4, hipMemcpyDeviceToHost, d->st));
-    G16_HIP(hipMemcpyAsync(d->h_out + cnt, d->d_nfail, (size_t)cnt * 4, hipMemcpyDeviceToHost, d->st));
-    G16_HIP(hipStreamSynchronize(d->st));
+    G16_HIP(d->ev.record(2, st));
+    G16_HIP(hipMemcpyAsync(d->h_out.p, d->d_first.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, st));
+    G16_HIP(hipMemcpyAsync(d->h_out.p + cnt, d->d_nfail.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, st));
+    G16_HIP(hipStreamSynchronize(st));
     for (uint32_t i = 0; i < cnt; i++) {
-      first[at + i] = d->h_out[i];
-      n_failed[at + i] = d->h_out[cnt + i];
+      first[at + i] = d->h_out.p[i];
+      n_failed[at + i] = d->h_out.p[cnt + i];
     }
-    if (ms) {
-      float t = 0.f;
-      G16_HIP(hipEventElapsedTime(&t, d->ev[0], d->ev[1]));
-      ms[0] += t;
-      G16_HIP(hipEventElapsedTime(&t, d->ev[1], d->ev[2]));
-      ms[1] += t;
-    }
+    if (ms)
+      for (int k = 0; k < 2; k++) ms[k] += d->ev.ms(k);
   }
+  drain.dismiss();
   return G16_OK;
 }
 

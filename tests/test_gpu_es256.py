@@ -22,10 +22,13 @@ def test_signature_vectors(amd):
 
 def test_batch_of_130_over_three_keys(amd):
     keys, digests, sigs, idx, want = cases.batch130()
+    amd.Es256Verifier(keys, device=0).close()   # a handle that never ran a batch
     dev, host = amd.Es256Verifier(keys, device=0), amd.Es256Verifier(keys, device=-1)
+    assert dev.verify_batch(digests[:1], sigs[:1], idx[:1]) == host.verify_batch(digests[:1], sigs[:1], idx[:1])   # then it grows
     got = dev.verify_batch(digests, sigs, idx)
     assert got == want
     assert got == host.verify_batch(digests, sigs, idx)
+    assert dev.verify_batch(digests[5:70], sigs[5:70], idx[5:70]) == host.verify_batch(digests[5:70], sigs[5:70], idx[5:70])
     assert [i for i, g in enumerate(got) if not g] == list(cases.BATCH_BAD)
     assert all(t >= 0 for t in dev.timings())
     dev.close()

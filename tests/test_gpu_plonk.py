@@ -328,6 +328,7 @@ def test_device_prover_and_verifier_on_the_golden_fixture(amd):
     proof, pub = prover.prove(open(golden_path("plonk_small.wtns"), "rb").read(), [int(x) for x in meta["blinding"]])
     prover.close()
     assert proof == meta["proof"] and pub == meta["public"]
+    amd.PlonkVerifier(meta["vkey"]).close()   # a handle that never ran a batch
     ver = amd.PlonkVerifier(meta["vkey"])
     assert ver.verify(pub, proof) is True
     assert ver.verify([str(int(pub[0]) + 1)] + pub[1:], proof) is False

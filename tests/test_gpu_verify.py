@@ -193,6 +193,7 @@ def test_batch_of_256_with_known_bad_indices(amd):
         proof, pub = prover.prove(w)
         base.append((pub, proof))
     prover.close()
+    amd.Verifier(vkey, p, device=0).close()   # a handle that never ran a batch
     ver = amd.Verifier(vkey, p, device=0)
     rng = random.Random(3)
     bad = set(rng.sample(range(256), 23))
@@ -206,6 +207,10 @@ def test_batch_of_256_with_known_bad_indices(amd):
     got = ver.verify_batch(items)
     assert got == [i not in bad for i in range(256)]
     assert len(ver.timings()) == 3
+    # the same handle again: across a 64-lane block edge on the grown scratch, one proof, the whole batch
+    assert ver.verify_batch(items[3:68]) == got[3:68]
+    assert ver.verify_batch(items[:1]) == got[:1]
+    assert ver.verify_batch(items) == got
     ver.close()
 
 

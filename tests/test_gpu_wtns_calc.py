@@ -55,6 +55,8 @@ def test_chain_of_2000_levels(amd):
     visibility (op i + 1 runs on the same thread or, in the second program, on another wavefront than op i)."""
     n, ops = ref.chain_program(2000)
     dev, host = both(amd, ref.write(n, ops))
+    dev.close(), host.close()   # handles that never ran a batch
+    dev, host = both(amd, ref.write(n, ops))
     assert dev.n_levels == 2000
     agree(dev, host, n, ops, [[2], [ref.R - 1]])
     dev.close(), host.close()
