@@ -1,5 +1,6 @@
 """Case builders shared by test_cpu_es256.py (device -1) and test_gpu_es256.py (device 0): inputs and the verdicts /
-values of the big-int reference p256_ref, each built once per session."""
+values of the big-int reference p256_ref, each built once per session; and the families that pin the verification
+schedule in the exponent (es256_exponent_ref), with the verdicts their construction gives."""
 import base64
 import functools
 import hashlib
@@ -7,6 +8,7 @@ import json
 import os
 import random
 
+import es256_exponent_ref as ex
 import p256_ref as ref
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -252,6 +254,216 @@ def mixed_wave():
     for slot, c in zip((1, 2, 17, 33, 34, 62), crafted + crafted[:2]):
         d[slot], s[slot], k[slot], w[slot] = c[1], c[2], 3 + c[3], c[4]
     return allkeys, d, s, k, w
+
+
+# ------------------------------------------------------------------ the verification schedule, pinned in the exponent
+# Signatures built by es256_exponent_ref for chosen (u1, u2): an accepted one on every table entry, lane position, tree
+# slot and compare branch, a rejected neighbour beside it.  A case is (name, key bytes, d or None, digest, r | s,
+# expected verdict): d the key's discrete log where it is known, the verdict the one the construction gives
+# (tests/test_cpu_es256_exponent.py pins it to p256_ref.verify).
+def _case(name, signature, want, d=None):
+    key, digest, sig = signature
+    return (name, key, d, digest, sig, want)
+
+
+def _r_of(signature):
+    return int.from_bytes(signature[2][:32], "big")
+
+
+@functools.lru_cache(None)
+def family_a():
+    """Every table entry: u2 = dg 16^w alone (the key's table; digests 0 and n in turn, so u1 = 0), then u1 = dg 16^w
+    with u2 = 1 (G's table), R read from the Python tables; then per window two rejects: a G-entry signature under the
+    digest of the next digit, and the key entry dg + 1 claiming the r of entry dg."""
+    d = random.Random(6).randrange(1, ref.N)
+    q = ex.key_point(d)
+    tg, tq = ex.table(ref.G), ex.table(q)
+    entries = [(w, dg) for w in range(ex.WINDOWS) for dg in range(1, 16) if dg << (4 * w) < ref.N]
+    out = [_case(f"a: key entry, window {w} digit {dg}",
+                 ex.signature_for(0, dg << (4 * w), d, digest_add=ref.N * ((w + dg) & 1), R=tq[w][dg - 1]), True, d)
+           for w, dg in entries]
+    g_sigs = {(w, dg): ex.signature_for(dg << (4 * w), 1, d, R=ref.add(tg[w][dg - 1], q)) for w, dg in entries}
+    out += [_case(f"a: G entry, window {w} digit {dg}", g_sigs[w, dg], True, d) for w, dg in entries]
+    for w in range(ex.WINDOWS):
+        dg = 1 + w % 14
+        if (w, dg + 1) not in g_sigs:
+            dg = 1
+        this, nxt = g_sigs[w, dg], g_sigs[w, dg + 1]
+        out.append(_case(f"a: G entry, window {w} digit {dg}, under the digest of digit {dg + 1}", (this[0], nxt[1], this[2]), False, d))
+        out.append(_case(f"a: key entry, window {w} digit {dg + 1}, claiming the r of digit {dg}",
+                         ex.signature_for(0, (dg + 1) << (4 * w), d, r=tq[w][dg - 1][0] % ref.N), False, d))
+    return out
+
+
+@functools.lru_cache(None)
+def family_b():
+    """Exceptional additions inside a lane.  Lane l adds G windows l, l + 16, l + 32, l + 48, then key windows l, l + 16,
+    l + 32, l + 48; two G entries never meet, so the places are the key positions j = 0..3.  Under 16^(16 j) Q = c G,
+    u1 = c 16^l and u2 = 16^(l + 16 j) make the key entry equal the accumulator (doubling, R = 2 c 16^l G); under -Q it
+    opposes it (infinity; the signature claims the doubling's r, so a verifier that doubled there would accept).
+    c = 5: the accumulator is one entry, Z = 1; c = 5 + 3 16^16: two entries, Z != 1.  Then, for j < 3: the lane
+    cancels at position j and adds a further key entry -- the accumulator restarts from an affine point."""
+    out = []
+    for j in range(4):
+        for c, what in ((5, "one-entry"), (5 + 3 * 16**16, "two-entry")):
+            d = c * pow(16, -16 * j, ref.N) % ref.N
+            for lane in (0, 7, 15):
+                u1, u2 = c << (4 * lane), 1 << (4 * (lane + 16 * j))
+                assert (u1 + u2 * d) % ref.N == 2 * u1 and (u1 - u2 * d) % ref.N == 0
+                tag = f"b: lane {lane}, key position {j}, {what} accumulator"
+                equal = ex.signature_for(u1, u2, d)
+                out.append(_case(f"{tag}: equal", equal, True, d))
+                out.append(_case(f"{tag}: opposite", ex.signature_for(u1, u2, ref.N - d, r=_r_of(equal)), False, ref.N - d))
+                if j < 3:
+                    more = u2 + (2 << (4 * (lane + 16 * (j + 1))))
+                    out.append(_case(f"{tag}: opposite, then a further key entry", ex.signature_for(u1, more, ref.N - d), True, ref.N - d))
+    return out
+
+
+@functools.lru_cache(None)
+def family_c():
+    """Exceptional operands at every slot of the tree: step s = 8, 4, 2, 1 adds slot l + s into slot l < s, and before
+    step s slot m holds the lanes congruent to m modulo 2 s.  Under 16^s Q = 5 G (one key per step, and its negative)
+    lane l's G entries and lane l + s's key entries have equal sums, every other lane idle: one-entry sums (Z = 1)
+    5 16^l G = 16^(l + s) Q, two-entry sums (5 + 15 16^16) 16^l G = (1 + 3 16^16) 16^(l + s) Q."""
+    out = []
+    for s in (8, 4, 2, 1):
+        d = 5 * pow(16, -s, ref.N) % ref.N
+        for slot in range(s):
+            for g_digits, k_digits, what in ((5, 1, "one-entry"), (5 + (15 << 64), 1 + (3 << 64), "two-entry")):
+                left, right = g_digits << (4 * slot), k_digits << (4 * (slot + s))
+                assert (left - right * d) % ref.N == 0
+                tag = f"c: step {s} slot {slot}, {what} sums"
+                two = what == "two-entry"
+
+                def lone(lane):   # (u1, u2) of a sum that sits in this lane alone: a key entry, or a G and a key entry
+                    return (5 << (4 * lane) if two else 0), (3 if two else 1) << (4 * lane)
+                equal = ex.signature_for(left, right, d)
+                out.append(_case(f"{tag}: equal", equal, True, d))
+                out.append(_case(f"{tag}: opposite", ex.signature_for(left, right, ref.N - d, r=_r_of(equal)), False, ref.N - d))
+                out.append(_case(f"{tag}: left idle", ex.signature_for(*lone(slot + s), d), True, d))
+                out.append(_case(f"{tag}: right idle", ex.signature_for(*lone(slot), d), True, d))
+                if s > 1:   # (at step 1 every lane has been folded into slots 0 and 1: no third party is left)
+                    # the infinity of slot `slot` meets lane m's sum at step s / 2, from the left or from the right
+                    m = slot + s // 2 if slot < s // 2 else slot - s // 2
+                    out.append(_case(f"{tag}: opposite, lane {m} finite", ex.signature_for(left + (7 << (4 * m)), right, ref.N - d),
+                                     True, ref.N - d))
+                    m = (slot + s + 1) % 16
+                    assert m % s != slot % s
+                    out.append(_case(f"{tag}: both idle, lane {m} finite", ex.signature_for(*lone(m), d), True, d))
+    return out
+
+
+@functools.lru_cache(None)
+def family_d():
+    """The compare x(R) mod n == r in a whole verification, R chosen by its abscissa (p - n is a 127-bit number)."""
+    rng = random.Random(8)
+    gap = ref.P - ref.N
+    out = []
+
+    def at(tag, lo, step, variants):
+        x, R = ex.find_x(lo, step)
+        u1, u2 = rng.randrange(1, ref.N), rng.randrange(1, ref.N)
+        for name, r, want in variants(x):
+            out.append(_case(f"d: x(R) {tag}: {name}", ex.signature_for_point(u1, u2, R, r=r), want))
+        return x
+    x = at("the first at or above n", ref.N, 1, lambda x: (("r = x - n", x - ref.N, True), ("r = x - n + 1", x - ref.N + 1, False)))
+    assert ref.N <= x < ref.P
+    x = at("the last below p", ref.P - 1, -1, lambda x: (("r = x - n", x - ref.N, True), ("r = x - n - 1", x - ref.N - 1, False)))
+    assert ref.N <= x < ref.P
+    x = at("the first at or above 1", 1, 1, lambda x: (("r = x", x, True), ("r = x + n", x + ref.N, False)))
+    assert x < gap
+    x = at("the last below p - n", gap - 1, -1, lambda x: (("r = x", x, True), ("r = x + 1", x + 1, False)))
+    assert x < gap
+    x = at("the first at or above p - n", gap, 1, lambda x: (("r = x", x, True), ("r = x - (p - n)", x - gap, False)))
+    assert gap <= x < ref.N
+    x = at("the last at or below n - 1", ref.N - 1, -1, lambda x: (("r = x", x, True), ("r = x - 1", x - 1, False)))
+    assert gap <= x < ref.N
+    return out
+
+
+@functools.lru_cache(None)
+def family_e():
+    """Scalar edges: u1 = u2 = n - 1 (every digit but a few is 15), s = 1 and s = n - 1, the digests n - 1 and n + 1, u2
+    with its top window alone beside a full u1."""
+    rng = random.Random(9)
+    d = rng.randrange(1, ref.N)
+    top = ex.signature_for(ref.N - 1, ref.N - 1, d)
+    out = [_case("e: u1 = u2 = n - 1", top, True, d),
+           _case("e: u1 = u2 = n - 1, claiming r + 1", ex.signature_for(ref.N - 1, ref.N - 1, d, r=_r_of(top) + 1), False, d)]
+    for s in (1, ref.N - 1):
+        k = rng.randrange(1, ref.N)
+        R = ex.mul_g(k)
+        u2 = R[0] % ref.N * pow(s, -1, ref.N) % ref.N
+        sig = ex.signature_for((k - u2 * d) % ref.N, u2, d, R=R)
+        assert int.from_bytes(sig[2][32:], "big") == s
+        out.append(_case("e: s = 1" if s == 1 else "e: s = n - 1", sig, True, d))
+    for e in (ref.N - 1, ref.N + 1):
+        r, s = ref.sign(d, rng.randrange(1, 2**40), e)
+        sig = ref.be(r) + ref.be(s)
+        name = "n - 1" if e < ref.N else "n + 1"
+        out.append(_case(f"e: digest {name}", (ref.point_bytes(ex.key_point(d)), ref.be(e), sig), True, d))
+        out.append(_case(f"e: the signature of digest {name} under digest n", (ref.point_bytes(ex.key_point(d)), ref.be(ref.N), sig), False, d))
+    u1 = rng.randrange(1, ref.N)
+    digits = [dg for dg in range(1, 16) if dg << 252 < ref.N]
+    sigs = {dg: ex.signature_for(u1, dg << 252, d) for dg in digits}
+    out += [_case(f"e: u2 = {dg} 16^63 beside a full u1", sigs[dg], True, d) for dg in digits]
+    out.append(_case(f"e: u2 = {digits[-1]} 16^63 claiming the r of digit {digits[-2]}",
+                     ex.signature_for(u1, digits[-1] << 252, d, r=_r_of(sigs[digits[-2]])), False, d))
+    return out
+
+
+EXPONENT_FAMILIES = {"a": family_a, "b": family_b, "c": family_c, "d": family_d, "e": family_e}
+
+
+def exponent_cases(names="abcde"):
+    return [c for n in names for c in EXPONENT_FAMILIES[n]()]
+
+
+def exponent_batches(cases):
+    """[(keys, [(name, digest, r | s, key index, expected)])]: the cases in order, cut where a 17th key would be needed
+    (a verifier takes 16); after every fifth item a range-check reject of signature_cases() -- on the device a group of
+    lanes that sums nothing but takes part in the shuffles -- and no batch's count a multiple of 4, so the last
+    wavefront is partial."""
+    dead = [(f"dead group, {c[0]}", c[1], c[2]) for c in signature_cases()[1] if c[0] in ("r = 0", "s = 0", "r = n", "s = n", "r = 2^256 - 1")]
+    assert len(dead) == 5
+    batches = []
+    for n, (name, key, _, digest, sig, want) in enumerate(cases):
+        if not batches or (key not in batches[-1][0] and len(batches[-1][0]) == 16):
+            batches.append(([], []))
+        keys, items = batches[-1]
+        if key not in keys:
+            keys.append(key)
+        items.append((name, digest, sig, keys.index(key), want))
+        if n % 5 == 4:
+            items.append(dead[n // 5 % 5] + (len(keys) - 1, False))
+    for keys, items in batches:
+        if len(items) % 4 == 0:
+            items.append(dead[0] + (0, False))
+    return batches
+
+
+def run_exponent_batches(amd, device, batches, rotations=(0,), against=None):
+    """Every batch through a verifier on `device`, as it is and rotated left by each of `rotations` items (a wavefront
+    holds four signatures: every item meets every group position): verdicts against the expectations, position by
+    position, and against the route `against` (a device ordinal) where given."""
+    for keys, items in batches:
+        v = amd.Es256Verifier(keys, device=device)
+        other = amd.Es256Verifier(keys, device=against) if against is not None else None
+        try:
+            for rot in rotations:
+                it = items[rot:] + items[:rot]
+                args = [c[1] for c in it], [c[2] for c in it], [c[3] for c in it]
+                got = v.verify_batch(*args)
+                wrong = [(c[0], g) for c, g in zip(it, got) if g != c[4]]
+                assert not wrong, (f"rotation {rot}: {len(wrong)} of {len(it)} verdicts differ from the construction's", wrong[:12])
+                if other is not None:
+                    theirs = other.verify_batch(*args)
+                    assert got == theirs, (rot, [c[0] for c, g, t in zip(it, got, theirs) if g != t][:12])
+        finally:
+            v.close()
+            if other is not None:
+                other.close()
 
 
 # ------------------------------------------------------------------ a 513-signal circuit for the combined verdict (GPU)

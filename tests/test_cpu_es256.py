@@ -113,3 +113,16 @@ def test_device_limb_forms_on_the_host(amd, tmp_path):
     cases.run_field_ops(native, None)
     cases.run_point_adds(native, None)
     cases.run_xcmp(native, None)
+    # whole verifications on the 8 x 32 forms: the schedule's exceptional additions, compare branches and scalar edges
+    # (families b to e of es256_cases), verdict by verdict against the construction's
+    every = cases.exponent_cases("bcde")
+    keys = list(dict.fromkeys(c[1] for c in every))
+    files = [tmp_path / n for n in ("keys.bin", "digests.bin", "sigs.bin", "idx.bin", "ok.bin")]
+    for path, blob in zip(files, (b"".join(keys), b"".join(c[3] for c in every), b"".join(c[4] for c in every),
+                                  b"".join(keys.index(c[1]).to_bytes(4, "little") for c in every))):
+        path.write_bytes(blob)
+    run = subprocess.run([str(exe), "verify"] + [str(p) for p in files], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stdout + run.stderr
+    got = [bool(v) for v in files[4].read_bytes()]
+    assert len(got) == len(every)
+    assert [(c[0], g) for c, g in zip(every, got) if g != c[5]] == []

@@ -1,6 +1,7 @@
 """ES256 pass-signature verification on the device: the vectors of test_cpu_es256.py (built by es256_cases) through the
 kernels of csrc/es256_verify.hip, the layer operator at the grid tails, device verdicts against the reference's and the
-host route's, and the relying party's combined verdict for proofs of a 513-signal circuit."""
+host route's, the verification schedule pinned in the exponent (es256_cases' families), and the relying party's
+combined verdict for proofs of a 513-signal circuit."""
 import pytest
 
 import es256_cases as cases
@@ -40,6 +41,21 @@ def test_exceptional_sums_inside_a_wave(amd):
     dev = amd.Es256Verifier(keys, device=0)
     assert dev.verify_batch(digests, sigs, idx) == want
     dev.close()
+
+
+@pytest.mark.parametrize("family", "abcde")
+def test_schedule_in_the_exponent(amd, family):
+    """es256_cases' families (every table entry; equal, opposite and infinite operands at every key position of a lane and
+    every slot of the shuffle tree; the compare's branches; scalar edges) at all four positions of a signature's lane
+    group in its wavefront, dead groups among them: device verdicts against the construction's and the host route's"""
+    batches = cases.exponent_batches(cases.EXPONENT_FAMILIES[family]())
+    cases.run_exponent_batches(amd, 0, batches, rotations=(0, 1, 2, 3), against=-1)
+
+
+def test_schedule_families_side_by_side(amd):
+    """the families' concatenation: wavefronts that hold cases of two families, other cuts into batches and handles"""
+    batches = cases.exponent_batches(cases.exponent_cases())
+    cases.run_exponent_batches(amd, 0, batches, rotations=(0, 3))
 
 
 def test_key_index_out_of_range(amd):
