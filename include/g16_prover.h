@@ -991,6 +991,67 @@ void g16_pass_verifier_destroy(g16_pass_verifier* v);
  * g16_pass_result: verdict 1, 2, 7, or 3 for every well-formed ES256 pass; no signature work is done. */
 int g16_pass_op(int device, int op, const uint8_t* text, const uint64_t* offsets, size_t count, uint8_t* out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Proving passes from their URIs: the holder's side in one call -- pass URI in, proof out.  The front end and the ES256
+ * kernels of g16_pass_verify_batch run first for the whole batch (on the pass verifier's ES256 stream); the host decides
+ * the outcome of every pass; the passes to prove are cut into the calculator's chunks (the 4 GiB rule, G16_WTNS_CALC_CHUNK)
+ * and their input words -- toBeSigned[8 M], a bit a word, and toBeSignedLen, the image g16_nzcp_inputs writes -- are
+ * formed by one kernel (csrc/pass_prove.hip, a workgroup per pass) on the calculator's stream, straight into the chunk
+ * buffer the witness kernel reads; the proofs then run as g16_fullprove_batch / g16_plonk_fullprove_batch run them.
+ * Only text, records, status words, public signals and proofs cross the bus.
+ * M comes from the program: its named inputs must be exactly toBeSigned with 8 M words and toBeSignedLen with 1 word, in
+ * this order, 1 <= M <= 503; otherwise G16_E_ARG, "pass prove: the program's inputs are not toBeSigned[8 M] and
+ * toBeSignedLen".
+ * res[i].outcome, the first that applies:
+ *   G16_PROVE_PASS      pass.verdict is nonzero (and not one of 3..6 with G16_PASS_PROVE_UNSIGNED)
+ *   G16_PROVE_TOO_LONG  ToBeSigned is longer than M bytes
+ *   G16_PROVE_CHECK     the witness violates check `check` of the program (g16_wtns_calc_check_text words it)
+ *   G16_PROVE_MISMATCH  with G16_PASS_PROVE_MATCH_PUBLIC: public signals 0..255 are not the bits of pass.cred_subj_sha256
+ *                       (MSB first), 256..511 not those of pass.tbs_sha256, 512 not pass.exp, or the record lacks
+ *                       G16_PASS_HAS_SUBJECT -- the front end and the circuit computed differently
+ *   G16_PROVE_DONE      proof i and row i of pub are the pass's
+ * Every outcome but DONE leaves proof i and row i of pub all zero and the other passes unaffected.  res[i].pass is the
+ * record g16_pass_verify_batch gives for (text, now); check is 0xffffffff unless the outcome is CHECK.  With explicit rs
+ * (blinding) proof i is byte for byte what g16_pass_inputs + g16_wtns_calc_wtns + g16_stage_witness + g16_prove_staged
+ * (g16_plonk_prove) give.  count = 0 succeeds and touches nothing.
+ * Refused before the device is touched, with g16_stage_inputs' texts behind "pass prove:" ("plonk pass prove:"): a
+ * calculator on the host route or on another device, wire or public counts that differ from the key's, a sharded Groth16
+ * handle; "...: the pass verifier runs on the host route (create it on the prover's device)" / "...: the pass verifier is
+ * on device A, the prover on device B" (G16_E_STATE); MATCH_PUBLIC with a program of other than 513 public signals
+ * (G16_E_ARG); the item checks of g16_pass_verify_batch.  A pass the host selected and the kernel refuses is
+ * G16_E_STATE, "pass prove: the device disagrees with the front end on pass I", never a proof.
+ * The prover and the pass verifier are locked for the length of the call (the calculator is not thread-safe, as ever).
+ * On an error exit every launch and copy of the call is drained first; all three handles stay usable.
+ * g16_pass_inputs: the layer operator -- the input words alone.  device -1 = host threads (at most 16), the same
+ * csrc/nzcp_pass.cuh code; out_words = count x (8 max_bytes + 1) x 32 bytes; a row of zeros and ok[i] = 0 for a pass that
+ * is not well-formed (g16_pass_verify_batch's rules 1 to 6) or whose ToBeSigned exceeds max_bytes.
+ * g16_pass_wtns_public: the device calculator alone over pass URIs, its chunks filled by the same kernel -- no key, no
+ * proof, no signature work: status[i] = 0xffffffff and row i of pub (n_public words) the witness's public signals, or the
+ * violated check and a zero row, or G16_PASS_WTNS_NO_ROW for a pass that g16_pass_inputs gives no row.  The program's
+ * inputs as above; a host-route calculator is G16_E_STATE. */
+#define G16_PASS_PROVE_UNSIGNED 1u     /* verdicts 3 (no key), 4 (signature), 5 (nbf), 6 (exp) are recorded but do not
+                                          block the proof: the circuit itself does not check the signature */
+#define G16_PASS_PROVE_MATCH_PUBLIC 2u /* NZCPPubIdentity programs only (n_public == 513, else G16_E_ARG) */
+enum { G16_PROVE_DONE = 0, G16_PROVE_PASS = 1 /* blocked by pass.verdict */, G16_PROVE_TOO_LONG = 2 /* tbs_len > M */,
+       G16_PROVE_CHECK = 3 /* the circuit refuses the pass: `check` names it */, G16_PROVE_MISMATCH = 4 };
+typedef struct {
+  uint32_t outcome, check /* 0xffffffff unless outcome 3 */;
+  g16_pass_result pass;
+} g16_pass_prove_result;
+int g16_pass_fullprove_batch(g16_prover* p, g16_wtns_calculator* h, g16_pass_verifier* v, const uint8_t* text,
+                             const uint64_t* offsets /* count + 1 */, size_t count, int64_t now, uint32_t flags,
+                             const uint8_t* rs /* count * 64 (r | s) or NULL */, g16_proof* out /* count */,
+                             uint8_t* pub /* count * n_public * 32, or NULL */, g16_pass_prove_result* res /* count */);
+int g16_plonk_pass_fullprove_batch(g16_plonk* p, g16_wtns_calculator* h, g16_pass_verifier* v, const uint8_t* text,
+                                   const uint64_t* offsets, size_t count, int64_t now, uint32_t flags,
+                                   const uint8_t* blinding /* count * 9 * 32 or NULL */, g16_plonk_proof* out, uint8_t* pub,
+                                   g16_pass_prove_result* res);
+int g16_pass_inputs(int device, const uint8_t* text, const uint64_t* offsets, size_t count, uint32_t max_bytes,
+                    uint8_t* out_words, uint8_t* ok);
+#define G16_PASS_WTNS_NO_ROW 0xfffffffeu
+int g16_pass_wtns_public(g16_wtns_calculator* h, const uint8_t* text, const uint64_t* offsets, size_t count, uint8_t* pub,
+                         uint32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

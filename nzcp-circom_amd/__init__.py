@@ -66,6 +66,10 @@ class PassResult(C.Structure):
                 ("nbf", C.c_int64), ("exp", C.c_int64), ("tbs_sha256", C.c_uint8 * 32), ("cred_subj_sha256", C.c_uint8 * 32)]
 
 
+class PassProveResult(C.Structure):
+    _fields_ = [("outcome", C.c_uint32), ("check", C.c_uint32), ("record", PassResult)]
+
+
 EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g16_prove_staged",
            "g16_prove_partial", "g16_prove_finish", "g16_get_info", "g16_get_timings", "g16_destroy",
            "g16_last_error", "g16_fr_fft", "g16_fr_ifft", "g16_fr_batch_mul", "g16_field_op",
@@ -103,7 +107,8 @@ EXPORTS = ["g16_create", "g16_prove", "g16_prove_batch", "g16_stage_witness", "g
            "g16_es256_verifier_create", "g16_es256_verify_batch", "g16_es256_verifier_timings", "g16_es256_verifier_destroy",
            "g16_p256_op", "g16_nzcp_pass_proof_verify_batch",
            "g16_pass_verifier_create", "g16_pass_verify_batch", "g16_pass_verifier_timings", "g16_pass_verifier_destroy",
-           "g16_pass_op"]
+           "g16_pass_op",
+           "g16_pass_fullprove_batch", "g16_plonk_pass_fullprove_batch", "g16_pass_inputs", "g16_pass_wtns_public"]
 
 
 def load():
@@ -280,6 +285,10 @@ def load():
     lib.g16_pass_verifier_destroy.argtypes = [vp]
     lib.g16_pass_verifier_destroy.restype = None
     lib.g16_pass_op.argtypes = [C.c_int, C.c_int, C.c_char_p, u64p, sz, C.c_char_p]
+    lib.g16_pass_fullprove_batch.argtypes = [vp, vp, vp, C.c_char_p, u64p, sz, C.c_int64, C.c_uint32, C.c_char_p, vp, vp, vp]
+    lib.g16_plonk_pass_fullprove_batch.argtypes = lib.g16_pass_fullprove_batch.argtypes
+    lib.g16_pass_inputs.argtypes = [C.c_int, C.c_char_p, u64p, sz, C.c_uint32, vp, vp]
+    lib.g16_pass_wtns_public.argtypes = [vp, C.c_char_p, u64p, sz, vp, u32p]
     lib.g16_free.argtypes = [vp]
     lib.g16_free.restype = None
     _lib = lib
@@ -386,6 +395,18 @@ class Prover:
                                           prs, pub, st))
         return [(proof_to_obj(prs[i]), pub.raw[i * p:(i + 1) * p], st[i]) if st[i] == NO_CHECK else (None, None, st[i])
                 for i in range(n)]
+
+    def pass_fullprove_batch(self, calc, verifier, uris, now, flags=0, rs=None):
+        """Pass URIs in, proofs out (g16_pass_fullprove_batch): the front end and the signature check of
+        PassVerifier.verify_batch, the circuit's input words formed on the device, the witnesses and the proofs; calc and
+        verifier on this prover's device.  flags: PASS_PROVE_UNSIGNED | PASS_PROVE_MATCH_PUBLIC; rs as for
+        fullprove_batch.  -> one dict per pass: outcome (an index of PROVE_OUTCOMES), check, text (the violated check's
+        for outcome 3, else None), pass (verify_batch's record), proof and public (bytes) -- both None unless outcome 0."""
+        blind = None if rs is None else b"".join(bytes(r) + bytes(s) for r, s in rs)
+        if blind is not None and len(blind) != len(uris) * 64:
+            raise G16Error(-1, "pass prove: rs takes one (r, s) pair of 32-byte scalars per pass")
+        return _pass_prove(load().g16_pass_fullprove_batch, self._h, Proof, proof_to_obj, self.info.n_public, calc, verifier,
+                           uris, now, flags, blind)
 
     def prove_staged(self, slot, r=None, s=None):
         pr, pub = Proof(), self._pub()
@@ -1064,6 +1085,52 @@ def pass_op(op, items, device=0):
     return [None if k == 0xFFFFFFFF else r[4:4 + k] for r, k in zip(rows, lens)]
 
 
+PASS_PROVE_UNSIGNED, PASS_PROVE_MATCH_PUBLIC = 1, 2
+PROVE_OUTCOMES = ("done", "pass", "too long", "check", "mismatch")
+
+
+def pass_inputs(uris, max_bytes, device=0):
+    """Layer operator g16_pass_inputs: the circuit's input words of each pass, toBeSigned[8 max_bytes] (a bit a word) and
+    toBeSignedLen; device -1 = host threads.  -> [(words: (8 max_bytes + 1) * 32 bytes, ok)]; a pass that is not
+    well-formed or whose ToBeSigned exceeds max_bytes has a row of zeros and ok False."""
+    text, offsets = _pass_items(uris)
+    n, row = len(uris), (8 * max_bytes + 1) * 32
+    out = C.create_string_buffer(max(1, n * row))
+    ok = C.create_string_buffer(max(1, n))
+    _check(load().g16_pass_inputs(device, text, offsets, n, max_bytes, out, ok))
+    return [(out.raw[i * row:(i + 1) * row], ok.raw[i] != 0) for i in range(n)]
+
+
+PASS_WTNS_NO_ROW = 0xFFFFFFFE
+
+
+def pass_wtns_public(calc, uris):
+    """g16_pass_wtns_public: the device calculator alone over pass URIs, fed on the device -> [(public bytes, NO_CHECK)],
+    (None, the violated check) or (None, PASS_WTNS_NO_ROW) for a pass that pass_inputs gives no row."""
+    text, offsets = _pass_items(uris)
+    n, p = len(uris), calc.n_public * 32
+    pub = C.create_string_buffer(max(1, n * p))
+    st = (C.c_uint32 * max(1, n))()
+    _check(load().g16_pass_wtns_public(calc._h, text, offsets, n, pub, st))
+    return [(pub.raw[i * p:(i + 1) * p], st[i]) if st[i] == NO_CHECK else (None, st[i]) for i in range(n)]
+
+
+def _pass_prove(fn, handle, proof_type, to_obj, n_public, calc, verifier, uris, now, flags, blind):
+    text, offsets = _pass_items(uris)
+    n, p = len(uris), n_public * 32
+    prs = (proof_type * max(1, n))()
+    pub = C.create_string_buffer(max(1, n * p))
+    res = (PassProveResult * max(1, n))()
+    _check(fn(handle, calc._h, verifier._h, text, offsets, n, int(now), flags, blind, prs, pub, res))
+    out = []
+    for i in range(n):
+        done = res[i].outcome == 0
+        out.append({"outcome": res[i].outcome, "check": res[i].check,
+                    "text": calc.check_text(res[i].check) if res[i].outcome == 3 else None, "pass": _pass_record(res[i].record),
+                    "proof": to_obj(prs[i]) if done else None, "public": pub.raw[i * p:(i + 1) * p] if done else None})
+    return out
+
+
 class PassVerifier:
     """A relying party's offline check of NZ COVID Passes from their URIs (g16_pass_*): keys is the {"<iss>#<kid>": {x, y}}
     object of a DID document's keys (base64url P-256 coordinates, at most 16); on one GPU, or on host threads with
@@ -1157,6 +1224,17 @@ class PlonkProver:
                                                 prs, pub, st))
         return [(plonk_proof_to_obj(prs[i]), pub.raw[i * p:(i + 1) * p], st[i]) if st[i] == NO_CHECK else (None, None, st[i])
                 for i in range(n)]
+
+    def pass_fullprove_batch(self, calc, verifier, uris, now, flags=0, blindings=None):
+        """Prover.pass_fullprove_batch's twin (g16_plonk_pass_fullprove_batch); blindings as for fullprove_batch."""
+        blind = None
+        if blindings is not None:
+            blind = b"".join(bytes(b) if isinstance(b, (bytes, bytearray)) else b"".join(int(x).to_bytes(32, "little") for x in b)
+                             for b in blindings)
+            if len(blind) != len(uris) * 288:
+                raise G16Error(-1, "plonk pass prove: blindings takes nine 32-byte scalars per pass")
+        return _pass_prove(load().g16_plonk_pass_fullprove_batch, self._h, PlonkProof, plonk_proof_to_obj, self.n_public, calc,
+                           verifier, uris, now, flags, blind)
 
     def fullprove(self, calc, inputs, blinding=None):
         """snarkjs `plonk.fullProve` -> (proof, publicSignals); a violated check raises G16Error with the check's text."""

@@ -416,6 +416,25 @@ G16_HD void pass_front(const PassBuf& b, const PassKeyName* keys, uint32_t n_key
   *sig_off = ps.sig_off;
 }
 
+// ---------------------------------------------------------------- the holder's side: the circuit's input words
+// NZCPPubIdentity's inputs are toBeSigned (8 M words, a bit each, MSB first per byte, zero beyond the length) and
+// toBeSignedLen: 8 M + 1 words of 32 bytes in standard form, the image g16_nzcp_inputs writes.  M is at most its bound.
+constexpr uint32_t kPassInputsMaxBytes = 503;
+G16_HD uint32_t pass_input_count(uint32_t max_bytes) { return 8 * max_bytes + 1; }
+// where ToBeSigned's two byte strings lie: the COSE_Sign1 walk alone, nothing of the claims is read
+G16_HD bool pass_tbs_locate(const PassBuf& b, uint32_t* stack, PassTbsSource* tbs) {
+  PassParsed ps;
+  if (!pass_scan_cose(b, &ps, stack)) return false;
+  *tbs = PassTbsSource{b, ps.prot_off, ps.prot_len, ps.payload_off, ps.payload_len};
+  return true;
+}
+// the low 32 bits of input word k < 8 M + 1 (the other 28 bytes of a word are zero); tbs_len <= max_bytes
+G16_HD uint32_t pass_input_word(const PassTbsSource& tbs, uint32_t tbs_len, uint32_t max_bytes, uint32_t k) {
+  if (k >= 8 * max_bytes) return tbs_len;
+  const uint32_t at = k >> 3;
+  return at < tbs_len ? (tbs(at) >> (7 - (k & 7))) & 1u : 0u;
+}
+
 // the relying party's last step: the signature's verdict, then nbf / exp against `now`
 G16_HD uint32_t pass_merge(uint32_t verdict, bool sig_ok, int64_t nbf, int64_t exp, int64_t now) {
   if (verdict != G16_PASS_OK) return verdict;

@@ -4,6 +4,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <mutex>
+#include <vector>
 
 #include "es256.h"
 #include "nzcp_pass.cuh"
@@ -59,5 +61,25 @@ void pass_device_destroy(PassDevice* d);
 int pass_device_batch(PassDevice* d, Es256Device* es, const uint8_t* text, const uint64_t* offsets, size_t count,
                       g16_pass_result* records, uint8_t* ok, float ms[3]);
 int pass_device_op(int device, int op, const uint8_t* text, const uint64_t* offsets, size_t count, uint8_t* out);
+// where the last batch's text and offsets lie on the device (until the next batch), for a kernel that reads them again
+void pass_device_uploaded(const PassDevice* d, const uint8_t** d_text, const uint64_t** d_offsets);
+int pass_device_id(const PassDevice* d);
+
+// the checks of a batch of items, "<route>: ..." (G16_E_ARG)
+int pass_check_items(const char* route, const uint8_t* text, const uint64_t* offsets, size_t count);
 
 }  // namespace g16
+
+// the handle of the C ABI (pass_verify_host.cpp; the pass prover in pass_prove_host.cpp reads it)
+struct g16_pass_verifier {
+  int device = -1;
+  g16_es256_verifier* es = nullptr;   // owned: the tables of G and the keys, and on a device the scratch the front end fills
+  std::vector<g16::PassKeyName> names;
+  g16::PassDevice* dev = nullptr;
+  float last_ms[3] = {0, 0, 0};
+  std::mutex mu;
+  ~g16_pass_verifier() {
+    if (dev) pass_device_destroy(dev);
+    if (es) g16_es256_verifier_destroy(es);
+  }
+};

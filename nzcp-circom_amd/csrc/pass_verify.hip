@@ -126,6 +126,12 @@ int pass_device_create(int device, const PassKeyName* names, uint32_t n_keys, Pa
 
 void pass_device_destroy(PassDevice* D) { delete D; }
 
+void pass_device_uploaded(const PassDevice* D, const uint8_t** d_text, const uint64_t** d_offsets) {
+  *d_text = D->d_text.p;
+  *d_offsets = D->d_offsets.p;
+}
+int pass_device_id(const PassDevice* D) { return D->device; }
+
 static int ensure_scratch(PassDevice* D, size_t count, size_t text_bytes) {
   if (count > D->cap) {
     D->cap = 0;

@@ -14,19 +14,6 @@
 
 using namespace g16;
 
-struct g16_pass_verifier {
-  int device = -1;
-  g16_es256_verifier* es = nullptr;   // owned: the tables of G and the keys, and on a device the scratch the front end fills
-  std::vector<PassKeyName> names;
-  PassDevice* dev = nullptr;
-  float last_ms[3] = {0, 0, 0};
-  std::mutex mu;
-  ~g16_pass_verifier() {
-    if (dev) pass_device_destroy(dev);
-    if (es) g16_es256_verifier_destroy(es);
-  }
-};
-
 namespace {
 
 int host_threads(size_t n) {
@@ -49,8 +36,10 @@ int take_name(const char* s, const char* what, uint32_t j, uint8_t* out, uint32_
   return G16_OK;
 }
 
+}  // namespace
+
 // offsets ascend; a batch is at most 2^24 passes and its text below 2^32 bytes
-int check_items(const char* route, const uint8_t* text, const uint64_t* offsets, size_t count) {
+int g16::pass_check_items(const char* route, const uint8_t* text, const uint64_t* offsets, size_t count) {
   if (count > (1u << 24)) { set_error(std::string(route) + ": batch too large"); return G16_E_ARG; }
   if (count == 0) return G16_OK;
   if (!text || !offsets) { set_error("NULL argument"); return G16_E_ARG; }
@@ -62,6 +51,8 @@ int check_items(const char* route, const uint8_t* text, const uint64_t* offsets,
   if (offsets[count] - offsets[0] >= (1ull << 32)) { set_error(std::string(route) + ": more than 4 GiB of text"); return G16_E_ARG; }
   return G16_OK;
 }
+
+namespace {
 
 // the host route's front end: a pass at a time, a thread's own decode buffer and stack
 void host_front(const PassKeyName* keys, uint32_t n_keys, const uint8_t* text, const uint64_t* offsets, size_t count,
@@ -102,7 +93,7 @@ extern "C" int g16_pass_verifier_create(const uint8_t* keys, const char* const* 
 extern "C" int g16_pass_verify_batch(g16_pass_verifier* V, const uint8_t* text, const uint64_t* offsets, size_t count, int64_t now,
                                      g16_pass_result* out) {
   if (!V || (count && !out)) { set_error("NULL argument"); return G16_E_ARG; }
-  if (const int rc = check_items("pass verify", text, offsets, count)) return rc;
+  if (const int rc = pass_check_items("pass verify", text, offsets, count)) return rc;
   if (count == 0) return G16_OK;
   std::lock_guard<std::mutex> lk(V->mu);
   return no_bad_alloc("pass verify", [&]() {
@@ -140,7 +131,7 @@ extern "C" int g16_pass_op(int device, int op, const uint8_t* text, const uint64
   if (op < 0 || op >= kPassOpCount) { set_error("pass operator: unknown op " + std::to_string(op)); return G16_E_ARG; }
   if (device < -1) { set_error("pass operator: bad device ordinal"); return G16_E_ARG; }
   if (count && !out) { set_error("NULL argument"); return G16_E_ARG; }
-  if (const int rc = check_items("pass operator", text, offsets, count)) return rc;
+  if (const int rc = pass_check_items("pass operator", text, offsets, count)) return rc;
   if (count == 0) return G16_OK;
   if (device >= 0) return pass_device_op(device, op, text, offsets, count, out);
   return no_bad_alloc("pass operator", [&]() {

@@ -1251,19 +1251,39 @@ extern "C" int g16_plonk_prove(g16_plonk* P, const uint8_t* wtns, size_t wtns_le
 // the chunk then run one after another, as g16_plonk_prove does, each reading its raw witness from the chunk buffer after
 // the main stream waited for the chunk's ready event.  Every proof ends with the main stream drained, so the buffer is
 // free again when the last proof of the chunk has returned: one buffer, and no overlap of chunks with proofs.
+// The body is g16::plonk_fullprove_run, over a source of input words (witness_program.h).
 extern "C" int g16_plonk_fullprove_batch(g16_plonk* P, g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, size_t count,
                                          const uint8_t* blinding, g16_plonk_proof* out, uint8_t* pub, uint32_t* status) {
   if (!P || !h) { set_error("NULL argument"); return G16_E_ARG; }
-  std::lock_guard<std::mutex> lk(P->mu);
-  // (the program knows the R1CS wires; the key's nVars counts the addition signals of the PLONK compilation on top)
-  if (const int rc = wcalc_match_prover(h, "plonk fullprove", P->device, P->nBase, P->nPublic)) return rc;
+  std::unique_lock<std::mutex> lk;
+  if (const int rc = plonk_fullprove_enter(P, h, "plonk fullprove", lk)) return rc;
   if (!count) return G16_OK;
   if (!out || !status || (n_inputs && !inputs)) { set_error("NULL argument"); return G16_E_ARG; }
   if (const int rc = wcalc_check_inputs(h, inputs, n_inputs, count)) return rc;   // (before the device is touched)
+  const size_t in_bytes = n_inputs * 32;
+  FullproveSource src;
+  src.who = "plonk fullprove";
+  src.fill = [&](Fr* d_in, size_t at, uint32_t cnt, hipStream_t st) -> int {
+    G16_HIP(hipMemcpyAsync(d_in, inputs + at * in_bytes, (size_t)cnt * in_bytes, hipMemcpyHostToDevice, st));
+    return G16_OK;
+  };
+  return plonk_fullprove_run(P, h, src, count, blinding, out, pub, status);
+}
+
+namespace g16 {
+
+int plonk_fullprove_enter(g16_plonk* P, const g16_wtns_calculator* h, const char* who, std::unique_lock<std::mutex>& lk) {
+  lk = std::unique_lock<std::mutex>(P->mu);
+  // (the program knows the R1CS wires; the key's nVars counts the addition signals of the PLONK compilation on top)
+  return wcalc_match_prover(h, who, P->device, P->nBase, P->nPublic);
+}
+
+int plonk_fullprove_run(g16_plonk* P, g16_wtns_calculator* h, const FullproveSource& src, size_t count, const uint8_t* blinding,
+                        g16_plonk_proof* out, uint8_t* pub, uint32_t* status) {
   G16_HIP(hipSetDevice(P->device));
   WcalcDevice* d = h->dev;
   const size_t chunk = wcalc_chunk_size(d);
-  const size_t in_bytes = n_inputs * 32, pub_bytes = (size_t)P->nPublic * 32;
+  const size_t pub_bytes = (size_t)P->nPublic * 32;
   auto fail = [&](int rc) -> int {   // nothing of this call stays on the device
     plonk_drain(P);
     wcalc_chunk_drain(d);
@@ -1272,16 +1292,19 @@ extern "C" int g16_plonk_fullprove_batch(g16_plonk* P, g16_wtns_calculator* h, c
   for (size_t at = 0; at < count; at += chunk) {
     const uint32_t cnt = (uint32_t)(count - at < chunk ? count - at : chunk);
     WcalcChunk c;
-    int rc = wcalc_chunk_launch(d, 0, inputs + at * in_bytes, cnt, pub != nullptr, &c);
+    int rc = wcalc_chunk_launch_from(d, 0, [&](Fr* d_in, uint32_t n, hipStream_t st) { return src.fill(d_in, at, n, st); }, cnt,
+                                     pub != nullptr, &c);
     if (rc) return fail(rc);
     {
       const hipError_t e = hipEventSynchronize(c.ready);
-      if (e != hipSuccess) { set_error(std::string("plonk fullprove: ") + hipGetErrorString(e)); return fail(G16_E_HIP); }
+      if (e != hipSuccess) { set_error(std::string(src.who) + ": " + hipGetErrorString(e)); return fail(G16_E_HIP); }
     }
     for (uint32_t i = 0; i < cnt; i++) {
       status[at + i] = c.status[i];
       uint8_t* row = pub ? pub + (at + i) * pub_bytes : nullptr;
-      if (c.status[i] != kWpNoCheck) {   // a verdict: no proof
+      int left_out = c.status[i] != kWpNoCheck;
+      if (!left_out && src.gate && (left_out = src.gate(at + i, c.pub ? c.pub + i * pub_bytes : nullptr)) < 0) return fail(left_out);
+      if (left_out) {   // a verdict: no proof
         memset(&out[at + i], 0, sizeof(g16_plonk_proof));
         if (row) memset(row, 0, pub_bytes);
         continue;
@@ -1290,13 +1313,15 @@ extern "C" int g16_plonk_fullprove_batch(g16_plonk* P, g16_wtns_calculator* h, c
       FrM b[10];
       PlonkProofM pr;
       if ((rc = plonk_blinding(blinding ? blinding + (at + i) * 9 * 32 : nullptr, b))) return fail(rc);
-      if (hipStreamWaitEvent(P->st, c.ready, 0) != hipSuccess) { set_error("plonk fullprove: hipStreamWaitEvent failed"); return fail(G16_E_HIP); }
+      if (hipStreamWaitEvent(P->st, c.ready, 0) != hipSuccess) { set_error(std::string(src.who) + ": hipStreamWaitEvent failed"); return fail(G16_E_HIP); }
       if ((rc = plonk_prove_device(P, c.d_w + (size_t)i * P->nBase, b, &pr))) return fail(rc);
       plonk_proof_out(pr, &out[at + i]);
     }
   }
   return G16_OK;
 }
+
+}  // namespace g16
 
 extern "C" int g16_plonk_get_info(const g16_plonk* P, uint32_t info[6]) {
   if (!P || !info) { set_error("NULL argument"); return G16_E_ARG; }

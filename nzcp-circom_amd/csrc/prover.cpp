@@ -1288,20 +1288,43 @@ int g16_prove_batch(g16_prover* p, const uint8_t* const* wtns, const size_t* wtn
 // public signals and the proofs cross the bus.  Ordering: a context's streams wait for the chunk's ready event before
 // the proof is launched; the calculator's stream waits, before it writes a buffer again, for the events after which the
 // proofs still in flight no longer read their witness (BatchPipe::release_to).
+// The body is g16::fullprove_run, over a source of input words (witness_program.h): the caller's host words here, a
+// kernel that forms them on the device for g16_pass_fullprove_batch.
 int g16_fullprove_batch(g16_prover* p, g16_wtns_calculator* h, const uint8_t* inputs, size_t n_inputs, size_t count,
                         const uint8_t* rs, g16_proof* out, uint8_t* pub, uint32_t* status) {
   if (!p || !h) { set_error("NULL argument"); return G16_E_ARG; }
-  std::lock_guard<std::mutex> lk(p->mu);
-  if (int rc = shard_guard(p)) return rc;
-  if (p->shard_count != 1) { set_error("sharded handle: use g16_prove_partial/g16_prove_finish"); return G16_E_STATE; }
-  if (int rc = wcalc_match_prover(h, "fullprove", p->device, p->nVars, p->nPublic)) return rc;
+  std::unique_lock<std::mutex> lk;
+  if (int rc = fullprove_enter(p, h, "fullprove", lk)) return rc;
   if (!count) return G16_OK;
   if (!out || !status || (n_inputs && !inputs)) { set_error("NULL argument"); return G16_E_ARG; }
   if (int rc = wcalc_check_inputs(h, inputs, n_inputs, count)) return rc;   // (before the device is touched)
+  const size_t in_bytes = n_inputs * 32;
+  FullproveSource src;
+  src.who = "fullprove";
+  src.fill = [&](Fr* d_in, size_t at, uint32_t cnt, hipStream_t st) -> int {
+    G16_HIP(hipMemcpyAsync(d_in, inputs + at * in_bytes, (size_t)cnt * in_bytes, hipMemcpyHostToDevice, st));
+    return G16_OK;
+  };
+  return fullprove_run(p, h, src, count, rs, out, pub, status);
+}
+
+}  // extern "C"
+
+namespace g16 {
+
+int fullprove_enter(g16_prover* p, const g16_wtns_calculator* h, const char* who, std::unique_lock<std::mutex>& lk) {
+  lk = std::unique_lock<std::mutex>(p->mu);
+  if (int rc = shard_guard(p)) return rc;
+  if (p->shard_count != 1) { set_error("sharded handle: use g16_prove_partial/g16_prove_finish"); return G16_E_STATE; }
+  return wcalc_match_prover(h, who, p->device, p->nVars, p->nPublic);
+}
+
+int fullprove_run(g16_prover* p, g16_wtns_calculator* h, const FullproveSource& src, size_t count, const uint8_t* rs,
+                  g16_proof* out, uint8_t* pub, uint32_t* status) {
   G16_HIP(hipSetDevice(p->device));
   WcalcDevice* d = h->dev;
   const size_t chunk = wcalc_chunk_size(d), nchunks = (count + chunk - 1) / chunk;
-  const size_t in_bytes = n_inputs * 32, pub_bytes = (size_t)p->nPublic * 32;
+  const size_t pub_bytes = (size_t)p->nPublic * 32;
   auto cnt_of = [&](size_t k) { return (uint32_t)(count - k * chunk < chunk ? count - k * chunk : chunk); };
   BatchPipe pipe(p, rs, out, count > 1, /*check_words=*/false);   // (the calculator writes canonical words)
   // every error exit: the contexts and the calculator's stream drained, so that nothing of this call is left on the
@@ -1311,8 +1334,13 @@ int g16_fullprove_batch(g16_prover* p, g16_wtns_calculator* h, const uint8_t* in
     wcalc_chunk_drain(d);
     return rc;
   };
+  auto launch = [&](size_t k, WcalcChunk* ck) -> int {
+    const size_t at = k * chunk;
+    return wcalc_chunk_launch_from(d, (int)(k & 1), [&](Fr* d_in, uint32_t cnt, hipStream_t st) { return src.fill(d_in, at, cnt, st); },
+                                   cnt_of(k), pub != nullptr, ck);
+  };
   WcalcChunk ck[2];
-  int rc = wcalc_chunk_launch(d, 0, inputs, cnt_of(0), pub != nullptr, &ck[0]);
+  int rc = launch(0, &ck[0]);
   if (rc) return fail(rc);
   for (size_t k = 0; k < nchunks; k++) {
     const size_t at = k * chunk;
@@ -1320,19 +1348,19 @@ int g16_fullprove_batch(g16_prover* p, g16_wtns_calculator* h, const uint8_t* in
     if (k + 1 < nchunks) {
       // the other buffer held chunk k - 1; no proof of chunk k is launched yet, so what is in flight reads that chunk
       // (or an earlier one)
-      if ((rc = pipe.release_to(d)) ||
-          (rc = wcalc_chunk_launch(d, (int)((k + 1) & 1), inputs + (at + cnt) * in_bytes, cnt_of(k + 1), pub != nullptr, &ck[(k + 1) & 1])))
-        return fail(rc);
+      if ((rc = pipe.release_to(d)) || (rc = launch(k + 1, &ck[(k + 1) & 1]))) return fail(rc);
     }
     const WcalcChunk& c = ck[k & 1];
     {
       const hipError_t e = hipEventSynchronize(c.ready);   // the verdicts, before a proof of the chunk takes a context
-      if (e != hipSuccess) { set_error(std::string("fullprove: ") + hipGetErrorString(e)); return fail(G16_E_HIP); }
+      if (e != hipSuccess) { set_error(std::string(src.who) + ": " + hipGetErrorString(e)); return fail(G16_E_HIP); }
     }
     for (uint32_t i = 0; i < cnt; i++) {
       status[at + i] = c.status[i];
       uint8_t* row = pub ? pub + (at + i) * pub_bytes : nullptr;
-      if (c.status[i] != kWpNoCheck) {   // a verdict: no proof, and no context taken
+      int left_out = c.status[i] != kWpNoCheck;
+      if (!left_out && src.gate && (left_out = src.gate(at + i, c.pub ? c.pub + i * pub_bytes : nullptr)) < 0) return fail(left_out);
+      if (left_out) {   // a verdict: no proof, and no context taken
         memset(&out[at + i], 0, sizeof(g16_proof));
         if (row) memset(row, 0, pub_bytes);
         continue;
@@ -1353,6 +1381,10 @@ int g16_fullprove_batch(g16_prover* p, g16_wtns_calculator* h, const uint8_t* in
   if ((rc = pipe.flush())) return fail(rc);
   return G16_OK;
 }
+
+}  // namespace g16
+
+extern "C" {
 
 // Host-only proof assembly from gathered partial sums: needs no GPU handle (the assembling rank
 // may hold only the zkey header).  Same arithmetic as g16_prove_finish.

@@ -26,6 +26,8 @@
 //   7 inputs    n_names x {first word, count, name length, bytes}
 //   8 outputs   n_outputs wires (the public signals; a gadget program's output values)
 #pragma once
+#include <functional>
+#include <mutex>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -118,6 +120,10 @@ uint32_t wcalc_chunk_size(const WcalcDevice* d);
 // `inputs` (host, cnt * n_inputs words) is read until `ready`.  The caller releases the buffer first: what still reads
 // its previous chunk is named to wcalc_chunk_release, whose events the calculator's stream waits for.
 int wcalc_chunk_launch(WcalcDevice* d, int which, const uint8_t* inputs, uint32_t cnt, bool want_pub, WcalcChunk* out);
+// ... with the input words formed on the device: `fill` enqueues on the calculator's stream `st` whatever writes all
+// cnt * n_inputs words at d_in (standard form, below r); what it reads stays alive until `ready`
+using WcalcFill = std::function<int(Fr* d_in, uint32_t cnt, hipStream_t st)>;
+int wcalc_chunk_launch_from(WcalcDevice* d, int which, const WcalcFill& fill, uint32_t cnt, bool want_pub, WcalcChunk* out);
 int wcalc_chunk_release(WcalcDevice* d, hipEvent_t ev);
 void wcalc_chunk_drain(WcalcDevice* d);   // error paths: the calculator's stream, synchronised
 
@@ -135,3 +141,29 @@ int wcalc_check_inputs(const g16_wtns_calculator* h, const uint8_t* inputs, size
 // what a prover on `device` with a key of n_wires wires and n_public public signals refuses, "<who>: ..." (G16_E_STATE): a
 // calculator on the host route or on another device, a program with other counts
 int wcalc_match_prover(const g16_wtns_calculator* h, const char* who, int device, uint32_t n_wires, uint32_t n_public);
+
+// ---------------------------------------------------------------- the batched fullprove over a source of input words
+// g16_fullprove_batch (prover.cpp) and g16_plonk_fullprove_batch (plonk.hip) are one routine each over a source: the
+// caller's host words there, a kernel that forms the words where they are consumed for the pass prover (pass_prove.hip).
+struct g16_prover;
+struct g16_plonk;
+struct g16_plonk_proof;
+namespace g16 {
+struct FullproveSource {
+  const char* who = "fullprove";   // the head of the texts
+  // enqueue on the calculator's stream what writes the input words of witnesses [at, at + cnt) of the batch at d_in
+  std::function<int(Fr* d_in, size_t at, uint32_t cnt, hipStream_t st)> fill;
+  // optional: asked for every witness without a violated check once its chunk's status words and public signals are on
+  // the host (pub_row: its public signals when the call asked for them).  0: prove it; 1: leave it out, proof and row
+  // zero as for a violated check; negative: the call fails with this code
+  std::function<int(size_t i, const uint8_t* pub_row)> gate;
+};
+// lock the prover (held by lk from here on), then its refusals and wcalc_match_prover's behind `who`
+int fullprove_enter(g16_prover* p, const g16_wtns_calculator* h, const char* who, std::unique_lock<std::mutex>& lk);
+// count >= 1 witnesses; the lock is held.  On an error exit the contexts and the calculator's stream are drained
+int fullprove_run(g16_prover* p, g16_wtns_calculator* h, const FullproveSource& src, size_t count, const uint8_t* rs,
+                  g16_proof* out, uint8_t* pub, uint32_t* status);
+int plonk_fullprove_enter(g16_plonk* p, const g16_wtns_calculator* h, const char* who, std::unique_lock<std::mutex>& lk);
+int plonk_fullprove_run(g16_plonk* p, g16_wtns_calculator* h, const FullproveSource& src, size_t count, const uint8_t* blinding,
+                        g16_plonk_proof* out, uint8_t* pub, uint32_t* status);
+}  // namespace g16

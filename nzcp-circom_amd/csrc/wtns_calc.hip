@@ -20,7 +20,8 @@
 // witnesses stay where they are and the prover reads them there.  Two buffers, so that chunk k + 1 is computed while the
 // proofs of chunk k run; each holds what the 4 GiB rule (or G16_WTNS_CALC_CHUNK) allows, so a batched fullprove takes at
 // most 2 x 4 GiB of device memory for witnesses (buffer 0 is the one g16_wtns_calc uses; both grow with the chunks
-// that arrive).
+// that arrive).  wcalc_chunk_launch_from is the routine; what fills d_in is its caller's: a copy of host words
+// (wcalc_chunk_launch), or a kernel that forms them on the device (pass_prove.hip).
 #include <memory>
 
 #include "witness_program.h"
@@ -201,7 +202,7 @@ int wcalc_chunk_release(WcalcDevice* d, hipEvent_t ev) {
   return G16_OK;
 }
 
-int wcalc_chunk_launch(WcalcDevice* d, int which, const uint8_t* inputs, uint32_t cnt, bool want_pub, WcalcChunk* out) {
+int wcalc_chunk_launch_from(WcalcDevice* d, int which, const WcalcFill& fill, uint32_t cnt, bool want_pub, WcalcChunk* out) {
   if (cnt < 1 || cnt > d->chunk || (which & ~1)) { set_error("wtns calc: bad chunk"); return G16_E_ARG; }
   G16_HIP(hipSetDevice(d->device));
   WcalcBuf& b = d->buf[which];
@@ -211,8 +212,8 @@ int wcalc_chunk_launch(WcalcDevice* d, int which, const uint8_t* inputs, uint32_
   int rc = wcalc_reserve(d, b, cnt);
   if (!rc && want_pub) rc = wcalc_reserve_pub(d, b, cnt);
   if (rc) return rc;
-  StreamDrain drain(d->st);   // (inputs is promised to `ready`, which a failing launch does not record)
-  if (d->n_inputs) G16_HIP(hipMemcpyAsync(b.d_in.p, inputs, (size_t)cnt * d->n_inputs * 32, hipMemcpyHostToDevice, d->st));
+  StreamDrain drain(d->st);   // (what the fill reads is promised to `ready`, which a failing launch does not record)
+  if (d->n_inputs && (rc = fill(b.d_in.p, cnt, d->st))) return rc;
   if ((rc = wcalc_launch(d, b.d_in.p, b.d_w.p, b.d_status.p, cnt, d->st))) return rc;
   G16_HIP(hipMemcpyAsync(b.h_status.p, b.d_status.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, d->st));
   if (want_pub) {
@@ -228,6 +229,14 @@ int wcalc_chunk_launch(WcalcDevice* d, int which, const uint8_t* inputs, uint32_
   out->pub = want_pub ? b.h_pub.p : nullptr;
   out->ready = b.ready.e;
   return G16_OK;
+}
+
+int wcalc_chunk_launch(WcalcDevice* d, int which, const uint8_t* inputs, uint32_t cnt, bool want_pub, WcalcChunk* out) {
+  const size_t bytes = (size_t)cnt * d->n_inputs * 32;
+  return wcalc_chunk_launch_from(d, which, [&](Fr* d_in, uint32_t, hipStream_t st) -> int {
+    G16_HIP(hipMemcpyAsync(d_in, inputs, bytes, hipMemcpyHostToDevice, st));
+    return G16_OK;
+  }, cnt, want_pub, out);
 }
 
 void wcalc_chunk_drain(WcalcDevice* d) {

@@ -57,6 +57,8 @@
  *           passVerifyBatch(keys: Buffer(nKeys*64), names: Buffer("iss\0kid\0" per key), text: Buffer, offsets:
  *               Buffer((count+1)*8, u64 LE), now, device) -> Promise<Buffer(count*96): g16_pass_result records>
  *               (g16_pass_verify_batch: ONE batch under a verifier created for the call; device -1 = host threads)
+ *           passProveBatch(plonk, programPath, zkey, keys, names, text, offsets, now, flags, device, blinding | null)
+ *               -> [{outcome, check, text, record: Buffer(96), proof, pub}]   (g16_pass_fullprove_batch and its PLONK twin)
  */
 #include <node_api.h>
 #include <stdio.h>
@@ -1806,6 +1808,127 @@ static napi_value js_pass_verify_batch(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* passProveBatch(plonk, programPath, zkey, keys, names, text, offsets, now, flags, device, blinding): pass URIs in, proofs
+ * out (g16_pass_fullprove_batch, g16_plonk_pass_fullprove_batch): the three handles live for the call; keys / names / text /
+ * offsets as passVerifyBatch takes them; blinding as fullProveBatch.  Synchronous, like fullProveBatch.
+ * -> [{outcome, check, text, record: Buffer(96), proof, pub}]: proof and pub are null unless outcome is 0. */
+static napi_value js_pass_prove_batch(napi_env env, napi_callback_info info) {
+  static const char* usage = "passProveBatch(plonk, programPath, zkey, keys: Buffer(n*64), names: Buffer('iss\\0kid\\0' per key), text: Buffer, offsets: Buffer((count+1)*8, u64 LE), now, flags, device, blinding)";
+  size_t argc = 11, n = 0;
+  napi_value argv[11], out = NULL, v;
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  char path[1024], msg[512];
+  bool is_plonk = false, is_buf = false;
+  int32_t device = 0;
+  uint32_t flags = 0;
+  double now = 0;
+  void* buf[5] = {NULL, NULL, NULL, NULL, NULL};   /* zkey, keys, names, text, offsets */
+  size_t len[5] = {0, 0, 0, 0, 0};
+  void* blind = NULL;
+  size_t blen = 0;
+  int ok = argc >= 10 && napi_get_value_bool(env, argv[0], &is_plonk) == napi_ok &&
+           napi_get_value_string_utf8(env, argv[1], path, sizeof(path), &n) == napi_ok &&
+           napi_get_value_double(env, argv[7], &now) == napi_ok && napi_get_value_uint32(env, argv[8], &flags) == napi_ok &&
+           napi_get_value_int32(env, argv[9], &device) == napi_ok;
+  for (int k = 0; k < 5 && ok; k++) {
+    ok = napi_is_buffer(env, argv[2 + k], &is_buf) == napi_ok && is_buf;
+    if (ok) napi_get_buffer_info(env, argv[2 + k], &buf[k], &len[k]);
+  }
+  /* the names end with a NUL, the offsets are whole words that ascend and stay inside the text */
+  if (ok) ok = len[1] % 64 == 0 && len[1] / 64 <= 16 && len[2] > 0 && ((const char*)buf[2])[len[2] - 1] == 0 && len[4] >= 8 && len[4] % 8 == 0;
+  const size_t count = ok ? len[4] / 8 - 1 : 0;
+  uint64_t prev = 0, cur = 0;
+  for (size_t i = 0; i <= count && ok; i++, prev = cur) {
+    memcpy(&cur, (const uint8_t*)buf[4] + i * 8, 8);
+    ok = cur >= prev && cur <= len[3];
+  }
+  const uint32_t n_keys = (uint32_t)(len[1] / 64);
+  const char* iss[16];
+  const char* kid[16];
+  uint32_t k = 0;
+  if (ok) {
+    const char* p = (const char*)buf[2];
+    const char* end = p + len[2];
+    for (; k < n_keys && p < end; k++) {
+      iss[k] = p;
+      p += strlen(p) + 1;
+      if (p >= end) break;
+      kid[k] = p;
+      p += strlen(p) + 1;
+    }
+    ok = k == n_keys;
+  }
+  if (!ok) { napi_throw_type_error(env, NULL, usage); return NULL; }
+  if (argc > 10 && napi_is_buffer(env, argv[10], &is_buf) == napi_ok && is_buf) napi_get_buffer_info(env, argv[10], &blind, &blen);
+  const size_t proof_bytes = is_plonk ? sizeof(g16_plonk_proof) : sizeof(g16_proof);
+  if (blind && blen != count * (is_plonk ? 288 : 64)) {
+    napi_throw_error(env, NULL, "pass prove: the blinding takes 64 bytes per proof (plonk: 288)");
+    return NULL;
+  }
+  msg[0] = 0;
+  g16_wtns_calculator* h = open_calculator(path, device, msg, sizeof(msg));
+  if (!h) { napi_throw_error(env, NULL, msg); return NULL; }
+  uint32_t inf[6];
+  g16_wtns_calc_info(h, inf);
+  const size_t pub_bytes = (size_t)inf[1] * 32;
+  uint8_t* proofs = (uint8_t*)calloc(count + 1, proof_bytes);
+  uint8_t* pub = (uint8_t*)calloc(count * inf[1] + 1, 32);
+  g16_pass_prove_result* res = (g16_pass_prove_result*)calloc(count + 1, sizeof(g16_pass_prove_result));
+  if (!proofs || !pub || !res) snprintf(msg, sizeof(msg), "pass prove: out of memory");
+  g16_prover* gp = NULL;
+  g16_plonk* pp = NULL;
+  g16_pass_verifier* pv = NULL;
+  if (!msg[0]) {
+    int rc = g16_pass_verifier_create((const uint8_t*)buf[1], iss, kid, n_keys, device, &pv);
+    if (!rc && is_plonk) {
+      rc = g16_plonk_create((const uint8_t*)buf[0], len[0], device, &pp);
+      if (!rc)
+        rc = g16_plonk_pass_fullprove_batch(pp, h, pv, (const uint8_t*)buf[3], (const uint64_t*)buf[4], count, (int64_t)now, flags,
+                                            (const uint8_t*)blind, (g16_plonk_proof*)proofs, pub, res);
+    } else if (!rc) {
+      g16_opts o;
+      memset(&o, 0, sizeof(o));
+      o.device = device;
+      o.shard_count = 1;
+      rc = g16_create((const uint8_t*)buf[0], len[0], &o, &gp);
+      if (!rc)
+        rc = g16_pass_fullprove_batch(gp, h, pv, (const uint8_t*)buf[3], (const uint64_t*)buf[4], count, (int64_t)now, flags,
+                                      (const uint8_t*)blind, (g16_proof*)proofs, pub, res);
+    }
+    if (rc) snprintf(msg, sizeof(msg), "%s", g16_last_error());
+  }
+  if (!msg[0]) {
+    napi_create_array_with_length(env, count, &out);
+    for (size_t i = 0; i < count; i++) {
+      napi_value obj;
+      void* copy = NULL;
+      const int done = res[i].outcome == G16_PROVE_DONE;
+      napi_create_object(env, &obj);
+      napi_create_uint32(env, res[i].outcome, &v);
+      napi_set_named_property(env, obj, "outcome", v);
+      napi_create_int64(env, res[i].check == 0xffffffffu ? -1 : (int64_t)res[i].check, &v);
+      napi_set_named_property(env, obj, "check", v);
+      const char* text = res[i].outcome == G16_PROVE_CHECK ? g16_wtns_calc_check_text(h, res[i].check) : "";
+      napi_create_string_utf8(env, text ? text : "", NAPI_AUTO_LENGTH, &v);
+      napi_set_named_property(env, obj, "text", v);
+      napi_create_buffer_copy(env, sizeof(g16_pass_result), &res[i].pass, &copy, &v);
+      napi_set_named_property(env, obj, "record", v);
+      if (done) napi_create_buffer_copy(env, proof_bytes, proofs + i * proof_bytes, &copy, &v); else napi_get_null(env, &v);
+      napi_set_named_property(env, obj, "proof", v);
+      if (done) napi_create_buffer_copy(env, pub_bytes, pub + i * pub_bytes, &copy, &v); else napi_get_null(env, &v);
+      napi_set_named_property(env, obj, "pub", v);
+      napi_set_element(env, out, (uint32_t)i, obj);
+    }
+  }
+  if (gp) g16_destroy(gp);
+  if (pp) g16_plonk_destroy(pp);
+  if (pv) g16_pass_verifier_destroy(pv);
+  g16_wtns_calc_destroy(h);
+  free(proofs); free(pub); free(res);
+  if (msg[0]) { napi_throw_error(env, NULL, msg); return NULL; }
+  return out;
+}
+
 
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
@@ -1848,6 +1971,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"nzcpProgramFile", NULL, js_nzcp_program_file, NULL, NULL, NULL, napi_default, NULL},
       {"wtnsCalculate", NULL, js_wtns_calculate, NULL, NULL, NULL, napi_default, NULL},
       {"fullProveBatch", NULL, js_full_prove_batch, NULL, NULL, NULL, napi_default, NULL},
+      {"passProveBatch", NULL, js_pass_prove_batch, NULL, NULL, NULL, napi_default, NULL},
   };
   NAPI_OK(napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props));
   return exports;

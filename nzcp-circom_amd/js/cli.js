@@ -57,6 +57,9 @@
 // a witness program likewise: the witness is computed on the GPU and proved from where it lies (g16_plonk_fullprove_batch).
 // A violated constraint prints "[ERROR] snarkJS: <its text>" and exits 1 before anything is written; a usage error exits 2.
 // [--blinding b1,..,b9]: TEST-ONLY, the nine blinding scalars (reproducible bytes).
+// `nzcp prove <file of URIs | URI> <program> <circuit.zkey> --keys keys.json [--out dir]` has no snarkjs counterpart: every
+// pass is checked as `nzcp verify --batch` checks it, its input words are formed on the GPU and its proof made there, in one
+// native call (g16_pass_fullprove_batch; --protocol plonk: its twin).  One line per pass; exit 0 iff all were proved.
 "use strict";
 const fs = require("fs");
 const { groth16 } = require("./index.js");
@@ -157,6 +160,45 @@ async function main(argv) {
     const res = await nzcp.verifyPass(uris, opts);
     res.forEach((r, i) => console.log(r.ok ? `pass ${i}: OK ${r.claims.givenName} ${r.claims.familyName} ${r.claims.dob}` : `pass ${i}: INVALID ${r.reason}`));
     if (!res.every((r) => r.ok)) process.exit(1);
+    return;
+  }
+  if (a[0] === "nzcp" && a[1] === "prove") {
+    // nzcp prove <file of URIs | URI> <program> <circuit.zkey> --keys keys.json [--out dir] [--now t] [--unsigned]
+    //   [--match-public] [--protocol groth16|plonk] [--device n]: every pass checked, its witness computed and proved in ONE
+    //   native call; one line per pass, proof_<i>.json / public_<i>.json into --out for the proved ones; exit 0 iff all are
+    const rest = a.slice(2);
+    const opts = {};
+    const pos = [];
+    let keysFile, outDir;
+    for (let i = 0; i < rest.length; i++) {
+      if (rest[i] === "--keys") keysFile = rest[++i];
+      else if (rest[i] === "--out") outDir = rest[++i];
+      else if (rest[i] === "--now") opts.now = parseInt(rest[++i], 10);
+      else if (rest[i] === "--device") opts.device = parseInt(rest[++i], 10);
+      else if (rest[i] === "--protocol") opts.protocol = rest[++i];
+      else if (rest[i] === "--unsigned") opts.unsigned = true;
+      else if (rest[i] === "--match-public") opts.matchPublic = true;
+      else pos.push(rest[i]);
+    }
+    if (!keysFile || pos.length < 3) {
+      console.error("usage: cli.js nzcp prove <file of URIs | URI> <program> <circuit.zkey> --keys keys.json [--out dir] [--now t] [--unsigned] [--match-public] [--protocol groth16|plonk] [--device n]");
+      process.exit(2);
+    }
+    const { nzcp } = require("./index.js");
+    const doc = JSON.parse(fs.readFileSync(keysFile, "utf-8"));
+    opts.keys = doc.keys || doc;
+    opts.program = pos[1];
+    opts.zkey = fs.readFileSync(pos[2]);
+    const uris = /^NZCP:/.test(pos[0]) ? [pos[0]] : fs.readFileSync(pos[0], "utf-8").split("\n").map((x) => x.trim()).filter((x) => x);
+    const res = await nzcp.provePasses(uris, opts);
+    res.forEach((r, i) => {
+      console.log(r.outcome === "done" ? `pass ${i}: PROVED` : `pass ${i}: NOT PROVED (${r.outcome}) ${r.text}`);
+      if (r.outcome === "done" && outDir) {
+        fs.writeFileSync(require("path").join(outDir, `proof_${i}.json`), JSON.stringify(r.proof, null, 1), "utf-8");
+        fs.writeFileSync(require("path").join(outDir, `public_${i}.json`), JSON.stringify(r.publicSignals, null, 1), "utf-8");
+      }
+    });
+    if (!res.every((r) => r.outcome === "done")) process.exit(1);
     return;
   }
   if (a[0] === "nzcp" && a[1] === "program") {

@@ -649,21 +649,53 @@ async function verifyPass(uriOrUris, opts = {}) {
 // strings, null where the pass is malformed or too long; credSubjSha256 is null too when the pass has no name or dob.
 const PASS_BATCH_REASONS = [null, PASS_REASONS.malformed, PASS_REASONS.alg, PASS_REASONS.key, PASS_REASONS.signature,
   PASS_REASONS.notYet, PASS_REASONS.expired, PASS_REASONS.tooLong];
-async function verifyPassBatch(uris, opts = {}) {
-  const { names, bytes } = issuerKeys(opts.keys);
+// the key table and the passes as the addon takes them: keys, "iss\0kid\0" per key, the text, the count + 1 offsets
+function passBatchBuffers(uris, keys) {
+  const { names, bytes } = issuerKeys(keys);
   const split = names.map((n) => { const at = n.lastIndexOf("#"); return [n.slice(0, Math.max(at, 0)), n.slice(at + 1)]; });
   const nameBytes = Buffer.concat(split.map(([iss, kid]) => Buffer.concat([Buffer.from(iss, "utf-8"), Buffer.from([0]), Buffer.from(kid, "utf-8"), Buffer.from([0])])));
   const texts = uris.map((u) => Buffer.from(String(u), "utf-8"));
   const offsets = Buffer.alloc((texts.length + 1) * 8);
   let at = 0;
   texts.forEach((t, i) => { at += t.length; offsets.writeBigUInt64LE(BigInt(at), (i + 1) * 8); });
-  const out = await native().passVerifyBatch(bytes, nameBytes, Buffer.concat(texts), offsets, passNow(opts), opts.device === undefined ? 0 : opts.device | 0);
-  return texts.map((_, i) => {
-    const r = out.subarray(i * 96, (i + 1) * 96);
-    const verdict = r.readUInt32LE(0), parsed = verdict !== 1 && verdict !== 7;
-    return { ok: verdict === 0, reason: PASS_BATCH_REASONS[verdict], nbf: parsed ? Number(r.readBigInt64LE(16)) : null,
-             exp: parsed ? Number(r.readBigInt64LE(24)) : null, toBeSignedSha256: parsed ? r.subarray(32, 64).toString("hex") : null,
-             credSubjSha256: parsed && (r.readUInt32LE(12) & 1) ? r.subarray(64, 96).toString("hex") : null };
+  return { bytes, nameBytes, text: Buffer.concat(texts), offsets };
+}
+// one g16_pass_result record (96 bytes) as verifyPassBatch reports it
+function passRecord(r) {
+  const verdict = r.readUInt32LE(0), parsed = verdict !== 1 && verdict !== 7;
+  return { ok: verdict === 0, reason: PASS_BATCH_REASONS[verdict], nbf: parsed ? Number(r.readBigInt64LE(16)) : null,
+           exp: parsed ? Number(r.readBigInt64LE(24)) : null, toBeSignedSha256: parsed ? r.subarray(32, 64).toString("hex") : null,
+           credSubjSha256: parsed && (r.readUInt32LE(12) & 1) ? r.subarray(64, 96).toString("hex") : null };
+}
+async function verifyPassBatch(uris, opts = {}) {
+  const b = passBatchBuffers(uris, opts.keys);
+  const out = await native().passVerifyBatch(b.bytes, b.nameBytes, b.text, b.offsets, passNow(opts), opts.device === undefined ? 0 : opts.device | 0);
+  return uris.map((_, i) => passRecord(out.subarray(i * 96, (i + 1) * 96)));
+}
+
+// nzcp.provePasses(uris, {program, zkey, keys, now, unsigned, matchPublic, protocol = "groth16", device = 0}) ->
+// [{outcome, text, pass, proof, publicSignals}]: the holder's side in ONE g16_pass_fullprove_batch (protocol "plonk": its
+// twin) -- the check of verifyPassBatch, the circuit's input words formed on the GPU, the witnesses, the proofs.  outcome is
+// one of PROVE_OUTCOMES; text words it (the violated check's text for "check"); pass is verifyPassBatch's entry; proof and
+// publicSignals are null unless the outcome is "done".  unsigned: prove passes the relying party would refuse for their
+// key, signature, nbf or exp (the circuit does not check the signature).  opts.rs / opts.blinding: TEST-ONLY fixed blinding.
+const PROVE_OUTCOMES = ["done", "pass", "tooLong", "check", "mismatch"];
+async function provePasses(uris, opts = {}) {
+  const isPlonk = (opts.protocol || "groth16") === "plonk";
+  if (!isPlonk && (opts.protocol || "groth16") !== "groth16") throw new Error(`nzcp prove: unknown protocol ${opts.protocol}`);
+  if (!opts.program || !opts.zkey) throw new Error("nzcp prove: the program and the zkey are needed");
+  const b = passBatchBuffers(uris, opts.keys);
+  const flags = (opts.unsigned ? 1 : 0) | (opts.matchPublic ? 2 : 0);
+  const one = isPlonk ? plonkBlinding(opts.blinding) : (opts.rs ? Buffer.concat([scalarToBuffer(opts.rs[0]), scalarToBuffer(opts.rs[1])]) : null);
+  const res = native().passProveBatch(isPlonk, String(opts.program), toBuffer(opts.zkey, "zkey"), b.bytes, b.nameBytes, b.text, b.offsets,
+    passNow(opts), flags, opts.device === undefined || opts.device === null ? 0 : opts.device | 0, one ? Buffer.concat(uris.map(() => one)) : null);
+  return res.map((r) => {
+    const pass = passRecord(r.record);
+    const outcome = PROVE_OUTCOMES[r.outcome];
+    const text = outcome === "done" ? null : outcome === "pass" ? pass.reason : outcome === "check" ? r.text
+      : outcome === "tooLong" ? "ToBeSigned is longer than the circuit takes" : "the public signals are not the pass's digests and exp";
+    return { outcome, text, pass, proof: r.proof ? (isPlonk ? plonkProofObject(r.proof) : proofObject(r.proof)) : null,
+             publicSignals: r.pub ? publicSignals(r.pub) : null };
   });
 }
 // nzcp.passPublicSignals(result): the 513 public signals of NZCPPubIdentity for a pass, from one entry of verifyPassBatch:
@@ -715,7 +747,9 @@ const nzcp = {
   verifyPassBatch,
   passPublicSignals,
   verifyPassProof,
+  provePasses,
   PASS_REASONS,
+  PROVE_OUTCOMES,
 };
 // what the CLI prints for a failed check (modelled on later snarkjs, not compared with it)
 function wtnsCheckReport(v) {
