@@ -1,7 +1,8 @@
 // What device code's host side owns: device and pinned buffers, its stream, its timing events, its status.
-// THE RULE, for every one-shot route: whatever work on the stream reads or writes -- a DeviceBuf, a NttTablesOwned, a
-// MsmJob -- is declared AHEAD of the DeviceStream.  Destructors run in reverse order, the stream's waits for its work and
-// then destroys it, so the stream has drained before anything is freed, on every path out of the route.
+// THE RULE, for every one-shot route: whatever work on the stream reads or writes -- a DeviceBuf, a NttTables, a
+// MsmGroup and its workspace -- is declared AHEAD of the DeviceStream.  Destructors run in reverse order, the stream's
+// waits for its work and then destroys it, so the stream has drained before anything is freed, on every path out of the
+// route.
 // ... and for every long-lived handle (a verifier, a witness checker or calculator): the members that work on its stream
 // touches -- DeviceBuf, PinnedBuf, PhaseEvents -- come BEFORE its DeviceStream member, and the handle's destructor body
 // does hipSetDevice(device) and nothing else: the members release themselves, the stream first.  A batch entry holds a
@@ -11,6 +12,8 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/g16_prover.h"
@@ -51,19 +54,25 @@ struct DeviceJob {
 };
 
 // ---------------------------------------------------------------- owners
-template <class T> struct DeviceBuf {
+// Movable, not copyable: a move leaves its source empty, and a move assignment releases what the target held first
+// (so `x = X()` is "release, then start from defaults").  Each converts to the raw pointer or handle it holds.
+template <class T> struct DeviceBuf {   // T = void: an allocation in bytes (the MSM's point buffers)
+  static constexpr size_t kElem = sizeof(std::conditional_t<std::is_void<T>::value, char, T>);
   T* p = nullptr;
   DeviceBuf() = default;
-  DeviceBuf(const DeviceBuf&) = delete;
-  DeviceBuf& operator=(const DeviceBuf&) = delete;
+  DeviceBuf(DeviceBuf&& o) noexcept : p(std::exchange(o.p, nullptr)) {}
+  DeviceBuf& operator=(DeviceBuf&& o) noexcept { if (this != &o) { reset(); p = std::exchange(o.p, nullptr); } return *this; }
   ~DeviceBuf() { reset(); }
   void reset() { if (p) (void)hipFree(p); p = nullptr; }
-  hipError_t alloc(size_t count) {   // (never empty; frees what it held first; null when it fails)
+  hipError_t alloc(size_t count) { return alloc_bytes((count ? count : 1) * kElem); }   // (never empty)
+  hipError_t alloc_bytes(size_t bytes) {   // exactly `bytes`; frees what it held first; null when it fails
     reset();
-    const hipError_t e = hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
+    const hipError_t e = hipMalloc((void**)&p, bytes);
     if (e != hipSuccess) p = nullptr;
     return e;
   }
+  operator T*() const { return p; }
+  template <class U> explicit operator U*() const { return (U*)p; }
 };
 // src on the device, in an allocation one element larger than src (so an empty array still has an address)
 template <class T> hipError_t upload(DeviceBuf<T>& dst, const std::vector<T>& src) {
@@ -74,29 +83,31 @@ template <class T> hipError_t upload(DeviceBuf<T>& dst, const std::vector<T>& sr
 template <class T> struct PinnedBuf {   // page-locked host memory, as DeviceBuf
   T* p = nullptr;
   PinnedBuf() = default;
-  PinnedBuf(const PinnedBuf&) = delete;
-  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  PinnedBuf(PinnedBuf&& o) noexcept : p(std::exchange(o.p, nullptr)) {}
+  PinnedBuf& operator=(PinnedBuf&& o) noexcept { if (this != &o) { reset(); p = std::exchange(o.p, nullptr); } return *this; }
   ~PinnedBuf() { reset(); }
   void reset() { if (p) (void)hipHostFree(p); p = nullptr; }
-  hipError_t alloc(size_t count) {
+  hipError_t alloc(size_t count) { return alloc_bytes((count ? count : 1) * sizeof(T)); }
+  hipError_t alloc_bytes(size_t bytes) {
     reset();
-    const hipError_t e = hipHostMalloc((void**)&p, (count ? count : 1) * sizeof(T), hipHostMallocDefault);
+    const hipError_t e = hipHostMalloc((void**)&p, bytes, hipHostMallocDefault);
     if (e != hipSuccess) p = nullptr;
     return e;
   }
+  operator T*() const { return p; }
+  template <class U> explicit operator U*() const { return (U*)p; }
 };
 
 struct DeviceStream {
   hipStream_t s = nullptr;
   DeviceStream() = default;
-  DeviceStream(const DeviceStream&) = delete;
-  DeviceStream& operator=(const DeviceStream&) = delete;
-  ~DeviceStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
-  hipError_t create() {
-    const hipError_t e = hipStreamCreate(&s);
-    if (e != hipSuccess) s = nullptr;
-    return e;
-  }
+  DeviceStream(DeviceStream&& o) noexcept : s(std::exchange(o.s, nullptr)) {}
+  DeviceStream& operator=(DeviceStream&& o) noexcept { if (this != &o) { reset(); s = std::exchange(o.s, nullptr); } return *this; }
+  ~DeviceStream() { reset(); }
+  void reset() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } s = nullptr; }
+  hipError_t created(hipError_t e) { if (e != hipSuccess) s = nullptr; return e; }
+  hipError_t create() { reset(); return created(hipStreamCreate(&s)); }
+  hipError_t create(unsigned flags, int priority) { reset(); return created(hipStreamCreateWithPriority(&s, flags, priority)); }
   operator hipStream_t() const { return s; }
 };
 
@@ -114,14 +125,14 @@ struct StreamDrain {
 struct DeviceEvent {   // one event: a hand-over to another stream or to the host
   hipEvent_t e = nullptr;
   DeviceEvent() = default;
-  DeviceEvent(const DeviceEvent&) = delete;
-  DeviceEvent& operator=(const DeviceEvent&) = delete;
-  ~DeviceEvent() { if (e) (void)hipEventDestroy(e); }
-  hipError_t create() {
-    const hipError_t r = hipEventCreate(&e);
-    if (r != hipSuccess) e = nullptr;
-    return r;
-  }
+  DeviceEvent(DeviceEvent&& o) noexcept : e(std::exchange(o.e, nullptr)) {}
+  DeviceEvent& operator=(DeviceEvent&& o) noexcept { if (this != &o) { reset(); e = std::exchange(o.e, nullptr); } return *this; }
+  ~DeviceEvent() { reset(); }
+  void reset() { if (e) (void)hipEventDestroy(e); e = nullptr; }
+  hipError_t created(hipError_t r) { if (r != hipSuccess) e = nullptr; return r; }
+  hipError_t create() { reset(); return created(hipEventCreate(&e)); }
+  hipError_t create(unsigned flags) { reset(); return created(hipEventCreateWithFlags(&e, flags)); }
+  operator hipEvent_t() const { return e; }
   hipError_t record(hipStream_t st) { return hipEventRecord(e, st); }
 };
 

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <functional>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -30,6 +31,20 @@ const char* get_error();
       return G16_E_HIP;                                                                    \
     }                                                                                      \
   } while (0)
+// Acquisitions by the owners of device_job.h; a failure keeps the text of the HIP call the owner makes
+#define G16_HIP_AS(expr, text)                                                             \
+  do {                                                                                     \
+    hipError_t _e = (expr);                                                                \
+    if (_e != hipSuccess) {                                                                \
+      g16::set_error(std::string(text) + ": " + hipGetErrorString(_e));                    \
+      return G16_E_HIP;                                                                    \
+    }                                                                                      \
+  } while (0)
+#define G16_ALLOC(buf, bytes) G16_HIP_AS((buf).alloc_bytes(bytes), "hipMalloc(&" #buf ", " #bytes ")")
+#define G16_PINNED(buf, bytes) G16_HIP_AS((buf).alloc_bytes(bytes), "hipHostMalloc((void**)&" #buf ", " #bytes ")")
+#define G16_EVENT(ev) G16_HIP_AS((ev).create(), "hipEventCreate(&" #ev ")")
+#define G16_EVENT_FLAGS(ev, flags) G16_HIP_AS((ev).create(flags), "hipEventCreateWithFlags(&" #ev ", " #flags ")")
+#define G16_STREAM(st, flags, prio) G16_HIP_AS((st).create(flags, prio), "hipStreamCreateWithPriority(&" #st ", " #flags ", " #prio ")")
 
 template <class Fn> int no_bad_alloc(const char* route, Fn fn) {   // no C++ exception crosses the C ABI
   try {
@@ -193,18 +208,12 @@ struct NttPass { int lo_bits, S, tb; };
 struct NttTables {
   int L = -1;                // log2 N
   int tile_log = 0;
-  F29* tw_fwd = nullptr;     // w_N^i, i < N/2 (9x29 lazy format, Montgomery 2^261)
-  F29* tw_inv = nullptr;     // w_N^-i
-  F29* coset = nullptr;      // coset[j] = N^-1 * w_2N^bitrev(j)  (position order after the DIF iNTT)
+  DeviceBuf<F29> tw_fwd;     // w_N^i, i < N/2 (9x29 lazy format, Montgomery 2^261)
+  DeviceBuf<F29> tw_inv;     // w_N^-i
+  DeviceBuf<F29> coset;      // coset[j] = N^-1 * w_2N^bitrev(j)  (position order after the DIF iNTT)
   std::vector<NttPass> passes;  // DIT order; DIF runs them reversed
 };
 int ntt_tables_create(NttTables& t, int L, hipStream_t st);
-void ntt_tables_destroy(NttTables& t);
-struct NttTablesOwned : NttTables {   // a one-shot route's tables (device_job.h: declared ahead of the stream)
-  NttTablesOwned() = default;
-  NttTablesOwned(const NttTablesOwned&) = delete;
-  ~NttTablesOwned() { ntt_tables_destroy(*this); }
-};
 // Batched in-place transforms over `nvec` vectors (device pointers in host array vecs).
 // dif_inverse: natural in -> bit-reversed out with w^-1 (no scaling);  dit_forward: bit-reversed
 // in -> natural out with w.
@@ -229,18 +238,18 @@ int ntt_join_abc(const F29* a, const F29* b, const F29* c, Fr* p_std, size_t n, 
 // ---------------------------------------------------------------- QAP (qap.hip)
 struct QapCsr {
   // CSR of zkey section 4 per matrix (0 = A, 1 = B): rows = domainSize
-  uint32_t* row_ptr[2] = {nullptr, nullptr};  // [N+1]
+  DeviceBuf<uint32_t> row_ptr[2];  // [N+1]
   // A row's records are ordered: first those whose coefficient is +1 or -1 (79 % of the real NZCP circuit's 4.2 M records:
   // they ADD the witness word's Montgomery image, bit 31 of col = minus), then the general ones (a product each)
-  uint32_t* col[2] = {nullptr, nullptr};      // signal index per record (| 0x80000000: coefficient -1, in the +-1 part)
-  uint32_t* mid[2] = {nullptr, nullptr};      // [N] where the general records of a row start (an index into col)
-  uint32_t* vptr[2] = {nullptr, nullptr};     // [N] ... and their first coefficient (an index into val)
-  F29* val[2] = {nullptr, nullptr};           // general records only: coef * 2^522 (lazy format): one product with the plain witness word
+  DeviceBuf<uint32_t> col[2];      // signal index per record (| 0x80000000: coefficient -1, in the +-1 part)
+  DeviceBuf<uint32_t> mid[2];      // [N] where the general records of a row start (an index into col)
+  DeviceBuf<uint32_t> vptr[2];     // [N] ... and their first coefficient (an index into val)
+  DeviceBuf<F29> val[2];           // general records only: coef * 2^522 (lazy format): one product with the plain witness word
   size_t nnz[2] = {0, 0}, ngen[2] = {0, 0};
   uint32_t N = 0;
   // rows with more than kQapLongRow terms in A or B (the modular-addition rows of a SHA-256 circuit carry
   // ~260): one wavefront each instead of one lane
-  uint32_t* long_rows = nullptr;   // first the n_mid rows of at most kQapWaveRow terms (eight lanes each), then the rest
+  DeviceBuf<uint32_t> long_rows;   // first the n_mid rows of at most kQapWaveRow terms (eight lanes each), then the rest
   uint32_t n_long = 0, n_mid = 0;
 };
 static constexpr uint32_t kQapLongRow = 16;
@@ -281,10 +290,10 @@ struct MsmGroup {
   uint32_t sec_n[kMsmMaxSections] = {0, 0, 0};       // non-infinity points per section
   uint32_t sec_begin[kMsmMaxSections] = {0, 0, 0};   // their start in the concatenated point index space
   uint32_t n = 0;                                    // total points
-  void* d_bases = nullptr;      // PackedAffine<G1>[pf * n], or nullptr (G2-only group)
-  void* d_bases2 = nullptr;     // PackedAffine<G2>[pf * sec_n[g2_sec]], or nullptr
+  DeviceBuf<void> d_bases;      // PackedAffine<G1>[pf * n], or nullptr (G2-only group)
+  DeviceBuf<void> d_bases2;     // PackedAffine<G2>[pf * sec_n[g2_sec]], or nullptr
   int g2_sec = -1;              // section the G2 lane rides on
-  uint32_t* d_src = nullptr;    // [n] scalar index of point g
+  DeviceBuf<uint32_t> d_src;    // [n] scalar index of point g
   // Window precomputation (single-section groups): the base table also holds 2^(c W k) * P_i for k < pf, so
   // scalar window j = k W + r of point i lands in row r as table entry k n + i; with pf = Ws (the dense H-MSM's
   // default) ONE row of buckets collects every window and wider windows pay: c = 20 needs 13 additions per point
@@ -339,20 +348,13 @@ struct MsmGroup {
 };
 size_t msm_point_bytes(int curve);   // canonical XYZZ bytes: 128 (G1) / 256 (G2)
 int msm_group_create(MsmGroup& g, const MsmSectionIn* secs, int nsec, const MsmConfig& cfg);
-void msm_group_destroy(MsmGroup& g);
-int msm_workspace_create(MsmWorkspace** ws, const MsmGroup& g);
+struct MsmWorkspaceDelete { void operator()(MsmWorkspace* ws) const; };   // (msm_g1.hip, where the struct is complete)
+using MsmWorkspacePtr = std::unique_ptr<MsmWorkspace, MsmWorkspaceDelete>;
+int msm_workspace_create(MsmWorkspacePtr& ws, const MsmGroup& g);   // filled on success only
 // priority of the streams the NEXT workspaces created on this thread make for themselves (the G2 lane's dup-row
 // stream); kMsmPrioHighest = the device's highest (default).  See prover.cpp create_impl: hardware-queue pools.
 static constexpr int kMsmPrioHighest = -1000;
 void msm_set_aux_stream_priority(int prio);
-void msm_workspace_destroy(MsmWorkspace* ws);
-struct MsmJob {   // a one-shot route's group and workspace (device_job.h: declared ahead of the stream)
-  MsmGroup g;
-  MsmWorkspace* ws = nullptr;
-  MsmJob() = default;
-  MsmJob(const MsmJob&) = delete;
-  ~MsmJob() { msm_workspace_destroy(ws); msm_group_destroy(g); }
-};
 // Per-section results of one launch: XYZZ sums in the canonical Montgomery(2^256) image.
 struct MsmResult {
   G1XYZZ g1[kMsmMaxSections];

@@ -90,47 +90,49 @@ struct MsmLaneWs {
   uint64_t max_tasks = 0;
   uint32_t task_len = 0;             // entries per task in THIS lane (the G2 lane has fewer lanes to fill and cuts shorter)
   uint32_t task_len_min = 0;         // shortest task length a launch may pick (sizes max_tasks)
-  uint32_t* h_stat = nullptr;        // pinned: [0] = end, [1] = start of the lane's sorted entries in the last launch;
+  PinnedBuf<uint32_t> h_stat;        // pinned: [0] = end, [1] = start of the lane's sorted entries in the last launch;
                                      // [2] != 0: that launch needed this many tasks, more than max_tasks; [3] != 0: its
                                      // medium / heavy bucket lists overflowed (both: msm_collect fails with G16_E_STATE)
   uint32_t seg_len = 0;              // buckets per reduce segment (a power of two) of the NEXT launch: seg_len_lat, or
   uint32_t seg_len_lat = 0, seg_len_thr = 0;   // seg_len_thr in throughput mode (msm_set_throughput)
   uint32_t row_pts = 0;              // canonical points the row block of d_canon / h_pinned holds: `rows` row sums, or
                                      // rows * ngroups * 3 triples when a row is cut into several workgroups (msm_reduce_plan)
-  uint32_t* d_off = nullptr;         // [nbk + 1] first sorted entry of a bucket (absolute position in d_sorted)
-  uint32_t* d_toff = nullptr;        // [nbk + 1] exclusive scan of ceil(cnt / task_len): first task id of a bucket
-  uint32_t* d_foff = nullptr;        // [nbk + 1] exclusive scan of floor(cnt / task_len): full-length tasks
-  uint32_t* d_tile_a = nullptr;
-  uint32_t* d_tile_b = nullptr;
-  uint32_t* d_tile_c = nullptr;
-  uint2* d_task_desc = nullptr;      // by task id
-  uint4* d_qdesc = nullptr;          // by queue position: full-length tasks first
-  uint32_t* d_class = nullptr;       // [2][kRemClasses]: remainder-class totals and cursors
-  uint32_t* d_queue = nullptr;       // [0] work-queue head of the accumulate kernel, [1] number of flagged tasks,
+  DeviceBuf<uint32_t> d_off;         // [nbk + 1] first sorted entry of a bucket (absolute position in d_sorted)
+  DeviceBuf<uint32_t> d_toff;        // [nbk + 1] exclusive scan of ceil(cnt / task_len): first task id of a bucket
+  DeviceBuf<uint32_t> d_foff;        // [nbk + 1] exclusive scan of floor(cnt / task_len): full-length tasks
+  DeviceBuf<uint32_t> d_tile_a;
+  DeviceBuf<uint32_t> d_tile_b;
+  DeviceBuf<uint32_t> d_tile_c;
+  DeviceBuf<uint2> d_task_desc;      // by task id
+  DeviceBuf<uint4> d_qdesc;          // by queue position: full-length tasks first
+  DeviceBuf<uint32_t> d_class;       // [2][kRemClasses]: remainder-class totals and cursors
+  DeviceBuf<uint32_t> d_queue;       // [0] work-queue head of the accumulate kernel, [1] number of flagged tasks,
                                      // [2] != 0: over capacity, no task exists (msm_scan_top_kernel)
-  uint32_t* d_redo = nullptr;        // tasks whose fast-path sum met an exceptional case
-  void* d_partial = nullptr;         // one XYZZ per task
-  void* d_bsum = nullptr;            // one XYZZ per bucket cut into several tasks
-  uint32_t* d_heavy = nullptr;       // [0] = count, [1..] = buckets with more than kMediumTasks partials
-  uint32_t* d_medium = nullptr;      // the same for light_max < partials <= kMediumTasks
+  DeviceBuf<uint32_t> d_redo;        // tasks whose fast-path sum met an exceptional case
+  DeviceBuf<void> d_partial;         // one XYZZ per task
+  DeviceBuf<void> d_bsum;            // one XYZZ per bucket cut into several tasks
+  DeviceBuf<uint32_t> d_heavy;       // [0] = count, [1..] = buckets with more than kMediumTasks partials
+  DeviceBuf<uint32_t> d_medium;      // the same for light_max < partials <= kMediumTasks
   uint32_t max_heavy = 0;
-  void* d_seg = nullptr;             // bucket reduce: one (V, W) pair per workgroup (rows cut into several workgroups)
-  void* d_red = nullptr;             // sparse rows: ping-pong buffers of the tree over the segment sums
+  DeviceBuf<void> d_seg;             // bucket reduce: one (V, W) pair per workgroup (rows cut into several workgroups)
+  DeviceBuf<void> d_red;             // sparse rows: ping-pong buffers of the tree over the segment sums
   bool reduce_scan = false;          // dense rows: msm_bucket_reduce_kernel (suffix scans); sparse rows: msm_bucket_reduce_mul_kernel
-  void* d_canon = nullptr;           // `rows` canonical XYZZ row sums, then nsec_lane * dup_bit_rows chunk sums of the dup rows
-  void* d_dseg = nullptr;            // dup rows: per (section, bit, chunk of 64 hash buckets) sums
-  void* d_dred = nullptr;            // ... and their tree
-  hipStream_t st_dup = nullptr;      // the dup-row stage runs beside the bucket reduce of the digit rows
-  hipEvent_t ev_dup_fork = nullptr, ev_dup_join = nullptr;
-  uint32_t* d_dcount = nullptr;      // [nsec_lane] qualifying non-empty dup buckets
-  uint32_t* d_dlist = nullptr;       // [nsec_lane][2^dup_bits] their hash-bucket ids, compacted
+  void* d_canon = nullptr;           // `rows` canonical XYZZ row sums, then nsec_lane * dup_bit_rows chunk sums of the dup rows: a
+                                     // view, of h_pinned seen from the device (rows_mapped) or of d_canon_own
+  DeviceBuf<void> d_canon_own;       // G16_ROWS_COPY alone
+  DeviceBuf<void> d_dseg;            // dup rows: per (section, bit, chunk of 64 hash buckets) sums
+  DeviceBuf<void> d_dred;            // ... and their tree
+  DeviceEvent ev_dup_fork, ev_dup_join;
+  DeviceBuf<uint32_t> d_dcount;      // [nsec_lane] qualifying non-empty dup buckets
+  DeviceBuf<uint32_t> d_dlist;       // [nsec_lane][2^dup_bits] their hash-bucket ids, compacted
   uint32_t nsec_lane = 0;            // sections this lane covers (G1: all, G2: one)
-  uint8_t* h_pinned = nullptr;
-  bool rows_mapped = false;          // d_canon IS h_pinned seen from the device (lane_create)
+  PinnedBuf<uint8_t> h_pinned;
+  bool rows_mapped = false;          // (lane_create)
   size_t out_bytes = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the bucket-accumulate kernel
-  hipEvent_t ev_done = nullptr;
-  hipEvent_t trace_ev[4] = {};       // G16_TRACE_HOST: queue built, combined, reduced, end
+  DeviceEvent ev0, ev1;   // around the bucket-accumulate kernel
+  DeviceEvent ev_done;
+  DeviceEvent trace_ev[4];           // G16_TRACE_HOST: queue built, combined, reduced, end (created on first use)
+  DeviceStream st_dup;               // the dup-row stage runs beside the bucket reduce of the digit rows (G2 lane; after what its work touches)
   float last_accum_ms = 0.f;
   // scheduling of the next launch (msm_launch_lanes / msm_set_waves)
   hipEvent_t gate = nullptr;         // the accumulate kernel waits for this event (nullptr: none)
@@ -140,27 +142,27 @@ struct MsmLaneWs {
 
 struct MsmWorkspace {
   // front end
-  uint32_t* d_hist = nullptr;        // [chunks][rows * bins] per-workgroup bin histograms -> run starts
-  uint32_t* d_bin_cnt = nullptr;     // [rows * bins]
-  uint32_t* d_bin_start = nullptr;   // [rows * bins + 1]
-  uint2* d_tmp = nullptr;            // binned entries: (table index | sign << 31, low bucket bits)
-  uint32_t* d_sorted = nullptr;      // final list: table index | sign << 31, grouped by bucket key
-  uint32_t* d_cnt = nullptr;         // [nb] bucket populations
+  DeviceBuf<uint32_t> d_hist;        // [chunks][rows * bins] per-workgroup bin histograms -> run starts
+  DeviceBuf<uint32_t> d_bin_cnt;     // [rows * bins]
+  DeviceBuf<uint32_t> d_bin_start;   // [rows * bins + 1]
+  DeviceBuf<uint2> d_tmp;            // binned entries: (table index | sign << 31, low bucket bits)
+  DeviceBuf<uint32_t> d_sorted;      // final list: table index | sign << 31, grouped by bucket key
+  DeviceBuf<uint32_t> d_cnt;         // [nb] bucket populations
   uint32_t nb = 0;
   // repeated-value detection (MsmGroup::dup_rows): per section and hash bucket
-  uint32_t* d_dup_cnt = nullptr;     // points hashed there (scalars other than 0 and 1)
-  uint32_t* d_dup_rep = nullptr;     // one of them (global point index), 0xffffffff = none
-  uint32_t* d_dup_mixed = nullptr;   // != 0: the bucket holds different values -> not used
+  DeviceBuf<uint32_t> d_dup_cnt;     // points hashed there (scalars other than 0 and 1)
+  DeviceBuf<uint32_t> d_dup_rep;     // one of them (global point index), 0xffffffff = none
+  DeviceBuf<uint32_t> d_dup_mixed;   // != 0: the bucket holds different values -> not used
   const Fr* d_scalars = nullptr;     // of the running launch
   // single-pass front end (dense single-row groups, msm_bin_direct_kernel): (row, bin) regions of bin_cap entries in d_tmp
   bool direct = false;
   uint32_t bin_cap = 0;
   uint32_t dup_chunk = 16, dup_bit_rows = 16;   // chunk width of the repeated values for the next launch (msm_set_throughput)
-  uint32_t* h_over = nullptr;        // pinned: != 0 when a bin overflowed in the last launch (msm_collect repeats it two-pass)
+  PinnedBuf<uint32_t> h_over;        // pinned: != 0 when a bin overflowed in the last launch (msm_collect repeats it two-pass)
   hipStream_t st_last = nullptr, st2_last = nullptr;   // streams of the running launch (for that repeat)
   MsmLaneWs lane[2];
-  hipEvent_t ev_sorted = nullptr;    // sort + scans done: the lanes may start
-  hipEvent_t trace_ev[4] = {};       // G16_TRACE_HOST: pass 0, bin scans, pass 1, bin sort
+  DeviceEvent ev_sorted;             // sort + scans done: the lanes may start
+  DeviceEvent trace_ev[4];           // G16_TRACE_HOST: pass 0, bin scans, pass 1, bin sort
   bool launched = false;
   bool empty = false;                // the last launch had no points
 };
@@ -1028,7 +1030,7 @@ int msm_launch_lane_t(const MsmGroup& g, MsmWorkspace* ws, MsmLaneWs& ln, const 
   static const bool trace = getenv("G16_TRACE_HOST") != nullptr;
   auto mark = [&](int k) {
     if (!trace) return;
-    if (!ln.trace_ev[k]) (void)hipEventCreate(&ln.trace_ev[k]);
+    if (!ln.trace_ev[k]) (void)ln.trace_ev[k].create();
     (void)hipEventRecord(ln.trace_ev[k], st);
   };
   int rc = msm_build_queue(g, ws, ln, st);

@@ -705,24 +705,21 @@ static bool is_inf_bytes(const uint8_t* p, size_t psz) {
 
 // upload `count` canonical affine points, convert to the packed lazy format, and (pf > 1) append the levels
 // 2^(ndbl[0] + .. + ndbl[k-1]) * P: dst holds pf * count packed points, level-major
-static int upload_table(int curve, const std::vector<uint8_t>& canon, uint32_t count, uint32_t pf, const std::vector<int>& ndbl, void** dst) {
+static int upload_table(int curve, const std::vector<uint8_t>& canon, uint32_t count, uint32_t pf, const std::vector<int>& ndbl, DeviceBuf<void>& dst) {
   const size_t lazy_pt = curve == 2 ? sizeof(PackedAffine<Fq2x29Ops>) : sizeof(PackedAffine<Fq29Ops>);
-  void* tmp = nullptr;
-  void* tmp2 = nullptr;
-  G16_HIP(hipMalloc(&tmp, canon.size()));
-  if (pf > 1) G16_HIP(hipMalloc(&tmp2, canon.size()));
-  G16_HIP(hipMalloc(dst, (size_t)pf * count * lazy_pt));
+  DeviceBuf<void> tmp, tmp2;
+  G16_ALLOC(tmp, canon.size());
+  if (pf > 1) G16_ALLOC(tmp2, canon.size());
+  G16_HIP_AS(dst.alloc_bytes((size_t)pf * count * lazy_pt), "hipMalloc(dst, (size_t)pf * count * lazy_pt)");
   G16_HIP(hipMemcpy(tmp, canon.data(), canon.size(), hipMemcpyHostToDevice));
   int rc = G16_OK;
   for (uint32_t k = 0; k < pf && !rc; k++) {
     void* cur = (k & 1) ? tmp2 : tmp;
     void* nxt = (k & 1) ? tmp : tmp2;
-    void* d = (uint8_t*)*dst + (size_t)k * count * lazy_pt;
+    void* d = (uint8_t*)dst + (size_t)k * count * lazy_pt;
     rc = curve == 2 ? msm_convert_bases_g2(cur, d, count) : msm_convert_bases_g1(cur, d, count);
     if (!rc && k + 1 < pf) rc = curve == 2 ? msm_precompute_g2(cur, nxt, count, ndbl[k]) : msm_precompute_g1(cur, nxt, count, ndbl[k]);
   }
-  (void)hipFree(tmp);
-  if (tmp2) (void)hipFree(tmp2);
   return rc;
 }
 
@@ -896,7 +893,7 @@ int msm_group_create(MsmGroup& g, const MsmSectionIn* secs, int nsec, const MsmC
   }
   if (g.n == 0) return G16_OK;
   // ---- resident tables
-  G16_HIP(hipMalloc(&g.d_src, (size_t)g.n * 4));
+  G16_ALLOC(g.d_src, (size_t)g.n * 4);
   G16_HIP(hipMemcpy(g.d_src, src.data(), (size_t)g.n * 4, hipMemcpyHostToDevice));
   int rc = G16_OK;
   std::vector<int> ndbl(g.pf, g.c * g.W);   // level k + 1 = 2^(bits of the windows of level k) * level k
@@ -904,18 +901,9 @@ int msm_group_create(MsmGroup& g, const MsmSectionIn* secs, int nsec, const MsmC
     const MsmPlan pl = msm_plan_of(g);
     for (uint32_t k = 0; k < g.pf; k++) ndbl[k] = (int)msm_win_bits(pl, k);
   }
-  if (has_g1) rc = upload_table(1, canon1, g.n, g.pf, ndbl, &g.d_bases);
-  if (!rc && g2_sec >= 0) rc = upload_table(2, canon2, g.sec_n[g2_sec], g.pf, ndbl, &g.d_bases2);
+  if (has_g1) rc = upload_table(1, canon1, g.n, g.pf, ndbl, g.d_bases);
+  if (!rc && g2_sec >= 0) rc = upload_table(2, canon2, g.sec_n[g2_sec], g.pf, ndbl, g.d_bases2);
   return rc;
-}
-
-void msm_group_destroy(MsmGroup& g) {
-  if (g.d_bases) (void)hipFree(g.d_bases);
-  if (g.d_bases2) (void)hipFree(g.d_bases2);
-  if (g.d_src) (void)hipFree(g.d_src);
-  g.d_bases = g.d_bases2 = nullptr;
-  g.d_src = nullptr;
-  g.n = 0;
 }
 
 static thread_local int t_aux_prio = kMsmPrioHighest;
@@ -953,27 +941,27 @@ static int lane_create(MsmLaneWs& ln, const MsmGroup& g, int curve, uint32_t key
   // test hook (tests/test_gpu_edges.py): undersized task buffers, to see the device-side capacity check fire
   if (const char* e = getenv("G16_TEST_MAX_TASKS"))
     if (atoll(e) > 0 && (uint64_t)atoll(e) < ln.max_tasks) ln.max_tasks = (uint64_t)atoll(e);
-  G16_HIP(hipHostMalloc((void**)&ln.h_stat, 64));
+  G16_PINNED(ln.h_stat, 64);
   for (int k = 0; k < 16; k++) ln.h_stat[k] = 0;
   const size_t pb = curve == 2 ? sizeof(G2XYZZ29) : sizeof(G1XYZZ29);   // device-side (lazy) points
   const size_t cpb = msm_point_bytes(curve);                             // canonical, host-visible
   const size_t ntiles = (size_t)nbk / kScanTile + 2;
-  G16_HIP(hipMalloc(&ln.d_off, (nbk + 4) * 4));
-  G16_HIP(hipMalloc(&ln.d_toff, (nbk + 4) * 4));
-  G16_HIP(hipMalloc(&ln.d_foff, (nbk + 4) * 4));
-  G16_HIP(hipMalloc(&ln.d_tile_a, ntiles * 4));
-  G16_HIP(hipMalloc(&ln.d_tile_b, ntiles * 4));
-  G16_HIP(hipMalloc(&ln.d_tile_c, ntiles * 4));
-  G16_HIP(hipMalloc(&ln.d_task_desc, (ln.max_tasks + 1) * sizeof(uint2)));
-  G16_HIP(hipMalloc(&ln.d_qdesc, (ln.max_tasks + 1) * sizeof(uint4)));
-  G16_HIP(hipMalloc(&ln.d_class, 2 * kRemClasses * 4));
-  G16_HIP(hipMalloc(&ln.d_queue, 64));
-  G16_HIP(hipMalloc(&ln.d_redo, (ln.max_tasks + 1) * 4));
-  G16_HIP(hipMalloc(&ln.d_partial, ln.max_tasks * pb + 256));
-  G16_HIP(hipMalloc(&ln.d_bsum, nbk * pb + 256));
+  G16_ALLOC(ln.d_off, (nbk + 4) * 4);
+  G16_ALLOC(ln.d_toff, (nbk + 4) * 4);
+  G16_ALLOC(ln.d_foff, (nbk + 4) * 4);
+  G16_ALLOC(ln.d_tile_a, ntiles * 4);
+  G16_ALLOC(ln.d_tile_b, ntiles * 4);
+  G16_ALLOC(ln.d_tile_c, ntiles * 4);
+  G16_ALLOC(ln.d_task_desc, (ln.max_tasks + 1) * sizeof(uint2));
+  G16_ALLOC(ln.d_qdesc, (ln.max_tasks + 1) * sizeof(uint4));
+  G16_ALLOC(ln.d_class, 2 * kRemClasses * 4);
+  G16_ALLOC(ln.d_queue, 64);
+  G16_ALLOC(ln.d_redo, (ln.max_tasks + 1) * 4);
+  G16_ALLOC(ln.d_partial, ln.max_tasks * pb + 256);
+  G16_ALLOC(ln.d_bsum, nbk * pb + 256);
   ln.max_heavy = (uint32_t)(ln.max_tasks / kLightTasks + 16);
-  G16_HIP(hipMalloc(&ln.d_heavy, ((size_t)ln.max_heavy + 2) * 4));
-  G16_HIP(hipMalloc(&ln.d_medium, ((size_t)ln.max_heavy + 2) * 4));
+  G16_ALLOC(ln.d_heavy, ((size_t)ln.max_heavy + 2) * 4);
+  G16_ALLOC(ln.d_medium, ((size_t)ln.max_heavy + 2) * 4);
   // dense rows: the scan-based reduce; sparse rows (witness lanes): r02's per-lane weighting (see msm.cuh).  G16_REDUCE_SCAN
   // = 0 / 1 forces one of them for every lane (sweeps).
   {
@@ -993,11 +981,11 @@ static int lane_create(MsmLaneWs& ln, const MsmGroup& g, int curve, uint32_t key
   }
   const MsmReducePlan rp = msm_reduce_plan(g, ln);
   if (ln.reduce_scan) {
-    G16_HIP(hipMalloc(&ln.d_seg, 2 * (size_t)ln.rows * rp.nwg * pb + 256));
+    G16_ALLOC(ln.d_seg, 2 * (size_t)ln.rows * rp.nwg * pb + 256);
   } else {
     const uint64_t nseg = (g.B + ln.seg_len - 1) / ln.seg_len;
-    G16_HIP(hipMalloc(&ln.d_seg, (size_t)ln.rows * nseg * pb + 256));
-    G16_HIP(hipMalloc(&ln.d_red, 2 * (size_t)ln.rows * ((nseg + 63) / 64) * pb + 256));
+    G16_ALLOC(ln.d_seg, (size_t)ln.rows * nseg * pb + 256);
+    G16_ALLOC(ln.d_red, 2 * (size_t)ln.rows * ((nseg + 63) / 64) * pb + 256);
   }
   ln.nsec_lane = ln.rows / g.rps;
   ln.row_pts = ln.reduce_scan ? ln.rows * msm_row_out_points(rp) : ln.rows;
@@ -1005,59 +993,47 @@ static int lane_create(MsmLaneWs& ln, const MsmGroup& g, int curve, uint32_t key
   if (g.dup_rows) {
     const size_t nchunk = ((size_t)1 << g.dup_bits) >> 6, drows = (size_t)ln.nsec_lane * g.dup_rows_cap;
     out_pts += drows;
-    G16_HIP(hipMalloc(&ln.d_dseg, drows * nchunk * pb + 256));
-    G16_HIP(hipMalloc(&ln.d_dred, 2 * drows * ((nchunk + 63) / 64) * pb + 256));
-    G16_HIP(hipMalloc(&ln.d_dcount, 64));
+    G16_ALLOC(ln.d_dseg, drows * nchunk * pb + 256);
+    G16_ALLOC(ln.d_dred, 2 * drows * ((nchunk + 63) / 64) * pb + 256);
+    G16_ALLOC(ln.d_dcount, 64);
     if (curve == 2) {   // G2: its own stream beside the bucket reduce (G1's dup stage is short: it stays on the lane's
       int plo = 0, phi = 0;   // stream -- hardware queues are scarce, see prover.cpp create_impl)
       G16_HIP(hipDeviceGetStreamPriorityRange(&plo, &phi));
       if (t_aux_prio != kMsmPrioHighest) phi = t_aux_prio;
-      G16_HIP(hipStreamCreateWithPriority(&ln.st_dup, hipStreamNonBlocking, phi));
+      G16_STREAM(ln.st_dup, hipStreamNonBlocking, phi);
     }
-    G16_HIP(hipEventCreateWithFlags(&ln.ev_dup_fork, hipEventDisableTiming));
-    G16_HIP(hipEventCreateWithFlags(&ln.ev_dup_join, hipEventDisableTiming));
-    G16_HIP(hipMalloc(&ln.d_dlist, ((size_t)ln.nsec_lane << g.dup_bits) * 4 + 64));
+    G16_EVENT_FLAGS(ln.ev_dup_fork, hipEventDisableTiming);
+    G16_EVENT_FLAGS(ln.ev_dup_join, hipEventDisableTiming);
+    G16_ALLOC(ln.d_dlist, ((size_t)ln.nsec_lane << g.dup_bits) * 4 + 64);
   }
   ln.out_bytes = out_pts * cpb;
-  G16_HIP(hipHostMalloc((void**)&ln.h_pinned, ln.out_bytes + 256));
+  G16_PINNED(ln.h_pinned, ln.out_bytes + 256);
   // the last kernels of a lane write their few KB of row sums straight into the pinned host block (it is mapped into the
   // device's address space): no copy-engine hop between the last kernel and the host's wake-up.  G16_ROWS_COPY=1: r02's
   // device buffer + hipMemcpyAsync
   ln.rows_mapped = !(getenv("G16_ROWS_COPY") && atoi(getenv("G16_ROWS_COPY")));
-  if (ln.rows_mapped) G16_HIP(hipHostGetDevicePointer(&ln.d_canon, ln.h_pinned, 0));
-  else G16_HIP(hipMalloc(&ln.d_canon, ln.out_bytes + 256));
-  G16_HIP(hipEventCreate(&ln.ev0));
-  G16_HIP(hipEventCreate(&ln.ev1));
-  G16_HIP(hipEventCreate(&ln.ev_done));
+  if (ln.rows_mapped) {
+    G16_HIP(hipHostGetDevicePointer(&ln.d_canon, ln.h_pinned, 0));
+  } else {
+    G16_HIP_AS(ln.d_canon_own.alloc_bytes(ln.out_bytes + 256), "hipMalloc(&ln.d_canon, ln.out_bytes + 256)");
+    ln.d_canon = ln.d_canon_own;
+  }
+  G16_EVENT(ln.ev0);
+  G16_EVENT(ln.ev1);
+  G16_EVENT(ln.ev_done);
   return G16_OK;
 }
 
-static void lane_destroy(MsmLaneWs& ln) {
-  void* ptrs[] = {ln.d_task_desc, ln.d_qdesc, ln.d_class, ln.d_queue, ln.d_redo, ln.d_partial, ln.d_bsum, ln.d_heavy, ln.d_medium,
-                  ln.d_seg, ln.d_red, ln.rows_mapped ? nullptr : ln.d_canon, ln.d_off, ln.d_toff, ln.d_foff, ln.d_tile_a, ln.d_tile_b, ln.d_tile_c,
-                  ln.d_dseg, ln.d_dred, ln.d_dcount, ln.d_dlist};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (ln.h_pinned) (void)hipHostFree(ln.h_pinned);
-  if (ln.h_stat) (void)hipHostFree(ln.h_stat);
-  if (ln.st_dup) (void)hipStreamDestroy(ln.st_dup);
-  hipEvent_t evs[] = {ln.ev0, ln.ev1, ln.ev_done, ln.trace_ev[0], ln.trace_ev[1], ln.trace_ev[2], ln.trace_ev[3],
-                      ln.ev_dup_fork, ln.ev_dup_join};
-  for (hipEvent_t e : evs)
-    if (e) (void)hipEventDestroy(e);
-  ln = MsmLaneWs();
-}
+void MsmWorkspaceDelete::operator()(MsmWorkspace* ws) const { delete ws; }
 
-int msm_workspace_create(MsmWorkspace** out, const MsmGroup& g) {
-  MsmWorkspace* ws = new MsmWorkspace();
-  *out = ws;
+static int workspace_fill(MsmWorkspace* ws, const MsmGroup& g) {
   if (g.n == 0) return G16_OK;
   msm_set_throughput(ws, g, false);
   const uint32_t nrb = g.rows * g.bins;
   ws->nb = g.rows * g.B;
-  G16_HIP(hipMalloc(&ws->d_hist, ((size_t)g.chunks * nrb + 4) * 4));
-  G16_HIP(hipMalloc(&ws->d_bin_cnt, ((size_t)nrb + 4) * 4));
-  G16_HIP(hipMalloc(&ws->d_bin_start, ((size_t)nrb + 4) * 4));
+  G16_ALLOC(ws->d_hist, ((size_t)g.chunks * nrb + 4) * 4);
+  G16_ALLOC(ws->d_bin_cnt, ((size_t)nrb + 4) * 4);
+  G16_ALLOC(ws->d_bin_start, ((size_t)nrb + 4) * 4);
   {
     // single-pass front end for dense single-section groups: fixed-capacity bins, 2.5x the average population (even
     // windows fill the low buckets ~1.4x the average, msm_bin_direct_kernel) + slack for small groups
@@ -1068,21 +1044,21 @@ int msm_workspace_create(MsmWorkspace** out, const MsmGroup& g) {
     ws->direct = g.dense && g.nsec == 1 && !g.ones && !g.dup_rows && !off && cap * nrb < 0x7fffffffull;
     ws->bin_cap = ws->direct ? (uint32_t)cap : 0u;
   }
-  G16_HIP(hipHostMalloc((void**)&ws->h_over, 64));
+  G16_PINNED(ws->h_over, 64);
   ws->h_over[0] = 0;
   // (the two-pass path -- the fallback of an overflowing single-pass launch -- needs room for every entry whatever the capacity)
   uint64_t tmp_entries = g.max_entries;
   if (ws->direct && (uint64_t)ws->bin_cap * nrb > tmp_entries) tmp_entries = (uint64_t)ws->bin_cap * nrb;
-  G16_HIP(hipMalloc(&ws->d_tmp, (tmp_entries + 4) * sizeof(uint2)));
-  G16_HIP(hipMalloc(&ws->d_sorted, (g.max_entries + 4) * 4));
-  G16_HIP(hipMalloc(&ws->d_cnt, ((size_t)ws->nb + 4) * 4));
+  G16_ALLOC(ws->d_tmp, (tmp_entries + 4) * sizeof(uint2));
+  G16_ALLOC(ws->d_sorted, (g.max_entries + 4) * 4);
+  G16_ALLOC(ws->d_cnt, ((size_t)ws->nb + 4) * 4);
   if (g.dup_rows) {
     const size_t nd = (size_t)g.nsec << g.dup_bits;
-    G16_HIP(hipMalloc(&ws->d_dup_cnt, nd * 4));
-    G16_HIP(hipMalloc(&ws->d_dup_rep, nd * 4));
-    G16_HIP(hipMalloc(&ws->d_dup_mixed, nd * 4));
+    G16_ALLOC(ws->d_dup_cnt, nd * 4);
+    G16_ALLOC(ws->d_dup_rep, nd * 4);
+    G16_ALLOC(ws->d_dup_mixed, nd * 4);
   }
-  G16_HIP(hipEventCreate(&ws->ev_sorted));
+  G16_EVENT(ws->ev_sorted);
   int rc = G16_OK;
   const uint32_t div = g.dense ? 1 : 3;   // effective (full-width) share of the scalars
   if (g.d_bases) rc = lane_create(ws->lane[0], g, 1, 0, ws->nb, 0, g.max_entries, g.max_entries / div);
@@ -1093,19 +1069,11 @@ int msm_workspace_create(MsmWorkspace** out, const MsmGroup& g) {
   }
   return rc;
 }
-
-void msm_workspace_destroy(MsmWorkspace* ws) {
-  if (!ws) return;
-  void* ptrs[] = {ws->d_hist, ws->d_bin_cnt, ws->d_bin_start, ws->d_tmp, ws->d_sorted, ws->d_cnt,
-                  ws->d_dup_cnt, ws->d_dup_rep, ws->d_dup_mixed};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (auto& ln : ws->lane) lane_destroy(ln);
-  if (ws->h_over) (void)hipHostFree(ws->h_over);
-  if (ws->ev_sorted) (void)hipEventDestroy(ws->ev_sorted);
-  for (hipEvent_t e : ws->trace_ev)
-    if (e) (void)hipEventDestroy(e);
-  delete ws;
+int msm_workspace_create(MsmWorkspacePtr& out, const MsmGroup& g) {
+  MsmWorkspacePtr ws(new MsmWorkspace());
+  const int rc = workspace_fill(ws.get(), g);
+  if (!rc) out = std::move(ws);
+  return rc;
 }
 
 int msm_front_end(const MsmGroup& g, MsmWorkspace* ws, const Fr* d_scalars, hipStream_t st) {
@@ -1116,7 +1084,7 @@ int msm_front_end(const MsmGroup& g, MsmWorkspace* ws, const Fr* d_scalars, hipS
   static const bool trace = getenv("G16_TRACE_HOST") != nullptr;
   auto mark = [&](int k) {
     if (!trace) return;
-    if (!ws->trace_ev[k]) (void)hipEventCreate(&ws->trace_ev[k]);
+    if (!ws->trace_ev[k]) (void)ws->trace_ev[k].create();
     (void)hipEventRecord(ws->trace_ev[k], st);
   };
   const size_t lds = (size_t)nrb * 4;
@@ -1260,7 +1228,7 @@ int msm_collect(const MsmGroup& g, MsmWorkspace* ws, MsmResult* out, const std::
     const MsmReducePlan rp = msm_reduce_plan(g, ln);
     const uint32_t ngroups = (rp.nwg + kPairGroup - 1) / kPairGroup;
     if (l == 0) {
-      const G1XYZZ* rows = reinterpret_cast<const G1XYZZ*>(ln.h_pinned);
+      const G1XYZZ* rows = reinterpret_cast<const G1XYZZ*>(ln.h_pinned.p);
       std::vector<G1XYZZ> folded;
       if (ln.reduce_scan && rp.nwg > kPairGroup) {   // long rows (the H-MSM's): the device left (P, Y, Wt) triples per pair group
         folded.resize(ln.rows);
@@ -1283,7 +1251,7 @@ int msm_collect(const MsmGroup& g, MsmWorkspace* ws, MsmResult* out, const std::
       }
       if (after_g1 && *after_g1) (*after_g1)(*out);
     } else {
-      const G2XYZZ* rows = reinterpret_cast<const G2XYZZ*>(ln.h_pinned);
+      const G2XYZZ* rows = reinterpret_cast<const G2XYZZ*>(ln.h_pinned.p);
       std::vector<G2XYZZ> folded;
       if (ln.reduce_scan && rp.nwg > kPairGroup) {
         folded.resize(ln.rows);

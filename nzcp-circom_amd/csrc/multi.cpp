@@ -108,22 +108,22 @@ struct g16_multi {
   std::vector<g16_prover*> h;
   std::vector<int> dev;
   std::vector<ShardView> view;                 // per shard: its stream, witness slot and vector buffers
-  hipEvent_t ev_w = nullptr;                   // witness resident on shard 0
-  hipEvent_t ev_vec[3] = {nullptr, nullptr, nullptr};   // vector v evaluated on shard v mod G
+  DeviceEvent ev_w;                            // witness resident on shard 0
+  DeviceEvent ev_vec[3];                       // vector v evaluated on shard v mod G
   uint32_t N = 0, n_public = 0;
   std::unique_ptr<ShardPool> pool;
   std::mutex mu;
 
   ~g16_multi() {
     pool.reset();   // (joins the threads before the handles they use go away)
+    // the events live on different devices, and each goes with its own device current: member order cannot say that
     if (!dev.empty()) {
       (void)hipSetDevice(dev[0]);
-      if (ev_w) (void)hipEventDestroy(ev_w);
-      for (uint32_t v = 0; v < 3; v++)
-        if (ev_vec[v]) {
-          (void)hipSetDevice(dev[v % dev.size()]);
-          (void)hipEventDestroy(ev_vec[v]);
-        }
+      ev_w.reset();
+      for (uint32_t v = 0; v < 3; v++) {
+        (void)hipSetDevice(dev[v % dev.size()]);
+        ev_vec[v].reset();
+      }
     }
     for (auto* p : h)
       if (p) g16_destroy(p);
@@ -176,10 +176,10 @@ int g16_multi_create(const uint8_t* zkey, size_t zkey_len, const int32_t* device
   M->N = inf.domain_size;
   M->n_public = inf.n_public;
   G16_HIP(hipSetDevice(M->dev[0]));
-  G16_HIP(hipEventCreateWithFlags(&M->ev_w, hipEventDisableTiming));
+  G16_EVENT_FLAGS(M->ev_w, hipEventDisableTiming);
   for (uint32_t v = 0; v < 3; v++) {
     G16_HIP(hipSetDevice(M->dev[v % ndev]));
-    G16_HIP(hipEventCreateWithFlags(&M->ev_vec[v], hipEventDisableTiming));
+    G16_EVENT_FLAGS(M->ev_vec[v], hipEventDisableTiming);
   }
   *out = M.release();
   return G16_OK;

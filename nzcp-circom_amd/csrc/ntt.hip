@@ -284,9 +284,9 @@ int ntt_tables_create(NttTables& t, int L, hipStream_t st) {
   G16_HIP(hipFuncSetAttribute((const void*)ntt_last_pass_join_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)(sizeof(F29) << kTileLogCap)));
   const size_t N = (size_t)1 << L, half = N > 1 ? N / 2 : 1;
-  G16_HIP(hipMalloc(&t.tw_fwd, half * sizeof(F29)));
-  G16_HIP(hipMalloc(&t.tw_inv, half * sizeof(F29)));
-  G16_HIP(hipMalloc(&t.coset, N * sizeof(F29)));
+  G16_ALLOC(t.tw_fwd, half * sizeof(F29));
+  G16_ALLOC(t.tw_inv, half * sizeof(F29));
+  G16_ALLOC(t.coset, N * sizeof(F29));
   const Fr wc = host_root(L);
   const F29 w = fr29_from_fr(wc), winv = fr29_from_fr(fp_inv(wc));
   const F29 inc = fr29_from_fr(host_root(L + 1));  // w_2N (L <= 27 so L+1 <= 28)
@@ -297,14 +297,6 @@ int ntt_tables_create(NttTables& t, int L, hipStream_t st) {
   ntt_coset_table_kernel<<<(unsigned)((N + bs - 1) / bs), bs, 0, st>>>(t.coset, inc, ninv, L);
   G16_HIP(hipGetLastError());
   return G16_OK;
-}
-
-void ntt_tables_destroy(NttTables& t) {
-  if (t.tw_fwd) (void)hipFree(t.tw_fwd);
-  if (t.tw_inv) (void)hipFree(t.tw_inv);
-  if (t.coset) (void)hipFree(t.coset);
-  t.tw_fwd = t.tw_inv = t.coset = nullptr;
-  t.L = -1;
 }
 
 static int run_passes(const NttTables& t, F29* const* vecs, int nvec, bool dif, const F29* post_last, hipStream_t st) {

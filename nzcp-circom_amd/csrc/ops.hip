@@ -89,18 +89,19 @@ template <class F>
 static int multiexp_device(int curve, const uint8_t* bases, const Fr* d_scalars, size_t n, int window_bits, uint8_t* out) {
   if (n >= 0x7fffffffu) { set_error("multiexp: too many points"); return G16_E_ARG; }
   DeviceJob job("multiexp");
-  MsmJob msm;
+  MsmGroup g;
+  MsmWorkspacePtr ws;
   DeviceStream st;
   MsmConfig cfg;
   cfg.c = window_bits;
   MsmSectionIn sec;
   if (curve == 2) sec.bases2_host = bases; else sec.bases_host = bases;
   sec.n_total = (uint32_t)n;
-  int rc = msm_group_create(msm.g, &sec, 1, cfg);
-  if (rc || (rc = msm_workspace_create(&msm.ws, msm.g))) return rc;
+  int rc = msm_group_create(g, &sec, 1, cfg);
+  if (rc || (rc = msm_workspace_create(ws, g))) return rc;
   if (job.fail(st.create())) return job.rc;
   MsmResult res;
-  if ((rc = msm_launch(msm.g, msm.ws, d_scalars, st, st)) || (rc = msm_collect(msm.g, msm.ws, &res))) return rc;
+  if ((rc = msm_launch(g, ws.get(), d_scalars, st, st)) || (rc = msm_collect(g, ws.get(), &res))) return rc;
   XYZZ<F> total;
   memcpy(&total, curve == 2 ? (const void*)&res.g2 : (const void*)&res.g1[0], sizeof(total));
   Affine<F> r;
@@ -131,7 +132,7 @@ static int fft_impl(int device, uint8_t* buf, size_t n, bool inverse) {
   while (((size_t)1 << L) < n) L++;
   if (n == 0 || ((size_t)1 << L) != n) { set_error("fft: size must be a power of two"); return G16_E_ARG; }
   DeviceJob job("fft");
-  NttTablesOwned t;
+  NttTables t;
   DeviceBuf<Fr> dx, dy;   // the canonical image in and out
   DeviceBuf<F29> dz;      // the lazy working vector
   DeviceStream st;

@@ -475,69 +475,48 @@ struct g16_plonk {
   int device = 0;
   uint32_t N = 0, L = 0, nVars = 0, nPublic = 0, nAdd = 0, nCons = 0, nBase = 0;
   FrM k1, k2, w1;
-  hipStream_t st = nullptr, st2 = nullptr;   // main chain (commitments); the 4N transforms of a round beside its commitments
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  DeviceEvent ev_fork, ev_join;
   NttTables ntt_n, ntt_4n;
-  FrM* d_sig[3] = {};     // S1 S2 S3 at the N domain points (every 4th of the zkey's 4N evaluations), canonical: round 2
-  F29* d_ext_l[8] = {};   // Qm Ql Qr Qo Qc S1 S2 S3, 4N evaluations in the lazy format: round 3
-  FrM* d_pol[8] = {};     // ... N coefficients
-  uint32_t* d_map[3] = {};
-  uint32_t *d_add_s1 = nullptr, *d_add_s2 = nullptr, *d_add_order = nullptr;
-  FrM *d_add_f1 = nullptr, *d_add_f2 = nullptr;
+  DeviceBuf<FrM> d_sig[3];   // S1 S2 S3 at the N domain points (every 4th of the zkey's 4N evaluations), canonical: round 2
+  DeviceBuf<F29> d_ext_l[8];   // Qm Ql Qr Qo Qc S1 S2 S3, 4N evaluations in the lazy format: round 3
+  DeviceBuf<FrM> d_pol[8];   // ... N coefficients
+  DeviceBuf<uint32_t> d_map[3];
+  DeviceBuf<uint32_t> d_add_s1, d_add_s2, d_add_order;
+  DeviceBuf<FrM> d_add_f1, d_add_f2;
   std::vector<uint32_t> level_start;
-  F29 *d_om4 = nullptr, *d_l1 = nullptr;   // the points g w_4N^i of the round-3 coset and L1 on it, lazy format
-  FrM* d_gtab = nullptr;                   // g^j as (lo: 4096 words, hi: gtab_hi words), then g^-j likewise: see PowTab
+  DeviceBuf<F29> d_om4, d_l1;   // the points g w_4N^i of the round-3 coset and L1 on it, lazy format
+  DeviceBuf<FrM> d_gtab;                   // g^j as (lo: 4096 words, hi: gtab_hi words), then g^-j likewise: see PowTab
   size_t gtab_hi = 1;
   FrM gN;                                  // g^N
   PowTab tab_g() const { return PowTab{d_gtab, d_gtab + 4096}; }
   PowTab tab_ginv() const { return PowTab{d_gtab + 4096 + gtab_hi, d_gtab + 8192 + gtab_hi}; }
   MsmGroup srs;
-  MsmWorkspace* ws = nullptr;             // slot 0 of the commitment lanes (on the main stream)
-  MsmWorkspace* wsx[2] = {nullptr, nullptr};   // slots 1, 2: independent commitments of a round run side by side
-  hipStream_t mst[2] = {nullptr, nullptr};
-  Fr* d_scalx[2] = {nullptr, nullptr};
-  hipEvent_t ev_pol = nullptr;
+  MsmWorkspacePtr ws;                     // slot 0 of the commitment lanes (on the main stream)
+  MsmWorkspacePtr wsx[2];                 // slots 1, 2: independent commitments of a round run side by side
+  DeviceBuf<Fr> d_scalx[2];
+  DeviceEvent ev_pol;
   // per-proof scratch
-  Fr* d_wraw = nullptr;                 // witness as uploaded (standard form)
-  FrM* d_w = nullptr;                   // extended witness, Montgomery
-  FrM *d_A = nullptr, *d_B = nullptr, *d_C = nullptr, *d_Z = nullptr;   // N evaluations
-  FrM *d_pa = nullptr, *d_pb = nullptr, *d_pc = nullptr, *d_pz = nullptr;   // blinded coefficient forms (N + 3)
-  F29 *d_A4 = nullptr, *d_B4 = nullptr, *d_C4 = nullptr, *d_Z4 = nullptr, *d_pi4 = nullptr;   // 4N evaluations, lazy format
-  FrM* d_T = nullptr;                   // 4N canonical words: padding scratch, then the quotient's coefficients
-  FrM *d_tmpN = nullptr, *d_tmpN2 = nullptr, *d_tmpN3 = nullptr, *d_tmpN4 = nullptr;   // N-sized scratch
-  FrM *d_cA = nullptr, *d_cB = nullptr, *d_cC = nullptr, *d_cZ = nullptr;   // unblinded coefficients (the side stream pads them)
-  FrM *d_pi_ev = nullptr, *d_pi_co = nullptr;
-  FrM *d_r = nullptr, *d_wxi = nullptr, *d_q = nullptr;
-  FrM *d_tot = nullptr, *d_tot2 = nullptr;   // chunk totals / Horner partials, and their combined carries
-  FrM* d_evals = nullptr;               // 8 evaluation results, read back once per round
-  F29 *d_lazy = nullptr, *d_lazy2 = nullptr;   // 4N lazy elements each: the transforms' working vectors (d_lazy: t in round 3)
-  Fr* d_scal = nullptr;                 // N + 6 standard-form MSM scalars
-  uint32_t* d_bad = nullptr;
+  DeviceBuf<Fr> d_wraw;                 // witness as uploaded (standard form)
+  DeviceBuf<FrM> d_w;                   // extended witness, Montgomery
+  DeviceBuf<FrM> d_A, d_B, d_C, d_Z;   // N evaluations
+  DeviceBuf<FrM> d_pa, d_pb, d_pc, d_pz;   // blinded coefficient forms (N + 3)
+  DeviceBuf<F29> d_A4, d_B4, d_C4, d_Z4, d_pi4;   // 4N evaluations, lazy format
+  DeviceBuf<FrM> d_T;                   // 4N canonical words: padding scratch, then the quotient's coefficients
+  DeviceBuf<FrM> d_tmpN, d_tmpN2, d_tmpN3, d_tmpN4;   // N-sized scratch
+  DeviceBuf<FrM> d_cA, d_cB, d_cC, d_cZ;   // unblinded coefficients (the side stream pads them)
+  DeviceBuf<FrM> d_pi_ev, d_pi_co;
+  DeviceBuf<FrM> d_r, d_wxi, d_q;
+  DeviceBuf<FrM> d_tot, d_tot2;   // chunk totals / Horner partials, and their combined carries
+  DeviceBuf<FrM> d_evals;               // 8 evaluation results, read back once per round
+  DeviceBuf<F29> d_lazy, d_lazy2;   // 4N lazy elements each: the transforms' working vectors (d_lazy: t in round 3)
+  DeviceBuf<Fr> d_scal;                 // N + 6 standard-form MSM scalars
+  DeviceBuf<uint32_t> d_bad;
   float last_ms[6] = {};
   std::mutex mu;
-  ~g16_plonk() {
-    (void)hipSetDevice(device);
-    for (auto p : d_sig) if (p) (void)hipFree(p);
-    for (auto p : d_ext_l) if (p) (void)hipFree(p);
-    for (auto p : d_pol) if (p) (void)hipFree(p);
-    for (auto p : d_map) if (p) (void)hipFree(p);
-    void* v[] = {d_add_s1, d_add_s2, d_add_order, d_add_f1, d_add_f2, d_om4, d_l1, d_wraw, d_w, d_A, d_B, d_C, d_Z, d_pa, d_pb, d_pc,
-                 d_pz, d_A4, d_B4, d_C4, d_Z4, d_T, d_gtab, d_pi4, d_tmpN, d_tmpN2, d_tmpN3, d_tmpN4, d_r, d_wxi, d_q, d_tot, d_lazy, d_lazy2, d_cA, d_cB, d_cC, d_cZ, d_pi_ev, d_pi_co, d_tot2, d_evals,
-                 d_scal, d_bad};
-    for (void* p : v) if (p) (void)hipFree(p);
-    if (ws) msm_workspace_destroy(ws);
-    for (auto w : wsx) if (w) msm_workspace_destroy(w);
-    for (auto p : d_scalx) if (p) (void)hipFree(p);
-    for (auto x : mst) if (x) (void)hipStreamDestroy(x);
-    if (ev_pol) (void)hipEventDestroy(ev_pol);
-    msm_group_destroy(srs);
-    ntt_tables_destroy(ntt_n);
-    ntt_tables_destroy(ntt_4n);
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (st2) (void)hipStreamDestroy(st2);
-    if (st) (void)hipStreamDestroy(st);
-  }
+  // (device_job.h: the streams after everything their work touches; the body of the destructor sets the device, no more)
+  DeviceStream st, st2;   // main chain (commitments); the 4N transforms of a round beside its commitments
+  DeviceStream mst[2];    // of the commitment slots 1, 2
+  ~g16_plonk() { (void)hipSetDevice(device); }
 };
 
 namespace {
@@ -613,10 +592,10 @@ int plonk_create_impl(const uint8_t* zkey, size_t len, int device, g16_plonk* P)
   G16_HIP(hipSetDevice(device));
   int prio_lo = 0, prio_hi = 0;
   G16_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-  G16_HIP(hipStreamCreateWithPriority(&P->st, hipStreamNonBlocking, prio_hi));
-  G16_HIP(hipStreamCreateWithPriority(&P->st2, hipStreamNonBlocking, 0));
-  G16_HIP(hipEventCreateWithFlags(&P->ev_fork, hipEventDisableTiming));
-  G16_HIP(hipEventCreateWithFlags(&P->ev_join, hipEventDisableTiming));
+  G16_STREAM(P->st, hipStreamNonBlocking, prio_hi);
+  G16_STREAM(P->st2, hipStreamNonBlocking, 0);
+  G16_EVENT_FLAGS(P->ev_fork, hipEventDisableTiming);
+  G16_EVENT_FLAGS(P->ev_join, hipEventDisableTiming);
   hipStream_t st = P->st;
   if ((rc = ntt_tables_create(P->ntt_n, (int)P->L, st))) return rc;
   if ((rc = ntt_tables_create(P->ntt_4n, (int)P->L + 2, st))) return rc;
@@ -634,21 +613,21 @@ int plonk_create_impl(const uint8_t* zkey, size_t len, int device, g16_plonk* P)
       const FrM step = fp_mul(lo[4095], base[t]);
       for (size_t k = 1; k < P->gtab_hi; k++) hi[k] = fp_mul(hi[k - 1], step);
     }
-    G16_HIP(hipMalloc(&P->d_gtab, tab.size() * 32));
+    G16_ALLOC(P->d_gtab, tab.size() * 32);
     G16_HIP(hipMemcpy(P->d_gtab, tab.data(), tab.size() * 32, hipMemcpyHostToDevice));
   }
   // polynomials: coefficients (N) then evaluations (4N)
   // the selectors' 4N evaluations pass through d_T (allocated here, scratch of the proofs later) on their way to the
   // lazy format
-  G16_HIP(hipMalloc(&P->d_T, (size_t)N * 128));
+  G16_ALLOC(P->d_T, (size_t)N * 128);
   FrM* d_stage = P->d_T;
   for (int k = 0; k < 8; k++) {
     const uint8_t* src = k < 5 ? s[7 + k].p : s[12].p + (size_t)(k - 5) * polb;
-    G16_HIP(hipMalloc(&P->d_pol[k], (size_t)N * 32));
-    G16_HIP(hipMalloc(&P->d_ext_l[k], (size_t)N * 4 * sizeof(F29)));
+    G16_ALLOC(P->d_pol[k], (size_t)N * 32);
+    G16_ALLOC(P->d_ext_l[k], (size_t)N * 4 * sizeof(F29));
     G16_HIP(hipMemcpyAsync(P->d_pol[k], src, (size_t)N * 32, hipMemcpyHostToDevice, st));
     if (k >= 5) {   // sigma: round 2 reads the canonical evaluations at the N-domain points (every 4th of the file's 4N)
-      G16_HIP(hipMalloc(&P->d_sig[k - 5], (size_t)N * 32));
+      G16_ALLOC(P->d_sig[k - 5], (size_t)N * 32);
       G16_HIP(hipMemcpyAsync(d_stage, src + (size_t)N * 32, (size_t)N * 128, hipMemcpyHostToDevice, st));
       k_stride4<<<nblk(N), 256, 0, st>>>(d_stage, N, P->d_sig[k - 5]);
     }
@@ -658,7 +637,7 @@ int plonk_create_impl(const uint8_t* zkey, size_t len, int device, g16_plonk* P)
   G16_HIP(hipStreamSynchronize(st));
   // maps, zero padded to N
   for (int c = 0; c < 3; c++) {
-    G16_HIP(hipMalloc(&P->d_map[c], (size_t)N * 4));
+    G16_ALLOC(P->d_map[c], (size_t)N * 4);
     G16_HIP(hipMemsetAsync(P->d_map[c], 0, (size_t)N * 4, st));
     if (P->nCons) G16_HIP(hipMemcpyAsync(P->d_map[c], s[4 + c].p, (size_t)P->nCons * 4, hipMemcpyHostToDevice, st));
     for (uint32_t i = 0; i < P->nCons; i++) {
@@ -691,11 +670,11 @@ int plonk_create_impl(const uint8_t* zkey, size_t len, int device, g16_plonk* P)
     std::vector<uint32_t> cur(cnt.begin(), cnt.end() - 1);
     for (uint32_t k = 0; k < na; k++) order[cur[lvl[k]]++] = k;
     if (na) {
-      G16_HIP(hipMalloc(&P->d_add_s1, (size_t)na * 4));
-      G16_HIP(hipMalloc(&P->d_add_s2, (size_t)na * 4));
-      G16_HIP(hipMalloc(&P->d_add_order, (size_t)na * 4));
-      G16_HIP(hipMalloc(&P->d_add_f1, (size_t)na * 32));
-      G16_HIP(hipMalloc(&P->d_add_f2, (size_t)na * 32));
+      G16_ALLOC(P->d_add_s1, (size_t)na * 4);
+      G16_ALLOC(P->d_add_s2, (size_t)na * 4);
+      G16_ALLOC(P->d_add_order, (size_t)na * 4);
+      G16_ALLOC(P->d_add_f1, (size_t)na * 32);
+      G16_ALLOC(P->d_add_f2, (size_t)na * 32);
       G16_HIP(hipMemcpy(P->d_add_s1, s1.data(), (size_t)na * 4, hipMemcpyHostToDevice));
       G16_HIP(hipMemcpy(P->d_add_s2, s2.data(), (size_t)na * 4, hipMemcpyHostToDevice));
       G16_HIP(hipMemcpy(P->d_add_order, order.data(), (size_t)na * 4, hipMemcpyHostToDevice));
@@ -705,21 +684,21 @@ int plonk_create_impl(const uint8_t* zkey, size_t len, int device, g16_plonk* P)
   }
   // scratch
   const size_t n4 = (size_t)N * 4;
-  F29** four_l[] = {&P->d_A4, &P->d_B4, &P->d_C4, &P->d_Z4, &P->d_pi4, &P->d_om4, &P->d_l1, &P->d_lazy, &P->d_lazy2};
-  for (F29** p : four_l) G16_HIP(hipMalloc(p, n4 * sizeof(F29)));
-  FrM** one[] = {&P->d_A, &P->d_B, &P->d_C, &P->d_Z, &P->d_tmpN, &P->d_tmpN2, &P->d_tmpN3, &P->d_tmpN4,
+  DeviceBuf<F29>* four_l[] = {&P->d_A4, &P->d_B4, &P->d_C4, &P->d_Z4, &P->d_pi4, &P->d_om4, &P->d_l1, &P->d_lazy, &P->d_lazy2};
+  for (DeviceBuf<F29>* p : four_l) G16_HIP_AS(p->alloc_bytes(n4 * sizeof(F29)), "hipMalloc(p, n4 * sizeof(F29))");
+  DeviceBuf<FrM>* one[] = {&P->d_A, &P->d_B, &P->d_C, &P->d_Z, &P->d_tmpN, &P->d_tmpN2, &P->d_tmpN3, &P->d_tmpN4,
                  &P->d_cA, &P->d_cB, &P->d_cC, &P->d_cZ, &P->d_pi_ev, &P->d_pi_co};
-  for (FrM** p : one) G16_HIP(hipMalloc(p, (size_t)N * 32));
-  FrM** plus[] = {&P->d_pa, &P->d_pb, &P->d_pc, &P->d_pz, &P->d_r, &P->d_wxi, &P->d_q};
-  for (FrM** p : plus) G16_HIP(hipMalloc(p, ((size_t)N + 8) * 32));
-  G16_HIP(hipMalloc(&P->d_wraw, (size_t)P->nBase * 32));
-  G16_HIP(hipMalloc(&P->d_w, (size_t)P->nVars * 32));
-  G16_HIP(hipMalloc(&P->d_scal, ((size_t)N + 8) * 32));
+  for (DeviceBuf<FrM>* p : one) G16_HIP_AS(p->alloc_bytes((size_t)N * 32), "hipMalloc(p, (size_t)N * 32)");
+  DeviceBuf<FrM>* plus[] = {&P->d_pa, &P->d_pb, &P->d_pc, &P->d_pz, &P->d_r, &P->d_wxi, &P->d_q};
+  for (DeviceBuf<FrM>* p : plus) G16_HIP_AS(p->alloc_bytes(((size_t)N + 8) * 32), "hipMalloc(p, ((size_t)N + 8) * 32)");
+  G16_ALLOC(P->d_wraw, (size_t)P->nBase * 32);
+  G16_ALLOC(P->d_w, (size_t)P->nVars * 32);
+  G16_ALLOC(P->d_scal, ((size_t)N + 8) * 32);
   const size_t tot_n = std::max<size_t>(n4 / kChunk + 8, 8 * ((3 * (size_t)N + 8) / kHorner + 2));
-  G16_HIP(hipMalloc(&P->d_tot, tot_n * 32));
-  G16_HIP(hipMalloc(&P->d_tot2, tot_n * 32));
-  G16_HIP(hipMalloc(&P->d_evals, 8 * 32));
-  G16_HIP(hipMalloc(&P->d_bad, 64));
+  G16_ALLOC(P->d_tot, tot_n * 32);
+  G16_ALLOC(P->d_tot2, tot_n * 32);
+  G16_ALLOC(P->d_evals, 8 * 32);
+  G16_ALLOC(P->d_bad, 64);
   // the coset points g w_4N^i and L1 = iNTT(e_0) on them
   k_powers<<<nblk(nblk(n4, kChunk)), 256, 0, st>>>(h_root((int)P->L + 2), (uint32_t)n4, P->d_T);
   k_mul_const<<<nblk(n4), 256, 0, st>>>(P->d_T, n4, h_root((int)P->L + 3));
@@ -741,20 +720,20 @@ int plonk_create_impl(const uint8_t* zkey, size_t len, int device, g16_plonk* P)
   cfg.dense = true;
   if ((rc = msm_group_create(P->srs, &sec, 1, cfg))) return rc;
   if (P->srs.n != N + 6) { set_error("zkey: a power of tau is the point at infinity"); return G16_E_FORMAT; }
-  if ((rc = msm_workspace_create(&P->ws, P->srs))) return rc;
+  if ((rc = msm_workspace_create(P->ws, P->srs))) return rc;
   // three of the accumulate kernel's four wavefronts per SIMD (as fast: it is issue-bound), so that the short kernels
   // of the other commitments -- task queues, reduce tails -- find a slot while it runs
   const uint32_t acc_waves = getenv("G16_PLONK_ACC_WAVES") ? (uint32_t)atoi(getenv("G16_PLONK_ACC_WAVES")) : 3u;
-  msm_set_waves(P->ws, acc_waves, 0);
+  msm_set_waves(P->ws.get(), acc_waves, 0);
   for (int k = 0; k < 2; k++) {
-    if ((rc = msm_workspace_create(&P->wsx[k], P->srs))) return rc;
-    msm_set_waves(P->wsx[k], acc_waves, 0);
+    if ((rc = msm_workspace_create(P->wsx[k], P->srs))) return rc;
+    msm_set_waves(P->wsx[k].get(), acc_waves, 0);
     // (HIP maps streams onto 4 hardware queues per priority level, FIFO within a queue: the main stream and the first
     // side stream take the high-priority pool, the others the normal one -- r02 trace: slot 0 and slot 2 shared a queue)
-    G16_HIP(hipStreamCreateWithPriority(&P->mst[k], hipStreamNonBlocking, k == 0 ? prio_hi : 0));
-    G16_HIP(hipMalloc(&P->d_scalx[k], ((size_t)N + 8) * 32));
+    G16_STREAM(P->mst[k], hipStreamNonBlocking, k == 0 ? prio_hi : 0);
+    G16_ALLOC(P->d_scalx[k], ((size_t)N + 8) * 32);
   }
-  G16_HIP(hipEventCreateWithFlags(&P->ev_pol, hipEventDisableTiming));
+  G16_EVENT_FLAGS(P->ev_pol, hipEventDisableTiming);
   return G16_OK;
 }
 
@@ -777,15 +756,15 @@ int commit_launch(g16_plonk* P, int slot, const FrM* d_coefs, uint32_t len) {
   }
   k_from_mont_pad<<<nblk(np), 256, 0, s>>>(d_coefs, len, scal, np);
   G16_HIP(hipGetLastError());
-  return msm_launch_front(P->srs, slot ? P->wsx[slot - 1] : P->ws, scal, s);   // digits -> sort; commit_lanes: the rest
+  return msm_launch_front(P->srs, (slot ? P->wsx[slot - 1] : P->ws).get(), scal, s);   // digits -> sort; commit_lanes: the rest
 }
 int commit_lanes(g16_plonk* P, int slot) {
   hipStream_t s = slot ? P->mst[slot - 1] : P->st;
-  return msm_launch_lanes(P->srs, slot ? P->wsx[slot - 1] : P->ws, s, s, nullptr, nullptr);
+  return msm_launch_lanes(P->srs, (slot ? P->wsx[slot - 1] : P->ws).get(), s, s, nullptr, nullptr);
 }
 int commit_collect(g16_plonk* P, int slot, G1Affine* out) {
   MsmResult res;
-  int rc = msm_collect(P->srs, slot ? P->wsx[slot - 1] : P->ws, &res);
+  int rc = msm_collect(P->srs, (slot ? P->wsx[slot - 1] : P->ws).get(), &res);
   if (rc) return rc;
   xyzz_to_affine(*out, res.g1[0]);
   return G16_OK;
@@ -1136,7 +1115,7 @@ int plonk_setup_polys(int device, int L, const Fr* const evals[8], uint8_t* cons
   G16_HIP(hipSetDevice(device));
   const size_t N = (size_t)1 << L, n4 = N * 4;
   DeviceJob job("plonk setup");
-  NttTablesOwned tn, t4;
+  NttTables tn, t4;
   DeviceBuf<FrM> d_ev, d_co, d_ext;
   DeviceBuf<F29> d_lazy;
   DeviceStream st;
@@ -1164,7 +1143,8 @@ int plonk_setup_commit(int device, const uint8_t* tau_g1, uint32_t N, const uint
   if (const int rc = require_hip_device(device, "plonk setup: no HIP device", "plonk setup: bad device ordinal")) return rc;
   G16_HIP(hipSetDevice(device));
   DeviceJob job("plonk setup");
-  MsmJob msm;
+  MsmGroup g;
+  MsmWorkspacePtr ws;
   DeviceBuf<FrM> d_co;
   DeviceBuf<Fr> d_sc;
   DeviceStream st;
@@ -1173,16 +1153,16 @@ int plonk_setup_commit(int device, const uint8_t* tau_g1, uint32_t N, const uint
   sec.n_total = N;
   MsmConfig cfg;
   cfg.dense = true;
-  int rc = msm_group_create(msm.g, &sec, 1, cfg);
+  int rc = msm_group_create(g, &sec, 1, cfg);
   if (rc) return rc;
-  if (msm.g.n != N) { set_error("ptau: a power of tau is the point at infinity"); return G16_E_FORMAT; }
-  if ((rc = msm_workspace_create(&msm.ws, msm.g))) return rc;
+  if (g.n != N) { set_error("ptau: a power of tau is the point at infinity"); return G16_E_FORMAT; }
+  if ((rc = msm_workspace_create(ws, g))) return rc;
   if (job.fail(st.create()) || job.fail(d_co.alloc(N)) || job.fail(d_sc.alloc(N))) return job.rc;
   for (int k = 0; k < 8; k++) {
     if (job.fail(hipMemcpyAsync(d_co.p, coefs[k], (size_t)N * 32, hipMemcpyHostToDevice, st))) return job.rc;
     k_from_mont_pad<<<nblk(N), 256, 0, st>>>(d_co.p, N, d_sc.p, N);
     MsmResult res;
-    if ((rc = msm_launch(msm.g, msm.ws, d_sc.p, st, st)) || (rc = msm_collect(msm.g, msm.ws, &res))) return rc;
+    if ((rc = msm_launch(g, ws.get(), d_sc.p, st, st)) || (rc = msm_collect(g, ws.get(), &res))) return rc;
     G1Affine a;
     xyzz_to_affine(a, res.g1[0]);
     memcpy(out + (size_t)k * 64, &a, 64);

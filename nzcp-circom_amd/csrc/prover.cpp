@@ -71,6 +71,10 @@ static_assert(sizeof(Partial) == G16_PARTIAL_BYTES, "partial blob layout");
 using namespace g16;
 
 // ====================================================================== the prover handle
+// Every device resource is an owner of device_job.h and releases itself; the declaration order is the release order
+// reversed.  The streams stand last in a context and the contexts last in the handle, so each stream has drained and gone
+// before anything its work touches is freed: the context's buffers, events and workspaces, then the handle's slots, groups,
+// tables and CSR.
 struct g16_prover {
   int device = 0;
   int shard_rank = 0, shard_count = 1;
@@ -86,64 +90,40 @@ struct g16_prover {
   MsmGroup grp[3];
   bool b2_solo = false;
   bool shard_begun = false;   // between g16_shard_begin and g16_shard_end
+  std::vector<DeviceBuf<Fr>> slot_dev;
+  std::vector<std::vector<uint8_t>> slot_pub;
   // Per-proof scratch.  Several contexts so that g16_prove_batch can have proof i+1 on the GPU while the
   // host collects and finishes proof i (BASELINE config 3); single proofs use ctx[0].
   struct ProofCtx {
-    hipStream_t st = nullptr;                        // QAP -> NTT -> H-MSM (critical chain)
-    hipStream_t wst = nullptr, wst2 = nullptr;       // witness group: front end + G1 lane; G2 lane
-    MsmWorkspace* ws[3] = {nullptr, nullptr, nullptr};   // one per group: they run concurrently
+    hipStream_t wst = nullptr, wst2 = nullptr;       // witness group: front end + G1 lane; G2 lane (views: of the owners
+                                                     // below, or of st with G16_SERIAL_MSM)
+    MsmWorkspacePtr ws[3];                           // one per group: they run concurrently
     // Proof events in two sets: a launch records into one (next_event_set) while the other may still hold the last
     // completed proof's, which g16_get_timings reads lazily.  ev[0], ev[1] (staging upload) are used from set 0 only.
-    hipEvent_t evs[2][8] = {};
-    hipEvent_t mevs[2][3][2] = {};
+    DeviceEvent evs[2][8];
+    DeviceEvent mevs[2][3][2];
     g16_timings tms[2] = {};
     int set = 0;
-    hipEvent_t* ev = evs[0];            // = evs[set]
-    hipEvent_t (*mev)[2] = mevs[0];     // = mevs[set]
-    F29 *d_a = nullptr, *d_b = nullptr, *d_c = nullptr;   // QAP/NTT vectors, lazy 9x29 format
-    F29* d_wm = nullptr;                                  // Montgomery image of the witness (qap_eval's +-1 records)
-    Fr* d_p = nullptr;                                    // H-MSM scalars, standard form
-    Fr* d_w = nullptr;                                    // batch mode: this context's witness copy
-    uint32_t* d_flag = nullptr;                           // canonicity check of the witness this context proves
-    uint32_t* h_flag = nullptr;                           // ... its pinned host copy
+    DeviceEvent* ev = evs[0];            // = evs[set]
+    DeviceEvent (*mev)[2] = mevs[0];     // = mevs[set]
+    DeviceBuf<F29> d_a, d_b, d_c;        // QAP/NTT vectors, lazy 9x29 format
+    DeviceBuf<F29> d_wm;                 // Montgomery image of the witness (qap_eval's +-1 records)
+    DeviceBuf<Fr> d_p;                   // H-MSM scalars, standard form
+    DeviceBuf<Fr> d_w;                   // batch mode: this context's witness copy
+    DeviceBuf<uint32_t> d_flag;          // canonicity check of the witness this context proves
+    PinnedBuf<uint32_t> h_flag;          // ... its pinned host copy
+    DeviceStream st;                     // QAP -> NTT -> H-MSM (critical chain)
+    DeviceStream wst2_own, wst_own;      // what wst2 / wst view when the context made streams for them
   };
   static constexpr int kCtx = 3;   // at most; `nctx` are created (a fourth context has to share hardware queues: r03, 272 proofs/s against 299)
-  ProofCtx ctx[kCtx];
   int nctx = 3;   // r02 sweep, 512-proof batches: 205 / 257 / 267 proofs/s with 1 / 2 / 3 contexts (each on its own hardware queues)
-  std::vector<Fr*> slot_dev;
-  std::vector<std::vector<uint8_t>> slot_pub;
   g16_timings tm{};    // of the last completed proof (refresh_timings)
   int tm_ctx = -1;     // context whose event set `tm_set` holds the last completed proof, newer than `tm`; or -1
   int tm_set = 0;
   std::mutex mu;
+  ProofCtx ctx[kCtx];
 
-  ~g16_prover() {
-    (void)hipSetDevice(device);
-    for (Fr* p : slot_dev) if (p) (void)hipFree(p);
-    for (auto& c : ctx) {
-      void* vs[] = {c.d_a, c.d_b, c.d_c, c.d_p, c.d_w, c.d_flag, c.d_wm};
-      for (void* p : vs) if (p) (void)hipFree(p);
-      if (c.h_flag) (void)hipHostFree(c.h_flag);
-      for (auto& w : c.ws) msm_workspace_destroy(w);
-      if (c.wst && c.wst != c.st) (void)hipStreamDestroy(c.wst);
-      if (c.wst2 && c.wst2 != c.st) (void)hipStreamDestroy(c.wst2);
-      for (auto& set : c.mevs)
-        for (auto& e : set) { if (e[0]) (void)hipEventDestroy(e[0]); if (e[1]) (void)hipEventDestroy(e[1]); }
-      for (auto& set : c.evs)
-        for (auto& e : set) if (e) (void)hipEventDestroy(e);
-      if (c.st) (void)hipStreamDestroy(c.st);
-    }
-    for (int m = 0; m < 2; m++) {
-      if (csr.row_ptr[m]) (void)hipFree(csr.row_ptr[m]);
-      if (csr.col[m]) (void)hipFree(csr.col[m]);
-      if (csr.mid[m]) (void)hipFree(csr.mid[m]);
-      if (csr.vptr[m]) (void)hipFree(csr.vptr[m]);
-      if (csr.val[m]) (void)hipFree(csr.val[m]);
-    }
-    if (csr.long_rows) (void)hipFree(csr.long_rows);
-    ntt_tables_destroy(ntt);
-    for (auto& m : grp) msm_group_destroy(m);
-  }
+  ~g16_prover() { (void)hipSetDevice(device); }
 };
 
 static int check_device(int device) {
@@ -206,7 +186,7 @@ static int build_csr(g16_prover* P, const BinSection& s4) {
     long_rows.insert(long_rows.end(), wave_rows.begin(), wave_rows.end());
     P->csr.n_long = (uint32_t)long_rows.size();
     if (!long_rows.empty()) {
-      G16_HIP(hipMalloc(&P->csr.long_rows, long_rows.size() * 4));
+      G16_ALLOC(P->csr.long_rows, long_rows.size() * 4);
       G16_HIP(hipMemcpy(P->csr.long_rows, long_rows.data(), long_rows.size() * 4, hipMemcpyHostToDevice));
     }
   }
@@ -237,22 +217,21 @@ static int build_csr(g16_prover* P, const BinSection& s4) {
     const size_t ngen = gen.size();
     P->csr.nnz[m] = nnz;
     P->csr.ngen[m] = ngen;
-    G16_HIP(hipMalloc(&P->csr.row_ptr[m], ((size_t)N + 1) * 4));
-    G16_HIP(hipMalloc(&P->csr.mid[m], ((size_t)N + 1) * 4));
-    G16_HIP(hipMalloc(&P->csr.vptr[m], ((size_t)N + 1) * 4));
-    G16_HIP(hipMalloc(&P->csr.col[m], (nnz + 1) * 4));
-    G16_HIP(hipMalloc(&P->csr.val[m], (ngen + 1) * sizeof(F29)));
+    G16_ALLOC(P->csr.row_ptr[m], ((size_t)N + 1) * 4);
+    G16_ALLOC(P->csr.mid[m], ((size_t)N + 1) * 4);
+    G16_ALLOC(P->csr.vptr[m], ((size_t)N + 1) * 4);
+    G16_ALLOC(P->csr.col[m], (nnz + 1) * 4);
+    G16_ALLOC(P->csr.val[m], (ngen + 1) * sizeof(F29));
     G16_HIP(hipMemcpy(P->csr.row_ptr[m], rp[m].data(), ((size_t)N + 1) * 4, hipMemcpyHostToDevice));
     G16_HIP(hipMemcpy(P->csr.mid[m], mid.data(), (size_t)N * 4, hipMemcpyHostToDevice));
     G16_HIP(hipMemcpy(P->csr.vptr[m], vptr.data(), (size_t)N * 4, hipMemcpyHostToDevice));
     if (nnz) G16_HIP(hipMemcpy(P->csr.col[m], col2.data(), nnz * 4, hipMemcpyHostToDevice));
     if (ngen) {
-      Fr* tmp = nullptr;   // file words -> lazy coefficient format, once
-      G16_HIP(hipMalloc(&tmp, ngen * sizeof(Fr)));
+      DeviceBuf<Fr> tmp;   // file words -> lazy coefficient format, once
+      G16_ALLOC(tmp, ngen * sizeof(Fr));
       G16_HIP(hipMemcpy(tmp, gen.data(), ngen * sizeof(Fr), hipMemcpyHostToDevice));
       int rc = qap_convert_coefs(tmp, P->csr.val[m], ngen, P->st);
       if (!rc && hipStreamSynchronize(P->st) != hipSuccess) { set_error("coefficient conversion failed"); rc = G16_E_HIP; }
-      (void)hipFree(tmp);
       if (rc) return rc;
     }
   }
@@ -321,15 +300,17 @@ static int create_impl(const uint8_t* zkey, size_t len, const g16_opts* opts, g1
   // three distinct queues), witness front end + G1 lane (low priority: its own pool).
   const bool serial_mode = getenv("G16_SERIAL_MSM") && atoi(getenv("G16_SERIAL_MSM"));
   for (auto& c : P->ctx) {
-    G16_HIP(hipStreamCreateWithPriority(&c.st, hipStreamNonBlocking, prio_hi));
+    G16_STREAM(c.st, hipStreamNonBlocking, prio_hi);
     if (serial_mode) {
       c.wst = c.wst2 = c.st;
     } else {
-      G16_HIP(hipStreamCreateWithPriority(&c.wst2, hipStreamNonBlocking, prio_hi));
-      G16_HIP(hipStreamCreateWithPriority(&c.wst, hipStreamNonBlocking, prio_lo));
+      G16_HIP_AS(c.wst2_own.create(hipStreamNonBlocking, prio_hi), "hipStreamCreateWithPriority(&c.wst2, hipStreamNonBlocking, prio_hi)");
+      G16_HIP_AS(c.wst_own.create(hipStreamNonBlocking, prio_lo), "hipStreamCreateWithPriority(&c.wst, hipStreamNonBlocking, prio_lo)");
+      c.wst2 = c.wst2_own;
+      c.wst = c.wst_own;
     }
     for (auto& set : c.evs)
-      for (auto& e : set) G16_HIP(hipEventCreate(&e));
+      for (auto& e : set) G16_EVENT(e);
     break;   // context 1 (batch pipelining) after context 0's workspaces, below
   }
   P->st = P->ctx[0].st;
@@ -362,7 +343,7 @@ static int create_impl(const uint8_t* zkey, size_t len, const g16_opts* opts, g1
     cfg.precomp = 1;
     rc = msm_group_create(P->grp[0], secs, 3, cfg);
     if (rc == G16_E_FORMAT) {   // sections 6 / 7 disagree on infinity: B2 gets its own front end
-      msm_group_destroy(P->grp[0]);
+      P->grp[0] = MsmGroup();
       MsmSectionIn b2 = secs[1];
       b2.bases_host = nullptr;
       secs[1].bases2_host = nullptr;
@@ -397,32 +378,34 @@ static int create_impl(const uint8_t* zkey, size_t len, const g16_opts* opts, g1
       const int prio_ctx = pools ? prio_hi + 1 : prio_hi;
       // (a third context -- G16_BATCH_CTX=3, sweeps -- takes what is left: the 4th high queue, the 4th normal one, two low ones)
       const int p_main = ci == 1 ? prio_ctx : prio_hi, p_g2 = prio_ctx, p_dup = (ci == 1 || !pools) ? prio_ctx : prio_lo;
-      G16_HIP(hipStreamCreateWithPriority(&c.st, hipStreamNonBlocking, p_main));
+      G16_STREAM(c.st, hipStreamNonBlocking, p_main);
       if (serial) {
         c.wst = c.wst2 = c.st;
       } else {
-        G16_HIP(hipStreamCreateWithPriority(&c.wst2, hipStreamNonBlocking, p_g2));
-        G16_HIP(hipStreamCreateWithPriority(&c.wst, hipStreamNonBlocking, prio_lo));
+        G16_HIP_AS(c.wst2_own.create(hipStreamNonBlocking, p_g2), "hipStreamCreateWithPriority(&c.wst2, hipStreamNonBlocking, p_g2)");
+        G16_HIP_AS(c.wst_own.create(hipStreamNonBlocking, prio_lo), "hipStreamCreateWithPriority(&c.wst, hipStreamNonBlocking, prio_lo)");
+        c.wst2 = c.wst2_own;
+        c.wst = c.wst_own;
       }
       for (auto& set : c.evs)
-        for (auto& e : set) G16_HIP(hipEventCreate(&e));
+        for (auto& e : set) G16_EVENT(e);
       msm_set_aux_stream_priority(p_dup);
     }
     for (int i = 0; i < 3; i++) {
-      if ((rc = msm_workspace_create(&c.ws[i], P->grp[i]))) return rc;   // (creates the G2 lane's dup-row stream)
+      if ((rc = msm_workspace_create(c.ws[i], P->grp[i]))) return rc;   // (creates the G2 lane's dup-row stream)
       for (auto& set : c.mevs) {
-        G16_HIP(hipEventCreate(&set[i][0]));
-        G16_HIP(hipEventCreate(&set[i][1]));
+        G16_EVENT(set[i][0]);
+        G16_EVENT(set[i][1]);
       }
     }
     const size_t vb = (size_t)P->N * sizeof(F29);
-    G16_HIP(hipMalloc(&c.d_a, vb));
-    G16_HIP(hipMalloc(&c.d_b, vb));
-    G16_HIP(hipMalloc(&c.d_c, vb));
-    G16_HIP(hipMalloc(&c.d_p, (size_t)P->N * sizeof(Fr)));
-    G16_HIP(hipMalloc(&c.d_wm, ((size_t)P->nVars + 1) * sizeof(F29)));
-    G16_HIP(hipMalloc(&c.d_flag, 64));
-    G16_HIP(hipHostMalloc((void**)&c.h_flag, 64));
+    G16_ALLOC(c.d_a, vb);
+    G16_ALLOC(c.d_b, vb);
+    G16_ALLOC(c.d_c, vb);
+    G16_ALLOC(c.d_p, (size_t)P->N * sizeof(Fr));
+    G16_ALLOC(c.d_wm, ((size_t)P->nVars + 1) * sizeof(F29));
+    G16_ALLOC(c.d_flag, 64);
+    G16_PINNED(c.h_flag, 64);
     *c.h_flag = 0xffffffffu;
   }
   msm_set_aux_stream_priority(kMsmPrioHighest);
@@ -469,8 +452,8 @@ static int stage_impl(g16_prover* P, uint32_t slot, const uint8_t* wtns, size_t 
   if (rc) return rc;
   if (slot >= 65536) { set_error("slot out of range"); return G16_E_ARG; }
   G16_HIP(hipSetDevice(P->device));
-  if (P->slot_dev.size() <= slot) { P->slot_dev.resize(slot + 1, nullptr); P->slot_pub.resize(slot + 1); }
-  if (!P->slot_dev[slot]) G16_HIP(hipMalloc(&P->slot_dev[slot], (size_t)P->nVars * sizeof(Fr)));
+  if (P->slot_dev.size() <= slot) { P->slot_dev.resize(slot + 1); P->slot_pub.resize(slot + 1); }
+  if (!P->slot_dev[slot]) G16_ALLOC(P->slot_dev[slot], (size_t)P->nVars * sizeof(Fr));
   auto& c0 = P->ctx[0];
   G16_HIP(hipEventRecord(c0.evs[0][0], P->st));
   G16_HIP(hipMemcpyAsync(P->slot_dev[slot], body, (size_t)P->nVars * 32, hipMemcpyHostToDevice, P->st));
@@ -621,11 +604,11 @@ static int launch_witness_front(g16_prover* P, ProofCtx& c, const Fr* d_w) {
   int rc;
   if (c.wst != c.st) G16_HIP(hipStreamWaitEvent(c.wst, c.ev[2], 0));
   G16_HIP(hipEventRecord(c.mev[0][0], c.wst));
-  if ((rc = msm_launch_front(P->grp[0], c.ws[0], d_w, c.wst))) return rc;
+  if ((rc = msm_launch_front(P->grp[0], c.ws[0].get(), d_w, c.wst))) return rc;
   if (P->b2_solo) {
     if (c.wst2 != c.st) G16_HIP(hipStreamWaitEvent(c.wst2, c.ev[2], 0));
     G16_HIP(hipEventRecord(c.mev[2][0], c.wst2));
-    if ((rc = msm_launch_front(P->grp[2], c.ws[2], d_w, c.wst2))) return rc;
+    if ((rc = msm_launch_front(P->grp[2], c.ws[2].get(), d_w, c.wst2))) return rc;
   }
   return G16_OK;
 }
@@ -640,15 +623,15 @@ static int launch_witness_lanes(g16_prover* P, ProofCtx& c, bool h_launched) {
     // 6.3 with both; the 1.7 M synthetic circuit 8.1 ms either way -- holding work back only moves the collision.)
     const uint32_t gsel = sched_digit("G16_GATE", l, 2, 0u);
     if (gsel == 1) gates[l] = c.ev[4];
-    else if (gsel == 2 && P->grp[1].n) gates[l] = msm_event(c.ws[1], 0);   // (recorded by the H front end, enqueued before)
+    else if (gsel == 2 && P->grp[1].n) gates[l] = msm_event(c.ws[1].get(), 0);   // (recorded by the H front end, enqueued before)
   }
-  msm_set_waves(c.ws[0], sched_digit("G16_ACC_WAVES", 0, 3, 0), sched_digit("G16_ACC_WAVES", 1, 3, 0));
-  msm_set_quota(c.ws[0], sched_digit("G16_ACC_QUOTA", 0, 3, 0), sched_digit("G16_ACC_QUOTA", 1, 3, 0));
-  if ((rc = msm_launch_lanes(P->grp[0], c.ws[0], c.wst, c.wst2, gates[0], gates[1]))) return rc;
+  msm_set_waves(c.ws[0].get(), sched_digit("G16_ACC_WAVES", 0, 3, 0), sched_digit("G16_ACC_WAVES", 1, 3, 0));
+  msm_set_quota(c.ws[0].get(), sched_digit("G16_ACC_QUOTA", 0, 3, 0), sched_digit("G16_ACC_QUOTA", 1, 3, 0));
+  if ((rc = msm_launch_lanes(P->grp[0], c.ws[0].get(), c.wst, c.wst2, gates[0], gates[1]))) return rc;
   G16_HIP(hipEventRecord(c.mev[0][1], c.wst));
   if (P->b2_solo) {
-    msm_set_waves(c.ws[2], 0, sched_digit("G16_ACC_WAVES", 1, 3, 0));
-    if ((rc = msm_launch_lanes(P->grp[2], c.ws[2], c.wst2, c.wst2, nullptr, gates[1]))) return rc;
+    msm_set_waves(c.ws[2].get(), 0, sched_digit("G16_ACC_WAVES", 1, 3, 0));
+    if ((rc = msm_launch_lanes(P->grp[2], c.ws[2].get(), c.wst2, c.wst2, nullptr, gates[1]))) return rc;
     G16_HIP(hipEventRecord(c.mev[2][1], c.wst2));
   }
   return G16_OK;
@@ -684,18 +667,18 @@ static int launch_join_h_front(g16_prover* P, ProofCtx& c, uint32_t lo, uint32_t
   if (!joined && hi > lo && (rc = ntt_join_abc(c.d_a + lo, c.d_b + lo, c.d_c + lo, c.d_p + lo, hi - lo, c.st))) return rc;
   G16_HIP(hipEventRecord(c.ev[4], c.st));
   G16_HIP(hipEventRecord(c.mev[1][0], c.st));
-  return msm_launch_front(P->grp[1], c.ws[1], c.d_p, c.st);
+  return msm_launch_front(P->grp[1], c.ws[1].get(), c.d_p, c.st);
 }
 // ... and its accumulate / combine / reduce.  G16_HGATE (sweeps): what the H accumulate waits for: 0 nothing, 1 the
 // end of the witness G2 lane, 2 both witness lanes
 static int launch_h_lanes(g16_prover* P, ProofCtx& c, bool w_launched) {
   int rc;
-  msm_set_waves(c.ws[1], sched_digit("G16_ACC_WAVES", 2, 3, 0), 0);
-  msm_set_quota(c.ws[1], sched_digit("G16_ACC_QUOTA", 2, 3, 0), 0);
+  msm_set_waves(c.ws[1].get(), sched_digit("G16_ACC_WAVES", 2, 3, 0), 0);
+  msm_set_quota(c.ws[1].get(), sched_digit("G16_ACC_QUOTA", 2, 3, 0), 0);
   const uint32_t hg = w_launched ? sched_digit("G16_HGATE", 0, 1, 0) : 0;
-  if (hg >= 2 && P->grp[0].n && msm_event(c.ws[0], 3)) G16_HIP(hipStreamWaitEvent(c.st, msm_event(c.ws[0], 3), 0));
-  hipEvent_t gate = (hg >= 1 && P->grp[0].n) ? msm_event(c.ws[0], 4) : nullptr;
-  if ((rc = msm_launch_lanes(P->grp[1], c.ws[1], c.st, c.st, gate, nullptr))) return rc;
+  if (hg >= 2 && P->grp[0].n && msm_event(c.ws[0].get(), 3)) G16_HIP(hipStreamWaitEvent(c.st, msm_event(c.ws[0].get(), 3), 0));
+  hipEvent_t gate = (hg >= 1 && P->grp[0].n) ? msm_event(c.ws[0].get(), 4) : nullptr;
+  if ((rc = msm_launch_lanes(P->grp[1], c.ws[1].get(), c.st, c.st, gate, nullptr))) return rc;
   G16_HIP(hipEventRecord(c.mev[1][1], c.st));
   G16_HIP(hipEventRecord(c.ev[5], c.st));   // end of the main stream's share of this proof (refresh_timings)
   return G16_OK;
@@ -707,9 +690,9 @@ static void next_event_set(g16_prover* P, ProofCtx& c);
 static int launch_ctx(g16_prover* P, ProofCtx& c, const Fr* d_w, bool pipelined = false) {
   G16_HIP(hipSetDevice(P->device));
   int rc;
-  msm_set_throughput(c.ws[0], P->grp[0], pipelined);
-  msm_set_throughput(c.ws[1], P->grp[1], pipelined);
-  if (P->b2_solo) msm_set_throughput(c.ws[2], P->grp[2], pipelined);
+  msm_set_throughput(c.ws[0].get(), P->grp[0], pipelined);
+  msm_set_throughput(c.ws[1].get(), P->grp[1], pipelined);
+  if (P->b2_solo) msm_set_throughput(c.ws[2].get(), P->grp[2], pipelined);
   const auto th0 = std::chrono::steady_clock::now();
   g_trace_origin = th0;
   next_event_set(P, c);
@@ -741,8 +724,8 @@ static int refresh_timings(g16_prover* P) {
   const int set = P->tm_set;
   P->tm_ctx = -1;
   G16_HIP(hipSetDevice(P->device));
-  hipEvent_t* ev = c.evs[set];
-  hipEvent_t (*mev)[2] = c.mevs[set];
+  const DeviceEvent* ev = c.evs[set];
+  const DeviceEvent (*mev)[2] = c.mevs[set];
   G16_HIP(hipEventSynchronize(ev[5]));
   G16_HIP(hipEventSynchronize(mev[0][1]));
   if (P->b2_solo) G16_HIP(hipEventSynchronize(mev[2][1]));
@@ -759,7 +742,7 @@ static int refresh_timings(g16_prover* P) {
       return G16_E_HIP;
     }
   }
-  const float g2 = msm_event_offset_ms(c.ws[P->b2_solo ? 2 : 0], mev[P->b2_solo ? 2 : 0][0], 1, 9);
+  const float g2 = msm_event_offset_ms(c.ws[P->b2_solo ? 2 : 0].get(), mev[P->b2_solo ? 2 : 0][0], 1, 9);
   t.msm_ms[0] = wg; t.msm_ms[1] = 0.f; t.msm_ms[2] = g2; t.msm_ms[3] = 0.f; t.msm_ms[4] = hg;
   static const bool trace_dev = getenv("G16_TRACE_HOST") != nullptr;
   if (trace_dev) {
@@ -772,7 +755,7 @@ static int refresh_timings(g16_prover* P) {
       float s0 = 0, s1 = 0;
       (void)hipEventElapsedTime(&s0, ev[2], mev[gi][0]);
       (void)hipEventElapsedTime(&s1, ev[2], mev[gi][1]);
-      auto off = [&](int lane, int k) { return msm_event_offset_ms(c.ws[gi], ev[2], lane, k); };
+      auto off = [&](int lane, int k) { return msm_event_offset_ms(c.ws[gi].get(), ev[2], lane, k); };
       fprintf(stderr, "[g16 dev] %s  start %.3f pass0 %.3f binscan %.3f pass1 %.3f binsort+scans %.3f | G1 queue %.3f accumulate "
               "%.3f..%.3f combine %.3f reduce %.3f end %.3f (stream end %.3f)\n", nm[gi], s0, off(0, 0), off(0, 1), off(0, 2),
               off(0, 3), off(0, 6), off(0, 4), off(0, 5), off(0, 7), off(0, 8), off(0, 9), s1);
@@ -809,30 +792,30 @@ static void mark_completed(g16_prover* P, ProofCtx& c) {
 static int collect_witness_msms(g16_prover* P, ProofCtx& c, Partial& out,
                                 const std::function<void(const MsmResult&)>* after_g1 = nullptr) {
   MsmResult r;
-  int rc = msm_collect(P->grp[0], c.ws[0], &r, after_g1);
+  int rc = msm_collect(P->grp[0], c.ws[0].get(), &r, after_g1);
   if (rc) return rc;
   out.A = r.g1[0];
   out.B1 = r.g1[1];
   out.C = r.g1[2];
   out.B2 = r.g2;
   g16_timings& tm = c.tms[c.set];
-  tm.msm_accum_kernel_ms[0] = msm_last_accum_ms(c.ws[0], 0);
+  tm.msm_accum_kernel_ms[0] = msm_last_accum_ms(c.ws[0].get(), 0);
   tm.msm_accum_kernel_ms[1] = tm.msm_accum_kernel_ms[3] = 0.f;
-  tm.msm_accum_kernel_ms[2] = msm_last_accum_ms(c.ws[0], 1);
+  tm.msm_accum_kernel_ms[2] = msm_last_accum_ms(c.ws[0].get(), 1);
   if (P->b2_solo) {
-    if ((rc = msm_collect(P->grp[2], c.ws[2], &r))) return rc;
+    if ((rc = msm_collect(P->grp[2], c.ws[2].get(), &r))) return rc;
     out.B2 = r.g2;
-    tm.msm_accum_kernel_ms[2] = msm_last_accum_ms(c.ws[2], 1);
+    tm.msm_accum_kernel_ms[2] = msm_last_accum_ms(c.ws[2].get(), 1);
   }
   return G16_OK;
 }
 static int collect_h_msm(g16_prover* P, ProofCtx& c, Partial& out) {
   MsmResult r;
-  int rc = msm_collect(P->grp[1], c.ws[1], &r);
+  int rc = msm_collect(P->grp[1], c.ws[1].get(), &r);
   if (rc) return rc;
   out.H = r.g1[0];
   trace_tail("H sum folded");
-  c.tms[c.set].msm_accum_kernel_ms[4] = msm_last_accum_ms(c.ws[1], 0);
+  c.tms[c.set].msm_accum_kernel_ms[4] = msm_last_accum_ms(c.ws[1].get(), 0);
   // the stream timings of this proof are read from its events when somebody asks (g16_get_timings, after
   // mark_completed): the record + synchronise + eight elapsed-time queries cost 0.05 ms of every proof when they sat
   // here (r03 host trace).  The streams need no draining either: each lane's ev_done, just waited for, is the last
@@ -907,8 +890,8 @@ namespace g16 {
 int shard_view(g16_prover* P, uint32_t slot, ShardView* out) {
   if (slot >= 65536) { set_error("slot out of range"); return G16_E_ARG; }
   G16_HIP(hipSetDevice(P->device));
-  if (P->slot_dev.size() <= slot) { P->slot_dev.resize(slot + 1, nullptr); P->slot_pub.resize(slot + 1); }
-  if (!P->slot_dev[slot]) G16_HIP(hipMalloc(&P->slot_dev[slot], (size_t)P->nVars * sizeof(Fr)));
+  if (P->slot_dev.size() <= slot) { P->slot_dev.resize(slot + 1); P->slot_pub.resize(slot + 1); }
+  if (!P->slot_dev[slot]) G16_ALLOC(P->slot_dev[slot], (size_t)P->nVars * sizeof(Fr));
   ProofCtx& c = P->ctx[0];
   out->device = P->device;
   out->st = c.st;
@@ -1055,8 +1038,8 @@ struct BatchPipe {
     for (size_t k = 0; k < nctx; k++) {
       if (!busy[k]) continue;
       ProofCtx& c = p->ctx[k];
-      hipEvent_t evs[4] = {c.ev[3], c.ws[0] ? msm_event(c.ws[0], 3) : nullptr, c.ws[0] ? msm_event(c.ws[0], 4) : nullptr,
-                           p->b2_solo && c.ws[2] ? msm_event(c.ws[2], 4) : nullptr};
+      hipEvent_t evs[4] = {c.ev[3], c.ws[0] ? msm_event(c.ws[0].get(), 3) : nullptr, c.ws[0] ? msm_event(c.ws[0].get(), 4) : nullptr,
+                           p->b2_solo && c.ws[2] ? msm_event(c.ws[2].get(), 4) : nullptr};
       for (hipEvent_t e : evs)
         if (e)
           if (int rc = wcalc_chunk_release(d, e)) return rc;
@@ -1217,8 +1200,8 @@ int g16_stage_inputs(g16_prover* p, uint32_t slot, g16_wtns_calculator* h, const
   if (slot >= 65536) { set_error("slot out of range"); return G16_E_ARG; }
   if (int rc = wcalc_check_inputs(h, inputs, n_inputs, 1)) return rc;
   G16_HIP(hipSetDevice(p->device));
-  if (p->slot_dev.size() <= slot) { p->slot_dev.resize(slot + 1, nullptr); p->slot_pub.resize(slot + 1); }
-  if (!p->slot_dev[slot]) G16_HIP(hipMalloc(&p->slot_dev[slot], (size_t)p->nVars * sizeof(Fr)));
+  if (p->slot_dev.size() <= slot) { p->slot_dev.resize(slot + 1); p->slot_pub.resize(slot + 1); }
+  if (!p->slot_dev[slot]) G16_ALLOC(p->slot_dev[slot], (size_t)p->nVars * sizeof(Fr));
   int rc = wcalc_device_run_into(h->dev, inputs, p->slot_dev[slot], p->st, status);
   if (!rc && *status == 0xffffffffu) {
     p->slot_pub[slot].resize((size_t)p->nPublic * 32);
@@ -1230,8 +1213,7 @@ int g16_stage_inputs(g16_prover* p, uint32_t slot, g16_wtns_calculator* h, const
   }
   // a violated check, or a failure: the slot holds no witness to prove
   (void)hipStreamSynchronize(p->st);
-  (void)hipFree(p->slot_dev[slot]);
-  p->slot_dev[slot] = nullptr;
+  p->slot_dev[slot].reset();
   return rc;
 }
 
@@ -1268,7 +1250,7 @@ int g16_prove_batch(g16_prover* p, const uint8_t* const* wtns, const size_t* wtn
       int e = parse_wtns(p, wtns[i], wtns_lens[i], &body);
       if (e) return e;
       G16_HIP(hipSetDevice(p->device));
-      if (!c.d_w) G16_HIP(hipMalloc(&c.d_w, wbytes));
+      if (!c.d_w) G16_ALLOC(c.d_w, wbytes);
       busy = true;
       G16_HIP(hipMemcpyAsync(c.d_w, body, wbytes, hipMemcpyHostToDevice, c.st));
       t_mid = pipe.now_ms();

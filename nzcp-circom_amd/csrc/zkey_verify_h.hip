@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void zkey_h_t_kernel(const Fr* __restrict__ u,
 
 namespace {
 struct HJob {   // (device_job.h: the stream last)
-  NttTablesOwned tab;
+  NttTables tab;
   DeviceBuf<Fr> d_u, d_rho, d_t;
   DeviceBuf<F29> d_z;
   DeviceTimer timer;

@@ -481,3 +481,109 @@ def test_multi_prove_task_buffer_overflow_is_an_error(amd, monkeypatch):
     mp = amd.MultiProver(zk, [0, 0])
     assert mp.prove(wt, r, s) == (meta["proof"], meta["public"])
     mp.close()
+
+
+# ------------------------------------------------------------------------------------------------ E: create ... destroy, over and over
+# Every device resource of the prover handles is an owner (csrc/device_job.h) that releases itself when the handle goes.
+# What a handle must not do is keep a share of itself, or hand the next handle a device in another state: four handles
+# in a row on one key give the same bytes, and the device's free memory comes back.
+def _free_bytes(amd):
+    """Free memory of the current device once it is idle: hipMemGetInfo, which torch.cuda.mem_get_info() wraps, read
+    through the HIP runtime the library itself is linked with (torch's bundled runtime, loaded after the library's in
+    this process, sees no device: see __graft_entry__.smoke)."""
+    lib = amd.load()
+    free, total = C.c_size_t(), C.c_size_t()
+    assert lib.hipDeviceSynchronize() == 0
+    assert lib.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+    return free.value
+
+
+def _four_cycles(amd, cycle, what):
+    """cycle() = create -> stage -> prove -> destroy with fixed blinding; `cycle(probe)` calls probe() while its handle
+    is live.  Returns cycle 1's result after checking that cycles 2 to 4 equal it, and that the device's free memory
+    after cycle 4 is below that after cycle 1 (the warm-up) by at most F / 2, F = what one live handle takes (measured in
+    cycle 2: free before its create minus free with the handle live).  A handle that leaks itself costs 3 F."""
+    free_after, live = [], []
+    results = []
+    for k in range(4):
+        before = _free_bytes(amd)
+        results.append(cycle(lambda: live.append(before - _free_bytes(amd))))
+        free_after.append(_free_bytes(amd))
+    for k in range(1, 4):
+        assert results[k] == results[0], f"{what}: cycle {k + 1} differs from cycle 1"
+    F, drift = live[1], free_after[0] - free_after[3]
+    print(f"{what}: a live handle takes F = {F} bytes (cycles: {live}); free memory after each cycle {free_after}, "
+          f"drift from cycle 1 to cycle 4 = {drift} bytes")
+    assert F > 0, f"{what}: a live handle takes no device memory ({live})"
+    assert drift <= F / 2, f"{what}: free memory fell by {drift} bytes over cycles 2 to 4, a live handle takes {F}"
+    return results[0]
+
+
+def _g16_cycle(amd, key):
+    def cycle(probe):
+        pv = amd.Prover(key.zkey)
+        pv.stage(0, key.wtns[0])
+        got = pv.prove_staged(0, f.le(RS[1][0]), f.le(RS[1][1]))
+        probe()
+        pv.close()
+        return got
+    return cycle
+
+
+def _g16_verifies(key, got):
+    pr, pub = got
+    return g.verify(key.zk, [int(x) for x in pub], (f.g1_from_obj(pr["pi_a"]), f.g2_from_obj(pr["pi_b"]), f.g1_from_obj(pr["pi_c"])))
+
+
+@pytest.mark.parametrize("env", [("G16_BATCH_CTX", "1"), ("G16_BATCH_CTX", "3"), ("G16_SERIAL_MSM", "1"), ("G16_ROWS_COPY", "1")],
+                         ids=lambda e: "=".join(e))
+def test_groth16_create_prove_destroy_four_times(amd, keys, monkeypatch, env):
+    """With one and three proof contexts, with the MSM streams aliased to the main stream (G16_SERIAL_MSM) and with the
+    lanes' row sums in a device buffer of their own (G16_ROWS_COPY): all read at create."""
+    monkeypatch.setenv(*env)
+    key = keys["small"]
+    got = _four_cycles(amd, _g16_cycle(amd, key), "groth16 " + "=".join(env))
+    assert got == key.want(0, 1) and _g16_verifies(key, got)
+
+
+def test_plonk_create_prove_destroy_four_times(amd):
+    import plonk as pk
+    zkey, wtns, meta = _golden("plonk_small")
+
+    def cycle(probe):
+        pv = amd.PlonkProver(zkey)
+        got = pv.prove(wtns, [int(x) for x in meta["blinding"]])
+        probe()
+        pv.close()
+        return got
+    proof, pub = _four_cycles(amd, cycle, "plonk")
+    assert (proof, pub) == (meta["proof"], meta["public"])
+    assert pk.verify(pk.vkey_from_zkey(zkey), [int(x) for x in pub], pk.proof_from_obj(proof))
+
+
+def test_multi_create_prove_destroy_four_times(amd, keys):
+    """g16_multi with two shards on device 0 (its events and both shard handles go with it)."""
+    key = keys["small"]
+
+    def cycle(probe):
+        mp = amd.MultiProver(key.zkey, [0, 0])
+        got = mp.prove(key.wtns[0], f.le(RS[1][0]), f.le(RS[1][1]))
+        probe()
+        mp.close()
+        return got
+    got = _four_cycles(amd, cycle, "multi")
+    assert got == key.want(0, 1) and _g16_verifies(key, got)
+
+
+def test_destroy_with_a_proof_in_flight(amd, keys):
+    """g16_shard_begin on a one-shard handle enqueues a proof and returns with the witness MSMs still running; the handle
+    is destroyed without g16_shard_end.  A legal sequence: the handle's streams are waited for before what their work
+    touches is freed, the call returns, and a fresh handle proves exactly."""
+    key = keys["small"]
+    vecs = _vec_bufs(amd, key.N)
+    pv = amd.Prover(key.zkey)
+    pv.stage(0, key.wtns[0])
+    pv.shard_begin(0, 7, [C.addressof(v) for v in vecs])
+    pv.close()
+    got = _g16_cycle(amd, key)(lambda: None)
+    assert got == key.want(0, 1) and _g16_verifies(key, got)
