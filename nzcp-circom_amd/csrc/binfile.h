@@ -66,10 +66,17 @@ inline bool bin_is_field(const uint8_t* p, uint64_t avail, const uint32_t prime[
 }
 
 // ------------------------------------------------------------------ writing
-struct Buf {   // a malloc'd image handed to the caller of the C ABI (g16_free)
+// A malloc'd image on its way to the caller of the C ABI (g16_free).  It owns the image until give() hands it out: an
+// early return or an exception before that frees it.  Move-only.
+struct Buf {
   uint8_t* p = nullptr;
   size_t len = 0, cap = 0;
-  bool reserve(size_t c) {
+  Buf() = default;
+  Buf(Buf&& o) noexcept : p(o.p), len(o.len), cap(o.cap) { o.p = nullptr; o.len = o.cap = 0; }
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() { free(p); }
+  bool reserve(size_t c) {   // once, on an empty Buf
     p = (uint8_t*)malloc(c ? c : 1);
     cap = c;
     return p != nullptr;
@@ -78,7 +85,10 @@ struct Buf {   // a malloc'd image handed to the caller of the C ABI (g16_free)
   void u32(uint32_t v) { put(&v, 4); }
   void u64(uint64_t v) { put(&v, 8); }
   uint8_t* skip(size_t n) { uint8_t* q = p + len; len += n; return q; }
-  void give(uint8_t** out, size_t* out_len) const { *out = p; *out_len = len; }
+  void give(uint8_t** out, size_t* out_len) {   // the image is the caller's from here on
+    *out = p; *out_len = len;
+    p = nullptr; len = cap = 0;
+  }
 };
 
 // The whole image reserved and framed: header, then for each of ids[0, nids) (each below 16, in file order) its record

@@ -326,7 +326,7 @@ extern "C" int g16_nzcp_witness_program(const uint32_t params[7], uint8_t** prog
     cb.rec = &rec;
     const uint8_t none = 0;
     cb.nzcp_pub_identity(params[0] != 0, params[1], params[2], params[3], params[4], params[5], params[6], &none, 0);
-    const Buf z = rec.finish(cb.c.n, cb.c.p);
+    Buf z = rec.finish(cb.c.n, cb.c.p);
     if (!z.p) { set_error("witness program: out of memory"); return G16_E_STATE; }
     z.give(prog, len);
     return G16_OK;
@@ -350,7 +350,7 @@ extern "C" int g16_nzcp_gadget_program(const char* name, const uint32_t* params,
       rec.quad(wire, {}, {}, o.lin.t);
       rec.outputs.push_back(wire);
     }
-    const Buf z = rec.finish((uint32_t)cb.w.size(), 0);
+    Buf z = rec.finish((uint32_t)cb.w.size(), 0);
     if (!z.p) { set_error("witness program: out of memory"); return G16_E_STATE; }
     z.give(prog, len);
     return G16_OK;

@@ -2,9 +2,8 @@
 // the product's own fp.cuh / ec.cuh compiled for the host), the Lagrange basis at a known tau, and FixedBaseMul, which
 // sends a batch to host threads or to a HIP device (setup_gpu.hip).
 #pragma once
-#include <thread>
-
 #include "circuit.h"
+#include "host_util.h"
 
 namespace g16 {
 
@@ -31,19 +30,6 @@ template <class F> void batch_to_affine(const XYZZ<F>* in, Affine<F>* out, size_
     out[i].x = F::mul(in[i].x, zzi);
     out[i].y = F::mul(in[i].y, zi);
   }
-}
-
-template <class Fn> void parallel_for(size_t n, int threads, Fn fn) {
-  if (threads < 1) threads = 1;
-  if ((size_t)threads > n) threads = n ? (int)n : 1;
-  std::vector<std::thread> th;
-  const size_t chunk = (n + threads - 1) / threads;
-  for (int t = 0; t < threads; t++) {
-    const size_t lo = (size_t)t * chunk, hi = lo + chunk < n ? lo + chunk : n;
-    if (lo >= hi) break;
-    th.emplace_back([=]() { fn(lo, hi); });
-  }
-  for (auto& x : th) x.join();
 }
 
 template <class F> void build_table(FixedBase<F>& fb, const Affine<F>& gen, int wb, int threads) {

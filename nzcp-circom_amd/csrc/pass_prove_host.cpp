@@ -18,11 +18,6 @@ namespace {
 
 constexpr uint32_t kNzcpPublic = 513;   // NZCPPubIdentity: 256 + 256 digest bits, exp
 
-int host_threads(size_t n) {
-  const unsigned hw = std::thread::hardware_concurrency();
-  return n < 2 ? 1 : (int)(hw < 1 ? 1 : hw > 16 ? 16 : hw);
-}
-
 bool well_formed(uint32_t verdict) { return verdict != G16_PASS_MALFORMED && verdict != G16_PASS_TOO_LONG; }
 
 // M of a program whose named inputs are exactly toBeSigned[8 M], toBeSignedLen; 0 otherwise

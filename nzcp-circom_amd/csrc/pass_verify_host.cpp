@@ -16,11 +16,6 @@ using namespace g16;
 
 namespace {
 
-int host_threads(size_t n) {
-  const unsigned hw = std::thread::hardware_concurrency();
-  return n < 2 ? 1 : (int)(hw < 1 ? 1 : hw > 16 ? 16 : hw);
-}
-
 double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }

@@ -89,7 +89,7 @@ int ptau_prepare_core(const uint8_t* ptau, size_t ptau_len, int device, uint8_t*
   if (!rc) rc = ptau_prepare_g2(device, pv.sec[3].p, n, P, sp[13], &st[1]);
   if (!rc) rc = ptau_prepare_g1(device, pv.sec[4].p, n, P, sp[14], &st[2]);
   if (!rc) rc = ptau_prepare_g1(device, pv.sec[5].p, n, P, sp[15], &st[3]);
-  if (rc) { free(z.p); return rc; }
+  if (rc) return rc;
   if (getenv("G16_TRACE_HOST")) {
     const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     fprintf(stderr,
@@ -174,7 +174,7 @@ extern "C" int g16_ptau_synth(uint32_t power, const uint8_t tab[3 * 32], int pre
       mul1(scaled(lag, alpha, 2 * n - 1), sp[14]);
       mul1(scaled(lag, beta, 2 * n - 1), sp[15]);
     }
-    if (fm.rc) { free(z.p); return fm.rc; }
+    if (fm.rc) return fm.rc;
     z.give(ptau, ptau_len);
     return G16_OK;
   });

@@ -37,11 +37,12 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <thread>
 
 #include "beacon.h"
+#include "host_util.h"
 #include "internal.h"
 #include "mapped_file.h"
+#include "pair_checks.h"
 #include "ptau.h"
 #include "zkey_mpc.h"
 
@@ -59,9 +60,9 @@ int ptau_records_parse(const BinSection& s7, std::vector<PtauRecord>& out) {
     const uint32_t plen = rd32(r + kPtauRecordFixed - 4);
     if (s7.size - pos - kPtauRecordFixed < plen) return ptau_bad("Invalid File format");
     const PtauRecord rec{r, kPtauRecordFixed + plen};
-    bool ok = mpc_g1_image_ok(rec.tau_g1()) && mpc_g2_image_ok(rec.tau_g2()) && mpc_g1_image_ok(rec.alpha_g1()) &&
-              mpc_g1_image_ok(rec.beta_g1()) && mpc_g2_image_ok(rec.beta_g2());
-    for (int x = 0; x < 3 && ok; x++) ok = mpc_g1_image_ok(rec.g1_s(x)) && mpc_g1_image_ok(rec.g1_sx(x)) && mpc_g2_image_ok(rec.g2_spx(x));
+    bool ok = g1_image_ok(rec.tau_g1()) && g2_image_ok(rec.tau_g2()) && g1_image_ok(rec.alpha_g1()) &&
+              g1_image_ok(rec.beta_g1()) && g2_image_ok(rec.beta_g2());
+    for (int x = 0; x < 3 && ok; x++) ok = g1_image_ok(rec.g1_s(x)) && g1_image_ok(rec.g1_sx(x)) && g2_image_ok(rec.g2_spx(x));
     if (!ok) return ptau_bad("Invalid File format");
     out.push_back(rec);
     pos += rec.len;
@@ -79,44 +80,7 @@ int power_above_limit(const char* route, uint32_t power) {
   return G16_E_ARG;
 }
 
-double ms_since(const std::chrono::steady_clock::time_point& t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-bool all_zero(const uint8_t* p, size_t n) {
-  for (size_t i = 0; i < n; i++) if (p[i]) return false;
-  return true;
-}
-
-struct Gens { uint8_t g1[64], g2[128]; };
-const Gens& gens() {
-  static const Gens g = [] {
-    Gens o;
-    G1Affine a;   // (1, 2)
-    a.x = fp_one<FqParams>();
-    a.y = fp_add(a.x, a.x);
-    G2Affine b;
-    b.x.a = Fq{G16_G2X0}; b.x.b = Fq{G16_G2X1}; b.y.a = Fq{G16_G2Y0}; b.y.b = Fq{G16_G2Y1};
-    memcpy(o.g1, &a, 64);
-    memcpy(o.g2, &b, 128);
-    return o;
-  }();
-  return g;
-}
-
-// [lo, hi) of n items over at most 16 host threads
-template <class Fn> void par_for(uint64_t n, Fn fn) {
-  const unsigned hw = std::thread::hardware_concurrency();
-  const uint64_t nt = n < 8192 ? 1 : std::min<uint64_t>(16, hw ? hw : 1);
-  if (nt <= 1) { fn((uint64_t)0, n); return; }
-  std::vector<std::thread> th;
-  const uint64_t per = (n + nt - 1) / nt;
-  for (uint64_t t = 0; t < nt; t++) {
-    const uint64_t lo = t * per, hi = std::min(n, lo + per);
-    if (lo < hi) th.emplace_back([=]() { fn(lo, hi); });
-  }
-  for (auto& t : th) t.join();
-}
+constexpr size_t kThreadedFrom = 8192;   // points of a section before the host loops over it take more than one thread
 
 // the ceremony as the two routes read it
 struct Ceremony {
@@ -146,8 +110,9 @@ int open_ceremony(const uint8_t* ptau, size_t len, const char* route, Ceremony& 
 void points_be_host(const uint8_t* const sec[7], const uint64_t cnt[7], uint8_t* q) {
   for (int id = 2; id <= 6; id++) {
     const uint8_t* s = sec[id];
-    if (Ceremony::psz(id) == 64) par_for(cnt[id], [=](uint64_t lo, uint64_t hi) { for (uint64_t i = lo; i < hi; i++) g1_uncompressed(s + i * 64, q + i * 64); });
-    else par_for(cnt[id], [=](uint64_t lo, uint64_t hi) { for (uint64_t i = lo; i < hi; i++) g2_uncompressed(s + i * 128, q + i * 128); });
+    const int threads = host_threads(cnt[id], kThreadedFrom);
+    if (Ceremony::psz(id) == 64) parallel_for(cnt[id], threads, [=](size_t lo, size_t hi) { for (size_t i = lo; i < hi; i++) g1_uncompressed(s + i * 64, q + i * 64); });
+    else parallel_for(cnt[id], threads, [=](size_t lo, size_t hi) { for (size_t i = lo; i < hi; i++) g2_uncompressed(s + i * 128, q + i * 128); });
     q += cnt[id] * Ceremony::psz(id);
   }
 }
@@ -195,46 +160,22 @@ void generator_challenge(const Ceremony& c, uint8_t out[64]) {
   blake2b512(feed.data(), feed.size(), out);
 }
 
-bool scalar_ok(const uint8_t* s, Fr& out) {   // standard form, in [1, r)
-  memcpy(out.v, s, 32);
-  return !fp_is_zero(out) && fr_below_modulus(out.v);
-}
-
-// secret (tau | alpha | beta | s_tau | s_alpha | s_beta, or NULL for the OS CSPRNG) -> key[3], sk[3]
-int read_secret(const char* route, const uint8_t* secret, Fr key[3], Fr sk[3]) {
-  if (secret) {
-    for (int x = 0; x < 3; x++)
-      if (!scalar_ok(secret + 32 * x, key[x]) || !scalar_ok(secret + 96 + 32 * x, sk[x])) {
-        set_error(std::string(route) + ": the secret scalars must be in [1, r)");
-        return G16_E_ARG;
-      }
-    return G16_OK;
-  }
-  for (Fr* x : {&key[0], &key[1], &key[2], &sk[0], &sk[1], &sk[2]})
-    for (;;) {
-      if (const int rc = mpc_os_random((uint8_t*)x->v, 32)) return rc;
-      x->v[7] &= 0x3fffffffu;
-      if (!fp_is_zero(*x) && fr_below_modulus(x->v)) break;
-    }
-  return G16_OK;
-}
-
-// the nine key points of a record (rec = its first byte) for the challenge it answers
+// the nine key points of a record (rec = its first byte) for the challenge it answers; key = tau, alpha, beta and
+// sk = s_tau, s_alpha, s_beta: the two halves of the six secret scalars
 void make_keys(const uint8_t challenge[64], const Fr key[3], const Fr sk[3], uint8_t* rec) {
   for (int x = 0; x < 3; x++) {
     uint8_t* g1_s = rec + kPtauKeysAt + 128 * x;
-    mpc_mul_g1(gens().g1, sk[x], g1_s);
-    mpc_mul_g1(g1_s, key[x], g1_s + 64);
+    mul_image<FqOps>(gens().g1, sk[x], g1_s);
+    mul_image<FqOps>(g1_s, key[x], g1_s + 64);
     G2Affine sp2;
     key_g2_sp(challenge, x, g1_s, g1_s + 64, sp2);
-    mpc_mul_g2((const uint8_t*)&sp2, key[x], rec + 832 + 128 * x);
+    mul_image<Fq2Ops>((const uint8_t*)&sp2, key[x], rec + 832 + 128 * x);
   }
 }
 
 // Step 2 of the verifier for ONE record against the state before it (cur: tauG1, alphaG1, betaG1, advanced to the
-// record's): the infinity test, then eight same-ratio checks appended to pairs (check k compares pairing 2k with pairing
-// 2k + 1 of ONE g16_pairing_op call) with their texts in reason.  -> the infinity text, or nullptr.  g2_sp must outlive
-// the pairing call.  Shared by `verify` and `import response`, which differ in the texts' prefix alone.
+// record's): the infinity test, then eight same-ratio checks with their texts appended to the batch.  -> the infinity
+// text, or nullptr.  Shared by `verify` and `import response`, which differ in the texts' prefix alone.
 struct RecordTexts { const char* inf; const char* key; const char* chain[3]; const char* tau_g2; const char* beta_g2; };
 #define G16_RECORD_TEXTS(route)                                                                                      \
   {route ": a contribution holds the point at infinity", route ": a contribution's public key is not consistent",    \
@@ -242,26 +183,22 @@ struct RecordTexts { const char* inf; const char* key; const char* chain[3]; con
     route ": a contribution's betaG1 does not continue the chain"},                                                  \
    route ": a contribution's tauG2 does not match its tauG1", route ": a contribution's betaG2 does not match its betaG1"}
 const char* record_checks(const RecordTexts& t, const PtauRecord& r, const uint8_t* cur[3], const uint8_t challenge[64],
-                          G2Affine g2_sp[3], std::vector<uint8_t>& pairs, std::vector<const char*>& reason) {
+                          PairChecks& checks) {
   bool inf = all_zero(r.tau_g1(), 64) || all_zero(r.tau_g2(), 128) || all_zero(r.alpha_g1(), 64) || all_zero(r.beta_g1(), 64) ||
              all_zero(r.beta_g2(), 128);
   for (int x = 0; x < 3; x++) inf = inf || all_zero(r.g1_s(x), 64) || all_zero(r.g1_sx(x), 64) || all_zero(r.g2_spx(x), 128);
   if (inf) return t.inf;
-  auto same_ratio = [&](const uint8_t* g1a, const uint8_t* g1b, const uint8_t* g2c, const uint8_t* g2d, const char* why) {
-    mpc_pair_words(pairs, g1a, g2d);   // e(a, d) = e(b, c)
-    mpc_pair_words(pairs, g1b, g2c);
-    reason.push_back(why);
-  };
   const Gens& G = gens();
   const uint8_t* now[3] = {r.tau_g1(), r.alpha_g1(), r.beta_g1()};
   for (int x = 0; x < 3; x++) {
-    key_g2_sp(challenge, x, r.g1_s(x), r.g1_sx(x), g2_sp[x]);
-    same_ratio(r.g1_s(x), r.g1_sx(x), (const uint8_t*)&g2_sp[x], r.g2_spx(x), t.key);
-    same_ratio(cur[x], now[x], (const uint8_t*)&g2_sp[x], r.g2_spx(x), t.chain[x]);
+    G2Affine g2_sp;
+    key_g2_sp(challenge, x, r.g1_s(x), r.g1_sx(x), g2_sp);
+    checks.same_ratio(r.g1_s(x), r.g1_sx(x), (const uint8_t*)&g2_sp, r.g2_spx(x), t.key);
+    checks.same_ratio(cur[x], now[x], (const uint8_t*)&g2_sp, r.g2_spx(x), t.chain[x]);
     cur[x] = now[x];
   }
-  same_ratio(G.g1, r.tau_g1(), G.g2, r.tau_g2(), t.tau_g2);
-  same_ratio(G.g1, r.beta_g1(), G.g2, r.beta_g2(), t.beta_g2);
+  checks.same_ratio(G.g1, r.tau_g1(), G.g2, r.tau_g2(), t.tau_g2);
+  checks.same_ratio(G.g1, r.beta_g1(), G.g2, r.beta_g2(), t.beta_g2);
   return nullptr;
 }
 
@@ -344,14 +281,9 @@ int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uin
   const char* route = bc ? "ptau beacon" : "ptau contribute";
   Ceremony c;
   if (const int rc = open_ceremony(ptau, len, route, c)) return rc;
-  Fr key[3], sk[3];
-  if (bc) {
-    Fr x[6];
-    if (const int rc = mpc_beacon_scalars(bc->hash, bc->len, bc->exp, 6, x)) return rc;
-    for (int i = 0; i < 3; i++) { key[i] = x[i]; sk[i] = x[3 + i]; }
-  } else if (const int rc = read_secret(route, secret, key, sk)) {
-    return rc;
-  }
+  Fr x[6];
+  if (const int rc = bc ? mpc_beacon_scalars(bc->hash, bc->len, bc->exp, 6, x) : read_secrets(route, secret, x, 6)) return rc;
+  const Fr *key = x, *sk = x + 3;
   if (const int rc = require_hip_device(route, device)) return rc;
 
   std::string params = mpc_name_params(name);
@@ -361,7 +293,6 @@ int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uin
   uint8_t* sp[16] = {};
   uint8_t* rec = layout_with_record(c, rec_len, z, sp);
   if (!rec) { set_error(std::string(route) + ": out of memory"); return G16_E_STATE; }
-  struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
   memset(rec, 0, rec_len);   // (partialHash stays zero)
 
   // the challenge this contribution answers
@@ -392,8 +323,8 @@ int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uin
   // the record; in a power-0 file tauG1 / tauG2 continue the last record's (or the generators)
   const auto th1 = std::chrono::steady_clock::now();
   if (c.pv.power == 0) {
-    mpc_mul_g1(c.rec.empty() ? gens().g1 : c.rec.back().tau_g1(), key[0], rec);
-    mpc_mul_g2(c.rec.empty() ? gens().g2 : c.rec.back().tau_g2(), key[0], rec + 64);
+    mul_image<FqOps>(c.rec.empty() ? gens().g1 : c.rec.back().tau_g1(), key[0], rec);
+    mul_image<Fq2Ops>(c.rec.empty() ? gens().g2 : c.rec.back().tau_g2(), key[0], rec + 64);
   }
   uint8_t response[64];
   seal_record(c, sp, challenge, feed, bc ? 1 : 0, params, rec, response);
@@ -414,7 +345,6 @@ int contribute_core(const uint8_t* ptau, size_t len, const char* name, const uin
             route, (unsigned long long)g1, (unsigned long long)g2, k1, k2, xf, hash_ms,
             c.rec.empty() ? ", of the input on the host" : "", ms_since(t0));
   }
-  guard.p = nullptr;
   z.give(out, out_len);
   return G16_OK;
 }
@@ -440,7 +370,6 @@ int export_challenge_core(const uint8_t* ptau, size_t len, uint8_t** out, size_t
   if (const int rc = open_ceremony(ptau, len, "ptau export challenge", c)) return rc;
   Buf z;
   if (!z.reserve(64 + c.points_bytes())) { set_error("ptau export challenge: out of memory"); return G16_E_STATE; }
-  struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
   last_response_hash(c, z.skip(64));
   const uint8_t* in[7] = {};
   for (int id = 2; id <= 6; id++) in[id] = c.pv.sec[id].p;
@@ -452,7 +381,6 @@ int export_challenge_core(const uint8_t* ptau, size_t len, uint8_t** out, size_t
     return G16_E_FORMAT;
   }
   if (challenge_hash) memcpy(challenge_hash, h, 64);
-  guard.p = nullptr;
   z.give(out, out_len);
   return G16_OK;
 }
@@ -486,14 +414,14 @@ int challenge_contribute_core(const uint8_t* ch, size_t len, const uint8_t* secr
     return G16_E_FORMAT;
   }
   if (n == 1) return power_zero("ptau challenge contribute");
-  Fr key[3], sk[3];
-  if (const int rc = read_secret("ptau challenge contribute", secret, key, sk)) return rc;
+  Fr x[6];
+  if (const int rc = read_secrets("ptau challenge contribute", secret, x, 6)) return rc;
+  const Fr *key = x, *sk = x + 3;
   if (const int rc = require_hip_device("ptau challenge contribute", device)) return rc;
 
   const uint64_t cnt[7] = {0, 0, 2 * n - 1, n, n, n, 1};
   Buf z;
   if (!z.reserve(192 * n + 864)) { set_error("ptau challenge contribute: out of memory"); return G16_E_STATE; }
-  struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
   uint8_t challenge[64];
   blake2b512(ch, len, challenge);
   z.put(challenge, 64);
@@ -525,7 +453,6 @@ int challenge_contribute_core(const uint8_t* ch, size_t len, const uint8_t* secr
   if (contribution_hash) response_hash(challenge, R, contribution_hash);
   static const char* const stages[3] = {"from-be", "scale", "compress"};
   trace_points("ptau challenge contribute", stages, st, ms_since(t0));
-  guard.p = nullptr;
   z.give(out, out_len);
   return G16_OK;
 }
@@ -558,8 +485,8 @@ int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, s
     const uint8_t* kp = resp + rlen - kKeysBytes;
     bool good = true;
     for (int x = 0; x < 3 && good; x++)
-      good = mpc_image_from_be(kp + 128 * x, 64, rec + kPtauKeysAt + 128 * x) && mpc_image_from_be(kp + 128 * x + 64, 64, rec + kPtauKeysAt + 128 * x + 64) &&
-             mpc_image_from_be(kp + 384 + 128 * x, 128, rec + 832 + 128 * x);
+      good = image_from_be(kp + 128 * x, 64, rec + kPtauKeysAt + 128 * x) && image_from_be(kp + 128 * x + 64, 64, rec + kPtauKeysAt + 128 * x + 64) &&
+             image_from_be(kp + 384 + 128 * x, 128, rec + 832 + 128 * x);
     if (!good) { set_error("ptau import response: a key point is not a valid image"); return G16_E_FORMAT; }
   }
   if (const int rc = require_hip_device("ptau import response", device)) return rc;
@@ -568,7 +495,6 @@ int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, s
   uint8_t* sp[16] = {};
   uint8_t* rec_out = layout_with_record(c, rec_len, z, sp);
   if (!rec_out) { set_error("ptau import response: out of memory"); return G16_E_STATE; }
-  struct Free { uint8_t* p; ~Free() { free(p); } } guard{z.p};
 
   // device: the sections, and the big-endian images of the new points straight into the next challenge's feed
   ChunkStats st[5][3];
@@ -595,15 +521,10 @@ int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, s
     const bool first = c.rec.empty();
     const uint8_t* cur[3] = {first ? G.g1 : c.rec.back().tau_g1(), first ? G.g1 : c.rec.back().alpha_g1(),
                              first ? G.g1 : c.rec.back().beta_g1()};
-    std::vector<uint8_t> pairs;
-    std::vector<const char*> reason;
-    G2Affine g2_sp[3];
-    if (const char* inf = record_checks(texts, R, cur, challenge, g2_sp, pairs, reason)) return verdict(inf);
-    const uint32_t np = (uint32_t)(pairs.size() / 192);
-    std::vector<uint8_t> gt((size_t)np * 384);
-    if (const int rc = g16_pairing_op(device, pairs.data(), np, gt.data())) return rc;
-    for (size_t k = 0; k < reason.size(); k++)
-      if (memcmp(gt.data() + 2 * k * 384, gt.data() + (2 * k + 1) * 384, 384) != 0) return verdict(reason[k]);
+    PairChecks checks;
+    if (const char* inf = record_checks(texts, R, cur, challenge, checks)) return verdict(inf);
+    if (const int rc = checks.run(device)) return rc;
+    if (const char* why = checks.first_failure()) return verdict(why);
   }
   memcpy(rec_out, rec, rec_len);
   if (contribution_hash) memcpy(contribution_hash, response, 64);
@@ -611,7 +532,6 @@ int import_response_core(const uint8_t* ptau, size_t len, const uint8_t* resp, s
   trace_points("ptau import response", stages, st, ms_since(t0));
   set_error("");
   *ok = 1;
-  guard.p = nullptr;
   z.give(out, out_len);
   return G16_OK;
 }
@@ -628,9 +548,9 @@ int verify_core(const uint8_t* ptau, size_t len, int device, int* ok) {
     for (int id = 2; id <= 6; id++) {
       const uint8_t* s = sec[id];
       const bool g1 = Ceremony::psz(id) == 64;
-      par_for(c.cnt[id], [&, s, g1](uint64_t lo, uint64_t hi) {
-        for (uint64_t i = lo; i < hi && !bad.load(std::memory_order_relaxed); i++)
-          if (!(g1 ? mpc_g1_image_ok(s + i * 64) : mpc_g2_image_ok(s + i * 128))) bad = true;
+      parallel_for(c.cnt[id], host_threads(c.cnt[id], kThreadedFrom), [&, s, g1](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi && !bad.load(std::memory_order_relaxed); i++)
+          if (!(g1 ? g1_image_ok(s + i * 64) : g2_image_ok(s + i * 128))) bad = true;
       });
     }
     if (bad) return ptau_bad("Invalid File format");
@@ -647,17 +567,15 @@ int verify_core(const uint8_t* ptau, size_t len, int device, int* ok) {
   // record's keys are bound to its challenge: the generator file's for the first record, the nextChallenge of the
   // record before for every other.  nextChallenge itself can only be recomputed where the state it hashes is at hand:
   // for the last record, from the file (check 4)
-  std::vector<uint8_t> pairs;        // 192 bytes each; check k compares pairing 2k with pairing 2k + 1
-  std::vector<const char*> reason;   // per check
+  PairChecks checks;
   static const RecordTexts texts = G16_RECORD_TEXTS("ptau verify");
   const uint8_t* cur[3] = {G.g1, G.g1, G.g1};   // tauG1, alphaG1, betaG1 before the record
   uint8_t challenge[64];
   const char* beacon_fail = nullptr;
-  std::vector<G2Affine> g2_sp(3 * c.rec.size());
   for (size_t i = 0; i < c.rec.size(); i++) {
     if (i == 0) generator_challenge(c, challenge);
     else memcpy(challenge, c.rec[i - 1].next_challenge(), 64);
-    if (const char* inf = record_checks(texts, c.rec[i], cur, challenge, &g2_sp[3 * i], pairs, reason)) return verdict(inf);
+    if (const char* inf = record_checks(texts, c.rec[i], cur, challenge, checks)) return verdict(inf);
     const PtauRecord& r = c.rec[i];
     if (rd32(r.p + kPtauNextChallengeAt + 64) == 1 && !beacon_fail) {   // a beacon: the keys are what anyone recomputes
       BeaconStated st;
@@ -711,58 +629,36 @@ int verify_core(const uint8_t* ptau, size_t len, int device, int* ok) {
                                             "ptau verify: the combination of section 4 is the point at infinity",
                                             "ptau verify: the combination of section 5 is the point at infinity"};
     std::vector<uint8_t> rho((c.cnt[2] - 1) * 32);
-    if (const int rc = mpc_random_fr(rho.data(), c.cnt[2] - 1)) return rc;
+    if (const int rc = random_fr(rho.data(), c.cnt[2] - 1)) return rc;
     const auto t1 = std::chrono::steady_clock::now();
-    uint8_t tau1[192], gen[192];   // (tauG1, tauG2) and (G1, G2) as pairing words
-    {
-      std::vector<uint8_t> w;
-      mpc_pair_words(w, sec[2] + 64, sec[3] + 128);
-      memcpy(tau1, w.data(), 192);
-      w.clear();
-      mpc_pair_words(w, G.g1, G.g2);
-      memcpy(gen, w.data(), 192);
-    }
+    const uint8_t *tau_g1 = sec[2] + 64, *tau_g2 = sec[3] + 128;
     for (int id = 2; id <= 5 && !inf_fail; id++) {
       const uint64_t m = c.cnt[id] - 1;
       uint8_t S1[128], S2[128];   // standard form
-      const size_t at = pairs.size();
       if (id != 3) {
         if (const int rc = g16_g1_multiexp(device, sec[id], rho.data(), m, 0, S1)) return rc;
         if (const int rc = g16_g1_multiexp(device, sec[id] + 64, rho.data(), m, 0, S2)) return rc;
         if (all_zero(S1, 64) || all_zero(S2, 64)) { inf_fail = inf_text[id]; break; }
-        pairs.resize(at + 2 * 192);
-        memcpy(pairs.data() + at, S1, 64);                    // e(S1, tauG2) = e(S2, G2)
-        memcpy(pairs.data() + at + 64, tau1 + 64, 128);
-        memcpy(pairs.data() + at + 192, S2, 64);
-        memcpy(pairs.data() + at + 192 + 64, gen + 64, 128);
+        checks.equal(pair_words(S1), pair_image(tau_g2), pair_words(S2), pair_image(G.g2), power_text[id]);   // e(S1, tauG2) = e(S2, G2)
       } else {
         if (const int rc = g16_g2_multiexp(device, sec[id], rho.data(), m, 0, S1)) return rc;
         if (const int rc = g16_g2_multiexp(device, sec[id] + 128, rho.data(), m, 0, S2)) return rc;
         if (all_zero(S1, 128) || all_zero(S2, 128)) { inf_fail = inf_text[id]; break; }
-        pairs.resize(at + 2 * 192);
-        memcpy(pairs.data() + at, tau1, 64);                  // e(tauG1, T1) = e(G1, T2)
-        memcpy(pairs.data() + at + 64, S1, 128);
-        memcpy(pairs.data() + at + 192, gen, 64);
-        memcpy(pairs.data() + at + 192 + 64, S2, 128);
+        checks.equal(pair_image(tau_g1), pair_words(S1), pair_image(G.g1), pair_words(S2), power_text[id]);   // e(tauG1, T1) = e(G1, T2)
       }
-      reason.push_back(power_text[id]);
       msm_points += 2 * m;
     }
     msm_ms = ms_since(t1);
   }
   const auto t2 = std::chrono::steady_clock::now();
-  const uint32_t np = (uint32_t)(pairs.size() / 192);
-  std::vector<uint8_t> gt((size_t)np * 384);
-  if (np)
-    if (const int rc = g16_pairing_op(device, pairs.data(), np, gt.data())) return rc;
+  if (const int rc = checks.run(device)) return rc;
   const double pair_ms = ms_since(t2);
+  const uint32_t np = checks.pairs();
   if (getenv("G16_TRACE_HOST"))
     fprintf(stderr, "[g16] ptau verify: power %u, records %zu; MSM %.3f ms (%llu points), pairings %.3f ms (%u); call %.3f ms\n",
             c.pv.power, c.rec.size(), msm_ms, (unsigned long long)msm_points, pair_ms, np, ms_since(t0));
   // (a host failure has spared the sums: every pairing check is then the walk's, and comes first)
-  for (size_t k = 0; k < reason.size(); k++) {
-    if (memcmp(gt.data() + 2 * k * 384, gt.data() + (2 * k + 1) * 384, 384) != 0) return verdict(reason[k]);
-  }
+  if (const char* why = checks.first_failure()) return verdict(why);
   if (host_fail) return verdict(host_fail);
   if (inf_fail) return verdict(inf_fail);
 
@@ -774,7 +670,7 @@ int verify_core(const uint8_t* ptau, size_t len, int device, int* ok) {
     uint8_t* prep = nullptr;
     size_t prep_len = 0;
     if (const int rc = g16_ptau_prepare(ptau, len, device, &prep, &prep_len)) return rc;
-    struct Free { uint8_t* p; ~Free() { free(p); } } guard{prep};
+    const MallocPtr guard(prep);
     PtauView pp;
     if (const int rc = ptau_open(prep, prep_len, pp, false)) return rc;
     for (int id = 12; id <= 15; id++)

@@ -117,7 +117,7 @@ int setup_core_td(const Circuit& c, const FrM td[5], int threads, uint8_t** zkey
   fm.mul2(v.data(), n, im.sec[7]);
   fm.mul1(kc.data(), kc.size(), im.sec[8]);
   fm.mul1(hs.data(), hs.size(), im.sec[9]);
-  if (fm.rc) { free(im.z.p); return fm.rc; }
+  if (fm.rc) return fm.rc;
   im.z.give(zkey, zkey_len);
   if (vkey && vkey_len) {
     // alpha1 | beta2 | gamma2 | delta2 | IC[0..p]   (affine Montgomery LE)
@@ -299,7 +299,7 @@ int g16::groth16_setup_ptau_checked(const uint8_t* r1cs, size_t r1cs_len, const 
       const size_t segn[1] = {N};
       rc = setup_sparse_g2(device, seg, segn, 1, t2, im.sec[7], &s2);
     }
-    if (rc) { free(im.z.p); return rc; }
+    if (rc) return rc;
     const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     memcpy(im.sec[5], o1.data(), (size_t)n * 64);
     memcpy(im.sec[6], o1.data() + (size_t)n * 64, (size_t)n * 64);

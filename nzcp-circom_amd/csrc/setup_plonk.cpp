@@ -177,7 +177,7 @@ static int plonk_setup_core(const uint8_t* r1cs, size_t r1cs_len, const PlonkTau
       evp[k] = ev[k].data();
       outp[k] = k < 5 ? sp[7 + k] : sp[12] + (size_t)(k - 5) * polb;
     }
-    if ((rc = plonk_setup_polys(device, L, evp, outp))) { free(z.p); return rc; }
+    if ((rc = plonk_setup_polys(device, L, evp, outp))) return rc;
     if (nlag) {   // Lagrange polynomials of the public inputs, 8 at a time
       std::vector<std::vector<Fr>> le(8, std::vector<Fr>(N));
       for (size_t j0 = 0; j0 < nlag; j0 += 8) {
@@ -188,7 +188,7 @@ static int plonk_setup_core(const uint8_t* r1cs, size_t r1cs_len, const PlonkTau
           evp[k] = le[k].data();
           outp[k] = sp[13] + j * polb;
         }
-        if ((rc = plonk_setup_polys(device, L, evp, outp))) { free(z.p); return rc; }
+        if ((rc = plonk_setup_polys(device, L, evp, outp))) return rc;
       }
     }
   }
@@ -206,7 +206,7 @@ static int plonk_setup_core(const uint8_t* r1cs, size_t r1cs_len, const PlonkTau
     const uint8_t* cf[8];
     for (int k = 0; k < 8; k++) cf[k] = k < 5 ? sp[7 + k] : sp[12] + (size_t)(k - 5) * polb;
     uint8_t cm[8 * 64];
-    if ((rc = plonk_setup_commit(device, src.tau_g1, (uint32_t)N, cf, cm))) { free(z.p); return rc; }
+    if ((rc = plonk_setup_commit(device, src.tau_g1, (uint32_t)N, cf, cm))) return rc;
     write_header(cm, src.tau_g2_1);
     z.give(zkey, zkey_len);
     return G16_OK;
@@ -218,7 +218,7 @@ static int plonk_setup_core(const uint8_t* r1cs, size_t r1cs_len, const PlonkTau
     FrM x = one;
     for (size_t i = 0; i < N + 6; i++) { pw[i] = x; x = fp_mul(x, tau); }
     fm.mul1(pw.data(), N + 6, sp[14]);
-    if (fm.rc) { free(z.p); return fm.rc; }
+    if (fm.rc) return fm.rc;
   }
   {
     FrM cm[8];

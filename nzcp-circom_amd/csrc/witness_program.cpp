@@ -441,7 +441,7 @@ extern "C" int g16_wtns_calc_wtns(g16_wtns_calculator* h, const uint8_t* inputs,
     uint8_t* q = bin_put_field(sec[1], kFrP);
     memcpy(q, &h->p.n_wires, 4);
     const int rc = g16_wtns_calc(h, inputs, n_inputs, 1, sec[2], status);
-    if (rc || *status != kWpNoCheck) { free(z.p); return rc; }   // (a violated check: the verdict, and no image)
+    if (rc || *status != kWpNoCheck) return rc;   // (a violated check: the verdict, and no image)
     z.give(wtns, len);
     return G16_OK;
   });

@@ -21,6 +21,7 @@
 
 #include <chrono>
 
+#include "host_util.h"
 #include "internal.h"
 #include "mapped_file.h"
 #include "zkey_mpc.h"
@@ -31,10 +32,6 @@ namespace {
 int mp_bad() { set_error("mpcparams: Invalid File format"); return G16_E_FORMAT; }
 uint32_t rd32be(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
 void wr32be(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
-bool zero_bytes(const uint8_t* p, size_t n) {
-  for (size_t i = 0; i < n; i++) if (p[i]) return false;
-  return true;
-}
 
 // flags and coordinates of an uncompressed big-endian image: a clean 0x40 with nothing else, or every coordinate < q
 bool be_plausible(const uint8_t* p, size_t psz) {
@@ -42,7 +39,7 @@ bool be_plausible(const uint8_t* p, size_t psz) {
     uint8_t b[32];
     QBe() { for (int i = 0; i < 8; i++) wr32be(b + 4 * i, kFqP[7 - i]); }
   } q;
-  if (p[0] & 0xc0) return p[0] == 0x40 && zero_bytes(p + 1, psz - 1);
+  if (p[0] & 0xc0) return p[0] == 0x40 && all_zero(p + 1, psz - 1);
   for (size_t c = 0; c < psz; c += 32)
     if (memcmp(p + c, q.b, 32) >= 0) return false;
   return true;
@@ -58,10 +55,6 @@ int log2_domain(const char* route, uint32_t N, int& L) {
   while (((uint32_t)1 << L) < N) L++;
   if (L > 24) { set_error(std::string(route) + ": the domain is above 2^24"); return G16_E_ARG; }
   return G16_OK;
-}
-
-double ms_since(const std::chrono::steady_clock::time_point& t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // a key's record as the MPCParams file holds it: its hashPubKey feed
@@ -85,8 +78,6 @@ void key_counts(const KeyView& k, uint32_t cnt[kMpRuns]) {
   cnt[3] = cnt[4] = cnt[5] = k.nVars;
 }
 
-struct Free { uint8_t* p; ~Free() { free(p); } };
-
 int export_core(const uint8_t* zkey, size_t len, int device, uint8_t** out, size_t* out_len) {
   const auto t0 = std::chrono::steady_clock::now();
   KeyView k;
@@ -101,7 +92,6 @@ int export_core(const uint8_t* zkey, size_t len, int device, uint8_t** out, size
   for (int r = 0; r < kMpRuns; r++) total += 4 + (size_t)cnt[r] * kMpRunPoint[r];
   Buf z;
   if (!z.reserve(total)) { set_error("zkey export bellman: out of memory"); return G16_E_STATE; }
-  Free guard{z.p};
   header_image(k.f.sec[2].p, z.skip(kMpHeader));
 
   std::vector<uint8_t> t((size_t)k.N * 64);
@@ -123,7 +113,6 @@ int export_core(const uint8_t* zkey, size_t len, int device, uint8_t** out, size
     fprintf(stderr, "[g16] zkey export bellman: basis %.3f ms (%llu products), to-be %.3f ms, transfers %.3f ms; call %.3f ms\n",
             bst.kern_ms, (unsigned long long)bst.muls, kern, xfer, ms_since(t0));
   }
-  guard.p = nullptr;
   z.give(out, out_len);
   return G16_OK;
 }
@@ -133,17 +122,17 @@ int contribute_core(const uint8_t* ch, size_t len, const uint8_t* secret, int de
   const auto t0 = std::chrono::steady_clock::now();
   MpView m;
   if (const int rc = mp_open(ch, len, m)) return rc;
-  Fr d, s;
-  if (const int rc = mpc_read_secret("zkey bellman contribute", secret, d, s)) return rc;
+  Fr ds[2];
+  if (const int rc = read_secrets("zkey bellman contribute", secret, ds, 2)) return rc;
+  const Fr &d = ds[0], &s = ds[1];
   uint8_t delta1[64], delta2[128];
-  if (!mpc_image_from_be(m.hdr + kMpDelta1, 64, delta1) || !mpc_image_from_be(m.hdr + kMpDelta2, 128, delta2) ||
-      zero_bytes(delta1, 64) || zero_bytes(delta2, 128))
+  if (!image_from_be(m.hdr + kMpDelta1, 64, delta1) || !image_from_be(m.hdr + kMpDelta2, 128, delta2) ||
+      all_zero(delta1, 64) || all_zero(delta2, 128))
     return mp_bad();
   if (const int rc = require_hip_device("zkey bellman contribute", device)) return rc;
 
   Buf z;
   if (!z.reserve(len + kMpRecord)) { set_error("zkey bellman contribute: out of memory"); return G16_E_STATE; }
-  Free guard{z.p};
   z.put(ch, len);
   uint8_t* rec = z.skip(kMpRecord);
   auto at = [&](const uint8_t* p) { return z.p + (p - ch); };   // the same place in the output
@@ -151,8 +140,8 @@ int contribute_core(const uint8_t* ch, size_t len, const uint8_t* secret, int de
   // host: delta and the record
   {
     uint8_t nd1[64], nd2[128], g1_s[64], g1_sx[64], g2_spx[128];
-    mpc_mul_g1(delta1, d, nd1);
-    mpc_mul_g2(delta2, d, nd2);
+    mul_image<FqOps>(delta1, d, nd1);
+    mul_image<Fq2Ops>(delta2, d, nd2);
     g1_uncompressed(nd1, at(m.hdr + kMpDelta1));
     g2_uncompressed(nd2, at(m.hdr + kMpDelta2));
     std::vector<uint8_t> feed(m.cs_hash, m.cs_hash + 64);
@@ -184,7 +173,6 @@ int contribute_core(const uint8_t* ch, size_t len, const uint8_t* secret, int de
     fprintf(stderr, "[g16] zkey bellman contribute: points %llu; kernels from-be %.3f ms, scale %.3f ms, to-be %.3f ms, transfers %.3f ms; call %.3f ms\n",
             (unsigned long long)m.cnt[1] + m.cnt[2], ms[0], ms[1], ms[2], xfer, ms_since(t0));
   }
-  guard.p = nullptr;
   z.give(out, out_len);
   return G16_OK;
 }
@@ -227,7 +215,7 @@ int import_core(const uint8_t* old, size_t old_len, const uint8_t* resp, size_t 
 
   // host: the few points the key takes as they are -- delta and the new records
   uint8_t delta1[64], delta2[128];
-  if (!mpc_image_from_be(m.hdr + kMpDelta1, 64, delta1) || !mpc_image_from_be(m.hdr + kMpDelta2, 128, delta2)) return mp_bad();
+  if (!image_from_be(m.hdr + kMpDelta1, 64, delta1) || !image_from_be(m.hdr + kMpDelta2, 128, delta2)) return mp_bad();
   const std::string params = mpc_name_params(name);
   const uint32_t plen = (uint32_t)params.size();
   const size_t rec_len = kMpcRecordFixed + plen, nnew = m.nrec - nold;
@@ -235,8 +223,8 @@ int import_core(const uint8_t* old, size_t old_len, const uint8_t* resp, size_t 
   for (size_t i = 0; i < nnew; i++) {
     const uint8_t* r = m.rec + (nold + i) * kMpRecord;
     uint8_t* q = recs.data() + i * rec_len;
-    if (!mpc_image_from_be(r, 64, q) || !mpc_image_from_be(r + 64, 64, q + 64) || !mpc_image_from_be(r + 128, 64, q + 128) ||
-        !mpc_image_from_be(r + 192, 128, q + 192))
+    if (!image_from_be(r, 64, q) || !image_from_be(r + 64, 64, q + 64) || !image_from_be(r + 128, 64, q + 128) ||
+        !image_from_be(r + 192, 128, q + 192))
       return mp_bad();
     memcpy(q + 320, r + 320, 64);
     const uint32_t type = 0;
@@ -262,33 +250,11 @@ int import_core(const uint8_t* old, size_t old_len, const uint8_t* resp, size_t 
     }
   }
 
-  // the image: every record of the old key's table in its order, the first section 10 longer by the new records
-  struct Entry { uint32_t id; const uint8_t* p; uint64_t size; };
-  std::vector<Entry> table;
-  {
-    const uint32_t nsec = rd32(old + 8);
-    size_t pos = 12;   // (bin_open has walked and bounded this table)
-    for (uint32_t i = 0; i < nsec; i++) {
-      table.push_back(Entry{rd32(old + pos), old + pos + 12, rd64(old + pos + 4)});
-      pos += 12 + table.back().size;
-    }
-  }
-  size_t total = 12 + recs.size();
-  for (const Entry& e : table) total += 12 + e.size;
+  // the image: the old key's sections in their order, section 10 longer by the new records
   Buf z;
-  if (!z.reserve(total)) { set_error("zkey import bellman: out of memory"); return G16_E_STATE; }
-  Free guard{z.p};
-  z.put(old, 12);
-  uint8_t* sp[16] = {};
-  for (const Entry& e : table) {
-    const bool first = e.id < 16 && e.p == k.f.sec[e.id].p;
-    z.u32(e.id);
-    z.u64(first && e.id == 10 ? e.size + recs.size() : e.size);
-    uint8_t* q = z.skip(e.size);
-    if (first) sp[e.id] = q;
-    if (!(first && (e.id == 8 || e.id == 9))) memcpy(q, e.p, e.size);
-    if (first && e.id == 10) z.put(recs.data(), recs.size());
-  }
+  uint8_t* sp[16];
+  if (!key_image_layout(old, k, recs.size(), z, sp)) { set_error("zkey import bellman: out of memory"); return G16_E_STATE; }
+  memcpy(sp[10] + k.f.sec[10].size, recs.data(), recs.size());
   memcpy(sp[2] + kHdrDelta1, delta1, 64);
   memcpy(sp[2] + kHdrDelta2, delta2, 128);
   memcpy(sp[10] + 64, &m.nrec, 4);
@@ -315,7 +281,6 @@ int import_core(const uint8_t* old, size_t old_len, const uint8_t* resp, size_t 
   }
   set_error("");
   *ok = 1;
-  guard.p = nullptr;
   z.give(out, out_len);
   return G16_OK;
 }

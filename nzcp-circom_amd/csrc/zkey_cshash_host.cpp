@@ -25,9 +25,6 @@ namespace g16 {
 namespace {
 
 void wr32be(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
-double ms_since(const std::chrono::steady_clock::time_point& t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 int log2_of(uint32_t N) {
   int L = 0;
   while (((uint32_t)1 << L) < N) L++;
@@ -41,7 +38,7 @@ int cshash_check_ptau(const PtauView& pv, int log_n) {
   const uint64_t m = 2 * ((uint64_t)1 << log_n) - 1;
   if (!pv.sec[2].p || pv.sec[2].size / 64 < m) return ptau_bad("Invalid File format");
   for (uint64_t j = 0; j < m; j++)
-    if (!mpc_g1_image_ok(pv.sec[2].p + j * 64)) return ptau_bad("Invalid File format");
+    if (!g1_image_ok(pv.sec[2].p + j * 64)) return ptau_bad("Invalid File format");
   return G16_OK;
 }
 
@@ -125,7 +122,7 @@ int zkey_new_entry(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, si
   uint8_t* z = nullptr;
   size_t zl = 0;
   if (const int rc = groth16_setup_ptau_checked(r1cs, r1cs_len, ptau, ptau_len, device, &z, &zl, &check)) return rc;
-  struct Free { uint8_t* p; ~Free() { free(p); } } guard{z};
+  MallocPtr guard(z);
   KeyView k;
   PtauView pv;
   if (const int rc = open_key(z, zl, k, true)) return rc;
@@ -134,8 +131,7 @@ int zkey_new_entry(const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, si
   if (const int rc = zkey_cs_hash_core(k, pv, device, h)) return rc;
   memcpy(z + (k.mpc.cs_hash - z), h, 64);
   if (cs_hash) memcpy(cs_hash, h, 64);
-  guard.p = nullptr;
-  *zkey = z;
+  *zkey = guard.release();
   *zkey_len = zl;
   return G16_OK;
 }

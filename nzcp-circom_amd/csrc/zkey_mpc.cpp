@@ -14,253 +14,25 @@
 //               fails that check here.
 // The csHash of `zkey new` is built in zkey_cshash_host.cpp (g16_zkey_new; the legacy keys of g16_groth16_setup_ptau
 // keep 64 zero bytes); here the chain is hashed from, and compared with, whatever section 10 holds.  The r1cs form of
-// verify sets its in-memory initial key up with the real csHash when the key under test carries one.  Blake2b-512 has a
-// streaming form (Blake2b512) for that hash, whose feed arrives chunk by chunk from the device.
+// verify sets its in-memory initial key up with the real csHash when the key under test carries one.
+// The hash is blake2b.cpp, the arithmetic on file images curve_host.cpp, the batch of pairing checks pair_checks.h.
 // That the csHash equals snarkjs's own value is NOT claimed (restated without the package), so neither is `snarkjs zkey
 // verify` of these keys: the file LAYOUT and the proofs are compatible.
 #include "zkey_mpc.h"
-
-#include <fcntl.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <chrono>
 
 #include "beacon.h"
+#include "host_util.h"
 #include "internal.h"
 #include "mapped_file.h"
+#include "pair_checks.h"
 #include "ptau.h"
 #include "zkey_cshash.h"
 
 namespace g16 {
 
-// ------------------------------------------------------------------ Blake2b-512 (RFC 7693)
-namespace {
-const uint64_t kB2Iv[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
-                           0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
-const uint8_t kB2Sigma[12][16] = {
-    {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
-    {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
-    {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
-    {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
-    {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0},
-    {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3}};
-inline uint64_t rotr64(uint64_t x, int n) { return (x >> n) | (x << (64 - n)); }
-
-void b2_compress(uint64_t h[8], const uint8_t block[128], uint64_t t, bool last) {
-  uint64_t m[16], v[16];
-  for (int i = 0; i < 16; i++) m[i] = rd64(block + 8 * i);
-  for (int i = 0; i < 8; i++) { v[i] = h[i]; v[i + 8] = kB2Iv[i]; }
-  v[12] ^= t;   // (t < 2^64: the high counter word stays zero)
-  if (last) v[14] = ~v[14];
-  auto G = [&](int a, int b, int c, int d, uint64_t x, uint64_t y) {
-    v[a] = v[a] + v[b] + x; v[d] = rotr64(v[d] ^ v[a], 32);
-    v[c] = v[c] + v[d];     v[b] = rotr64(v[b] ^ v[c], 24);
-    v[a] = v[a] + v[b] + y; v[d] = rotr64(v[d] ^ v[a], 16);
-    v[c] = v[c] + v[d];     v[b] = rotr64(v[b] ^ v[c], 63);
-  };
-  for (int r = 0; r < 12; r++) {
-    const uint8_t* s = kB2Sigma[r];
-    G(0, 4, 8, 12, m[s[0]], m[s[1]]);
-    G(1, 5, 9, 13, m[s[2]], m[s[3]]);
-    G(2, 6, 10, 14, m[s[4]], m[s[5]]);
-    G(3, 7, 11, 15, m[s[6]], m[s[7]]);
-    G(0, 5, 10, 15, m[s[8]], m[s[9]]);
-    G(1, 6, 11, 12, m[s[10]], m[s[11]]);
-    G(2, 7, 8, 13, m[s[12]], m[s[13]]);
-    G(3, 4, 9, 14, m[s[14]], m[s[15]]);
-  }
-  for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
-}
-}  // namespace
-
-// The streaming form.  A full block is compressed only once a byte beyond it has arrived: the block that turns out to
-// be the last must carry the final flag, also when the total length is a non-zero multiple of 128.
-Blake2b512::Blake2b512() {
-  for (int i = 0; i < 8; i++) h_[i] = kB2Iv[i];
-  h_[0] ^= 0x01010000ull ^ 64;   // digest length 64, no key, fanout = depth = 1
-}
-void Blake2b512::update(const uint8_t* data, size_t len) {
-  if (!len) return;
-  if (have_) {   // top up the held-back bytes first
-    const size_t take = std::min(len, (size_t)128 - have_);
-    memcpy(buf_ + have_, data, take);
-    have_ += take; data += take; len -= take;
-    if (!len) return;   // (a full buffer stays: it may be the last block)
-    t_ += 128;
-    b2_compress(h_, buf_, t_, false);
-    have_ = 0;
-  }
-  while (len > 128) {   // whole blocks where they lie, all but a last full one
-    t_ += 128;
-    b2_compress(h_, data, t_, false);
-    data += 128; len -= 128;
-  }
-  memcpy(buf_, data, len);
-  have_ = len;
-}
-void Blake2b512::final(uint8_t out[64]) {
-  memset(buf_ + have_, 0, 128 - have_);
-  b2_compress(h_, buf_, t_ + have_, true);
-  memcpy(out, h_, 64);   // little-endian words
-}
-
-void blake2b512(const uint8_t* data, size_t len, uint8_t out[64]) {
-  Blake2b512 b;
-  b.update(data, len);
-  b.final(out);
-}
-
-// ------------------------------------------------------------------ field and curve helpers
-namespace {
-
-bool limbs_below(const uint32_t a[8], const uint32_t m[8]) {
-  for (int i = 7; i >= 0; i--)
-    if (a[i] != m[i]) return a[i] < m[i];
-  return false;
-}
-Fq fq_load(const uint8_t* p) { Fq x; memcpy(x.v, p, 32); return x; }
-Fq fq_b3() { Fq t = fp_zero<FqParams>(); t.v[0] = 3; return fp_to_mont(t); }
-Fq2 twist_b() { return Fq2{Fq{G16_G2B_C0}, Fq{G16_G2B_C1}}; }
-
-// file images (affine LE Montgomery): coordinates below q and the point on its curve; the all-zero image is infinity
-bool g1_image_ok(const uint8_t* p) {
-  const Fq x = fq_load(p), y = fq_load(p + 32);
-  if (!limbs_below(x.v, kFqP) || !limbs_below(y.v, kFqP)) return false;
-  if (fp_is_zero(x) && fp_is_zero(y)) return true;
-  return fp_eq(fp_sqr(y), fp_add(fp_mul(fp_sqr(x), x), fq_b3()));
-}
-bool g2_image_ok(const uint8_t* p) {
-  Fq c[4];
-  for (int i = 0; i < 4; i++) {
-    c[i] = fq_load(p + 32 * i);
-    if (!limbs_below(c[i].v, kFqP)) return false;
-  }
-  const Fq2 x{c[0], c[1]}, y{c[2], c[3]};
-  if (Fq2Ops::is_zero(x) && Fq2Ops::is_zero(y)) return true;
-  return Fq2Ops::eq(Fq2Ops::sqr(y), Fq2Ops::add(Fq2Ops::mul(Fq2Ops::sqr(x), x), twist_b()));
-}
-bool all_zero(const uint8_t* p, size_t n) {
-  for (size_t i = 0; i < n; i++) if (p[i]) return false;
-  return true;
-}
-
-void be32(const Fq& std_form, uint8_t out[32]) {
-  for (int i = 0; i < 8; i++) {
-    const uint32_t w = std_form.v[7 - i];
-    out[4 * i] = (uint8_t)(w >> 24); out[4 * i + 1] = (uint8_t)(w >> 16); out[4 * i + 2] = (uint8_t)(w >> 8); out[4 * i + 3] = (uint8_t)w;
-  }
-}
-
-// a^((q + 1) / 4): the square root when a is a square (q = 3 mod 4)
-bool fq_sqrt(const Fq& a, Fq& root) {
-  uint32_t e[8];
-  uint64_t c = 1;
-  for (int i = 0; i < 8; i++) { c += kFqP[i]; e[i] = (uint32_t)c; c >>= 32; }
-  for (int i = 0; i < 8; i++) e[i] = (e[i] >> 2) | (i < 7 ? e[i + 1] << 30 : 0);
-  root = fp_pow(a, e);
-  return fp_eq(fp_sqr(root), a);
-}
-bool fq2_sqrt(const Fq2& a, Fq2& root) {
-  const Fq zero = fp_zero<FqParams>();
-  if (fp_is_zero(a.b)) {
-    Fq s;
-    if (fq_sqrt(a.a, s)) { root = Fq2{s, zero}; return true; }
-    if (fq_sqrt(fp_neg(a.a), s)) { root = Fq2{zero, s}; return true; }   // (s u)^2 = -s^2
-    return false;
-  }
-  Fq n;
-  if (!fq_sqrt(fp_add(fp_sqr(a.a), fp_sqr(a.b)), n)) return false;   // the norm of a square is a square
-  const Fq two_inv = fp_inv(fp_add(fp_one<FqParams>(), fp_one<FqParams>()));
-  Fq x0;
-  if (!fq_sqrt(fp_mul(fp_add(a.a, n), two_inv), x0) && !fq_sqrt(fp_mul(fp_sub(a.a, n), two_inv), x0)) return false;
-  const Fq x1 = fp_mul(a.b, fp_inv(fp_add(x0, x0)));
-  root = Fq2{x0, x1};
-  return Fq2Ops::eq(Fq2Ops::sqr(root), a);
-}
-// "negative": the standard value is above (q - 1) / 2; for Fq2 that of c1 unless c1 = 0
-bool fq_is_negative(const Fq& a_mont) {
-  uint32_t half[8];
-  for (int i = 0; i < 8; i++) half[i] = (kFqP[i] >> 1) | (i < 7 ? kFqP[i + 1] << 31 : 0);   // (q - 1) / 2, q odd
-  const Fq s = fp_from_mont(a_mont);
-  return !limbs_below(s.v, half) && memcmp(s.v, half, 32) != 0;
-}
-bool fq2_is_negative(const Fq2& a) { return fp_is_zero(a.b) ? fq_is_negative(a.a) : fq_is_negative(a.b); }
-
-// ChaCha20 block function as a word stream
-struct ChaCha {
-  uint32_t key[8];
-  uint64_t counter = 0;
-  uint32_t buf[16];
-  int have = 0;
-  static uint32_t rotl(uint32_t x, int n) { return (x << n) | (x >> (32 - n)); }
-  void refill() {
-    uint32_t s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
-    for (int i = 0; i < 8; i++) s[4 + i] = key[i];
-    s[12] = (uint32_t)counter; s[13] = (uint32_t)(counter >> 32); s[14] = 0; s[15] = 0;
-    uint32_t x[16];
-    memcpy(x, s, sizeof(x));
-    auto qr = [&](int a, int b, int c, int d) {
-      x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 16);
-      x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 12);
-      x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 8);
-      x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 7);
-    };
-    for (int r = 0; r < 10; r++) {
-      qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15);
-      qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14);
-    }
-    for (int i = 0; i < 16; i++) buf[i] = x[i] + s[i];
-    counter++;
-    have = 16;
-  }
-  uint32_t next_u32() {
-    if (!have) refill();
-    return buf[16 - have--];
-  }
-  uint64_t next_u64() { const uint64_t hi = next_u32(); return hi << 32 | next_u32(); }
-  // sum_i next_u64 2^(64 i) masked to 254 bits, redrawn until below the modulus
-  void next_below(const uint32_t mod[8], uint32_t out[8]) {
-    for (;;) {
-      for (int i = 0; i < 4; i++) { const uint64_t w = next_u64(); out[2 * i] = (uint32_t)w; out[2 * i + 1] = (uint32_t)(w >> 32); }
-      out[7] &= 0x3fffffffu;
-      if (limbs_below(out, mod)) return;
-    }
-  }
-};
-
-int os_random(uint8_t* out, size_t n) {
-  const int fd = open("/dev/urandom", O_RDONLY);
-  if (fd < 0) { set_error("cannot open /dev/urandom"); return G16_E_STATE; }
-  const bool ok = read(fd, out, n) == (ssize_t)n;
-  close(fd);
-  if (!ok) { set_error("short read from /dev/urandom"); return G16_E_STATE; }
-  return G16_OK;
-}
-
-template <class F> void mul_image(const uint8_t* lem, const Fr& k_std, uint8_t* out) {   // [k] P on the host, file images
-  Affine<F> p, r;
-  memcpy(&p, lem, sizeof(p));
-  XYZZ<F> acc;
-  xyzz_mul_scalar(acc, p, k_std.v);
-  xyzz_to_affine(r, acc);
-  memcpy(out, &r, sizeof(r));
-}
-
-}  // namespace
-
-// the helpers above for the .ptau ceremony (ptau_mpc.cpp)
-bool mpc_g1_image_ok(const uint8_t* p) { return g1_image_ok(p); }
-bool mpc_g2_image_ok(const uint8_t* p) { return g2_image_ok(p); }
-void mpc_mul_g1(const uint8_t* lem, const Fr& k_std, uint8_t* out) { mul_image<FqOps>(lem, k_std, out); }
-void mpc_mul_g2(const uint8_t* lem, const Fr& k_std, uint8_t* out) { mul_image<Fq2Ops>(lem, k_std, out); }
-int mpc_os_random(uint8_t* out, size_t n) { return os_random(out, n); }
-int mpc_random_fr(uint8_t* out, uint64_t n) {
-  ChaCha rng;
-  if (const int rc = os_random((uint8_t*)rng.key, 32)) return rc;
-  for (uint64_t i = 0; i < n; i++) rng.next_below(kFrP, (uint32_t*)(out + i * 32));
-  return G16_OK;
-}
 // a record's params: byte 1, byte len, the name's UTF-8 bytes cut to 64 characters and to what one length byte can
 // hold; nothing without a name
 std::string mpc_name_params(const char* name) {
@@ -281,45 +53,6 @@ std::string mpc_name_params(const char* name) {
   return std::string(1, (char)1) + std::string(1, (char)(uint8_t)nm.size()) + nm;
 }
 
-void g1_uncompressed(const uint8_t lem[64], uint8_t out[64]) {
-  if (all_zero(lem, 64)) { memset(out, 0, 64); out[0] = 0x40; return; }
-  be32(fp_from_mont(fq_load(lem)), out);
-  be32(fp_from_mont(fq_load(lem + 32)), out + 32);
-}
-void g2_uncompressed(const uint8_t lem[128], uint8_t out[128]) {   // x.c1 | x.c0 | y.c1 | y.c0
-  if (all_zero(lem, 128)) { memset(out, 0, 128); out[0] = 0x40; return; }
-  be32(fp_from_mont(fq_load(lem + 32)), out);
-  be32(fp_from_mont(fq_load(lem)), out + 32);
-  be32(fp_from_mont(fq_load(lem + 96)), out + 64);
-  be32(fp_from_mont(fq_load(lem + 64)), out + 96);
-}
-
-// uncompressed big-endian standard form -> the file image; false for a flag other than a clean 0x40, a coordinate >= q
-// or a point off its curve
-bool mpc_image_from_be(const uint8_t* be, size_t psz, uint8_t* lem) {
-  if (be[0] & 0xc0) {
-    if (be[0] != 0x40 || !all_zero(be + 1, psz - 1)) return false;
-    memset(lem, 0, psz);
-    return true;
-  }
-  const int nc = (int)(psz / 32);
-  for (int c = 0; c < nc; c++) {
-    Fq s;
-    for (int i = 0; i < 8; i++) {
-      const uint8_t* w = be + 32 * c + 4 * (7 - i);
-      s.v[i] = (uint32_t)w[0] << 24 | (uint32_t)w[1] << 16 | (uint32_t)w[2] << 8 | w[3];
-    }
-    bool below = false;
-    for (int i = 7; i >= 0; i--)
-      if (s.v[i] != kFqP[i]) { below = s.v[i] < kFqP[i]; break; }
-    if (!below) return false;
-    s = fp_to_mont(s);
-    memcpy(lem + 32 * (nc == 2 ? c : c ^ 1), s.v, 32);
-  }
-  if (all_zero(lem, psz)) return false;   // (infinity is the flagged image alone)
-  return nc == 2 ? g1_image_ok(lem) : g2_image_ok(lem);
-}
-
 void mpc_hash_pubkey(std::vector<uint8_t>& feed, const MpcRecord& r) {
   const size_t at = feed.size();
   feed.resize(at + 64 + 64 + 64 + 128 + 64);
@@ -329,43 +62,6 @@ void mpc_hash_pubkey(std::vector<uint8_t>& feed, const MpcRecord& r) {
   g1_uncompressed(r.g1_sx(), q + 128);
   g2_uncompressed(r.g2_spx(), q + 192);
   memcpy(q + 320, r.transcript(), 64);
-}
-
-// The transcript's point on G2, ffjavascript's construction as far as it can be restated without the package: a
-// ChaCha20 word stream keyed with the first 32 transcript bytes (eight big-endian words), field elements drawn as four
-// 64-bit words (low word first, each word = first u32 * 2^32 + second u32) masked to 254 bits and redrawn until below
-// q, THE DRAWN VALUE TAKEN AS THE MONTGOMERY IMAGE; x = (c0, c1), then one bit `greatest`; both redrawn until
-// x^3 + b' is a square; y = the root that is negative exactly when `greatest`; the point times the cofactor 2q - r.
-// NOT CROSS-CHECKED AGAINST snarkjs (ffjavascript is not available to the tests): the twin in tests/zkey_mpc_ref.py is
-// written from the same description.  The whole derivation lives in this one function, so a correction is a one-place
-// change (and one in the twin).
-void hash_to_g2(const uint8_t transcript[64], G2Affine& out) {
-  ChaCha rng;
-  for (int i = 0; i < 8; i++)
-    rng.key[i] = (uint32_t)transcript[4 * i] << 24 | (uint32_t)transcript[4 * i + 1] << 16 | (uint32_t)transcript[4 * i + 2] << 8 |
-                 transcript[4 * i + 3];
-  G2Affine p;
-  for (;;) {
-    rng.next_below(kFqP, p.x.a.v);
-    rng.next_below(kFqP, p.x.b.v);
-    const bool greatest = rng.next_u32() & 1;
-    const Fq2 rhs = Fq2Ops::add(Fq2Ops::mul(Fq2Ops::sqr(p.x), p.x), twist_b());
-    if (!fq2_sqrt(rhs, p.y)) continue;
-    if (fq2_is_negative(p.y) != greatest) p.y = Fq2Ops::neg(p.y);
-    break;
-  }
-  uint32_t cof[8];   // 2q - r
-  {
-    int64_t c = 0;
-    for (int i = 0; i < 8; i++) {
-      c += 2 * (int64_t)kFqP[i] - (int64_t)kFrP[i];
-      cof[i] = (uint32_t)c;
-      c >>= 32;
-    }
-  }
-  G2XYZZ acc;
-  xyzz_mul_scalar(acc, p, cof);
-  xyzz_to_affine(out, acc);
 }
 
 int mpc_parse(const BinSection& s10, MpcSection& out) {
@@ -422,27 +118,45 @@ int open_key(const uint8_t* zkey, size_t len, KeyView& k, bool exact_89) {
   return mpc_parse(k.f.sec[10], k.mpc);
 }
 
-namespace {
-bool scalar_ok(const uint8_t* s, Fr& out) {   // standard form, in [1, r)
-  memcpy(out.v, s, 32);
-  return !fp_is_zero(out) && fr_below_modulus(out.v);
-}
-}  // namespace
-
-int mpc_read_secret(const char* route, const uint8_t* secret, Fr& d, Fr& s) {
-  if (secret) {
-    if (!scalar_ok(secret, d) || !scalar_ok(secret + 32, s)) {
-      set_error(std::string(route) + ": the secret scalars must be in [1, r)");
-      return G16_E_ARG;
-    }
-    return G16_OK;
+bool key_image_layout(const uint8_t* zkey, const KeyView& k, size_t extra, Buf& z, uint8_t* sp[16]) {
+  const uint32_t nsec = rd32(zkey + 8);
+  size_t end = 12;   // (bin_open has walked and bounded this table)
+  for (uint32_t i = 0; i < nsec; i++) end += 12 + rd64(zkey + end + 4);
+  if (!z.reserve(end + extra)) return false;
+  z.put(zkey, 12);
+  for (int id = 0; id < 16; id++) sp[id] = nullptr;
+  for (size_t pos = 12; pos < end;) {
+    const uint32_t id = rd32(zkey + pos);
+    const uint64_t size = rd64(zkey + pos + 4);
+    const uint8_t* p = zkey + pos + 12;
+    const bool first = id < 16 && p == k.f.sec[id].p;
+    z.u32(id);
+    z.u64(first && id == 10 ? size + extra : size);
+    uint8_t* q = z.skip(size);
+    if (first) sp[id] = q;
+    if (!(first && (id == 8 || id == 9))) memcpy(q, p, size);
+    if (first && id == 10) z.skip(extra);
+    pos += 12 + size;
   }
-  for (Fr* x : {&d, &s})
-    for (;;) {
-      if (const int rc = os_random((uint8_t*)x->v, 32)) return rc;
-      x->v[7] &= 0x3fffffffu;
-      if (!fp_is_zero(*x) && fr_below_modulus(x->v)) break;
+  return true;
+}
+
+int read_secrets(const char* route, const uint8_t* secret, Fr* out, int count) {
+  for (int i = 0; i < count; i++) {
+    Fr& x = out[i];
+    if (secret) {   // standard form, in [1, r)
+      memcpy(x.v, secret + 32 * i, 32);
+      if (fp_is_zero(x) || !fr_below_modulus(x.v)) {
+        set_error(std::string(route) + ": the secret scalars must be in [1, r)");
+        return G16_E_ARG;
+      }
+    } else {
+      do {
+        if (const int rc = os_random((uint8_t*)x.v, 32)) return rc;
+        x.v[7] &= 0x3fffffffu;
+      } while (fp_is_zero(x) || !fr_below_modulus(x.v));
     }
+  }
   return G16_OK;
 }
 
@@ -462,11 +176,8 @@ int mpc_beacon_scalars(const uint8_t* beacon, size_t beacon_len, uint32_t exp, i
 }
 
 bool mpc_beacon_key_ok(const uint8_t* g1_s, const uint8_t* g1_sx, const Fr& x, const Fr& s) {
-  G1Affine g1;   // (1, 2)
-  g1.x = fp_one<FqParams>();
-  g1.y = fp_add(g1.x, g1.x);
   uint8_t want[64];
-  mul_image<FqOps>((const uint8_t*)&g1, s, want);
+  mul_image<FqOps>(gens().g1, s, want);
   if (memcmp(want, g1_s, 64) != 0) return false;
   mul_image<FqOps>(want, x, want);
   return memcmp(want, g1_sx, 64) == 0;
@@ -474,10 +185,7 @@ bool mpc_beacon_key_ok(const uint8_t* g1_s, const uint8_t* g1_sx, const Fr& x, c
 
 void mpc_contribution(std::vector<uint8_t>& feed, const Fr& d, const Fr& s, uint8_t g1_s[64], uint8_t g1_sx[64],
                       uint8_t g2_spx[128], uint8_t transcript[64]) {
-  G1Affine g1;   // (1, 2)
-  g1.x = fp_one<FqParams>();
-  g1.y = fp_add(g1.x, g1.x);
-  mul_image<FqOps>((const uint8_t*)&g1, s, g1_s);
+  mul_image<FqOps>(gens().g1, s, g1_s);
   mul_image<FqOps>(g1_s, d, g1_sx);
   const size_t at = feed.size();
   feed.resize(at + 128);
@@ -502,10 +210,6 @@ void transcript_of(const MpcSection& m, size_t upto, const uint8_t* g1_s, const 
   blake2b512(feed.data(), feed.size(), out);
 }
 
-double ms_since(const std::chrono::steady_clock::time_point& t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // bc: `zkey beacon` -- the secret is the beacon's (the chain runs here, on this thread, before the device is touched),
 // the record is of type 1 and states the beacon after the name; everything else is the contribution's
 int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, const uint8_t* secret, const BeaconArg* bc, int device,
@@ -514,14 +218,9 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
   const char* route = bc ? "zkey beacon" : "zkey contribute";
   KeyView k;
   if (const int rc = open_key(zkey, zkey_len, k, true)) return rc;
-  Fr d, s;
-  if (bc) {
-    Fr ds[2];
-    if (const int rc = mpc_beacon_scalars(bc->hash, bc->len, bc->exp, 2, ds)) return rc;
-    d = ds[0]; s = ds[1];
-  } else if (const int rc = mpc_read_secret(route, secret, d, s)) {
-    return rc;
-  }
+  Fr ds[2];
+  if (const int rc = bc ? mpc_beacon_scalars(bc->hash, bc->len, bc->exp, 2, ds) : read_secrets(route, secret, ds, 2)) return rc;
+  const Fr &d = ds[0], &s = ds[1];
   if (const int rc = require_hip_device(route, device)) return rc;
 
   std::string params = mpc_name_params(name);
@@ -529,33 +228,10 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
   const uint32_t plen = (uint32_t)params.size();
   const size_t rec_len = kMpcRecordFixed + plen;
 
-  // the image: every record of the input's table in its order, the first section 10 one record longer
-  struct Entry { uint32_t id; const uint8_t* p; uint64_t size; };
-  std::vector<Entry> table;
-  {
-    const uint32_t nsec = rd32(zkey + 8);
-    size_t pos = 12;   // (bin_open has walked and bounded this table)
-    for (uint32_t i = 0; i < nsec; i++) {
-      table.push_back(Entry{rd32(zkey + pos), zkey + pos + 12, rd64(zkey + pos + 4)});
-      pos += 12 + table.back().size;
-    }
-  }
-  size_t total = 12;
-  for (const Entry& e : table) total += 12 + e.size;
-  total += rec_len;
+  // the image: the input's sections in their order, section 10 one record longer
   Buf z;
-  if (!z.reserve(total)) { set_error(std::string(route) + ": out of memory"); return G16_E_STATE; }
-  z.put(zkey, 12);
-  uint8_t* sp[16] = {};
-  for (const Entry& e : table) {
-    const bool first = e.id < 16 && e.p == k.f.sec[e.id].p;
-    z.u32(e.id);
-    z.u64(first && e.id == 10 ? e.size + rec_len : e.size);
-    uint8_t* q = z.skip(e.size);
-    if (first) sp[e.id] = q;
-    if (!(first && (e.id == 8 || e.id == 9))) memcpy(q, e.p, e.size);
-    if (first && e.id == 10) z.skip(rec_len);
-  }
+  uint8_t* sp[16];
+  if (!key_image_layout(zkey, k, rec_len, z, sp)) { set_error(std::string(route) + ": out of memory"); return G16_E_STATE; }
 
   // host: the contribution's points and the header's delta
   uint8_t* rec = sp[10] + k.f.sec[10].size;
@@ -583,7 +259,7 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
   ChunkStats st[2];
   int rc = zkey_scale_g1(device, k.f.sec[8].p, k.f.sec[8].size / 64, dinv, sp[8], &st[0]);
   if (!rc) rc = zkey_scale_g1(device, k.f.sec[9].p, k.f.sec[9].size / 64, dinv, sp[9], &st[1]);
-  if (rc) { free(z.p); return rc; }
+  if (rc) return rc;
   if (getenv("G16_TRACE_HOST"))
     fprintf(stderr, "[g16] %s: points %llu; kernels %.3f ms, transfers %.3f ms, MSM 0.000 ms, pairings 0.000 ms; call %.3f ms\n",
             route, (unsigned long long)(st[0].points + st[1].points), st[0].kern_ms + st[1].kern_ms, st[0].xfer_ms + st[1].xfer_ms, ms_since(t0));
@@ -592,14 +268,6 @@ int contribute_core(const uint8_t* zkey, size_t zkey_len, const char* name, cons
 }
 
 // ---- verify
-}  // namespace
-void mpc_pair_words(std::vector<uint8_t>& in, const uint8_t* g1_lem, const uint8_t* g2_lem) {   // g16_pairing_op's input
-  const size_t at = in.size();
-  in.resize(at + 192);
-  for (int i = 0; i < 2; i++) { const Fq v = fp_from_mont(fq_load(g1_lem + 32 * i)); memcpy(in.data() + at + 32 * i, v.v, 32); }
-  for (int i = 0; i < 4; i++) { const Fq v = fp_from_mont(fq_load(g2_lem + 32 * i)); memcpy(in.data() + at + 64 + 32 * i, v.v, 32); }
-}
-namespace {
 // ptau != nullptr: the ptau leg as well (step 6): section 9 of the key under test against the first 2N - 1 points of
 // the ceremony's section 2 -- prepared or not, no other section of the ptau is read
 int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_t ptau_len, const uint8_t* zkey, size_t zkey_len,
@@ -641,26 +309,23 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
     return verdict("zkey verify: section 8 or 9 has not the initial key's length");
 
   // 3. the chain: hashes on the host, the pairs of every same-ratio check collected for ONE device call
-  std::vector<uint8_t> pairs;        // 192 bytes each; check c compares pairing 2c with pairing 2c + 1
-  std::vector<const char*> reason;   // per check
+  PairChecks checks;
   auto same_ratio = [&](const uint8_t* g1a, const uint8_t* g1b, const uint8_t* g2c, const uint8_t* g2d, const char* why) {
     if (all_zero(g1a, 64) || all_zero(g1b, 64) || all_zero(g2c, 128) || all_zero(g2d, 128)) return false;
-    mpc_pair_words(pairs, g1a, g2d);   // e(a, d) = e(b, c)
-    mpc_pair_words(pairs, g1b, g2c);
-    reason.push_back(why);
+    checks.same_ratio(g1a, g1b, g2c, g2d, why);
     return true;
   };
   const char* inf_text = "zkey verify: a contribution holds the point at infinity";
   const uint8_t* cur = ha + kHdrDelta1;
   const char* beacon_fail = nullptr;   // reported after the pairing checks: a beacon record passes its own checks first
-  std::vector<G2Affine> g2_sp(b.mpc.rec.size());
   for (size_t i = a.mpc.rec.size(); i < b.mpc.rec.size(); i++) {
     const MpcRecord& r = b.mpc.rec[i];
     uint8_t tr[64];
     transcript_of(b.mpc, i, r.g1_s(), r.g1_sx(), tr);
     if (memcmp(tr, r.transcript(), 64) != 0) return verdict("zkey verify: a contribution's transcript hash does not match");
-    hash_to_g2(tr, g2_sp[i]);
-    const uint8_t* sp2 = (const uint8_t*)&g2_sp[i];
+    G2Affine g2_sp;
+    hash_to_g2(tr, g2_sp);
+    const uint8_t* sp2 = (const uint8_t*)&g2_sp;
     if (!same_ratio(r.g1_s(), r.g1_sx(), sp2, r.g2_spx(), "zkey verify: a contribution's public key is not consistent")) return verdict(inf_text);
     if (!same_ratio(cur, r.delta_after(), sp2, r.g2_spx(), "zkey verify: a contribution's delta does not continue the chain")) return verdict(inf_text);
     cur = r.delta_after();
@@ -714,16 +379,8 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
   const bool s_inf = all_zero(S, 64);
   if (!s_inf) {
     if (all_zero(T, 64)) return verdict("zkey verify: sections 8 and 9 are not the initial key's scaled by 1 / delta");
-    const size_t at = pairs.size();
-    pairs.resize(at + 2 * 192);
-    memcpy(pairs.data() + at, S, 64);
-    memcpy(pairs.data() + at + 192, T, 64);
-    for (int i = 0; i < 4; i++) {
-      const Fq v = fp_from_mont(fq_load(hb + kHdrDelta2 + 32 * i)), w = fp_from_mont(fq_load(ha + kHdrDelta2 + 32 * i));
-      memcpy(pairs.data() + at + 64 + 32 * i, v.v, 32);
-      memcpy(pairs.data() + at + 192 + 64 + 32 * i, w.v, 32);
-    }
-    reason.push_back("zkey verify: sections 8 and 9 are not the initial key's scaled by 1 / delta");
+    checks.equal(pair_words(S), pair_image(hb + kHdrDelta2), pair_words(T), pair_image(ha + kHdrDelta2),
+                 "zkey verify: sections 8 and 9 are not the initial key's scaled by 1 / delta");
   } else if (n8 || L >= 1) {   // (some scalar was drawn)
     return verdict("zkey verify: the combination of sections 8 and 9 is the point at infinity");
   }
@@ -743,24 +400,19 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
     const bool sh_inf = all_zero(Sh, 64);
     if (sh_inf != all_zero(Th, 64)) return verdict(h_text);
     if (!sh_inf) {
-      G1Affine s, t, s2n;
-      s.x = fp_to_mont(fq_load(Sh)); s.y = fp_to_mont(fq_load(Sh + 32));
-      t.x = fp_to_mont(fq_load(Th)); t.y = fp_to_mont(fq_load(Th + 32));
+      G1Affine s, s2n;
+      memcpy(&s, Sh, 64);
+      s.x = fp_to_mont(s.x); s.y = fp_to_mont(s.y);
       Fr two_n = fp_zero<FrParams>();
       two_n.v[0] = 2 * b.N;   // L <= 27
       mul_image<FqOps>((const uint8_t*)&s, two_n, (uint8_t*)&s2n);
-      const G2Affine g2{Fq2{Fq{G16_G2X0}, Fq{G16_G2X1}}, Fq2{Fq{G16_G2Y0}, Fq{G16_G2Y1}}};
-      mpc_pair_words(pairs, (const uint8_t*)&s2n, hb + kHdrDelta2);
-      mpc_pair_words(pairs, (const uint8_t*)&t, (const uint8_t*)&g2);
-      reason.push_back(h_text);
+      checks.equal(pair_image((const uint8_t*)&s2n), pair_image(hb + kHdrDelta2), pair_words(Th), pair_image(gens().g2), h_text);
     }
   }
   const auto t2 = std::chrono::steady_clock::now();
-  const uint32_t np = (uint32_t)(pairs.size() / 192);
-  std::vector<uint8_t> gt((size_t)np * 384);
-  if (np)
-    if (const int rc = g16_pairing_op(device, pairs.data(), np, gt.data())) return rc;
+  if (const int rc = checks.run(device)) return rc;
   const double pair_ms = ms_since(t2);
+  const uint32_t np = checks.pairs();
   if (getenv("G16_TRACE_HOST")) {
     if (leg)
       fprintf(stderr, "[g16] zkey verify: points %llu; kernels 0.000 ms, transfers 0.000 ms, MSM %.3f ms, pairings %.3f ms (%u); "
@@ -770,8 +422,7 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
       fprintf(stderr, "[g16] zkey verify: points %llu; kernels 0.000 ms, transfers 0.000 ms, MSM %.3f ms, pairings %.3f ms (%u); call %.3f ms\n",
               (unsigned long long)n, msm_ms, pair_ms, np, ms_since(t0));
   }
-  for (size_t c = 0; c < reason.size(); c++)
-    if (memcmp(gt.data() + 2 * c * 384, gt.data() + (2 * c + 1) * 384, 384) != 0) return verdict(reason[c]);
+  if (const char* why = checks.first_failure()) return verdict(why);
   if (beacon_fail) return verdict(beacon_fail);
   set_error("");
   *ok = 1;
@@ -782,38 +433,6 @@ int verify_core(const uint8_t* init, size_t init_len, const uint8_t* ptau, size_
 }  // namespace g16
 
 using namespace g16;
-
-extern "C" int g16_blake2b512(const uint8_t* data, size_t len, uint8_t out[64]) {
-  if ((!data && len) || !out) { set_error("NULL argument"); return G16_E_ARG; }
-  blake2b512(data, len, out);
-  return G16_OK;
-}
-
-extern "C" int g16_blake2b512_parts(const uint8_t* data, size_t len, const size_t* cuts, size_t n_cuts, uint8_t out[64]) {
-  if ((!data && len) || (!cuts && n_cuts) || !out) { set_error("NULL argument"); return G16_E_ARG; }
-  size_t at = 0;
-  for (size_t i = 0; i < n_cuts; i++) {
-    if (cuts[i] < at || cuts[i] > len) { set_error("blake2b512 parts: the cuts must ascend and lie within the data"); return G16_E_ARG; }
-    at = cuts[i];
-  }
-  Blake2b512 b;
-  at = 0;
-  for (size_t i = 0; i < n_cuts; i++) {
-    b.update(data + at, cuts[i] - at);
-    at = cuts[i];
-  }
-  b.update(data + at, len - at);
-  b.final(out);
-  return G16_OK;
-}
-
-extern "C" int g16_zkey_hash_to_g2(const uint8_t transcript[64], uint8_t out[128]) {
-  if (!transcript || !out) { set_error("NULL argument"); return G16_E_ARG; }
-  G2Affine p;
-  hash_to_g2(transcript, p);
-  memcpy(out, &p, 128);
-  return G16_OK;
-}
 
 extern "C" int g16_zkey_contribute(const uint8_t* zkey, size_t zkey_len, const char* name, const uint8_t secret[64], int device,
                                    uint8_t** out, size_t* out_len, uint8_t contribution_hash[64]) {
@@ -894,7 +513,7 @@ extern "C" int g16_zkey_verify_r1cs(const uint8_t* r1cs, size_t r1cs_len, const 
   uint8_t* init = nullptr;
   size_t init_len = 0;
   if (const int rc = g16_groth16_setup_ptau(r1cs, r1cs_len, ptau, ptau_len, device, &init, &init_len)) return rc;
-  struct Free { uint8_t* p; ~Free() { free(p); } } guard{init};
+  const MallocPtr guard(init);
   // A key that carries a circuit hash (anything but the legacy 64 zero bytes) is held against the initial key WITH its
   // real csHash.  Only where that can matter: the key parses and has the initial key's domain -- every other input
   // gets its error or verdict from the route below before section 10 is compared, exactly as without this step; and

@@ -1,5 +1,6 @@
-// Phase-2 ceremony pieces of a Groth16 .zkey (zkey_mpc.cpp): section 10 in snarkjs's zkey_utils.js layout, Blake2b-512,
-// the public-key hash of a contribution and the transcript's point on G2.  Host code.
+// Phase-2 ceremony pieces of a Groth16 .zkey (zkey_mpc.cpp): section 10 in snarkjs's zkey_utils.js layout, the key as
+// the ceremony routes read and rewrite it, the public-key hash of a contribution, and the secrets of a contribution or a
+// beacon.  Host code.  Hashing is blake2b.h, arithmetic on file images curve_host.h.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -8,23 +9,10 @@
 #include <vector>
 
 #include "binfile.h"
-#include "ec.cuh"
+#include "blake2b.h"
+#include "curve_host.h"
 
 namespace g16 {
-
-void blake2b512(const uint8_t* data, size_t len, uint8_t out[64]);   // RFC 7693, unkeyed
-// the same over a feed that arrives in parts of any length (empty ones included); final() once
-class Blake2b512 {
- public:
-  Blake2b512();
-  void update(const uint8_t* data, size_t len);
-  void final(uint8_t out[64]);
-
- private:
-  uint64_t h_[8], t_ = 0;   // t_: bytes compressed so far
-  uint8_t buf_[128];
-  size_t have_ = 0;         // bytes held back in buf_, 0 .. 128
-};
 
 // One contribution record of section 10, as it lies in the file (p[0, len)):
 //   deltaAfter G1 (64) | delta.g1_s (64) | delta.g1_sx (64) | delta.g2_spx (128) | transcript (64) | u32 type |
@@ -51,12 +39,6 @@ int mpc_parse(const BinSection& s10, MpcSection& out);
 // snarkjs hashPubKey fed into a running buffer: the four points in uncompressed big-endian standard form, then the
 // transcript
 void mpc_hash_pubkey(std::vector<uint8_t>& feed, const MpcRecord& r);
-void g1_uncompressed(const uint8_t lem[64], uint8_t out[64]);
-void g2_uncompressed(const uint8_t lem[128], uint8_t out[128]);
-// the inverse (psz = 64 / 128): false for a flag other than a clean 0x40, a coordinate >= q or a point off its curve
-bool mpc_image_from_be(const uint8_t* be, size_t psz, uint8_t* lem);
-
-void hash_to_g2(const uint8_t transcript[64], G2Affine& out);
 
 // A Groth16 key as the ceremony routes read it (zkey_mpc.cpp, zkey_bellman_host.cpp).  Section 2: alpha1 at 84, beta1 at 148,
 // beta2 at 212, gamma2 at 340, delta1 at 468, delta2 at 532.
@@ -69,9 +51,15 @@ struct KeyView {
 // exact_89: sections 8 and 9 must have the header's sizes (the verifier only needs whole points: a short section is a
 // verdict there, not a malformed file)
 int open_key(const uint8_t* zkey, size_t len, KeyView& k, bool exact_89);
-// a contribution's secret: d | s, standard form in [1, r) (else G16_E_ARG "<route>: the secret scalars must be in
-// [1, r)"), or NULL for the OS CSPRNG
-int mpc_read_secret(const char* route, const uint8_t* secret, Fr& d, Fr& s);
+// The image of a key that continues the opened key k = zkey: every record of its section table in its order, copied,
+// but the first section 10 `extra` bytes longer (room after its old bytes) and the first sections 8 and 9 left unfilled.
+// sp[id] = the first section id in the image.  false: the reservation failed (the caller words the error).
+bool key_image_layout(const uint8_t* zkey, const KeyView& k, size_t extra, Buf& z, uint8_t* sp[16]);
+
+// A contribution's secret scalars: `count` of them behind each other in standard form, each in [1, r) (else G16_E_ARG
+// "<route>: the secret scalars must be in [1, r)"), or NULL for the OS CSPRNG.  count 2: d | s; count 6: tau | alpha |
+// beta | s_tau | s_alpha | s_beta.
+int read_secrets(const char* route, const uint8_t* secret, Fr* out, int count);
 // A contribution's own points (file images): g1_s = [s] G, g1_sx = [d] g1_s, transcript = Blake2b-512(feed | g1_s |
 // g1_sx uncompressed) with feed = csHash | hashPubKey of every earlier record (extended here), g2_spx = [d] of the
 // transcript's point on G2.
@@ -87,15 +75,6 @@ int mpc_beacon_scalars(const uint8_t* beacon, size_t beacon_len, uint32_t exp, i
 // a beacon record's key under the verifiers: g1_s = [s] G1 and g1_sx = [x] g1_s (file images)
 bool mpc_beacon_key_ok(const uint8_t* g1_s, const uint8_t* g1_sx, const Fr& x, const Fr& s);
 
-// Shared with the .ptau ceremony (ptau_mpc.cpp).  File images are affine little-endian Montgomery, infinity = zeros.
-bool mpc_g1_image_ok(const uint8_t* p);   // coordinates below q and the point on its curve (infinity passes)
-bool mpc_g2_image_ok(const uint8_t* p);
-void mpc_mul_g1(const uint8_t* lem, const Fr& k_std, uint8_t* out);   // [k] P on the host
-void mpc_mul_g2(const uint8_t* lem, const Fr& k_std, uint8_t* out);
-int mpc_os_random(uint8_t* out, size_t n);
-int mpc_random_fr(uint8_t* out, uint64_t n);   // n fresh standard-form scalars below r: ChaCha20 keyed from the OS CSPRNG
 std::string mpc_name_params(const char* name);   // a record's params for a contribution's name (or NULL)
-// one pair of g16_pairing_op's input appended: six standard-form words
-void mpc_pair_words(std::vector<uint8_t>& in, const uint8_t* g1_lem, const uint8_t* g2_lem);
 
 }  // namespace g16

@@ -6,6 +6,7 @@
 // back by bin_open.
 #include <stdio.h>
 
+#include <utility>
 #include <vector>
 
 #include "binfile.h"
@@ -48,6 +49,13 @@ static bool open_exact(const uint8_t* img, size_t len, uint32_t max_version) {
   }
   free(buf);
   return rc == G16_OK;
+}
+
+static Buf filled(size_t n) {   // by value, as write_wtns / write_r1cs return theirs
+  Buf b;
+  CHECK(b.reserve(n));
+  for (size_t i = 0; i < n; i++) { const uint8_t v = (uint8_t)i; b.put(&v, 1); }
+  return b;
 }
 
 int main() {
@@ -111,7 +119,32 @@ int main() {
   CHECK(open_exact(z.p, total, 2));
   CHECK(!open_exact(z.p, total - 1, 2));
   CHECK(parsed > 0 && parsed < runs);
-  free(z.p);
+
+  // Buf owns its image until give(): the sanitizer's leak checker and its double-free check are the asserts here
+  {   // dropped after reserve, as an early return or an exception drops it
+    Buf b;
+    CHECK(b.reserve(100));
+    b.u32(7);
+  }
+  {   // moved through a return value, then handed out: the caller frees it, exactly once
+    Buf b = filled(64);
+    CHECK(b.p != nullptr && b.len == 64 && b.cap == 64);
+    Buf c(std::move(b));
+    CHECK(b.p == nullptr && b.len == 0 && c.p != nullptr && c.len == 64);
+    uint8_t* p = nullptr;
+    size_t n = 0;
+    c.give(&p, &n);
+    CHECK(p != nullptr && n == 64 && p[0] == 0 && p[63] == 63);
+    CHECK(c.p == nullptr && c.len == 0 && c.cap == 0);   // after give() the Buf holds nothing
+    free(p);
+  }
+  {   // give() on a temporary, as write_wtns(w).give(...) does
+    uint8_t* p = nullptr;
+    size_t n = 0;
+    filled(8).give(&p, &n);
+    CHECK(p != nullptr && n == 8 && p[7] == 7);
+    free(p);
+  }
 
   {   // the field record
     uint8_t rec[36];

@@ -126,7 +126,6 @@ int main() {
     }
   printf("mutations: %zu accepted and evaluated, %zu refused\n", accepted, refused);
   CHECK(refused > accepted);
-  free(img.p);
   if (g_fail) { printf("%d FAILED\n", g_fail); return 1; }
   printf("ALL OK\n");
   return 0;

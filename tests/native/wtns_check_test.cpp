@@ -90,7 +90,6 @@ int main() {
   }
   Buf rb = write_r1cs(c, 0, 0);
   Exact r1cs(rb.p, rb.len);
-  free(rb.p);
 
   // the file read back and the CSR built from it
   Circuit back;
@@ -142,7 +141,6 @@ int main() {
     }
     Buf wb = wtns_of(ws);
     Exact img(wb.p, wb.len);
-    free(wb.p);
     g16_wtns_verdict v;
     memset(&v, 0x5a, sizeof(v));
     CHECK(g16_wtns_check(k, img.p, img.len, &v) == G16_OK);
@@ -187,7 +185,6 @@ int main() {
     const size_t ls[2] = {good.len, good.len};
     g16_wtns_verdict vs[2];
     CHECK(g16_wtns_check_batch(k, ptrs, ls, 2, vs) == G16_OK && vs[0].constraint == -1 && vs[1].constraint == -1);
-    free(wb.p);
   }
   g16_r1cs_checker_destroy(k);
 
@@ -204,14 +201,12 @@ int main() {
     e.rowA.assign(1, 0); e.rowB.assign(1, 0); e.rowC.assign(1, 0);
     Buf eb = write_r1cs(e, 0, 0);
     Exact img(eb.p, eb.len);
-    free(eb.p);
     g16_r1cs_checker* kk = nullptr;
     CHECK(g16_r1cs_checker_create(img.p, img.len, -1, &kk) == G16_OK && kk);
     std::vector<Fr> ws(3, w[0]);
     Buf wb = wtns_of(ws);
     g16_wtns_verdict v;
     CHECK(g16_wtns_check(kk, wb.p, wb.len, &v) == G16_OK && v.constraint == -1 && v.n_failed == 0);
-    free(wb.p);
     Circuit back0;
     WcCsr q0;
     CHECK(read_r1cs(img.p, img.len, back0, true) == G16_OK && read_r1cs(img.p, img.len, back0, false) == G16_E_FORMAT);

@@ -1,7 +1,8 @@
 """Memory safety of the one container reader and layout helper (csrc/binfile.h), as a stand-alone host program under
 AddressSanitizer and UndefinedBehaviorSanitizer: tests/native/binfile_test.cpp runs bin_open on every prefix of a
 three-section file held in a heap buffer of exactly that length, with every size field overwritten by hostile values,
-and reads bin_layout's image back.  Nothing is loaded into Python.  What the parsers built on it ANSWER is pinned by
+reads bin_layout's image back, and drops, moves and hands out the owning Buf (the leak checker and the double-free check
+are the asserts there).  Nothing is loaded into Python.  What the parsers built on it ANSWER is pinned by
 tests/test_cpu_parser_errors.py."""
 import os
 import subprocess

@@ -8,6 +8,7 @@ import struct
 
 import pytest
 
+import bn254 as b
 import formats as f
 import synth
 import zkey_mpc_ref as zref
@@ -259,6 +260,26 @@ def test_zkey_verify_rejects_an_ordinary_record_that_claims_to_be_a_beacon(amd, 
     assert ok, why
     ok, why = amd.zkey_verify_r1cs(ceremony["r1cs"], ceremony["ptau"], _zkey_retype(ceremony["final"], 0, 1, name_params("first")), device=0)
     assert not ok and why == "zkey verify: " + NOT_STATED
+
+
+def test_zkey_verify_reports_a_broken_chain_before_a_beacon_that_is_not_its_key(amd, zkeys):
+    """Two failures in one run: the first new record's delta does not continue the chain (the initial key states
+    another delta1), and the LATER beacon record's key is not the beacon's.  The verdicts of the pairing checks come
+    first, in the order the checks were collected; a beacon's verdict follows them."""
+    chain_text = "zkey verify: a contribution's delta does not continue the chain"
+    base = open(golden_path("small.zkey"), "rb").read()
+    secs = f.read_binfile(base, "zkey", 2)
+    order = sorted(secs, key=lambda sid: secs[sid][0][0])
+    hdr = f.section(base, secs, 2)
+    doubled = f.g1_to_lem(b.G1.mul(f.g1_from_lem(hdr[468:532]), 2))
+    other_init = f.write_binfile("zkey", struct.unpack_from("<I", base, 4)[0],
+                                 [(sid, hdr[:468] + doubled + hdr[532:] if sid == 2 else f.section(base, secs, sid)) for sid in order])
+    good = zkeys["small"]["named"][0]
+    bad_beacon = _zkey_retype(good, -1, 1, _tampers("final")["hash_byte"][0])
+    assert [r["type"] for r in parse_section10(_zkey_sections(bad_beacon)[10])[1]] == [0, 1]
+    assert amd.zkey_verify_from_init(other_init, good, device=0) == (False, chain_text)                      # each alone
+    assert amd.zkey_verify_from_init(base, bad_beacon, device=0) == (False, "zkey verify: " + NOT_THE_KEY)
+    assert amd.zkey_verify_from_init(other_init, bad_beacon, device=0) == (False, chain_text)                # together
 
 
 def test_a_ceremony_closed_by_two_beacons_verifies_from_the_r1cs(amd, ceremony):

@@ -282,6 +282,17 @@ def test_verify_rejects_tampered_records(amd, chain):
     _reject(amd, rewrite(chain[3], lambda sid, d: g2 + d[128:] if sid == 3 else d), "the first point of section 2 or 3 is not the generator")
 
 
+def test_verify_reports_a_pairing_failure_before_a_host_failure(amd, chain):
+    """Two failures in one file: the middle record's beta key fails its pairing check, and the last record's challenge
+    hash does not match the file.  The verdicts of the pairing checks come first; the host checks' follow them."""
+    recs = parse_section7(split(chain[3])[1][7])
+    bad_key = _edit7(chain[3], 1, 448 + 2 * 128 + 64, _double(recs[1]["beta.g1_sx"]))
+    flip = bytes([recs[2]["nextChallenge"][9] ^ 1])
+    _reject(amd, bad_key, "a contribution's public key is not consistent")                                     # each alone
+    _reject(amd, _edit7(chain[3], 2, 1432 + 9, flip), "the last contribution's challenge hash does not match the file")
+    _reject(amd, _edit7(bad_key, 2, 1432 + 9, flip), "a contribution's public key is not consistent")          # together
+
+
 def test_verify_rejects_wrong_prepared_sections(amd, chain):
     prep = amd.ptau_prepare(chain[1], device=0)
     swapped = rewrite(prep, lambda sid, d: d[:5 * 64] + d[6 * 64:7 * 64] + d[5 * 64:6 * 64] + d[7 * 64:] if sid == 14 else d)

@@ -12,7 +12,7 @@ set -e
 HIPCC=/opt/rocm/bin/hipcc
 OUT=/tmp/asan
 SAN="-fsanitize=address,undefined -fno-omit-frame-pointer -shared-libsan"
-for f in prover multi circuit synth circuit_builders setup_groth16 setup_plonk ptau; do $HIPCC -O1 -g -std=c++17 -fPIC $SAN -c $f.cpp -o $OUT/$f.o & done
+for f in prover multi circuit synth circuit_builders setup_groth16 setup_plonk ptau blake2b curve_host zkey_mpc ptau_mpc zkey_bellman_host zkey_cshash_host; do $HIPCC -O1 -g -std=c++17 -fPIC $SAN -c $f.cpp -o $OUT/$f.o & done
 wait
 for f in ntt qap msm_g2 ops setup_gpu verify plonk verify_plonk; do $HIPCC --offload-arch=gfx950 -O1 -std=c++17 -fPIC -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer -c $f.hip -o $OUT/$f.o & done
 wait
